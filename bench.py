@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- images/sec of the NSGAN D+G step (BASELINE.json metric), bs=256 per GPU, fp32.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: one rank per GPU; started under torch.distributed.run it uses the RANK/WORLD_SIZE it is
     given, started from a bare shell it re-launches itself under torch.distributed.run)
 
@@ -10,12 +10,21 @@ backward -> Adam(D) -> train_G -> backward -> Adam(G), in PARITY mode (reference
 bit-exact sampling indices).  The dataset (synthetic 50 000 x 28x28 Bernoulli images, seed 3435)
 is resident in HBM before the timed region; the host-side RNG prefetch is inside it.
 Weak scaling: every rank runs bs=256 (global batch 256*N), gradients all-reduced over RCCL.
-The K-step timed region (barrier + synchronize on both sides, max over ranks) is repeated
-`--reps` times on fresh draws; `ms_per_step` / `value` are the MEDIAN repetition (all of them are
-listed in config.reps_ms_per_step).  The host draws of a timed step happen inside its timed region.
-At N=1 the same line carries `configs`: BASELINE.json configs 3/4/5 (WGAN-GP bs=256, VAE bs=512,
-NSGAN/LSGAN bs=1024) measured the same way, each with its dominant GEMM's roofline fraction and a
-bounded CPU-oracle baseline.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, runs W warm-up steps, times ONE region of exactly K steps (barrier +
+synchronize on both sides, max over ranks; the host draws of a timed step happen inside it), writes
+the outputs of the timed path if --dump-outputs is given, and prints the result line.
+--dump-outputs DIR: what a caller of the timed path receives after its last step, as DIR/<name>.npy --
+the per-step G / D losses of the timed region (float64, as the trainer collects them) and every
+parameter of the model (float32, state_dict names); the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
+
+--full adds everything else the benchmark measures: the K-step region repeated `--reps` times (default
+5; `ms_per_step` / `value` are then the MEDIAN repetition, all of them in config.reps_ms_per_step), a
+512-step steady region and a sustained window behind it, the per-kernel roofline and clock probe, the
+drop-in trainer and README-override legs, at N=1 BASELINE.json configs 3/4/5 (WGAN-GP bs=256, VAE
+bs=512, NSGAN/LSGAN bs=1024) each with its dominant GEMM's roofline fraction, at N>1 the N=1 figure and
+the batch-1024 data-parallel series, and the CPU-oracle baselines.  Prints ONE JSON line on rank 0.
 """
 import argparse
 import contextlib
@@ -489,9 +498,10 @@ SUSTAINED_MAX_STEPS = 120000      # room in the schedule / loss buffers for the 
 
 
 def bench_gan(variant, B_global, W, K, reps, dev, world=1, rank=0, use_graph=True, force_dp=False,
-              lrs=(2e-4, 2e-4), D_steps=1, solo=False, long_steps=0, sustained_s=0.0):
+              lrs=(2e-4, 2e-4), D_steps=1, solo=False, long_steps=0, sustained_s=0.0, dump_dir=None):
     """W warm-up + reps x K timed iterations of the fused engine.  Returns (engine, [seconds]).
-    solo: a 1-rank engine timed on this rank alone inside a multi-rank job (no barrier / max)."""
+    solo: a 1-rank engine timed on this rank alone inside a multi-rank job (no barrier / max).
+    dump_dir: write the outputs of the timed iterations there (dump_outputs) before anything else runs."""
     import importlib
     from generative_models_amd import engine as gm_engine
     mod, cls = {"ns": ("ns_gan", "NSGAN"), "ls": ("ls_gan", "LSGAN"), "wgp": ("w_gp_gan", "WGPGAN"),
@@ -514,6 +524,8 @@ def bench_gan(variant, B_global, W, K, reps, dev, world=1, rank=0, use_graph=Tru
         eng.run(K, it_start=W + r * K)
         marks.append(time.perf_counter())
     secs = timed_reps(rep, reps, K, 1 if solo else world, dev)
+    if dump_dir is not None:
+        dump_outputs(eng, dump_dir, W, W + reps * K, rank)
     if eng._trace:                                   # GM_TRACE_RUN=1: host timeline of each repetition
         for r in range(reps):
             t0, t1 = marks[2 * r], marks[2 * r + 1]
@@ -540,6 +552,28 @@ def bench_gan(variant, B_global, W, K, reps, dev, world=1, rank=0, use_graph=Tru
     G, D = eng.losses(W, W + reps * K + long_steps + n_sus)
     assert np.isfinite(G).all() and np.isfinite(D).all(), "non-finite losses"
     return eng, secs
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir, it0, it1, rank):
+    """What a caller of the timed path receives after iteration it1 - 1: the G / D losses of iterations [it0, it1)
+    (float64, the trainer's Glosses / Dlosses) and the model's parameters (float32, one file per state_dict entry),
+    as out_dir/<name>.npy on rank 0.  eng.losses is a collective at N > 1: every rank calls this."""
+    G, D = eng.losses(it0, it1)
+    if rank != 0:
+        return
+    arrays = {"G_loss": np.asarray(G, dtype=np.float64), "D_loss": np.asarray(D, dtype=np.float64)}
+    for k, v in eng.model.state_dict().items():
+        arrays[k] = v.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs exceed %d" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("wrote %d outputs (%d bytes) to %s" % (len(arrays), total, out_dir))
 
 
 def bench_vae(B, dev, with_eval, warm_epochs=1, epochs=5, n_val=10000):
@@ -650,6 +684,44 @@ def pmc_traffic(kernel, tag):
         return sum((v["read_bytes"] + v["write_bytes"]) * v["dispatches"] for v in rows) / nd, "profiles/" + src
     except Exception:                                # noqa: BLE001
         return None, None
+
+
+def headline_roofline(eng, img_s_per_gpu):
+    """--full: the headline step's roofline entry -- every GEMM launch shape of the engine's step timed in isolation,
+    the dominant kernel against the FP32-MFMA peak, the effective shader clock, and the whole step against the peaks."""
+    kt = time_kernels_isolated(B_PER_GPU, fused_head=eng.fuse_head, batch_gen=eng._batch_gen(),
+                               group_head=eng.group_head, fold_head=eng._fold_head(),
+                               ride_gather=eng._gather_rides(),
+                               pair_dw=eng.pair_dw, fused_adam=eng._adam_in_epilogue("G"),
+                               ride_head_dx=eng.ride_head_dx)
+    mhz, cyc_per_mfma = clock_probe()
+    log('clock probe: %.0f MHz effective, %.1f cycles per dependent v_mfma_f32_32x32x2_f32' % (mhz, cyc_per_mfma))
+    dom = max(kt, key=lambda k: kt[k][0])
+    t_us, flop, n = kt[dom]
+    # HBM/fabric bytes per launch of that kernel from the COMMITTED PMC pass (profiles/: FETCH_SIZE
+    # x2 gfx950 correction + WRITE_SIZE per dispatch; PMC counters cannot be read from inside this
+    # process) -- the source file is named next to the number
+    traffic, traffic_src = pmc_traffic(dom, "nsgan_b256")
+    achieved = flop / (t_us * 1e-6) / 1e12
+    roof = {"bound": "mfma", "kernel": dom, "achieved": achieved,
+            "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
+            "frac": achieved / PEAK_FP32_MFMA_TFLOPS, "traffic": traffic,
+            "traffic_source": traffic_src,
+            "shader_clock_mhz": round(mhz),
+            "mfma_busy_frac": mfma_busy_frac(dom, t_us / n, mhz),
+            # fabric / HBM-side bytes of the committed PMC pass over this run's launch duration
+            "hbm_gbps": (traffic / (t_us / n * 1e-6) / 1e9) if traffic else None,
+            "hbm_frac_of_8tbs": (traffic / (t_us / n * 1e-6) / 8.0e12) if traffic else None,
+            "launches_per_step": n, "avg_launch_us": t_us / n,
+            "per_kernel_us_per_step": {k: round(v[0], 2) for k, v in kt.items()},
+            # the WHOLE step against the same peak (6 326 400 FLOP per image), and its compulsory HBM bytes
+            # (SURVEY.md 8d: 82 944 B per image at B = 256) against 8 TB/s: nowhere near the HBM roof
+            "step_frac": img_s_per_gpu * FLOP_PER_IMAGE / (PEAK_FP32_MFMA_TFLOPS * 1e12),
+            "step_hbm_frac": img_s_per_gpu * BYTES_PER_IMAGE_B256 / 8.0e12}
+    # the committed rocprofv3 average of the same kernel beside the live figure: a profile that no longer
+    # describes the built kernels shows here, not in a reviewer's diff
+    roof.update(profile_check(dom, t_us / n, "nsgan_b256"))
+    return roof
 
 
 def other_configs(dev, steps, warmup, reps, cpu=True, only=None):
@@ -977,12 +1049,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the K-step timed region (median reported)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the configs 3/4/5 section")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the K-step timed region (median reported); default 1, with --full 5")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other measurement and check (steady and sustained regions, roofline, "
+                    "trainer legs, configs 3/4/5 or the data-parallel series, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed (losses of the timed steps, parameters after the last "
+                    "one) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the configs 3/4/5 section")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--sustained", type=float, default=6.0,
-                    help="seconds of ONE uninterrupted window of the headline step behind the timed regions (0: skip)")
+                    help="--full: seconds of ONE uninterrupted window of the headline step behind the timed regions "
+                    "(0: skip)")
     ap.add_argument("--general-path", action="store_true", help="run only the README-override leg and print its entry")
     ap.add_argument("--only", default=None, help="profiling: run ONE of the extra configs (wgp_b256, ns_b1024, "
                     "ls_b1024, dra_b256, info_b256, be_b256, vae_b512) and print its entry instead of the contract line")
@@ -1017,7 +1097,10 @@ def main():
         ranks_seen = dist.get_world_size()
 
     dev = torch.device("cuda", local_rank)
-    W, K, reps = args.warmup, args.steps, max(1, args.reps)
+    full = args.full
+    W, K = args.warmup, args.steps
+    # a plain run times ONE K-step region; --full and the --only profiling runs repeat it
+    reps = max(1, args.reps if args.reps is not None else (5 if (full or args.only) else 1))
     if args.general_path:
         print(json.dumps(bench_general_path()))
         return
@@ -1026,14 +1109,14 @@ def main():
         return
     B_global = B_PER_GPU * world
     eng, secs = bench_gan("ns", B_global, W, K, reps, dev, world=world, rank=rank,
-                          use_graph=not args.no_graph, force_dp=force_dp, long_steps=512,
-                          sustained_s=(args.sustained if world == 1 else 0.0))
+                          use_graph=not args.no_graph, force_dp=force_dp, long_steps=512 if full else 0,
+                          sustained_s=(args.sustained if (full and world == 1) else 0.0), dump_dir=args.dump_outputs)
     dt = float(np.median(secs))
     log('timed regions done: %s' % ["%.4f" % x for x in secs])
     ranks_info = dp_identity(eng, world) if (world > 1 or force_dp) else None          # (collective: every rank)
     img_s = K * B_global / dt
     n1_img_s, series = None, None
-    if world > 1:
+    if world > 1 and full:
         # N = 1 figure of THIS run (rank 0 alone, same K / W / reps), then the batch-1024 series
         if rank == 0:
             e1, s1 = bench_gan("ns", B_PER_GPU, W, K, reps, dev, world=1, rank=0,
@@ -1045,20 +1128,6 @@ def main():
             series = dp_series(dev, world, rank, ranks_seen, max(K, 100), max(W, 10), min(reps, 3))
 
     if rank == 0:
-        kt = time_kernels_isolated(B_PER_GPU, fused_head=eng.fuse_head, batch_gen=eng._batch_gen(),
-                                   group_head=eng.group_head, fold_head=eng._fold_head(),
-                                   ride_gather=eng._gather_rides(),
-                                   pair_dw=eng.pair_dw, fused_adam=eng._adam_in_epilogue("G"),
-                                   ride_head_dx=eng.ride_head_dx)
-        mhz, cyc_per_mfma = clock_probe()
-        log('clock probe: %.0f MHz effective, %.1f cycles per dependent v_mfma_f32_32x32x2_f32' % (mhz, cyc_per_mfma))
-        dom = max(kt, key=lambda k: kt[k][0])
-        t_us, flop, n = kt[dom]
-        # HBM/fabric bytes per launch of that kernel from the COMMITTED PMC pass (profiles/: FETCH_SIZE
-        # x2 gfx950 correction + WRITE_SIZE per dispatch; PMC counters cannot be read from inside this
-        # process) -- the source file is named next to the number
-        traffic, traffic_src = pmc_traffic(dom, "nsgan_b256")
-        achieved = flop / (t_us * 1e-6) / 1e12
         line = {
             "metric": "images/sec (28x28 MNIST) per D+G step, NSGAN bs=256",
             "value": img_s, "unit": "images/sec", "n_gpus": world, "steps": K, "warmup": W,
@@ -1078,7 +1147,8 @@ def main():
                        "parallelism": "dp%d" % world, "ranks_seen": ranks_seen,
                        "gradient_exchange": comm_mode_of(eng),
                        "ranks": ranks_info,
-                       "timing": "median of %d repetitions of the %d-step timed region" % (reps, K),
+                       "timing": ("median of %d repetitions of the %d-step timed region" % (reps, K)) if reps > 1
+                       else "one %d-step timed region" % K,
                        # a short timed region is COLD-START-INCLUSIVE: every repetition starts with no draws ahead of it
                        # (the host's first two iterations of draws, two graph hand-offs and the final synchronisation
                        # sit inside it: run_fixed_cost_us); the steady step is steady_us_per_step
@@ -1102,32 +1172,16 @@ def main():
             "steady_us_per_step": eng.steady_us_per_step,
             "run_fixed_cost_us": (dt * 1e6 - K * eng.steady_us_per_step) if (eng.steady_us_per_step and K <= 200) else None,
             "step_mfma_frac": img_s / world * FLOP_PER_IMAGE / (PEAK_FP32_MFMA_TFLOPS * 1e12),
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": achieved,
-                         "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / PEAK_FP32_MFMA_TFLOPS, "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "shader_clock_mhz": round(mhz),
-                         "mfma_busy_frac": mfma_busy_frac(dom, t_us / n, mhz),
-                         # fabric / HBM-side bytes of the committed PMC pass over this run's launch duration
-                         "hbm_gbps": (traffic / (t_us / n * 1e-6) / 1e9) if traffic else None,
-                         "hbm_frac_of_8tbs": (traffic / (t_us / n * 1e-6) / 8.0e12) if traffic else None,
-                         "launches_per_step": n, "avg_launch_us": t_us / n,
-                         "per_kernel_us_per_step": {k: round(v[0], 2) for k, v in kt.items()},
-                         # the WHOLE step against the same peak (6 326 400 FLOP per image), and its compulsory HBM bytes
-                         # (82 944 B per image at B = 256) against 8 TB/s: nowhere near the HBM roof
-                         "step_frac": img_s / world * FLOP_PER_IMAGE / (PEAK_FP32_MFMA_TFLOPS * 1e12),
-                         "step_hbm_frac": img_s / world * BYTES_PER_IMAGE_B256 / 8.0e12},
         }
-        # the committed rocprofv3 average of the same kernel beside the live figure: a profile that no longer
-        # describes the built kernels shows here, not in a reviewer's diff
-        line["roofline"].update(profile_check(dom, t_us / n, "nsgan_b256"))
+        if full:
+            line["roofline"] = headline_roofline(eng, img_s / world)
         del eng
-        if world > 1:
+        if world > 1 and full:
             line["config"]["n1_img_s_same_run"] = n1_img_s
             line["config"]["efficiency_vs_n1_same_run"] = img_s / (world * n1_img_s) if n1_img_s else None
             if series is not None:
                 line["dp_series"] = series
-        if world == 1 and not force_dp:
+        if world == 1 and not force_dp and full:
             if not args.no_configs:
                 # INSIDE `config`: the driver's record keeps the contract keys + config / roofline / cpu_baseline
                 line["config"]["trainer"] = bench_trainer()

@@ -1743,15 +1743,15 @@ def test_vae_hidden_wider_than_the_fused_backward(hidden):
 
 
 def test_bench_contract_line_end_to_end():
-    """`python bench.py` with the driver's flags (short: no CPU legs, no configs section) runs through and prints the
-    contract's JSON line last on stdout, with the roofline object -- the one command of the repo that no other test
-    executes, and the one the round is judged by (round 4: an engine clean-up removed an attribute only bench.py read)."""
+    """`python bench.py --full` (short: no CPU legs, no configs section) runs through and prints the contract's JSON
+    line last on stdout, with the roofline object -- the one command of the repo that no other test executes, and the
+    one the round is judged by (round 4: an engine clean-up removed an attribute only bench.py read)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--reps", "2", "--no-cpu-baseline", "--no-configs", "--sustained", "0"],
+                        "--full", "--reps", "2", "--no-cpu-baseline", "--no-configs", "--sustained", "0"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().split("\n")[-1])
@@ -1765,3 +1765,35 @@ def test_bench_contract_line_end_to_end():
     # the evidence lives inside the objects the driver's record keeps (config / roofline), not in extra top-level keys
     assert 0.02 < rf["step_frac"] < rf["frac"] and "profile_kernel_us" in rf and isinstance(rf["stale_profile"], bool)
     assert line["config"]["steady_us_per_step"] > 10 and line["config"]["run_fixed_cost_us"] is not None
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_outputs(tmp_path):
+    """A plain `python bench.py` times exactly --steps steps in one region, reports ms_per_step, runs none of the --full
+    legs, and with --dump-outputs writes what the timed path computed: the timed steps' losses and the parameters after
+    the last one.  Two runs with the same arguments draw the same inputs and dump the same outputs."""
+    import subprocess
+    root = os.path.dirname(HERE)
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "24", "--warmup",
+                            "5", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().split("\n")[-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line, k
+        assert line["steps"] == 24 and line["warmup"] == 5 and len(line["config"]["reps_ms_per_step"]) == 1
+        assert abs(line["value"] - 256 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+        assert "roofline" not in line and "cpu_baseline" not in line and "other_configs" not in line["config"]
+        assert line["config"]["steady_us_per_step"] is None and line["config"]["sustained_window"] is None
+        out = {os.path.basename(p)[:-4]: np.load(p) for p in glob.glob(os.path.join(str(d), "*.npy"))}
+        assert out["G_loss"].shape == out["D_loss"].shape == (24,) and out["G_loss"].dtype == np.float64
+        import ns_gan
+        ref = ns_gan.NSGAN(image_size=784, hidden_dim=400, z_dim=20).state_dict()
+        assert sorted(out) == sorted(list(ref) + ["G_loss", "D_loss"])
+        for k, v in ref.items():
+            assert out[k].shape == tuple(v.shape) and out[k].dtype == np.float32, k
+        assert all(np.isfinite(a).all() for a in out.values())
+        dumps.append(out)
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k], err_msg=k)

@@ -253,6 +253,9 @@ _SIGNATURES = {
     "gm_event_sync": (c_int, [_P]),
     "gm_event_elapsed_ms": (c_int, [_P, _P, POINTER(c_float)]),
     "gm_event_destroy": (c_int, [_P]),
+    "gm_parzen_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "gm_parzen_ll": (c_int, [_P, _P, c_int64, c_int, _P, c_int64, c_int, c_int, _P, c_int, _P, c_int64, _P,
+                             c_int64]),
 }
 
 _lib = None

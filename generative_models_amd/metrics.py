@@ -1,0 +1,82 @@
+"""Gaussian Parzen-window log-likelihood: the MNIST number of the GAN paper the reference's GAN headers link
+(arXiv 1406.2661, table 1; ns_gan.py:1-5), for comparing trained generators by a distribution-level score.
+
+For query rows x, generator samples s_1..s_N and bandwidth sigma (d = row length):
+
+    ll_sigma(x) = logsumexp_i(-|x - s_i|^2 / (2 sigma^2)) - log N - d log(sigma sqrt(2 pi))
+
+The values come from one fused HIP kernel (gm_parzen_ll, csrc/gm_eval.hip); there is no CPU fallback.
+parzen_evaluate picks sigma on validation rows (argmax of the mean, ties to the smaller sigma) and reports the mean
+over the test rows with its standard error std / sqrt(n_test) (population std, as numpy's default).
+Under data parallelism every rank computes the same value locally: nothing here communicates."""
+import collections
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import GMError
+
+MAX_SIGMAS = 16
+
+ParzenResult = collections.namedtuple("ParzenResult", "sigma ll_mean ll_stderr val_means")
+
+
+def default_sigmas():
+    """numpy.logspace(-1, 0, 10): the sigma grid of the evaluation."""
+    return np.logspace(-1, 0, 10)
+
+
+def workspace_bytes(nq, ns, n_sigma):
+    """Bytes of device workspace gm_parzen_ll needs (include/gm_hip.h gives the formula)."""
+    n = _lib.load().gm_parzen_workspace_bytes(int(nq), int(ns), int(n_sigma))
+    if n < 0:
+        _lib.check(int(n), "gm_parzen_workspace_bytes")
+    return int(n)
+
+
+def _rows(x, what):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+        raise GMError("parzen: %s must be a float32 tensor on the MI355X (got %s); there is no CPU fallback"
+                      % (what, x.device if isinstance(x, torch.Tensor) else type(x).__name__))
+    x = x.reshape(x.shape[0], -1)
+    return x if x.stride(1) == 1 else x.contiguous()
+
+
+def parzen_log_likelihood(samples, data, sigmas):
+    """ll[k, j] = ll_{sigmas[k]}(data[j]) under the Parzen window of `samples` -> float32 [len(sigmas), n_data]."""
+    s, q = _rows(samples, "samples"), _rows(data, "data")
+    if s.shape[1] != q.shape[1]:
+        raise GMError("parzen: samples have %d values per row, data %d" % (s.shape[1], q.shape[1]))
+    sig = torch.as_tensor(np.asarray(sigmas, dtype=np.float32).reshape(-1)).to(q.device)
+    ns, nq, d, k = s.shape[0], q.shape[0], q.shape[1], sig.numel()
+    if not 1 <= k <= MAX_SIGMAS:
+        raise GMError("parzen: 1 to %d bandwidths per call, got %d" % (MAX_SIGMAS, k))
+    if not bool(torch.all(sig > 0)):
+        raise GMError("parzen: every sigma must be > 0")
+    with torch.cuda.device(q.device):
+        ws = torch.empty(workspace_bytes(nq, ns, k), dtype=torch.uint8, device=q.device)
+        out = torch.empty(k, nq, dtype=torch.float32, device=q.device)
+        _lib.call("gm_parzen_ll", torch.cuda.current_stream().cuda_stream, q.data_ptr(), q.stride(0), nq,
+                  s.data_ptr(), s.stride(0), ns, d, sig.data_ptr(), k, ws.data_ptr(), ws.numel(), out.data_ptr(),
+                  out.stride(0))
+    return out
+
+
+def select_sigma(sigmas, val_means):
+    """Index of the sigma with the largest validation mean; ties go to the smaller sigma."""
+    sigmas, val_means = np.asarray(sigmas, dtype=np.float64), np.asarray(val_means, dtype=np.float64)
+    if not np.all(np.isfinite(val_means)):
+        raise GMError("parzen: non-finite validation mean %s" % val_means)
+    best = np.flatnonzero(val_means == val_means.max())
+    return int(best[np.argmin(sigmas[best])])
+
+
+def parzen_evaluate(samples, val, test, sigmas=None):
+    """sigma* = argmax over `sigmas` of the mean validation ll; mean and standard error of ll_sigma* on `test`."""
+    sig = default_sigmas() if sigmas is None else np.asarray(sigmas, dtype=np.float64).reshape(-1)
+    val_means = parzen_log_likelihood(samples, val, sig).double().mean(1).cpu().numpy()
+    k = select_sigma(sig, val_means)
+    ll = parzen_log_likelihood(samples, test, sig[k:k + 1])[0].double()
+    return ParzenResult(float(sig[k]), float(ll.mean()), float(ll.std(unbiased=False)) / np.sqrt(ll.numel()),
+                        val_means)

@@ -209,6 +209,34 @@ class FlatAdam(torch.optim.Optimizer):
                 p.data.copy_(self.flat[o:o + p.numel()].view(p.shape))
 
 
+def _dataset_rows(loader, n=None):
+    """The first n rows (all when n is None) of a loader's dataset, flattened: its images, not its batches."""
+    ds = loader.dataset
+    x = ds.tensors[0] if hasattr(ds, "tensors") else \
+        torch.stack([ds[i][0] for i in range(len(ds) if n is None else min(n, len(ds)))])
+    if n is not None:
+        x = x[:n]
+    return x.reshape(x.shape[0], -1)
+
+
+def _parzen(trainer, n_samples, sigmas, n_val, seed):
+    """metrics.parzen_evaluate of trainer.sample(n_samples, seed) against the val_iter / test_iter images."""
+    from . import metrics
+    samples = trainer.sample(n_samples, seed)
+    dev = samples.device
+    val = _dataset_rows(trainer.val_iter, n_val).to(dev, torch.float32).contiguous()
+    test = _dataset_rows(trainer.test_iter).to(dev, torch.float32).contiguous()
+    return metrics.parzen_evaluate(samples, val, test, sigmas)
+
+
+def _decode_rows(net, z, batch=1024):
+    """net(z) in batches, after every launch already queued (the engines' last Adam step included: the parameters
+    are views of their flat buffers) -- no autograd, no mode change, no RNG use."""
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        return torch.cat([net(to_cuda(z[i:i + batch])) for i in range(0, z.shape[0], batch)])
+
+
 class GANTrainer:
     """ns_gan.py:77-226 and siblings.  Subclasses set `variant` and the train() signature."""
     variant = "ns"
@@ -515,6 +543,21 @@ class GANTrainer:
 
     # ---- visualisation (ns_gan.py:166-170, 228-281) ---------------------
     viz_dir = None          # default: ../viz/<name>/ like the reference (scripts run from src/)
+
+    def _sample_noise(self, n, gen):
+        """compute_noise's draw (ns_gan.py:218-220) from a private CPU generator."""
+        return torch.randn(n, self.model.z_dim, generator=gen)
+
+    def sample(self, n, seed=0):
+        """n generator samples [n, image_size] (ns_gan.py:228-235 without the plot): noise from
+        torch.Generator().manual_seed(seed), never the global generator; the model's mode is left as it is."""
+        gen = torch.Generator().manual_seed(int(seed))
+        return _decode_rows(self.model.G, self._sample_noise(int(n), gen))
+
+    def parzen(self, n_samples=10000, sigmas=None, n_val=10000, seed=0):
+        """Parzen-window log-likelihood of the test images under n_samples generator samples, sigma chosen on the
+        first n_val validation images (metrics.parzen_evaluate) -> metrics.ParzenResult."""
+        return _parzen(self, n_samples, sigmas, n_val, seed)
 
     def _viz_epoch(self, epoch):
         if self.viz:
@@ -883,6 +926,17 @@ class VAETrainer:
         if self.viz:
             self.sample_images(epoch)               # vae.py:190: one randn(36, z_dim) from the global generator
 
+    def sample(self, n, seed=0):
+        """n decoded samples [n, image_size]: z ~ N(0, I) from torch.Generator().manual_seed(seed) through
+        model.decoder (vae.py:254-261 without the plot); the global generator and the model's mode are untouched."""
+        gen = torch.Generator().manual_seed(int(seed))
+        return _decode_rows(self.model.decoder, torch.randn(int(n), self.model.z_dim, generator=gen))
+
+    def parzen(self, n_samples=10000, sigmas=None, n_val=10000, seed=0):
+        """Parzen-window log-likelihood of the test images under n_samples decoded prior samples, sigma chosen on
+        the first n_val validation images (metrics.parzen_evaluate) -> metrics.ParzenResult."""
+        return _parzen(self, n_samples, sigmas, n_val, seed)
+
     def sample_images(self, epoch=-100, num_images=36, save=True):
         from . import viz
         return viz.vae_sample_images(self, epoch, num_images, save, self.viz_dir)
@@ -1190,6 +1244,12 @@ class AutoencoderTrainer(VAETrainer):
         self.num_epochs = 0
         self._engine = None
         self.use_graph = True
+
+    def sample(self, n, seed=0):
+        raise GMError("an Autoencoder has no prior to sample: sample() / parzen() need a VAE or a GAN")
+
+    def parzen(self, n_samples=10000, sigmas=None, n_val=10000, seed=0):
+        raise GMError("an Autoencoder has no prior to sample: sample() / parzen() need a VAE or a GAN")
 
     def compute_batch(self, batch):
         """ae.py:147-160 (general path: autograd over the fused linear kernels)."""
@@ -1502,6 +1562,14 @@ class InfoGANTrainerBase(GANTrainer):
     def _noise(self, images):
         m = self.model
         return self.compute_noise(images.shape[0], m.z_dim, m.disc_dim, m.cont_dim)
+
+    def _sample_noise(self, n, gen):
+        """compute_noise's layout (info_gan.py:306-325): [z | one-hot code | continuous code], same draw order."""
+        m = self.model
+        z = torch.randn(n, m.z_dim, generator=gen)
+        disc_c = torch.zeros((n, m.disc_dim))
+        disc_c[range(n), torch.randint(0, m.disc_dim, (n,), dtype=torch.long, generator=gen)] = 1
+        return torch.cat((z, disc_c, torch.randn(n, m.cont_dim, generator=gen)), dim=1)
 
     def generate_images(self, epoch, num_outputs=36, save=True, c=None):
         """info_gan.py:333-365: c fixes the categorical code of every sample (latent exploration)."""

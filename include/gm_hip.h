@@ -653,6 +653,24 @@ int gm_host_replay_threads(int n_threads);
 int gm_numpy_legacy_normal_f32(uint32_t* key, int32_t* pos, int32_t* has_gauss, double* gauss, double loc,
                                double scale, int64_t n, float* out, int n_threads);
 
+/* ---- Gaussian Parzen-window log-likelihood (csrc/gm_eval.hip): the MNIST evaluation of the GAN paper that
+ * ns_gan.py:1-5 / mm_gan.py:1-5 link (arXiv 1406.2661, table 1).  The reference has no evaluation of its own: its
+ * runs end in loss curves and sample grids (ns_gan.py:228-281).  For query rows x (q [nq, d], ld ldq), sample rows
+ * s_i (s [ns, d], ld lds) and each of the n_sigma bandwidths in `sigmas` (device fp32, each > 0):
+ *     out[k, j] = logsumexp_i(-|x_j - s_i|^2 / (2 sigma_k^2)) - log ns - d log(sigma_k sqrt(2 pi))
+ * fp32 in and out (out [n_sigma, nq], ld ldo), fp64 row norms and chunk combination.  The sample axis is cut into
+ * fixed chunks of GM_PARZEN_CHUNK rows whose partial (max, sum) pairs go to `workspace` (caller-owned device memory,
+ * 8-byte aligned, at least gm_parzen_workspace_bytes(nq, ns, n_sigma) =
+ *     8 * n_sigma * nq * ceil(ns / GM_PARZEN_CHUNK) + 4 * (nq + ns)  bytes).
+ * Bitwise deterministic, and a query's row does not depend on which other queries are in the call.
+ * metrics.parzen_log_likelihood (Python) is the call site; trainers' parzen() selects sigma on the validation rows.
+ * gm_parzen_workspace_bytes returns GM_EINVAL for nq, ns < 1 or n_sigma outside [1, GM_PARZEN_MAX_SIGMAS]. */
+#define GM_PARZEN_CHUNK 128
+#define GM_PARZEN_MAX_SIGMAS 16
+int64_t gm_parzen_workspace_bytes(int nq, int ns, int n_sigma);
+int gm_parzen_ll(void* stream, const float* q, int64_t ldq, int nq, const float* s, int64_t lds, int ns, int d,
+                 const float* sigmas, int n_sigma, void* workspace, int64_t ws_bytes, float* out, int64_t ldo);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

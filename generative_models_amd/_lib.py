@@ -52,6 +52,17 @@ class HeadFoldArgs(ctypes.Structure):
                 ("pen", c_void_p), ("S", c_void_p), ("dS", c_void_p), ("rowloss", c_void_p)]
 
 
+class LabelSrc(ctypes.Structure):
+    """gm_label_src (include/gm_hip.h): row m's class is labels[idx ? idx_row[m] : m] (int32 labels, int64 idx)."""
+    _fields_ = [("labels", c_void_p), ("idx", c_void_p), ("idx_slot", Slot)]
+
+
+class LabelGradArgs(ctypes.Structure):
+    """gm_label_grad_args (include/gm_hip.h): one conditioned layer of gm_label_grad_adam."""
+    _fields_ = [("dPre", c_void_p), ("ld", c_int64), ("N", c_int), ("gE", c_void_p), ("E", c_void_p),
+                ("mE", c_void_p), ("vE", c_void_p)]
+
+
 class DwAdamArgs(ctypes.Structure):
     """gm_dw_adam_args (include/gm_hip.h): gm_linear_bwd_dw_adam's arguments as one block."""
     _fields_ = [("dA", c_void_p), ("lda", c_int64), ("X", c_void_p), ("ldx", c_int64),
@@ -253,6 +264,12 @@ _SIGNATURES = {
     "gm_event_sync": (c_int, [_P]),
     "gm_event_elapsed_ms": (c_int, [_P, _P, POINTER(c_float)]),
     "gm_event_destroy": (c_int, [_P]),
+    "gm_linear_fwd_label": (c_int, [_P, _P, c_int64, _P, _P, _P, c_int, LabelSrc, _P, c_int64, c_int, c_int, c_int,
+                                    c_int]),
+    "gm_vae_reparam_fwd_label": (c_int, [_P, _P, c_int64, _P, Slot, _P, c_int64, _P, c_int, c_int, c_int, _P, _P, _P,
+                                         c_int64, c_int, c_int, _P, c_int, LabelSrc]),
+    "gm_label_grad_adam": (c_int, [_P, POINTER(LabelGradArgs), c_int, LabelSrc, c_int, c_int, _P, Slot,
+                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
     "gm_parzen_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "gm_parzen_ll": (c_int, [_P, _P, c_int64, c_int, _P, c_int64, c_int, c_int, _P, c_int, _P, c_int64, _P,
                              c_int64]),

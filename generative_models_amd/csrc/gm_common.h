@@ -95,6 +95,13 @@ __device__ __forceinline__ float gm_reparam_z(float mu, float e, float lv) {
     return mu + t;
 }
 
+// Class of batch row m (gm_label_src, gm_hip.h), clamped into [0, C): the host validates every dataset, the clamp
+// keeps an index into E inside E whatever reaches the kernel.
+__device__ __forceinline__ int gm_row_label(const gm_label_src& s, int m, int C) {
+    const int64_t r = s.idx ? (s.idx + gm_slot_offset(s.idx_slot))[m] : (int64_t)m;
+    return min(max(s.labels[r], 0), C - 1);
+}
+
 // eps * x + (1 - eps) * g as torch computes it (w_gp_gan.py:197-201): two rounded products and an add.  The pragma is
 // what keeps hipcc (-ffp-contract=fast) from fusing one product into the add wherever this gets inlined; HIP's
 // __fmul_rn / __fadd_rn are plain operators and do not.

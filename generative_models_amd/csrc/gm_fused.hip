@@ -467,13 +467,16 @@ __global__ __launch_bounds__(256) void vae_reparam_wide_kernel(const float* __re
 // ------------------------------------------------------------------------------------------
 typedef float rp_f32x4 __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(256) void vae_reparam_fwd_kernel(const float* __restrict__ ml, int64_t ldml,
-                                                             const float* __restrict__ eps, gm_slot eps_slot,
-                                                             float* __restrict__ z, int64_t ldz,
-                                                             float* __restrict__ kl_part, int B, int Z, int nrp,
-                                                             const float* __restrict__ W, const float* __restrict__ bias,
-                                                             float* __restrict__ H, int64_t ldh, int N, int act,
-                                                             int tiles_n) {
+// LBL (gm_vae_reparam_fwd_label, the class-conditional decoder): E[:, y_m] joins the tile's sum before the bias
+template <bool LBL>
+__device__ __forceinline__ void vae_reparam_fwd_body(const float* __restrict__ ml, int64_t ldml,
+                                                     const float* __restrict__ eps, gm_slot eps_slot,
+                                                     float* __restrict__ z, int64_t ldz,
+                                                     float* __restrict__ kl_part, int B, int Z, int nrp,
+                                                     const float* __restrict__ W, const float* __restrict__ bias,
+                                                     float* __restrict__ H, int64_t ldh, int N, int act,
+                                                     int tiles_n, const float* __restrict__ E, int C,
+                                                     const gm_label_src& lab) {
     __shared__ double sh[4];
     const float* e = eps + gm_slot_offset(eps_slot);
     if ((int)blockIdx.x < nrp) {                             // workgroup-uniform
@@ -526,11 +529,36 @@ __global__ __launch_bounds__(256) void vae_reparam_fwd_kernel(const float* __res
         float v = 0.f;                                       // the 16-wave reduction's order: 0 + chunk 0 + chunk 1
         v += a0[r];
         if (Z > 16) v += a1[r];
+        if constexpr (LBL) v += E[(int64_t)min(n, N - 1) * C + gm_row_label(lab, min(m, B - 1), C)];
         v += bv;
         if (act == GM_ACT_RELU) v = fmaxf(v, 0.f);
         else if (act == GM_ACT_SIGMOID) v = gm_sigmoid(v);
         if (m < B && n < N) H[(int64_t)m * ldh + n] = v;
     }
+}
+
+__global__ __launch_bounds__(256) void vae_reparam_fwd_kernel(const float* __restrict__ ml, int64_t ldml,
+                                                             const float* __restrict__ eps, gm_slot eps_slot,
+                                                             float* __restrict__ z, int64_t ldz,
+                                                             float* __restrict__ kl_part, int B, int Z, int nrp,
+                                                             const float* __restrict__ W, const float* __restrict__ bias,
+                                                             float* __restrict__ H, int64_t ldh, int N, int act,
+                                                             int tiles_n) {
+    vae_reparam_fwd_body<false>(ml, ldml, eps, eps_slot, z, ldz, kl_part, B, Z, nrp, W, bias, H, ldh, N, act, tiles_n,
+                                nullptr, 1, gm_label_src{});
+}
+
+__global__ __launch_bounds__(256) void vae_reparam_fwd_label_kernel(const float* __restrict__ ml, int64_t ldml,
+                                                                   const float* __restrict__ eps, gm_slot eps_slot,
+                                                                   float* __restrict__ z, int64_t ldz,
+                                                                   float* __restrict__ kl_part, int B, int Z, int nrp,
+                                                                   const float* __restrict__ W,
+                                                                   const float* __restrict__ bias,
+                                                                   float* __restrict__ H, int64_t ldh, int N, int act,
+                                                                   int tiles_n, const float* __restrict__ E, int C,
+                                                                   gm_label_src lab) {
+    vae_reparam_fwd_body<true>(ml, ldml, eps, eps_slot, z, ldz, kl_part, B, Z, nrp, W, bias, H, ldh, N, act, tiles_n,
+                               E, C, lab);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -711,6 +739,23 @@ extern "C" int gm_vae_reparam_fwd(void* stream, const float* ml, int64_t ldml, c
     const int tiles_n = (N + 31) / 32, tiles_m = (B + 31) / 32;
     hipLaunchKernelGGL(vae_reparam_fwd_kernel, dim3(nrp + tiles_m * tiles_n), dim3(256), 0, (hipStream_t)stream, ml,
                        ldml, eps, eps_slot, z, ldz, kl_part, B, Z, nrp, W, bias, H, ldh, N, act, tiles_n);
+    GM_LAUNCH_RET();
+}
+
+extern "C" int gm_vae_reparam_fwd_label(void* stream, const float* ml, int64_t ldml, const float* eps, gm_slot eps_slot,
+                                        float* z, int64_t ldz, float* kl_part, int n_part, int B, int Z, const float* W,
+                                        const float* bias, float* H, int64_t ldh, int N, int act, const float* E, int C,
+                                        gm_label_src lab) {
+    GM_CHECK_ARG(ml && eps && z && kl_part && W && H && E && lab.labels && B > 0 && Z > 0 && N > 0 && C > 0 && C <= 32 &&
+                 ldml >= 2 * Z && ldz >= Z && ldh >= N);
+    GM_CHECK_ARG(Z <= 32 && Z % 4 == 0 && ldml % 4 == 0 && eps_slot.stride % 4 == 0 &&
+                 ((reinterpret_cast<uintptr_t>(ml) | reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(W)) & 15) == 0);
+    GM_CHECK_ARG(act >= GM_ACT_ID && act <= GM_ACT_SIGMOID && (const float*)H != ml && H != z && (const float*)z != ml);
+    const int nrp = (B * Z + 255) / 256;
+    GM_CHECK_ARG(n_part >= nrp);
+    const int tiles_n = (N + 31) / 32, tiles_m = (B + 31) / 32;
+    hipLaunchKernelGGL(vae_reparam_fwd_label_kernel, dim3(nrp + tiles_m * tiles_n), dim3(256), 0, (hipStream_t)stream,
+                       ml, ldml, eps, eps_slot, z, ldz, kl_part, B, Z, nrp, W, bias, H, ldh, N, act, tiles_n, E, C, lab);
     GM_LAUNCH_RET();
 }
 

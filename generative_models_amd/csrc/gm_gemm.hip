@@ -150,6 +150,9 @@ struct GemmP {
     // pk_rows % 32 == 0: a forward tile / a 16-row reduction chunk is packed or fp32 as a whole, and each kind gets its own
     // branch-free loop (selecting per fragment inside one loop made hipcc serialise the loads behind s_waitcnt vmcnt(0)).
     const uint32_t* pk_bits; int pk_wpr; int pk_rows;
+    // fwd, class-conditional layer (gm_linear_fwd_label; read only by the LBL instantiations): v += lb_E[n * lb_C + y_m]
+    // before the bias, y_m = row m's class (gm_row_label)
+    gm_label_src lb; const float* lb_E; int lb_C;
 #ifdef GM_STAMPS
     gm_stamps::Ctx stamp;     // timeline probe build only
 #endif
@@ -230,9 +233,10 @@ __device__ __forceinline__ float fwd_value(const GemmP& p, float v, int n) {
     return v;
 }
 
-template <int MODE>
+template <int MODE, bool LBL = false>
 __device__ __forceinline__ void store_element(const GemmP& p, float v, int m, int n) {
     if (MODE == MODE_FWD) {
+        if constexpr (LBL) v += p.lb_E[(int64_t)n * p.lb_C + gm_row_label(p.lb, m, p.lb_C)];
         v = fwd_value(p, v, n);
         p.C[(int64_t)m * p.ldc + n] = v;
         if (p.ip_out && m < p.ip_rows) {
@@ -368,7 +372,7 @@ __device__ __forceinline__ int red_idx(int w, int row, int col) {
 // Sum the per-wave partial tiles (red[w][32][32]) and apply the epilogue of the mode.
 // ncap: columns >= ncap are not this block's to store (the 16-column last block of a 48-wide tile);
 // rcap: rows of the block that belong to the tile (16 for the last block of a 48-row tile)
-template <int MODE, int WAVES, int ROWS = 32>
+template <int MODE, int WAVES, int ROWS = 32, bool LBL = false>
 __device__ __forceinline__ void reduce_and_store(const GemmP& p, const float* red, int t, int m0,
                                                  int n0, int ncap = 0x7fffffff, int rcap = 32) {
     if (MODE == MODE_FWD && p.hd_part) {                     // kernel-argument uniform
@@ -446,7 +450,7 @@ __device__ __forceinline__ void reduce_and_store(const GemmP& p, const float* re
         for (int ww = 0; ww < WAVES; ++ww) v += red[red_idx(ww, row, col)];
         const int m = m0 + row, n = n0 + col;
         if (m >= p.M || n >= p.N || n >= ncap) continue;
-        store_element<MODE>(p, v, m, n);
+        store_element<MODE, LBL>(p, v, m, n);
     }
 }
 
@@ -1134,7 +1138,7 @@ template <int MODE, bool DMA, int MI, int NI> struct RedSize {
 // formed from h[m][k], sds[m - m0] and w2[k].  sds: the workgroup's LDS copy of dS.
 // TP (with FOLD == 1): the rows' dS come from the two-phase prologue (RaGAN / Fisher critic steps, gm_head.h).
 template <int MODE, bool VEC, int WAVES, int G, bool XV, int MI, int NI, bool OF = false, int FOLD = 0, bool DMA = false,
-          bool TP = false, bool PK = false, bool SL = true>
+          bool TP = false, bool PK = false, bool SL = true, bool LBL = false>
 __device__ __forceinline__ void gemm16_body(const GemmP& p, float* red, int bx, int by,
                                             float* sds = nullptr, const FoldP* fold = nullptr, int gx = 0) {
     static_assert(!TP || (FOLD == 1 && !DMA), "two-phase losses: folded weight gradient, operands through registers");
@@ -1433,7 +1437,7 @@ __device__ __forceinline__ void gemm16_body(const GemmP& p, float* red, int bx, 
             }
             __syncthreads();
             if (bm + bn == 0) GM_STAMP(st_slot, st_tile, 10); // partial tiles of all waves in LDS (first block)
-            reduce_and_store<MODE, WAVES, (MI > 1 ? 32 : 16)>(p, red, t, m0 + 32 * bm, n0 + 32 * bn,
+            reduce_and_store<MODE, WAVES, (MI > 1 ? 32 : 16), LBL>(p, red, t, m0 + 32 * bm, n0 + 32 * bn,
                                                               (2 * bn + 1 < NI) ? 0x7fffffff : n0 + 32 * bn + 16,
                                                               (2 * bm + 1 < MI) ? 32 : 16);
         }
@@ -1446,6 +1450,15 @@ __global__ __launch_bounds__(WAVES * 64) void gemm16_kernel(GemmP p) {
     __shared__ __attribute__((aligned(16))) float red[(WAVES == 16) ? RedSize<MODE, DMA, MI, NI>::value : WAVES * 32 * 32];
     gemm16_body<MODE, VEC, WAVES, G, XV, MI, NI, false, 0, DMA, false, false, SL>(p, red, blockIdx.x, blockIdx.y, nullptr, nullptr,
                                                                                   (int)gridDim.x);
+}
+
+// Class-conditional forward (gm_linear_fwd_label): the plain kernel's body with E[:, y_m] added in the epilogue.  Its own
+// instantiations, so that the label term costs the unconditional launches nothing.
+template <bool VEC, int MI, int NI>
+__global__ __launch_bounds__(1024) void gemm16_fwd_label_kernel(GemmP p) {
+    __shared__ __attribute__((aligned(16))) float red[RedSize<MODE_FWD, false, MI, NI>::value];
+    gemm16_body<MODE_FWD, VEC, 16, 1, false, MI, NI, false, 0, false, false, false, false, true>(p, red, blockIdx.x, blockIdx.y,
+                                                                                                nullptr, nullptr, (int)gridDim.x);
 }
 
 // The weight-gradient GEMM with the critic head's backward workgroups riding in the same grid:
@@ -1981,6 +1994,31 @@ extern "C" int gm_linear_fwd(void* stream, const float* X, int64_t ldx, gm_slot 
     const bool vec = aligned16(X) && aligned16(W) && (ldx % 4 == 0) && (K % 4 == 0) &&
                      (x_slot.stride % 4 == 0);
     return launch<MODE_FWD>((hipStream_t)stream, p, vec);
+}
+
+extern "C" int gm_linear_fwd_label(void* stream, const float* X, int64_t ldx, const float* W, const float* bias,
+                                   const float* E, int C, gm_label_src lab, float* Y, int64_t ldy, int M, int K, int N,
+                                   int act) {
+    GM_CHECK_ARG(X && W && E && lab.labels && Y && M > 0 && K > 0 && N > 0 && C > 0 && C <= 32 && ldx >= K && ldy >= N);
+    GM_CHECK_ARG(act >= GM_ACT_ID && act <= GM_ACT_SIGMOID);
+    GemmP p{};
+    p.A = X; p.B = W; p.C = Y; p.M = M; p.N = N; p.K = K;
+    p.lda = ldx; p.ldb = K; p.ldc = ldy; p.bias = bias; p.epi = act;
+    p.a_slot = no_slot(); p.b_slot = no_slot();
+    p.lb = lab; p.lb_E = E; p.lb_C = C;
+    const bool vec = aligned16(X) && aligned16(W) && (ldx % 4 == 0) && (K % 4 == 0);
+    // every shape through the 16-wave split-reduction kernel (its tile choice): the label term lives in its epilogue only
+    const int tile = pick_tile<MODE_FWD>(p);
+    const dim3 grid((N + 16 * tile_ni(tile) - 1) / (16 * tile_ni(tile)), (M + 16 * tile_mi(tile) - 1) / (16 * tile_mi(tile)));
+    hipStream_t s = (hipStream_t)stream;
+#define GM_LBL(MI_, NI_, D_)                                                                                \
+    do {                                                                                                    \
+        if (vec) hipLaunchKernelGGL((gemm16_fwd_label_kernel<true, MI_, NI_>), grid, dim3(1024), 0, s, p);  \
+        else hipLaunchKernelGGL((gemm16_fwd_label_kernel<false, MI_, NI_>), grid, dim3(1024), 0, s, p);     \
+    } while (0)
+    GM_TILE_SWITCH(tile, false, GM_LBL);
+#undef GM_LBL
+    GM_LAUNCH_RET();
 }
 
 extern "C" int gm_linear_fwd_interp(void* stream, const float* X, int64_t ldx, gm_slot x_slot,

@@ -42,6 +42,66 @@ def linear_fwd(x, W, b, y, act, M=None, x_slot=NO_SLOT, stream=None):
     return y
 
 
+def label_src(labels, idx=None, idx_slot=NO_SLOT):
+    """gm_label_src: row m's class is labels[idx_row[m]] (idx_row: the slot's row of the int64 index ring idx) or
+    labels[m] when idx is None.  labels: int32 device tensor, every value in [0, C) (checked by the caller)."""
+    if not (labels.is_cuda and labels.dtype == torch.int32):
+        raise _lib.GMError("labels must be an int32 device tensor (got %s on %s)" % (labels.dtype, labels.device))
+    if idx is not None and not (idx.is_cuda and idx.dtype == torch.int64):
+        raise _lib.GMError("idx must be an int64 device tensor")
+    src = _lib.LabelSrc(labels.data_ptr(), idx.data_ptr() if idx is not None else None, idx_slot)
+    src.keep = (labels, idx)            # the tensors live as long as the descriptor that points at them
+    return src
+
+
+def _check_labels(lab, M):
+    """The rows a launch reads through a label_src exist: without an index ring, labels[0..M)."""
+    labels, idx = lab.keep
+    if idx is None and labels.numel() < M:
+        raise _lib.GMError("%d labels for %d rows" % (labels.numel(), M))
+
+
+def linear_fwd_label(x, W, b, E, lab, y, act, M=None, stream=None):
+    """y[M,N] = act(x[M,K] @ W[N,K]^T + b + E[:, y_m]) (E: [N, C]; lab: label_src) -- the split form of
+    linear(cat[x, onehot(y)]) with weight [W | E] (cvae.py)."""
+    N, K = W.shape
+    M = x.shape[0] if M is None else M
+    if E.dim() != 2 or E.shape[0] != N or not 1 <= E.shape[1] <= 32 or not E.is_contiguous():
+        raise _lib.GMError("label weight E must be a contiguous [N=%d, C], 1 <= C <= 32, got %s" % (N, tuple(E.shape)))
+    if x.dim() != 2 or x.shape[1] != K or x.shape[0] < M or y.dim() != 2 or y.shape[0] < M or y.shape[1] != N:
+        raise _lib.GMError("linear_fwd_label: x %s / y %s do not fit M=%d, K=%d, N=%d"
+                           % (tuple(x.shape), tuple(y.shape), M, K, N))
+    _check_labels(lab, M)
+    _lib.call("gm_linear_fwd_label", stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x), _chk(W, "W").data_ptr(),
+              b.data_ptr() if b is not None else None, _chk(E, "E").data_ptr(), E.shape[1], lab,
+              _chk(y, "y").data_ptr(), _ld(y), M, K, N, ACT[act] if not isinstance(act, int) else act)
+    return y
+
+
+def label_grad_adam(layers, lab, M, C, adam=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, stream=None):
+    """dE[n, c] = sum_{m: y_m = c} dPre[m, n] for one or two conditioned layers in one launch, in a fixed order.
+    layers: dicts(dPre, gE=None, E=None, mE=None, vE=None); with E given, Adam steps (E, mE, vE) in the same
+    launch with the schedule row of adam = dict(sched, sched_slot)."""
+    arr = (_lib.LabelGradArgs * len(layers))()
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _check_labels(lab, M)
+    for a, d in zip(arr, layers):
+        dp = _chk(d["dPre"], "dPre")
+        if dp.dim() != 2 or dp.shape[0] < M:
+            raise _lib.GMError("dPre must be [>= M=%d, N], got %s" % (M, tuple(dp.shape)))
+        for k in ("gE", "E", "mE", "vE"):          # every [N, C] array the launch reads or writes
+            t = d.get(k)
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()
+                                  or tuple(t.shape) != (dp.shape[1], C)):
+                raise _lib.GMError("%s must be a contiguous float32 device tensor [N=%d, C=%d], got %s"
+                                   % (k, dp.shape[1], C, tuple(t.shape)))
+        a.dPre, a.ld, a.N = dp.data_ptr(), _ld(dp), dp.shape[1]
+        a.gE, a.E, a.mE, a.vE = ptr(d.get("gE")), ptr(d.get("E")), ptr(d.get("mE")), ptr(d.get("vE"))
+    _lib.call("gm_label_grad_adam", stream or stream_ptr(), arr, len(layers), lab, M, C,
+              adam["sched"].data_ptr() if adam else None, adam["sched_slot"] if adam else NO_SLOT,
+              betas[0], betas[1], eps, weight_decay)
+
+
 def linear_fwd_interp(x, W, b, y, act, eps, eps_slot, x_real, x_hat, rows, M=None, x_slot=NO_SLOT,
                       stream=None):
     """linear_fwd + WGAN-GP's x_hat = eps*x_real + (1-eps)*y for the first `rows` output rows
@@ -638,6 +698,45 @@ class _FusedLinear(torch.autograd.Function):
         elif ctx.has_bias and ctx.needs_input_grad[2]:
             gb = dA.sum(0)
         return gx, gW, gb, None
+
+
+class _LabelLinear(torch.autograd.Function):
+    """h = act(x W^T + b + E[:, y]) (the split form of a layer over cat[x, onehot(y)], cvae.py) on the HIP kernels;
+    first-order backward: dX / dW / db through the plain GEMMs, dE through gm_label_grad_adam."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, E, y, act):
+        x = x.contiguous()
+        lab = y.to(device=x.device, dtype=torch.int32).contiguous()
+        out = torch.empty(x.shape[0], W.shape[0], device=x.device)
+        linear_fwd_label(x, W, b, E, label_src(lab), out, act)
+        ctx.act, ctx.has_bias, ctx.C = act, b is not None, E.shape[1]
+        ctx.save_for_backward(x, W, out, lab)
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, W, out, lab = ctx.saved_tensors
+        gy = gy.contiguous()
+        dA = gy if ctx.act in ("id", None) else act_bwd(gy, out, torch.empty_like(gy), ctx.act)
+        gx = gW = gb = gE = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            linear_bwd_dx(dA, W, gx)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gW = torch.empty_like(W)
+            gb = torch.empty(W.shape[0], device=W.device) if ctx.has_bias else None
+            linear_bwd_dw(dA, x, gW, gb)
+        if ctx.needs_input_grad[3]:
+            gE = torch.empty(W.shape[0], ctx.C, device=W.device)
+            label_grad_adam([dict(dPre=dA, gE=gE)], label_src(lab), x.shape[0], ctx.C)
+        return gx, gW, gb, gE, None, None
+
+
+def label_linear(x, weight, bias, label_weight, labels, act):
+    """act(F.linear(x, weight, bias) + label_weight[:, labels].T) on device tensors (autograd through the HIP
+    kernels); labels: integer tensor of classes in [0, label_weight.shape[1])."""
+    return _LabelLinear.apply(x, weight, bias, label_weight, labels, act)
 
 
 def fused_linear(x, weight, bias, act):

@@ -90,6 +90,20 @@ def vae_reparam_fwd(ml, eps, z, kl_part, B, Z, W, bias, H, act, eps_slot=NO_SLOT
     return (B * Z + 255) // 256
 
 
+def vae_reparam_fwd_label(ml, eps, z, kl_part, B, Z, W, bias, H, act, E, lab, eps_slot=NO_SLOT, stream=None):
+    """vae_reparam_fwd whose decoder layer adds E[:, y_m] before the activation (gm_vae_reparam_fwd_label; the
+    class-conditional decoder of cvae.py).  lab: ops.label_src."""
+    from .ops import ACT, _check_labels
+    if E.dim() != 2 or E.shape[0] != W.shape[0] or not 1 <= E.shape[1] <= 32 or not E.is_contiguous():
+        raise _lib.GMError("label weight E must be [N=%d, C] with 1 <= C <= 32, got %s" % (W.shape[0], tuple(E.shape)))
+    _check_labels(lab, B)
+    _lib.call("gm_vae_reparam_fwd_label", stream or stream_ptr(), ml.data_ptr(), _ld(ml), eps.data_ptr(), eps_slot,
+              z.data_ptr(), _ld(z), kl_part.data_ptr(), kl_part.numel(), B, Z, W.data_ptr(),
+              bias.data_ptr() if bias is not None else None, H.data_ptr(), _ld(H), W.shape[0], ACT[act],
+              E.data_ptr(), E.shape[1], lab)
+    return (B * Z + 255) // 256
+
+
 def sum_finalize2(pa, na, out_a, slot_a, pb, nb, out_b, slot_b, scale_a=1.0, scale_b=1.0, tick=None, stream=None):
     """Two fixed-order fp64 sums in one launch; tick: device step counter to advance (last launch of a step)."""
     _lib.call("gm_sum_finalize2_tick", stream or stream_ptr(), pa.data_ptr(), na, scale_a, out_a.data_ptr(),

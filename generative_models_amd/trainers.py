@@ -820,7 +820,8 @@ class VAETrainer:
                 and not it.sampler.replacement and it.num_workers == 0 and not it.drop_last
                 and it.batch_size is not None)
 
-    def _stock(self):
+    def _hooks_stock(self):
+        """True iff none of _hook_names is overridden: each resolves to a class shipped by this package."""
         cls = type(self)
         for name in self._hook_names:
             if name in self.__dict__:
@@ -830,6 +831,11 @@ class VAETrainer:
                     if not base.__dict__.get("_gm_stock_class", False):
                         return False
                     break
+        return True
+
+    def _stock(self):
+        if not self._hooks_stock():
+            return False
         m = self.model
         enc, dec = getattr(m, "encoder", None), getattr(m, "decoder", None)
         n_enc = 3 if isinstance(enc, Encoder) else 1       # VAE: linear, mu, log_var; AE: one layer
@@ -861,14 +867,13 @@ class VAETrainer:
         if self._stock():
             if not torch.cuda.is_available():
                 raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            from .engine import VAEEngine
             dev = next(self.model.parameters()).device
             if self._engine is None:
                 from . import dp
                 world, rank, group = dp.current()
-                self._engine = VAEEngine(self.model, dev, use_graph=self.use_graph, world_size=world,
-                                         rank=rank, process_group=group,
-                                         force_dp=getattr(self, "force_dp", False))
+                self._engine = self._engine_class()(self.model, dev, use_graph=self.use_graph, world_size=world,
+                                                    rank=rank, process_group=group,
+                                                    force_dp=getattr(self, "force_dp", False))
             eng = self._engine
             eng.use_graph = self.use_graph
             B = self.train_iter.batch_size
@@ -905,6 +910,10 @@ class VAETrainer:
             self.model.eval()
             val_loss = self.evaluate(self.val_iter)
             self._end_epoch(epoch, num_epochs, recon, kl, val_loss, deepcopy, quiet)
+
+    def _engine_class(self):
+        from .engine import VAEEngine
+        return VAEEngine
 
     def _end_epoch(self, epoch, num_epochs, recon, kl, val_loss, deepcopy, quiet):
         self.kl_loss.extend(kl)

@@ -312,9 +312,13 @@ class VAEEngine:
         return {"m": self.fp.m.detach().cpu().clone(), "v": self.fp.v.detach().cpu().clone(),
                 "step": self.step0 + self.steps_planned, "config": dict(self.run_config)}
 
+    def _data_key(self):
+        """What a captured graph reads besides its own buffers: the pass's dataset."""
+        return self.data.data_ptr()
+
     def _graph(self, b, train, k=1):
         """hipGraph of k consecutive batches of size b (the device counter advances per batch)."""
-        key = (b, train, self.data.data_ptr(), k)
+        key = (b, train, self._data_key(), k)
         if key not in self.graphs:
             torch.cuda.synchronize()
             # full batches: every power-of-two size at once (an epoch's chunking asks for different
@@ -328,7 +332,7 @@ class VAEEngine:
                 if k not in sizes:
                     sizes.append(k)
             for n in sizes:
-                kk = (b, train, self.data.data_ptr(), n)
+                kk = (b, train, self._data_key(), n)
                 if kk not in self.graphs:
                     self.graphs[kk] = ops.Graph().capture(
                         lambda st, n=n: [self._issue(st, 0, b, train, pos=i, of=n) for i in range(n)])
@@ -572,3 +576,146 @@ class BIRVAEEngine(VAEEngine):
         # reconstruction sum and 1000 * MMD in the step's last launch, which also carries the tick
         of_.sum_finalize2(part, n_part, recon_out, loss_slot, self.partm, b, mmd_out, loss_slot,
                           scale_b=self.LAMBDA, tick=self.ctr if self.use_graph else None, stream=st)
+
+
+def validate_labels(labels, num_classes, error=GMError):
+    """Host check of a dataset's classes, once per dataset and before any launch that reads them: integral values in
+    [0, num_classes), else `error`.  Returns them as an int32 CPU tensor.  (The kernels index the label weights with
+    these.)"""
+    y = torch.as_tensor(labels).reshape(-1)
+    if y.is_floating_point():
+        if not bool(torch.isfinite(y).all()) or not bool((y == torch.round(y)).all()):
+            raise error("class labels must be integers")
+    elif y.dtype == torch.bool or y.is_complex():
+        raise error("class labels must be integers (got %s)" % y.dtype)
+    if y.numel() and (int(y.min()) < 0 or int(y.max()) >= num_classes):
+        raise error("class labels must lie in [0, %d): found %d .. %d" % (num_classes, int(y.min()), int(y.max())))
+    return y.to(torch.int32)
+
+
+class CVAEEngine(VAEEngine):
+    """The class-conditional VAE (cvae.py) on the VAE engine's batch: the encoder's and the decoder's first layers take
+    E[:, y_m] in their forward epilogues (gm_linear_fwd_label, gm_vae_reparam_fwd_label), row m's class read through
+    the batch's row of the index ring -- no gather of its own -- and one more launch (gm_label_grad_adam) forms both
+    label weights' gradients by class and steps them with Adam.  9 launches per batch (the VAE's 8 + that one).
+    One GPU only; the fused form of the VAE batch only (configure() refuses the toggles that would turn off fused
+    Adam / paired weight gradients); the decoder's and the middle launches fall back to the VAE's generic forms
+    outside their limits (Z > 32 or Z % 4 != 0, hidden width > 512)."""
+
+    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None,
+                 force_dp=False):
+        if world_size > 1 or force_dp:
+            raise GMError("the CVAE engine runs on one GPU: data parallelism is not implemented for it")
+        self.model, self.device, self.use_graph = model, device, use_graph
+        enc, dec = model.encoder, model.decoder
+        self.C = enc.label.weight.shape[1]
+        if not 1 <= self.C <= 32:
+            raise GMError("the CVAE engine supports 1 <= num_classes <= 32 (got %d)" % self.C)
+        # each label weight is [its layer's width, C]: the kernels index E[n * C + c] for every output column n
+        for lab, lin in ((enc.label, enc.linear), (dec.label, dec.linear)):
+            if tuple(lab.weight.shape) != (lin.weight.shape[0], self.C):
+                raise GMError("a label layer's weight must be [%d, %d] (its linear layer's width x num_classes), got %s"
+                              % (lin.weight.shape[0], self.C, tuple(lab.weight.shape)))
+        plist = [enc.linear.weight, enc.linear.bias,
+                 (enc.mu.weight, enc.log_var.weight), (enc.mu.bias, enc.log_var.bias),
+                 dec.linear.weight, dec.linear.bias, dec.recon.weight, dec.recon.bias,
+                 enc.label.weight, dec.label.weight]
+        self._dp_init(plist, 1, 0, None, False)
+        self.fp = FlatParams(plist, device)
+        fp = self.fp
+        self.E1, self.D1, self.D2 = _Linear(fp, enc.linear), _Linear(fp, dec.linear), _Linear(fp, dec.recon)
+        Z, H = enc.mu.weight.shape
+        self.Z, self.H, self.I = Z, H, enc.linear.weight.shape[1]
+        i_w = [i for i, p in enumerate(fp.params) if p is enc.mu.weight][0]
+        i_b = [i for i, p in enumerate(fp.params) if p is enc.mu.bias][0]
+        o_w, o_b = fp.offsets[i_w], fp.offsets[i_b]
+
+        class _Packed:          # [mu ; log_var] as one 2Z x H layer
+            W = fp.flat[o_w:o_w + 2 * Z * H].view(2 * Z, H)
+            b = fp.flat[o_b:o_b + 2 * Z]
+            gW = fp.grad[o_w:o_w + 2 * Z * H].view(2 * Z, H)
+            gb = fp.grad[o_b:o_b + 2 * Z]
+            mW, vW = fp.m[o_w:o_w + 2 * Z * H], fp.v[o_w:o_w + 2 * Z * H]
+            mb, vb = fp.m[o_b:o_b + 2 * Z], fp.v[o_b:o_b + 2 * Z]
+        self.ML = _Packed
+
+        def label_views(p):     # (E, m, v) of a label weight [H, C]
+            i = [k for k, q in enumerate(fp.params) if q is p][0]
+            o = fp.offsets[i]
+            return dict(E=fp.views[i], gE=fp.gviews[i], mE=fp.m[o:o + p.numel()].view(p.shape),
+                        vE=fp.v[o:o + p.numel()].view(p.shape))
+        self.LE, self.LD = label_views(enc.label.weight), label_views(dec.label.weight)
+        self.labels = None
+        self._common_init(device)
+
+    def _data_key(self):
+        return self.data.data_ptr(), self.labels.data_ptr()       # the graphs read the labels too
+
+    def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
+        off = [f for f in ("fuse_adam", "pair_dw", "fin_in_dw", "fuse_reparam_bwd") if not getattr(self, f)]
+        if off:
+            raise GMError("the CVAE engine runs the fused VAE batch only (Adam in the weight-gradient epilogues, paired "
+                          "weight gradients); these cannot be turned off for it: %s" % ", ".join(off))
+        super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
+
+    def run_pass(self, data, perm, train, t0):
+        """data: (images, labels) -- the labels an int32 device tensor that validate_labels has passed."""
+        images, self.labels = data
+        if self.labels.dtype != torch.int32 or self.labels.numel() != images.shape[0]:
+            raise GMError("CVAE labels: one validated int32 class per image")
+        return super().run_pass(images, perm, train, t0)
+
+    def _issue(self, st, t, b, train, pos=0, of=1):
+        """One batch of size b: CVAE.forward + losses (+ backward + Adam when train); VAEEngine._issue with the label
+        terms."""
+        from . import ops_fused as of_
+        of = max(1, of)
+        R, B, Z = self.R, self.B, self.Z
+        E1, ML, D1, D2 = self.E1, self.ML, self.D1, self.D2
+        idx_slot = self._slot(t, 1, 0, R, B)
+        eps_slot = self._slot(t, 1, 0, R, B * Z)
+        loss_slot = self._slot(t, 1, 0, 0, 1)
+        recon_out, kl_out = (self.recon, self.kl) if train else (self.vrecon, self.vkl)
+        idx = self.idx_ring.view(-1)
+        lab = ops.label_src(self.labels, idx, idx_slot)         # y_m = labels[idx_ring[slot][m]]
+        X, own, nxt = self._gather_plan(pos, of)
+        if own:
+            ops.gather_rows(self.data, idx, X, B=b, idx_slot=idx_slot, stream=st)
+        ops.linear_fwd_label(X, E1.W, E1.b, self.LE["E"], lab, self.He, "relu", M=b, stream=st)
+        self._fwd_with_prefetch(st, t, 0, b, self.He, ML, self.ml, "id", nxt)
+        eps_base = self.eps_ring.view(-1)
+        if self.fuse_reparam_fwd and Z <= 32 and Z % 4 == 0:
+            n_kl = of_.vae_reparam_fwd_label(self.ml, eps_base, self.Zs, self.part_kl, b, Z, D1.W, D1.b, self.Hdec,
+                                             "relu", self.LD["E"], lab, eps_slot=eps_slot, stream=st)
+        else:
+            n_kl = of_.vae_reparam_wide(self.ml, eps_base, self.Zs, self.part_kl, b, Z, eps_slot=eps_slot, stream=st)
+            ops.linear_fwd_label(self.Zs, D1.W, D1.b, self.LD["E"], lab, self.Hdec, "relu", M=b, stream=st)
+        part, n_part = self._recon_fwd(st, self.Hdec, D2, X, b)
+        if not train:
+            of_.sum_finalize2(part, n_part, recon_out, loss_slot, self.part_kl, n_kl, kl_out, loss_slot,
+                              tick=self.ctr if self.use_graph else None, stream=st)
+            return
+        adam = dict(sched=self.sched, sched_slot=self._slot(t, 1, 0, 0, 1))
+        ops.linear_bwd_dx(self.dA, D2.W, self.dHdec, below=self.Hdec, epi="relu", M=b, stream=st)
+        mid = (self.fuse_bwd_mid and Z <= 32 and self.H % 4 == 0 and self.H <= 512 and D1.W.shape[0] == self.H
+               and ML.W.shape[1] == self.H)
+        if mid:
+            of_.vae_bwd_mid(self.dHdec, D1.W, self.ml, eps_base, self.dml, ML.W, self.He, self.dHe, b,
+                            eps_slot=eps_slot, stream=st)
+        else:
+            ops.linear_bwd_dx_reparam(self.dHdec, D1.W, self.dZ, self.ml, eps_base, self.dml, M=b,
+                                      eps_slot=eps_slot, stream=st)
+        ops.linear_bwd_dw_adam_pair(dict(dA=self.dA, X=self.Hdec, lin=D2, adam=adam, M=b),
+                                    dict(dA=self.dHdec, X=self.Zs, lin=D1, adam=adam, M=b),
+                                    weight_decay=self.wd, stream=st)
+        if not mid:
+            ops.linear_bwd_dx(self.dml, ML.W, self.dHe, below=self.He, epi="relu", M=b, stream=st)
+        # both label weights: gradient by class (d loss / d pre-activation of the two conditioned layers) + Adam
+        # (the gradients also land in the flat gradient buffer, like every other layer's)
+        ops.label_grad_adam([dict(dPre=self.dHe, **self.LE), dict(dPre=self.dHdec, **self.LD)], lab, b, self.C,
+                            adam=adam, weight_decay=self.wd, stream=st)
+        ops.linear_bwd_dw_adam_pair_finalize(
+            dict(dA=self.dHe, X=X, lin=E1, adam=adam, M=b), dict(dA=self.dml, X=self.He, lin=ML, adam=adam, M=b),
+            dict(pa=part, na=n_part, out_a=recon_out, slot_a=loss_slot, pb=self.part_kl, nb=n_kl, out_b=kl_out,
+                 slot_b=loss_slot, done=self.fin_done, tick=self.ctr if self.use_graph else None),
+            weight_decay=self.wd, stream=st)

@@ -671,6 +671,45 @@ int64_t gm_parzen_workspace_bytes(int nq, int ns, int n_sigma);
 int gm_parzen_ll(void* stream, const float* q, int64_t ldq, int nq, const float* s, int64_t lds, int ns, int d,
                  const float* sigmas, int n_sigma, void* workspace, int64_t ws_bytes, float* out, int64_t ldo);
 
+/* ---- class-conditional VAE (NEW: the reference's README lists "Models: CVAE" as to-do, README.md:95;
+ * generative_models_amd/src/cvae.py).  A conditioned layer computes linear(cat[x, onehot(y)]) in its split form
+ * x W^T + b + E[:, y], E = label.weight [N, C] (nn.Linear(C, N, bias=False)): the one-hot input is one column of E
+ * per row, added where the bias is added.  Row m's class is  y_m = labels[idx ? idx_row[m] : m]  with
+ * idx_row = idx + idx_slot's offset: the batch's row of the index ring its images were gathered through (int64),
+ * labels the dataset's classes (int32).  Every label must lie in [0, C): the engine validates a dataset on the host
+ * before its first launch; the kernels clamp the class they index E with all the same. */
+typedef struct gm_label_src {
+    const int32_t* labels;
+    const int64_t* idx;       /* NULL: row m reads labels[m] */
+    gm_slot idx_slot;
+} gm_label_src;
+/* Y = act(X W^T + b + E[:, y_m]), 1 <= C <= 32: the first layers of CVAE Encoder.forward / Decoder.forward
+ * (cvae.py), called from vae_engine.CVAEEngine._issue (encoder; decoder when Z > 32 or Z % 4 != 0) and from
+ * ops._LabelLinear (the autograd path). */
+int gm_linear_fwd_label(void* stream, const float* X, int64_t ldx, const float* W, const float* bias,
+                        const float* E, int C, gm_label_src lab, float* Y, int64_t ldy, int M, int K, int N,
+                        int act);
+/* gm_vae_reparam_fwd whose decoder-layer workgroups add E[:, y_m] before the activation: CVAE.forward's
+ * reparameterisation + Decoder.linear/label (cvae.py), called from vae_engine.CVAEEngine._issue. */
+int gm_vae_reparam_fwd_label(void* stream, const float* ml, int64_t ldml, const float* eps, gm_slot eps_slot,
+                             float* z, int64_t ldz, float* kl_part, int n_part, int B, int Z, const float* W,
+                             const float* bias, float* H, int64_t ldh, int N, int act, const float* E, int C,
+                             gm_label_src lab);
+/* Label-weight gradient of up to two conditioned layers in ONE launch: dE[n, c] = sum over rows m with y_m = c of
+ * dPre[m, n] (dPre: d loss / d pre-activation, [M, N]), added in ascending m and combined in a fixed order -- no
+ * atomics, the same bits on every run; a class absent from the batch gets exactly 0.  gE != NULL: the gradient is
+ * written there [N, C].  E != NULL: Adam (torch's, weight decay folded into the gradient) steps (E, mE, vE) with the
+ * schedule row sched[2 * slot .. +1] in the same launch.  Called from vae_engine.CVAEEngine._issue (both layers +
+ * Adam) and ops._LabelLinear.backward (gradient only). */
+typedef struct gm_label_grad_args {
+    const float* dPre; int64_t ld; int N;
+    float* gE;
+    float* E; float* mE; float* vE;
+} gm_label_grad_args;
+int gm_label_grad_adam(void* stream, const gm_label_grad_args* layers, int n_layers, gm_label_src lab, int M, int C,
+                       const float* sched, gm_slot sched_slot, double beta1, double beta2, double eps,
+                       double weight_decay);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

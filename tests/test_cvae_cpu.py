@@ -1,0 +1,152 @@
+"""Class-conditional VAE without a GPU: module layout, the split form against the concatenated one, label checks,
+fast-path selection and the C-ABI of the new kernels."""
+import os
+import sys
+
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "generative_models_amd", "src"))
+
+import cvae  # noqa: E402
+from generative_models_amd import _lib  # noqa: E402
+from generative_models_amd._lib import GMError  # noqa: E402
+
+NEW = ("gm_linear_fwd_label", "gm_vae_reparam_fwd_label", "gm_label_grad_adam")
+
+
+def _loaders(n=40, C=3, batch=8):
+    x = torch.bernoulli(torch.full((n, 1, 4, 4), 0.5))
+    ds = torch.utils.data.TensorDataset(x, torch.arange(n) % C)
+    dl = lambda: torch.utils.data.DataLoader(ds, batch_size=batch, shuffle=True)
+    return dl(), dl(), dl()
+
+
+def test_module_names_and_state_dict_keys():
+    m = cvae.CVAE(image_size=16, hidden_dim=12, z_dim=4, num_classes=3)
+    assert list(m.state_dict()) == [
+        "encoder.linear.weight", "encoder.linear.bias", "encoder.label.weight", "encoder.mu.weight",
+        "encoder.mu.bias", "encoder.log_var.weight", "encoder.log_var.bias", "decoder.linear.weight",
+        "decoder.linear.bias", "decoder.label.weight", "decoder.recon.weight", "decoder.recon.bias"]
+    assert m.encoder.label.bias is None and m.decoder.label.bias is None
+    assert m.encoder.label.weight.shape == (12, 3) and m.decoder.label.weight.shape == (12, 3)
+    assert (m.image_size, m.hidden_dim, m.z_dim, m.num_classes, m.shape) == (16, 12, 4, 3, 4)
+    d = cvae.CVAE()
+    assert (d.image_size, d.hidden_dim, d.z_dim, d.num_classes) == (784, 400, 20, 10)
+
+
+@pytest.mark.parametrize("C", [1, 3, 10, 17])
+def test_split_form_equals_concatenated_form_fp64(C):
+    torch.manual_seed(C)
+    m = cvae.CVAE(image_size=30, hidden_dim=20, z_dim=6, num_classes=C).double()
+    x, y = torch.randn(9, 30, dtype=torch.float64), torch.randint(0, C, (9,))
+    oh = F.one_hot(y, C).double()
+    for first, label, inp in ((m.encoder.linear, m.encoder.label, x),
+                              (m.decoder.linear, m.decoder.label, torch.randn(9, 6, dtype=torch.float64))):
+        split = first(inp) + label(oh)
+        cat = nn.Linear(inp.shape[1] + C, first.out_features).double()
+        with torch.no_grad():
+            cat.weight.copy_(torch.cat([first.weight, label.weight], 1))
+            cat.bias.copy_(first.bias)
+        ref = cat(torch.cat([inp, oh], 1))
+        assert torch.allclose(split, ref, rtol=1e-12, atol=1e-12)
+        # ... and the column-of-E form the kernels compute
+        assert torch.allclose(split, first(inp) + label.weight[:, y].T, rtol=1e-12, atol=1e-12)
+
+
+def test_sample_label_validation():
+    tr = object.__new__(cvae.CVAETrainer)          # the checks run before anything touches the model or a GPU
+    tr.model = cvae.CVAE(16, 8, 4, 3)
+    for bad in ([0, 1, 3], [0, -1, 2], [0.5, 1, 2], 3, -1, [True, False, True], [0, 1], 1.5, "a", True):
+        with pytest.raises(ValueError):                # the documented contract (also a GMError)
+            tr.sample(3, labels=bad)
+    from generative_models_amd.cvae import _labels_arg
+    y = _labels_arg(None, 7, 3)
+    assert y.tolist() == [0, 1, 2, 0, 1, 2, 0]
+    assert _labels_arg(2, 3, 3).tolist() == [2, 2, 2]
+    assert _labels_arg([2.0, 0.0], 2, 3).tolist() == [2, 0]
+
+
+def test_dataset_label_validation():
+    from generative_models_amd.engine import validate_labels
+    assert validate_labels(torch.tensor([0, 2, 1]), 3).dtype == torch.int32
+    for bad in (torch.tensor([0, 3]), torch.tensor([-1, 0]), torch.tensor([0.5]), torch.tensor([float("nan")]),
+                torch.tensor([True])):
+        with pytest.raises(GMError):
+            validate_labels(bad, 3)
+
+
+def test_stock_selection():
+    its = _loaders()
+    tr = object.__new__(cvae.CVAETrainer)
+    tr.model, tr.train_iter, tr.val_iter, tr.test_iter = cvae.CVAE(16, 8, 4, 3), *its
+    assert tr._stock()
+
+    class Mine(cvae.CVAETrainer):
+        def compute_batch(self, batch):
+            return super().compute_batch(batch)
+    tr2 = object.__new__(Mine)
+    tr2.model, tr2.train_iter, tr2.val_iter, tr2.test_iter = cvae.CVAE(16, 8, 4, 3), *its
+    assert not tr2._stock()
+    tr.model.decoder.extra = nn.Linear(2, 2)        # an edited network
+    assert not tr._stock()
+
+
+def test_new_symbols_declared_bound_and_reject_bad_arguments():
+    declared = _lib.declared_symbols()
+    for s in NEW:
+        assert s in declared and s in _lib._SIGNATURES
+    if not os.path.isfile(_lib.LIB_PATH):
+        pytest.skip("libgm_hip.so not built")
+    lib = _lib.load()
+    for s in NEW:
+        assert hasattr(lib, s)
+    src = _lib.LabelSrc(None, None, _lib.NO_SLOT)
+    p = 16                                             # a non-null placeholder; never dereferenced on these paths
+    okl = _lib.LabelSrc(p, None, _lib.NO_SLOT)
+    E = _lib.GM_EINVAL
+    # null pointers, non-positive sizes, C out of [1, 32]
+    assert lib.gm_linear_fwd_label(None, p, 4, p, p, p, 3, src, p, 4, 2, 4, 4, 1) == E
+    assert lib.gm_linear_fwd_label(None, None, 4, p, p, p, 3, okl, p, 4, 2, 4, 4, 1) == E
+    assert lib.gm_linear_fwd_label(None, p, 4, p, p, None, 3, okl, p, 4, 2, 4, 4, 1) == E
+    for M, K, N, C in ((0, 4, 4, 3), (2, 0, 4, 3), (2, 4, 0, 3), (2, 4, 4, 0), (2, 4, 4, 33)):
+        assert lib.gm_linear_fwd_label(None, p, 4, p, p, p, C, okl, p, 4, M, K, N, 1) == E
+    for B, Z, N, C in ((0, 4, 4, 3), (2, 0, 4, 3), (2, 4, 0, 3), (2, 4, 4, 0), (2, 4, 4, 33)):
+        assert lib.gm_vae_reparam_fwd_label(None, p, 8, p, _lib.NO_SLOT, p, 4, p, 4, B, Z, p, p, p, 4, N, 1,
+                                            p, C, okl) == E
+    assert lib.gm_vae_reparam_fwd_label(None, p, 8, p, _lib.NO_SLOT, p, 4, p, 4, 2, 4, p, p, p, 4, 4, 1,
+                                        None, 3, okl) == E
+    args = (_lib.LabelGradArgs * 2)()
+    args[0].dPre, args[0].ld, args[0].N, args[0].gE = p, 4, 4, p
+    args[1] = args[0]
+    assert lib.gm_label_grad_adam(None, None, 1, okl, 2, 3, None, _lib.NO_SLOT, 0.9, 0.999, 1e-8, 0.0) == E
+    assert lib.gm_label_grad_adam(None, args, 3, okl, 2, 3, None, _lib.NO_SLOT, 0.9, 0.999, 1e-8, 0.0) == E
+    assert lib.gm_label_grad_adam(None, args, 1, src, 2, 3, None, _lib.NO_SLOT, 0.9, 0.999, 1e-8, 0.0) == E
+    for M, C in ((0, 3), (2, 0), (2, 33)):
+        assert lib.gm_label_grad_adam(None, args, 2, okl, M, C, None, _lib.NO_SLOT, 0.9, 0.999, 1e-8, 0.0) == E
+    args[0].gE = None                                  # neither a gradient output nor Adam
+    assert lib.gm_label_grad_adam(None, args, 1, okl, 2, 3, None, _lib.NO_SLOT, 0.9, 0.999, 1e-8, 0.0) == E
+    args[0].E, args[0].mE, args[0].vE = p, p, p        # Adam without a schedule
+    assert lib.gm_label_grad_adam(None, args, 1, okl, 2, 3, None, _lib.NO_SLOT, 0.9, 0.999, 1e-8, 0.0) == E
+
+
+def test_label_weight_shape_is_checked_before_anything_runs():
+    from generative_models_amd.engine import CVAEEngine
+    from generative_models_amd import ops
+    m = cvae.CVAE(16, 8, 4, 3)
+    m.decoder.label = nn.Linear(3, 12, bias=False)     # wider than the decoder's first layer (8)
+    with pytest.raises(GMError, match="label layer"):
+        CVAEEngine(m, "cpu")
+    with pytest.raises(GMError, match="label weight"):   # the op refuses an E that does not fit N
+        ops.linear_fwd_label(torch.zeros(2, 16), torch.zeros(8, 16), None, torch.zeros(12, 3), None,
+                             torch.zeros(2, 8), "relu")
+
+
+def test_world_size_above_one_is_refused():
+    from generative_models_amd.engine import CVAEEngine
+    with pytest.raises(GMError):
+        CVAEEngine(cvae.CVAE(16, 8, 4, 3), "cpu", world_size=2)

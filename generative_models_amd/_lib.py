@@ -73,6 +73,27 @@ class DwAdamArgs(ctypes.Structure):
                 ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("clamp", c_float)]
 
 
+class AAECriticArgs(ctypes.Structure):
+    """gm_aae_critic_args (include/gm_hip.h): the adversarial autoencoder's critic step."""
+    _fields_ = [("z_real", c_void_p), ("real_slot", Slot), ("z_fake", c_void_p), ("ld_fake", c_int64),
+                ("B", c_int), ("Z", c_int), ("H", c_int),
+                ("W1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p),
+                ("gW1", c_void_p), ("gb1", c_void_p), ("gw2", c_void_p), ("gb2", c_void_p),
+                ("mW1", c_void_p), ("vW1", c_void_p), ("mb1", c_void_p), ("vb1", c_void_p),
+                ("mw2", c_void_p), ("vw2", c_void_p), ("mb2", c_void_p), ("vb2", c_void_p),
+                ("sched", c_void_p), ("sched_slot", Slot), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("loss_out", c_void_p),
+                ("loss_slot", Slot), ("ws", c_void_p), ("ws_bytes", c_int64)]
+
+
+class AAEGenArgs(ctypes.Structure):
+    """gm_aae_gen_args (include/gm_hip.h): the adversarial autoencoder's generator-phase middle launch."""
+    _fields_ = [("z", c_void_p), ("ldz", c_int64), ("He", c_void_p), ("ldhe", c_int64),
+                ("W1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p), ("Wz", c_void_p),
+                ("dz", c_void_p), ("lddz", c_int64), ("dHe", c_void_p), ("lddhe", c_int64),
+                ("loss_part", c_void_p), ("B", c_int), ("Z", c_int), ("H", c_int)]
+
+
 class Finalize2Args(ctypes.Structure):
     """gm_finalize2_args (include/gm_hip.h): the two loss sums + counter tick that ride in a VAE batch's last launch."""
     _fields_ = [("pa", c_void_p), ("na", c_int), ("scale_a", c_float), ("out_a", c_void_p), ("slot_a", Slot),
@@ -271,6 +292,9 @@ _SIGNATURES = {
     "gm_label_grad_adam": (c_int, [_P, POINTER(LabelGradArgs), c_int, LabelSrc, c_int, c_int, _P, Slot,
                                    ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
     "gm_parzen_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "gm_aae_critic_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "gm_aae_critic_step": (c_int, [_P, POINTER(AAECriticArgs)]),
+    "gm_aae_gen_mid": (c_int, [_P, POINTER(AAEGenArgs)]),
     "gm_parzen_ll": (c_int, [_P, _P, c_int64, c_int, _P, c_int64, c_int, c_int, _P, c_int, _P, c_int64, _P,
                              c_int64]),
 }

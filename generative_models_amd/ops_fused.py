@@ -251,3 +251,63 @@ def dragan_head_bwd(H, T, da2, w2, gw2, gb2, dA1, B, store=False, stream=None):
     _lib.call("gm_dragan_head_bwd_store" if store else "gm_dragan_head_bwd", stream or stream_ptr(), H.data_ptr(), _ld(H), T.data_ptr(), _ld(T),
               da2.data_ptr(), w2.data_ptr(), gw2.data_ptr(), gb2.data_ptr(), dA1.data_ptr(), _ld(dA1),
               B, H.shape[1])
+
+
+def _aae_shape(B, Z, H):
+    if not (B > 0 and 0 < Z <= 32 and Z % 4 == 0 and 0 < H <= 512):
+        raise _lib.GMError("the AAE kernels take 1 <= Z <= 32 with Z %% 4 == 0 and 1 <= H <= 512 (got B=%d, Z=%d, "
+                           "H=%d); other shapes train on the general path" % (B, Z, H))
+
+
+def aae_critic_workspace(B, Z, H, device):
+    """A workspace for aae_critic_step at this shape (float32 device tensor)."""
+    _aae_shape(B, Z, H)
+    n = _lib.load().gm_aae_critic_workspace_bytes(B, Z, H)
+    return torch.zeros((n + 3) // 4, device=device)
+
+
+def aae_critic_step(z_real, z_fake, B, W1, b1, w2, b2, ws, grads=None, adam=None, moments=None, loss_out=None,
+                    real_slot=NO_SLOT, loss_slot=NO_SLOT, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, stream=None):
+    """The AAE's discriminator phase (gm_aae_critic_step): D = (W1 [H, Z], b1, w2 [1, H] or [H], b2) on B prior rows
+    (z_real + real_slot) and B encoder rows z_fake; grads = (gW1, gb1, gw2, gb2) receive the gradient of
+    -mean(log(D(z_real) + 1e-8) + log(1 - D(z_fake) + 1e-8)); with adam = dict(sched, sched_slot) and moments =
+    (mW1, vW1, mb1, vb1, mw2, vw2, mb2, vb2) Adam steps D in the same launches; loss_out[loss_slot] = the loss."""
+    from ._lib import AAECriticArgs
+    H, Z = W1.shape
+    _aae_shape(B, Z, H)
+    if w2.numel() != H or b1.numel() != H or b2.numel() != 1 or z_fake.shape[0] < B or z_fake.shape[1] != Z:
+        raise _lib.GMError("aae_critic_step: D must be [H, Z], [H], [1, H], [1] and z_fake [>= B, Z]")
+    if ws.numel() * 4 < _lib.load().gm_aae_critic_workspace_bytes(B, Z, H):
+        raise _lib.GMError("aae_critic_step: workspace too small (use aae_critic_workspace)")
+    p = lambda t: t.data_ptr() if t is not None else None
+    a = AAECriticArgs()
+    a.z_real, a.real_slot, a.z_fake, a.ld_fake = p(z_real), real_slot, p(z_fake), _ld(z_fake)
+    a.B, a.Z, a.H = B, Z, H
+    a.W1, a.b1, a.w2, a.b2 = p(W1), p(b1), p(w2), p(b2)
+    if grads is not None:
+        a.gW1, a.gb1, a.gw2, a.gb2 = (p(g) for g in grads)
+    if adam is not None:
+        a.mW1, a.vW1, a.mb1, a.vb1, a.mw2, a.vw2, a.mb2, a.vb2 = (p(m) for m in moments)
+        a.sched, a.sched_slot = p(adam["sched"]), adam["sched_slot"]
+    a.beta1, a.beta2, a.eps, a.weight_decay = betas[0], betas[1], eps, weight_decay
+    a.loss_out, a.loss_slot = p(loss_out), loss_slot
+    a.ws, a.ws_bytes = p(ws), ws.numel() * 4
+    import ctypes
+    _lib.call("gm_aae_critic_step", stream or stream_ptr(), ctypes.byref(a))
+
+
+def aae_gen_mid(z, He, W1, b1, w2, b2, Wz, dz, dHe, loss_part, B, stream=None):
+    """The AAE's generator-phase middle launch (gm_aae_gen_mid): D (W1, b1, w2, b2) on the encoder rows z, the row terms
+    -log(D(z) + 1e-8) into loss_part[:B], dz = d G_loss / d z and dHe = (dz Wz) . [He > 0]."""
+    from ._lib import AAEGenArgs
+    H, Z = W1.shape
+    _aae_shape(B, Z, H)
+    if tuple(Wz.shape) != (Z, H) or He.shape[1] != H or z.shape[1] != Z or loss_part.numel() < B:
+        raise _lib.GMError("aae_gen_mid: Wz must be [Z, H], He [B, H], z [B, Z] and loss_part >= B floats")
+    a = AAEGenArgs()
+    a.z, a.ldz, a.He, a.ldhe = z.data_ptr(), _ld(z), He.data_ptr(), _ld(He)
+    a.W1, a.b1, a.w2, a.b2, a.Wz = W1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), Wz.data_ptr()
+    a.dz, a.lddz, a.dHe, a.lddhe = dz.data_ptr(), _ld(dz), dHe.data_ptr(), _ld(dHe)
+    a.loss_part, a.B, a.Z, a.H = loss_part.data_ptr(), B, Z, H
+    import ctypes
+    _lib.call("gm_aae_gen_mid", stream or stream_ptr(), ctypes.byref(a))

@@ -719,3 +719,191 @@ class CVAEEngine(VAEEngine):
             dict(pa=part, na=n_part, out_a=recon_out, slot_a=loss_slot, pb=self.part_kl, nb=n_kl, out_b=kl_out,
                  slot_b=loss_slot, done=self.fin_done, tick=self.ctr if self.use_graph else None),
             weight_decay=self.wd, stream=st)
+
+
+def aae_fused_ok(model):
+    """True iff an AAE's shapes fit the fused kernels (gm_aae.hip): 1 <= Z <= 32 with Z % 4 == 0, hidden width <= 512,
+    the decoder's and the discriminator's hidden widths equal to the encoder's, one discriminator output."""
+    enc, dec, dis = model.encoder, model.decoder, model.discriminator
+    Z, H = enc.z.weight.shape
+    return (0 < Z <= 32 and Z % 4 == 0 and 0 < H <= 512 and tuple(enc.linear.weight.shape)[0] == H
+            and tuple(dec.linear.weight.shape) == (H, Z) and tuple(dis.linear.weight.shape) == (H, Z)
+            and tuple(dis.discriminate.weight.shape) == (1, H) and dec.recon.weight.shape[1] == H)
+
+
+class AAEEngine(VAEEngine):
+    """The adversarial autoencoder (aae.py) on the VAE engine's batch: three phases per batch, in this order.
+      1. reconstruction: the AE's forward and backward on the existing launches, Adam(AE) in the weight-gradient
+         epilogues (gradients: the flat gradient buffer's encoder / decoder segments);
+      2. discriminator: the encoder forward again (its weights just changed), then gm_aae_critic_step on the batch's
+         prior rows (torch.randn(b, Z), host-replayed into the prior ring) and the encoder rows -- D's gradient in the
+         flat gradient buffer's discriminator segment, Adam(D) in the same launches;
+      3. generator: gm_aae_gen_mid with D as phase 2 left it, then the encoder's paired weight gradients with the
+         G optimizer's own moments and schedule (gradients: `gG`), the loss sums and the counter tick.
+    One GPU only; the fused shapes only (aae_fused_ok) -- the trainer takes the general path outside them."""
+
+    has_eps = False
+    fused_ok = staticmethod(aae_fused_ok)
+
+    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False):
+        if world_size > 1 or force_dp:
+            raise GMError("the AAE engine runs on one GPU: data parallelism is not implemented for it")
+        if not aae_fused_ok(model):
+            raise GMError("AAEEngine: shapes outside the fused kernels' limits (Z <= 32, Z % 4 == 0, H <= 512, equal "
+                          "hidden widths); AAETrainer trains these on the general path")
+        self.model, self.device, self.use_graph = model, device, use_graph
+        enc, dec, dis = model.encoder, model.decoder, model.discriminator
+        plist = [enc.linear.weight, enc.linear.bias, enc.z.weight, enc.z.bias,
+                 dec.linear.weight, dec.linear.bias, dec.recon.weight, dec.recon.bias,
+                 dis.linear.weight, dis.linear.bias, dis.discriminate.weight, dis.discriminate.bias]
+        self._dp_init(plist, 1, 0, None, False)
+        self.fp = FlatParams(plist, device)
+        fp = self.fp
+        self.E1, self.EZ = _Linear(fp, enc.linear), _Linear(fp, enc.z)
+        self.D1, self.D2 = _Linear(fp, dec.linear), _Linear(fp, dec.recon)
+        self.C1, self.C2 = _Linear(fp, dis.linear), _Linear(fp, dis.discriminate)
+        self.Z, self.H = enc.z.weight.shape
+        self.I = enc.linear.weight.shape[1]
+        # the generator phase's optimizer: its own moments and its own gradient buffer over the encoder's tensors
+        self.gG, self.mG, self.vG = (torch.zeros(fp.n, device=device) for _ in range(3))
+        self.G1, self.GZ = self._g_linear(enc.linear), self._g_linear(enc.z)
+        self._drawing = True
+        self._common_init(device)
+
+    def _g_linear(self, lin):
+        g = _Linear(self.fp, lin, m=self.mG, v=self.vG)
+        ow = self.fp.offsets[[i for i, p in enumerate(self.fp.params) if p is lin.weight][0]]
+        ob = self.fp.offsets[[i for i, p in enumerate(self.fp.params) if p is lin.bias][0]]
+        g.gW = self.gG[ow:ow + lin.weight.numel()].view(lin.weight.shape)
+        g.gb = self.gG[ob:ob + lin.bias.numel()]
+        return g
+
+    def phase_grads(self):
+        """The three phases' gradients of the last training batch: {"ae": 8 tensors, "d": 4, "g": 4}, keyed by the
+        model's state_dict names (views of the engine's buffers)."""
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        out = {"ae": {}, "d": {}, "g": {}}
+        for p, gv in zip(self.fp.params, self.fp.gviews):
+            n = names[id(p)]
+            out["d" if n.startswith("discriminator.") else "ae"][n] = gv
+        for pre, g in (("encoder.linear.", self.G1), ("encoder.z.", self.GZ)):
+            out["g"][pre + "weight"], out["g"][pre + "bias"] = g.gW, g.gb
+        return out
+
+    def _alloc(self, B):
+        if self._bufB == B:
+            return
+        dev, I, H, Z = self.device, self.I, self.H, self.Z
+        z = lambda *s: torch.zeros(*s, device=dev)
+        self.X, self.He, self.Zs = z(B, I), z(B, H), z(B, Z)
+        self.Xb = (self.X, z(B, I))
+        self.Hdec, self.Xr, self.dA = z(B, H), z(B, I), z(B, I)
+        self.dHdec, self.dZ, self.dHe = z(B, H), z(B, Z), z(B, H)
+        self.part = z(B)
+        self._sq_alloc(B)
+        # regularization phase: the encoder's rows after phase 1, the generator's dz / dHe and its row losses
+        self.He2, self.Zf, self.dZg, self.dHeg, self.gpart = z(B, H), z(B, Z), z(B, Z), z(B, H), z(B)
+        from . import ops_fused as of_
+        self.ws = of_.aae_critic_workspace(B, Z, H, dev)
+        self._bufB = B
+        self.graphs = {}
+
+    def configure(self, B, n_train_steps, lr, weight_decay, D_lr=2e-4, G_lr=2e-4, resume=None):
+        if resume is not None and resume.get("config") is not None and not resume.get("lenient", False):
+            saved = resume["config"]
+            now = {"D_lr": float(D_lr), "G_lr": float(G_lr)}
+            diff = {k: (saved[k], now[k]) for k in now if k in saved and saved[k] != now[k]}
+            if diff:
+                raise GMError("checkpoint was written by a run with different settings (saved, now): %s; "
+                              "load_checkpoint(path, strict=False) overrides" % diff)
+        super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
+        self.run_config.update(D_lr=float(D_lr), G_lr=float(G_lr))
+        self.gG.zero_()
+        self.mG.zero_()
+        self.vG.zero_()
+        if resume is not None:
+            if resume["mG"].numel() != self.mG.numel():
+                raise GMError("checkpoint optimizer state does not match this model")
+            self.mG.copy_(resume["mG"]); self.vG.copy_(resume["vG"])
+        n = max(1, n_train_steps)
+        self.sched_D = GANEngine._pbuf(self, "sched_D", ops.adam_schedule(D_lr, n, start=self.step0 + 1))
+        self.sched_G = GANEngine._pbuf(self, "sched_G", ops.adam_schedule(G_lr, n, start=self.step0 + 1))
+        self.dloss = GANEngine._pbuf(self, "dloss", n)
+        self.gloss = GANEngine._pbuf(self, "gloss", n)
+        if getattr(self, "_prior_B", None) != B or "prior" not in self.stage[0]:
+            self.prior_ring = torch.zeros(self.R, B, self.Z, device=self.device)
+            for s in self.stage:
+                s["prior"] = torch.zeros(self.R, B, self.Z).pin_memory()
+            self._prior_B = B
+            self._moved = True
+        if self._moved:
+            self.graphs = {}
+
+    def optim_state(self):
+        st = super().optim_state()
+        # one Adam step per batch for each of the three optimizers: their step counts are equal
+        st.update(mG=self.mG.detach().cpu().clone(), vG=self.vG.detach().cpu().clone(),
+                  steps={"AE": st["step"], "D": st["step"], "G": st["step"]})
+        return st
+
+    def run_pass(self, data, perm, train, t0):
+        self._drawing = bool(train)                  # validation draws nothing (reconstruction loss only)
+        return super().run_pass(data, perm, train, t0)
+
+    def _draw_chunk(self, s, sizes):
+        if self._drawing:                            # train_D: torch.randn(b, z_dim), the batch's only draw
+            self._torch_normal_rows(s["prior"], sizes)
+
+    def _upload_chunk(self, s, r, cnt):
+        if self._drawing:
+            self.prior_ring[r:r + cnt].copy_(s["prior"][:cnt], non_blocking=True)
+
+    def _issue(self, st, t, b, train, pos=0, of=1):
+        """One batch of size b: reconstruction (+ when training: backward + Adam(AE), the critic step, the generator
+        step)."""
+        from . import ops_fused as of_
+        R, B, Z = self.R, self.B, self.Z
+        E1, EZ, D1, D2, C1, C2 = self.E1, self.EZ, self.D1, self.D2, self.C1, self.C2
+        idx_slot = self._slot(t, 1, 0, R, B)
+        prior_slot = self._slot(t, 1, 0, R, B * Z)
+        loss_slot = self._slot(t, 1, 0, 0, 1)
+        tick = self.ctr if self.use_graph else None
+        X, own, nxt = self._gather_plan(pos, of)
+        if own:
+            ops.gather_rows(self.data, self.idx_ring.view(-1), X, B=b, idx_slot=idx_slot, stream=st)
+        # ---- 1. reconstruction: sum (x - decoder(encoder(x)))^2, Adam(AE)
+        ops.linear_fwd(X, E1.W, E1.b, self.He, "relu", M=b, stream=st)
+        self._fwd_with_prefetch(st, t, 0, b, self.He, EZ, self.Zs, "id", nxt)
+        ops.linear_fwd(self.Zs, D1.W, D1.b, self.Hdec, "relu", M=b, stream=st)
+        part, n_part = self._recon_fwd(st, self.Hdec, D2, X, b)
+        if not train:
+            of_.sum_finalize(part, n_part, self.vrecon, out_slot=loss_slot, tick=tick, stream=st)
+            return
+        sched_slot = self._slot(t, 1, 0, 0, 1)
+        ae = dict(sched=self.sched, sched_slot=sched_slot)
+        pair = lambda a1, a2: ops.linear_bwd_dw_adam_pair(
+            dict(dA=a1[0], X=a1[1], lin=a1[2], adam=ae, M=b), dict(dA=a2[0], X=a2[1], lin=a2[2], adam=ae, M=b),
+            weight_decay=self.wd, stream=st)
+        # every dX reads a layer's weights BEFORE that layer's dW(+Adam) launch updates them
+        ops.linear_bwd_dx(self.dA, D2.W, self.dHdec, below=self.Hdec, epi="relu", M=b, stream=st)
+        ops.linear_bwd_dx(self.dHdec, D1.W, self.dZ, M=b, stream=st)
+        pair((self.dA, self.Hdec, D2), (self.dHdec, self.Zs, D1))
+        ops.linear_bwd_dx(self.dZ, EZ.W, self.dHe, below=self.He, epi="relu", M=b, stream=st)
+        pair((self.dHe, X, E1), (self.dZ, self.He, EZ))
+        # ---- 2. discriminator on z_real (prior ring) and z_fake = encoder(x) with the stepped encoder, Adam(D)
+        ops.linear_fwd(X, E1.W, E1.b, self.He2, "relu", M=b, stream=st)
+        ops.linear_fwd(self.He2, EZ.W, EZ.b, self.Zf, "id", M=b, stream=st)
+        of_.aae_critic_step(self.prior_ring.view(-1), self.Zf, b, C1.W, C1.b, C2.W, C2.b, self.ws,
+                            grads=(C1.gW, C1.gb, C2.gW, C2.gb), adam=dict(sched=self.sched_D, sched_slot=sched_slot),
+                            moments=(C1.mW, C1.vW, C1.mb, C1.vb, C2.mW, C2.vW, C2.mb, C2.vb), loss_out=self.dloss,
+                            real_slot=prior_slot, loss_slot=loss_slot, stream=st)
+        # ---- 3. generator: -mean(log(D(encoder(x)) + 1e-8)) through the stepped D (the encoder is unchanged since 2)
+        of_.aae_gen_mid(self.Zf, self.He2, C1.W, C1.b, C2.W, C2.b, EZ.W, self.dZg, self.dHeg, self.gpart, b, stream=st)
+        gadam = dict(sched=self.sched_G, sched_slot=sched_slot)
+        # the batch's LAST launch: the encoder's weight gradients + Adam(G), both loss sums, the counter tick
+        ops.linear_bwd_dw_adam_pair_finalize(
+            dict(dA=self.dHeg, X=X, lin=self.G1, adam=gadam, M=b), dict(dA=self.dZg, X=self.He2, lin=self.GZ,
+                                                                         adam=gadam, M=b),
+            dict(pa=part, na=n_part, out_a=self.recon, slot_a=loss_slot, pb=self.gpart, nb=b, scale_b=1.0 / b,
+                 out_b=self.gloss, slot_b=loss_slot, done=self.fin_done, tick=tick),
+            weight_decay=0.0, stream=st)

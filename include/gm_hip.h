@@ -710,6 +710,47 @@ int gm_label_grad_adam(void* stream, const gm_label_grad_args* layers, int n_lay
                        const float* sched, gm_slot sched_slot, double beta1, double beta2, double eps,
                        double weight_decay);
 
+/* ---- adversarial autoencoder (NEW: the reference's README lists "adversarial autoencoder" as to-do;
+ * generative_models_amd/aae.py).  The regularization phase of a batch of B rows: the latent critic
+ * D: z (Z) -> relu(W1 z + b1) (H) -> sigmoid(w2 . h + b2) on the B prior rows z_real and the B encoder rows z_fake,
+ * loss -mean(log(D(z_real) + 1e-8) + log(1 - D(z_fake) + 1e-8)), then the encoder's generator loss
+ * -mean(log(D(encoder(x)) + 1e-8)).  Fused limits: 1 <= Z <= 32 with Z % 4 == 0, 1 <= H <= 512; every entry point
+ * returns GM_EINVAL outside them.  No atomics: the same bits on every run. */
+typedef struct gm_aae_critic_args {
+    const float* z_real; gm_slot real_slot;   /* prior rows: z_real + real_slot's offset, B rows of Z floats */
+    const float* z_fake; int64_t ld_fake;     /* the encoder's rows, B of them */
+    int B, Z, H;
+    float* W1; float* b1; float* w2; float* b2;          /* D.linear [H, Z], [H]; D.discriminate [1, H], [1] */
+    float* gW1; float* gb1; float* gw2; float* gb2;      /* gradient outputs (all four, or none with Adam on) */
+    float* mW1; float* vW1; float* mb1; float* vb1;      /* Adam moments (with sched) */
+    float* mw2; float* vw2; float* mb2; float* vb2;
+    const float* sched; gm_slot sched_slot;   /* NULL: gradients only, parameters untouched */
+    double beta1, beta2, eps, weight_decay;
+    float* loss_out; gm_slot loss_slot;       /* the batch's D loss (or NULL) */
+    float* ws; int64_t ws_bytes;              /* workspace of gm_aae_critic_workspace_bytes(B, Z, H) bytes */
+} gm_aae_critic_args;
+/* Bytes of the critic step's workspace, -1 for a shape outside the fused limits. */
+int64_t gm_aae_critic_workspace_bytes(int B, int Z, int H);
+/* The whole discriminator phase (aae.py AAETrainer.train_D) in two launches: per 16-row block the forward, loss
+ * terms and weight-gradient partials; then one thread per parameter element adds the partials in block order,
+ * writes the gradient, steps Adam with the schedule row sched[2 * slot .. +1], and block 0 writes the loss.  Called
+ * from vae_engine.AAEEngine._issue and ops_fused.aae_critic_step. */
+int gm_aae_critic_step(void* stream, const gm_aae_critic_args* a);
+typedef struct gm_aae_gen_args {
+    const float* z; int64_t ldz;              /* the encoder's z rows [B, Z] */
+    const float* He; int64_t ldhe;            /* the encoder's hidden rows [B, H] (after relu) */
+    const float* W1; const float* b1; const float* w2; const float* b2;   /* D after its step */
+    const float* Wz;                          /* encoder.z.weight [Z, H] */
+    float* dz; int64_t lddz;                  /* out: d G_loss / d z [B, Z] */
+    float* dHe; int64_t lddhe;                /* out: d G_loss / d (encoder hidden pre-activation) [B, H] */
+    float* loss_part;                         /* out: B row terms -log(D(z) + 1e-8); G_loss is their sum / B */
+    int B, Z, H;
+} gm_aae_gen_args;
+/* The generator phase's narrow part (aae.py AAETrainer.train_G) as ONE launch, 16 rows per workgroup: s = D(z),
+ * dz = (dlogit w2 . [h > 0]) W1 and dHe = (dz Wz) . [He > 0].  Called from vae_engine.AAEEngine._issue and
+ * ops_fused.aae_gen_mid. */
+int gm_aae_gen_mid(void* stream, const gm_aae_gen_args* a);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

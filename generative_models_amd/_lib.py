@@ -195,6 +195,12 @@ _SIGNATURES = {
                                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, c_float,
                                                      POINTER(HeadBwdArgs), POINTER(HeadFoldArgs), _P, c_int, c_int]),
     "gm_linear_bwd_dw_adam_pair": (c_int, [_P, POINTER(DwAdamArgs), POINTER(DwAdamArgs)]),
+    "gm_linear_bwd_dw_adam_pair_l1": (c_int, [_P, POINTER(DwAdamArgs), POINTER(DwAdamArgs), _P, c_int64, Slot, _P,
+                                              c_int64, c_int]),
+    "gm_linear_bwd_dx_gather": (c_int, [_P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int, c_int, c_int,
+                                        _P, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
+    "gm_linear_bwd_dx_gather_bits": (c_int, [_P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int, c_int,
+                                             c_int, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
     "gm_linear_bwd_dw_adam_pair_finalize": (c_int, [_P, POINTER(DwAdamArgs), POINTER(DwAdamArgs),
                                                     POINTER(Finalize2Args)]),
     "gm_linear_bwd_dw_adam_head": (c_int, [_P, _P, c_int64, _P, c_int64, Slot, _P, _P, c_int, c_int,

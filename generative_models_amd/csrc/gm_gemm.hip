@@ -233,8 +233,9 @@ __device__ __forceinline__ float fwd_value(const GemmP& p, float v, int n) {
     return v;
 }
 
+// kept (weight gradient with Adam only): where the stepped parameter is also copied (LDS of the layer-1 rider below)
 template <int MODE, bool LBL = false>
-__device__ __forceinline__ void store_element(const GemmP& p, float v, int m, int n) {
+__device__ __forceinline__ void store_element(const GemmP& p, float v, int m, int n, float* kept = nullptr) {
     if (MODE == MODE_FWD) {
         if constexpr (LBL) v += p.lb_E[(int64_t)n * p.lb_C + gm_row_label(p.lb, m, p.lb_C)];
         v = fwd_value(p, v, n);
@@ -286,6 +287,7 @@ __device__ __forceinline__ void store_element(const GemmP& p, float v, int m, in
             adam_update(P, v, M, V, step_size, bc2_sqrt, p.adam.omb1, p.adam.b2, p.adam.omb2,
                         p.adam.eps, p.adam.wd, p.adam.clamp);
             *pp = P; *mm = M; *vv = V;
+            if (kept) *kept = P;
         }
     }
 }
@@ -372,9 +374,12 @@ __device__ __forceinline__ int red_idx(int w, int row, int col) {
 // Sum the per-wave partial tiles (red[w][32][32]) and apply the epilogue of the mode.
 // ncap: columns >= ncap are not this block's to store (the 16-column last block of a 48-wide tile);
 // rcap: rows of the block that belong to the tile (16 for the last block of a 48-row tile)
+// kept: row-major copy of the block's stepped parameters, row stride KEEP_LD (weight gradient with Adam; see store_element)
+constexpr int KEEP_LD = 68;
 template <int MODE, int WAVES, int ROWS = 32, bool LBL = false>
 __device__ __forceinline__ void reduce_and_store(const GemmP& p, const float* red, int t, int m0,
-                                                 int n0, int ncap = 0x7fffffff, int rcap = 32) {
+                                                 int n0, int ncap = 0x7fffffff, int rcap = 32,
+                                                 float* kept = nullptr) {
     if (MODE == MODE_FWD && p.hd_part) {                     // kernel-argument uniform
         // Folded critic head: every row of this 32-column block also leaves its partial dot with w2.
         // The 32 lanes that hold a row (one half of a wave) sum their products in a fixed butterfly;
@@ -450,7 +455,7 @@ __device__ __forceinline__ void reduce_and_store(const GemmP& p, const float* re
         for (int ww = 0; ww < WAVES; ++ww) v += red[red_idx(ww, row, col)];
         const int m = m0 + row, n = n0 + col;
         if (m >= p.M || n >= p.N || n >= ncap) continue;
-        store_element<MODE, LBL>(p, v, m, n);
+        store_element<MODE, LBL>(p, v, m, n, kept ? kept + row * KEEP_LD + col : nullptr);
     }
 }
 
@@ -1140,7 +1145,8 @@ template <int MODE, bool DMA, int MI, int NI> struct RedSize {
 template <int MODE, bool VEC, int WAVES, int G, bool XV, int MI, int NI, bool OF = false, int FOLD = 0, bool DMA = false,
           bool TP = false, bool PK = false, bool SL = true, bool LBL = false>
 __device__ __forceinline__ void gemm16_body(const GemmP& p, float* red, int bx, int by,
-                                            float* sds = nullptr, const FoldP* fold = nullptr, int gx = 0) {
+                                            float* sds = nullptr, const FoldP* fold = nullptr, int gx = 0,
+                                            float* kept = nullptr) {
     static_assert(!TP || (FOLD == 1 && !DMA), "two-phase losses: folded weight gradient, operands through registers");
     static_assert(FOLD == 0 || (FOLD == 1 && MODE == MODE_DW && XV) || (FOLD == 2 && MODE == MODE_DX && VEC),
                   "folded head: 16-byte operand paths only");
@@ -1439,7 +1445,8 @@ __device__ __forceinline__ void gemm16_body(const GemmP& p, float* red, int bx, 
             if (bm + bn == 0) GM_STAMP(st_slot, st_tile, 10); // partial tiles of all waves in LDS (first block)
             reduce_and_store<MODE, WAVES, (MI > 1 ? 32 : 16), LBL>(p, red, t, m0 + 32 * bm, n0 + 32 * bn,
                                                               (2 * bn + 1 < NI) ? 0x7fffffff : n0 + 32 * bn + 16,
-                                                              (2 * bm + 1 < MI) ? 32 : 16);
+                                                              (2 * bm + 1 < MI) ? 32 : 16,
+                                                              kept ? kept + 32 * bm * KEEP_LD + 32 * bn : nullptr);
         }
     GM_STAMP(st_slot, st_tile, 12);                           // epilogue stores issued
     GM_STAMP_EDGE(p, true, st_tile, MODE);
@@ -1531,6 +1538,19 @@ __global__ __launch_bounds__(1024) void gemm16_fwd_gather_kernel(GemmP p, Gather
     gemm16_body<MODE_FWD, VEC, 16, G, false, MI, NI>(p, red, blockIdx.x, blockIdx.y - grows);
 }
 
+// The same with an input-gradient GEMM (the generator's dH launch carrying the NEXT iteration's batch gather when the
+// next iteration's first layer rides in the weight-gradient pair: gemm16_dw_pair_l1_kernel).
+template <bool VEC, bool XV, int MI, int NI>
+__global__ __launch_bounds__(1024) void gemm16_dx_gather_kernel(GemmP p, GatherP gp, int grows, int gblocks) {
+    __shared__ __attribute__((aligned(16))) float red[16 * 32 * 32];
+    if ((int)blockIdx.y < grows) {                           // workgroup-uniform
+        const int bid = blockIdx.y * gridDim.x + blockIdx.x;
+        if (bid < gblocks) gather_body(gp, bid);
+        return;
+    }
+    gemm16_body<MODE_DX, VEC, 16, 1, XV, MI, NI, false, 0, false, false, false, false>(p, red, blockIdx.x, blockIdx.y - grows);
+}
+
 // Forward GEMM whose reduction is at most 32 long (the generator's / the VAE decoder's first layer: K = z_dim = 20), round 6.
 // The 16-wave kernels give such a launch 16 waves per 32 x 32 tile of which two have a chunk; the other fourteen resolve
 // their arguments, zero accumulators, write zero partial tiles and sit in the barrier in front of a 16-image sum --
@@ -1541,6 +1561,25 @@ __global__ __launch_bounds__(1024) void gemm16_fwd_gather_kernel(GemmP p, Gather
 // the two partial tiles are added in wave order onto 0.f (reduce_and_store: v = 0; v += image[w], the other fourteen
 // images being zeros); fragments and fix-ups are the same functions.  The batch gather's workgroups ride in rows
 // [0, grows) of the grid as in gemm16_fwd_gather_kernel (4 image rows per workgroup here).
+// The arithmetic of one 16 x 16 output block of such a forward, shared by gemm16_k32_fwd_kernel and the layer-1 rider of
+// the generator's weight-gradient pair (gemm16_dw_pair_l1_kernel): chunk c (k = 16c + 4g + j: MFMA j takes component j
+// of the fixed-up fragments) is a chain of four MFMAs started from 0, and the output is 0 + chunk 0 + chunk 1 (+ bias).
+__device__ __forceinline__ f32x4 k32_chunk(float4 fa, float4 fb) {
+    f32x4 c4 = f32x4{0.f, 0.f, 0.f, 0.f};
+    c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.x, fb.x, c4, 0, 0, 0);
+    c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.y, fb.y, c4, 0, 0, 0);
+    c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.z, fb.z, c4, 0, 0, 0);
+    c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.w, fb.w, c4, 0, 0, 0);
+    return c4;
+}
+__device__ __forceinline__ float k32_sum(float part0, float part1, bool has_bias, float bv) {
+    float x = 0.f;
+    x += part0;
+    x += part1;
+    if (has_bias) x += bv;
+    return x;
+}
+
 template <bool SL, bool GATHER>
 __global__ __launch_bounds__(256) void gemm16_k32_fwd_kernel(GemmP p, GatherP gp, int grows, int gblocks) {
     if constexpr (GATHER) {
@@ -1578,12 +1617,7 @@ __global__ __launch_bounds__(256) void gemm16_k32_fwd_kernel(GemmP p, GatherP gp
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
             const float4 fb = fix_kc(rb[c][ni], n0 + 16 * ni + i16, p.N, kb, p.K);
-            f32x4 c4 = f32x4{0.f, 0.f, 0.f, 0.f};
-            c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.x, fb.x, c4, 0, 0, 0);
-            c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.y, fb.y, c4, 0, 0, 0);
-            c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.z, fb.z, c4, 0, 0, 0);
-            c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.w, fb.w, c4, 0, 0, 0);
-            part[c][ni] = c4;
+            part[c][ni] = k32_chunk(fa, fb);
             if (c == 0 && ni == 0) { GM_STAMP_AFTER(fa.x); GM_STAMP_AFTER(fb.x); GM_STAMP(st_slot, st_tile, 1); }   // first operands in
         }
     }
@@ -1597,13 +1631,7 @@ __global__ __launch_bounds__(256) void gemm16_k32_fwd_kernel(GemmP p, GatherP gp
         const int n = min(n0 + 16 * ni + i16, p.N - 1);
         const float bv = p.bias ? p.bias[n] : 0.f;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float x = 0.f;
-            x += part[0][ni][r];
-            x += part[1][ni][r];
-            if (p.bias) x += bv;
-            v[ni][r] = x;
-        }
+        for (int r = 0; r < 4; ++r) v[ni][r] = k32_sum(part[0][ni][r], part[1][ni][r], p.bias != nullptr, bv);
     }
     if (p.epi == GM_ACT_RELU) {
 #pragma unroll
@@ -1680,6 +1708,77 @@ __global__ __launch_bounds__(1024) void gemm16_dw_pair_fin_kernel(GemmP pa, Gemm
     }
 }
 
+// The generator's weight-gradient pair carrying the NEXT iteration's first layer (H = relu(z W1^T + b1) over the 2B rows
+// of the next noise-ring slot), so that the next iteration needs no launch for it.  The second GEMM (dW1 + Adam on W1, b1)
+// runs on 16-row tiles (MI = 1: every hidden unit h of the tile, every column of [W1 | b1] in one tile; the same
+// per-element arithmetic as the pair's own tile shape -- chunks by wave, 16 images summed in wave order -- so the same
+// bits), and store_element leaves the stepped W1[h, :], b1[h] of the tile's 16 hidden units in LDS.  After one barrier
+// the tile forms H[:, h0 .. h0 + 16) for every row from those values: no other workgroup's data, no re-read of W1.
+// Bit-identical to gemm16_k32_fwd_kernel: the same fragments (z rows clamped + fix_kc, W1 rows fix_kc), the same k32_chunk
+// / k32_sum; the MFMA's operand ROLES are swapped (A = W1 rows, B = z rows: a lane ends up with four consecutive hidden
+// units of one row, stored as one 16-byte store) -- each output is still the same products added in the same k order.
+struct L1RideP {
+    const float* z; int64_t ldz; gm_slot z_slot;   // [rows, K] rows of the next iteration's ring slot
+    float* H; int64_t ldh;                          // [rows, N] output (N = hidden units = pb.M, K = pb.n_real)
+    int rows;
+    int vec;                                        // H 16-byte aligned, ldh % 4 == 0
+};
+
+__device__ __forceinline__ void l1_ride_fwd(const L1RideP& r, const float* kept, int h0, int N, int K) {
+    const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int i16 = lane & 15, g4 = lane >> 4;
+    const float* Z = r.z + gm_slot_offset(r.z_slot);
+    float4 fw[2];                                   // W1 rows h0 + i16, k = 16c + 4g4 + j
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const int kb = 16 * c + 4 * g4;
+        fw[c] = fix_kc(*reinterpret_cast<const float4*>(kept + i16 * KEEP_LD + kb), h0 + i16, N, kb, K);
+    }
+    float bv[4];                                    // b1 of the hidden units this lane's outputs hold: h0 + 4g4 + q
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bv[q] = kept[(4 * g4 + q) * KEEP_LD + K];
+    const int h = h0 + 4 * g4;
+    const int nblk = (r.rows + 15) >> 4;
+    for (int b = w; b < nblk; b += 16) {
+        const int m = 16 * b + i16;
+        float4 rz[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) rz[c] = raw_kc<true>(Z, r.ldz, m, r.rows, 16 * c + 4 * g4, K);
+        f32x4 part[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) part[c] = k32_chunk(fw[c], fix_kc(rz[c], m, r.rows, 16 * c + 4 * g4, K));
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = fmaxf(k32_sum(part[0][q], part[1][q], true, bv[q]), 0.f);
+        if (m < r.rows) {
+            float* hp = r.H + (int64_t)m * r.ldh + h;
+            if (r.vec && h + 3 < N) st4(hp, make_float4(v[0], v[1], v[2], v[3]));
+            else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (h + q < N) hp[q] = v[q];
+            }
+        }
+    }
+}
+
+template <int MI, int NI>
+__global__ __launch_bounds__(1024) void gemm16_dw_pair_l1_kernel(GemmP pa, GemmP pb, int na, int tna, L1RideP r) {
+    __shared__ __attribute__((aligned(16))) float red[RedSize<MODE_DW, false, MI, NI>::value];
+    __shared__ __attribute__((aligned(16))) float kept[16 * KEEP_LD];
+    static_assert(NI <= 4 && 16 * NI <= KEEP_LD, "one 16-row tile of [W1 | b1] in `kept`");
+    const int id = blockIdx.x;
+    if (id < na) {
+        gemm16_body<MODE_DW, false, 16, 1, true, MI, NI, false, 0, false, false, false, false>(pa, red, id % tna, id / tna);
+        return;
+    }
+    const int by = id - na;                         // one column tile: [W1 | b1] has n_real + 1 <= 16 NI columns (host)
+    gemm16_body<MODE_DW, false, 16, 1, true, 1, NI, false, 0, false, false, false, true>(pb, red, 0, by, nullptr, nullptr, 0,
+                                                                                        kept);
+    __syncthreads();                                // the tile's stepped parameters are in `kept`
+    l1_ride_fwd(r, kept, 16 * by, pb.M, pb.n_real);
+}
+
 // May the epilogue move whole float4s (store4)?  Every array it touches 16-byte aligned, leading dimensions in
 // whole float4s.
 template <int MODE>
@@ -1700,10 +1799,11 @@ int vec_epi_ok(const GemmP& p) {
 // Work that rides in (or pairs with) a GEMM launch.
 struct Rider {
     const HeadBwdP* head = nullptr;      // MODE_DW: critic-head backward workgroups
-    const GatherP* gather = nullptr;     // MODE_FWD: batch-gather workgroups
+    const GatherP* gather = nullptr;     // MODE_FWD / MODE_DX: batch-gather workgroups
     const GemmP* pair = nullptr;         // MODE_DW: a second weight-gradient GEMM
     bool pair_xvec = false;
     const gm_fin2* fin = nullptr;        // MODE_DW pair: the VAE batch's two loss sums + counter tick
+    const L1RideP* l1 = nullptr;         // MODE_DW pair: the next iteration's first layer from the second GEMM's W1, b1
 };
 
 // Tile shapes of the 16-wave kernels, as sub-tiles (16 x 16) per wave: MI x NI
@@ -1903,6 +2003,20 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
     }
     if (head)        // this configuration cannot carry the head workgroups: separate launch
         hipLaunchKernelGGL(head_bwd_kernel, dim3(gm_head_bwd_blocks(*head)), dim3(1024), 0, s, *head);
+    if constexpr (MODE == MODE_DX) {
+        if (rider.gather) {
+            const GatherP& gp = *rider.gather;
+            if (vec && xv && (tile == T22 || tile == T12)) {     // the batch gather rides in rows [0, grows) of the grid
+                const int gblocks = gm_gather_blocks(gp, 16);
+                const int grows = (gblocks + (int)grid.x - 1) / (int)grid.x;
+                const dim3 ggrid(grid.x, grid.y + grows);
+                if (tile == T12) hipLaunchKernelGGL((gemm16_dx_gather_kernel<true, true, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
+                else hipLaunchKernelGGL((gemm16_dx_gather_kernel<true, true, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
+                GM_LAUNCH_RET();
+            }
+            hipLaunchKernelGGL(gather_rows_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp);
+        }
+    }
     if constexpr (MODE == MODE_FWD) {
         if (rider.gather) {
             const GatherP& gp = *rider.gather;
@@ -1921,11 +2035,40 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
         if (rider.pair) {
             GemmP pb = *rider.pair;
             pb.vec_epi = vec_epi_ok<MODE_DW>(pb);
-            if (xv && rider.pair_xvec && tile != T12 && pb.K == p.K) {
+            const bool pairable = xv && rider.pair_xvec && tile != T12 && pb.K == p.K;
+            // the next iteration's first layer rides on the second GEMM's 16-row tiles (gemm16_dw_pair_l1_kernel): the
+            // pair through registers, no slots on the first GEMM, Adam in the epilogue, [W1 | b1] in one column tile
+            // (and the forward's operands as gemm16_k32_fwd_kernel takes them: K <= 32, 16-byte rows of z)
+            const bool l1_rides = rider.l1 && pairable && !(p.dma && dma_ok(pb, true)) && !slots && !rider.fin &&
+                                  pb.adam.enabled && pb.db && pb.n_real + 1 <= 16 * ni && pb.n_real <= 32 &&
+                                  pb.n_real % 4 == 0 && aligned16(rider.l1->z) && rider.l1->ldz % 4 == 0 &&
+                                  rider.l1->z_slot.stride % 4 == 0;
+            if (rider.l1 && !l1_rides) {            // the pair as it would run alone, then the forward on its own
+                Rider r2 = rider;
+                r2.l1 = nullptr;
+                const int rc = launch<MODE_DW>(s, p_in, vec, xvec, r2);
+                if (rc) return rc;
+                const L1RideP& l = *rider.l1;
+                GemmP f{};
+                f.A = l.z; f.B = pb.adam.pW; f.C = l.H; f.M = l.rows; f.N = pb.M; f.K = pb.n_real;
+                f.lda = l.ldz; f.ldb = pb.ldc; f.ldc = l.ldh; f.bias = pb.adam.pb; f.epi = GM_ACT_RELU;
+                f.a_slot = l.z_slot; f.b_slot = gm_slot{};
+                const bool fvec = aligned16(l.z) && aligned16(pb.adam.pW) && (l.ldz % 4 == 0) && (f.K % 4 == 0) &&
+                                  (pb.ldc % 4 == 0) && (l.z_slot.stride % 4 == 0);
+                return launch<MODE_FWD>(s, f, fvec);
+            }
+            if (pairable) {
                 // both GEMMs on one tile shape; LDS-DMA only when both may take it
                 const bool dma = p.dma && dma_ok(pb, true);
                 p.dma = pb.dma = dma;
                 const int tna = (int)grid.x, na = (int)(grid.x * grid.y);
+                if (l1_rides) {
+                    const dim3 lgrid(na + (pb.M + 15) / 16);
+#define GM_LL1(MI_, NI_, D_) hipLaunchKernelGGL((gemm16_dw_pair_l1_kernel<MI_, NI_>), lgrid, dim3(1024), 0, s, p, pb, na, tna, *rider.l1)
+                    GM_TILE_SWITCH(tile, false, GM_LL1);
+#undef GM_LL1
+                    GM_LAUNCH_RET();
+                }
                 const int tnb = (pb.N + 16 * ni - 1) / (16 * ni), tmb = (pb.M + 16 * mi - 1) / (16 * mi);
                 const dim3 pgrid(na + tnb * tmb);
                 const bool sl_b = has_slot(pb.a_slot) || has_slot(pb.b_slot);
@@ -2156,7 +2299,7 @@ static int fwd_gather_impl(void* stream, const float* X, int64_t ldx, gm_slot x_
 static int dx_impl(void* stream, const float* dA, int64_t lda, const float* W, float* dX, int64_t ldx,
                    const float* below, int64_t ld_below, int M, int K, int N, int epi,
                    const float* add, int64_t ldadd, float add_scale, const HeadBwdP* head = nullptr,
-                   const float* fold_w2 = nullptr);
+                   const float* fold_w2 = nullptr, const GatherP* gather = nullptr);
 
 extern "C" int gm_linear_bwd_dx_head(void* stream, const float* dA, int64_t lda, const float* W,
                                      float* dX, int64_t ldx, const float* below, int64_t ld_below,
@@ -2215,10 +2358,35 @@ extern "C" int gm_linear_bwd_dx_add(void* stream, const float* dA, int64_t lda, 
     return dx_impl(stream, dA, lda, W, dX, ldx, below, ld_below, M, K, N, epi, add, ldadd, add_scale);
 }
 
+extern "C" int gm_linear_bwd_dx_gather(void* stream, const float* dA, int64_t lda, const float* W,
+                                       float* dX, int64_t ldx, const float* below, int64_t ld_below,
+                                       int M, int K, int N, int epi, const float* data, int64_t n_rows,
+                                       const int64_t* idx, gm_slot idx_slot, float* out, int64_t ld_out,
+                                       int B, int row_elems) {
+    // the gathered rows must not be an operand or the output of this GEMM
+    GM_CHECK_ARG(out && out != dA && out != W && out != dX && out != below);
+    GatherP g{};
+    const int rc = gm_gather_fill(data, n_rows, idx, idx_slot, out, ld_out, B, row_elems, &g);
+    if (rc) return rc;
+    return dx_impl(stream, dA, lda, W, dX, ldx, below, ld_below, M, K, N, epi, nullptr, 0, 0.f, nullptr, nullptr, &g);
+}
+
+extern "C" int gm_linear_bwd_dx_gather_bits(void* stream, const float* dA, int64_t lda, const float* W,
+                                            float* dX, int64_t ldx, const float* below, int64_t ld_below,
+                                            int M, int K, int N, int epi, const uint32_t* bits, int words_per_row,
+                                            int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out,
+                                            int64_t ld_out, int B, int row_elems) {
+    GM_CHECK_ARG(out && out != dA && out != W && out != dX && out != below);
+    GatherP g{};
+    const int rc = gm_gather_fill_bits(bits, words_per_row, n_rows, idx, idx_slot, out, ld_out, B, row_elems, &g);
+    if (rc) return rc;
+    return dx_impl(stream, dA, lda, W, dX, ldx, below, ld_below, M, K, N, epi, nullptr, 0, 0.f, nullptr, nullptr, &g);
+}
+
 static int dx_impl(void* stream, const float* dA, int64_t lda, const float* W, float* dX, int64_t ldx,
                    const float* below, int64_t ld_below, int M, int K, int N, int epi,
                    const float* add, int64_t ldadd, float add_scale, const HeadBwdP* head,
-                   const float* fold_w2) {
+                   const float* fold_w2, const GatherP* gather) {
     GM_CHECK_ARG(dA && W && dX && M > 0 && K > 0 && N > 0 && lda >= N && ldx >= K);
     GM_CHECK_ARG(epi == GM_ACT_ID || (below && ld_below >= K));
     GemmP p{};
@@ -2232,6 +2400,7 @@ static int dx_impl(void* stream, const float* dA, int64_t lda, const float* W, f
     const bool xvec = aligned16(W) && (K % 4 == 0);
     Rider r;
     r.head = head;
+    r.gather = gather;
     return launch<MODE_DX>((hipStream_t)stream, p, vec, xvec, r);
 }
 
@@ -2377,8 +2546,29 @@ static int dw_adam_fill(const gm_dw_adam_args& a, GemmP* p, bool* xvec) {
     return dw_fill(a.dA, a.lda, a.X, a.ldx, a.x_slot, a.dW, a.db, a.M, a.K, a.N, 0, &e, p, xvec);
 }
 
+static int pair_launch(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second,
+                       const L1RideP* l1);
+
 extern "C" int gm_linear_bwd_dw_adam_pair(void* stream, const gm_dw_adam_args* first,
                                           const gm_dw_adam_args* second) {
+    return pair_launch(stream, first, second, nullptr);
+}
+
+extern "C" int gm_linear_bwd_dw_adam_pair_l1(void* stream, const gm_dw_adam_args* first,
+                                             const gm_dw_adam_args* second, const float* z, int64_t ldz,
+                                             gm_slot z_slot, float* H, int64_t ldh, int rows) {
+    GM_CHECK_ARG(first && second && second->sched && z && H && rows > 0 && ldz >= second->K && ldh >= second->N);
+    // H is written while the pair runs: it may be none of the pair's operands or outputs
+    const void* pair_arrays[] = {first->dA, first->X, first->dW, first->db, first->pW, first->pb,
+                                 second->dA, second->X, second->dW, second->db, second->pW, second->pb};
+    for (const void* q : pair_arrays) GM_CHECK_ARG(q != (const void*)H);
+    GM_CHECK_ARG((const void*)z != (const void*)H);
+    const L1RideP l{z, ldz, z_slot, H, ldh, rows, (aligned16(H) && ldh % 4 == 0) ? 1 : 0};
+    return pair_launch(stream, first, second, &l);
+}
+
+static int pair_launch(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second,
+                       const L1RideP* l1) {
     GM_CHECK_ARG(first && second);
     // neither may consume what the other produces or updates
     GM_CHECK_ARG(first->dW != second->dW && (first->pW != second->pW || !first->pW));
@@ -2394,6 +2584,7 @@ extern "C" int gm_linear_bwd_dw_adam_pair(void* stream, const gm_dw_adam_args* f
     Rider r;
     r.pair = &pb;
     r.pair_xvec = xb;
+    r.l1 = l1;
     return launch<MODE_DW>((hipStream_t)stream, pa, false, xa, r);
 }
 

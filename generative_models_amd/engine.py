@@ -453,6 +453,10 @@ class GANEngine(CriticStep, InfoQStep, GeneratorStep, PenaltySteps):
         # penalty steps take where a fused one does not apply (_adam_in_epilogue, _fold_ok, _tick_in_head ...).
         self.fuse_head = self.fuse_adam = self.fold_tick = self.ride_head_dx = True
         self.group_head = self.ride_gather = self.pair_dw = self.batch_gen_env = True
+        # the next iteration's generator layer 1 in this iteration's weight-gradient pair and its batch gather in the dH
+        # launch (_l1_rides): 7 launches per iteration instead of 8, inside a graph or an eager run
+        self.ride_l1 = True
+        self._l1_in = self._l1_out = False
         # folded critic head (round 3): no launch for the N = 1 layer -- partial dots in the hidden
         # layer's forward epilogue, scores / losses / dS rebuilt in the consumers' prologues, dH formed
         # in registers (csrc/gm_head.h).  "2": also where the forward would take the LDS macro-tile kernel
@@ -482,6 +486,8 @@ class GANEngine(CriticStep, InfoQStep, GeneratorStep, PenaltySteps):
         self.X2, self.Xg2 = self.XX[:2 * Bl], self.XX[2 * Bl:]
         self.HG = z(2 * Bl, H)
         self.Hg, self.Hg2 = self.HG[:Bl], self.HG[Bl:]
+        # HG by iteration parity while layer 1 rides (_l1_rides; allocated here, never inside a capture)
+        self._HG_pp = [self.HG, z(2 * Bl, H) if variant in ("ns", "ls") else None]
         self.Hd = z(2 * Bl, Hd)
         self.S2 = z(2 * Bl)                # scores
         self.dS = z(2 * Bl)                # d loss / d pre-activation score
@@ -666,13 +672,38 @@ class GANEngine(CriticStep, InfoQStep, GeneratorStep, PenaltySteps):
         seg(tail, None)
         return segs
 
-    def _issue_iteration(self, st, it):
+    def _l1_rides(self):
+        """The next iteration's generator layer 1 rides in this iteration's generator weight-gradient pair
+        (gm_linear_bwd_dw_adam_pair_l1: its W1 tiles form H from the parameters they just stepped) and the next batch
+        gather in this iteration's dH launch (the real rows are last read by the critic's weight gradient).  One GPU,
+        one critic step, NSGAN / LSGAN with the batched generator forward, the paired weight gradients with Adam in
+        their epilogue; up to 512 generator rows (the bs = 1024 shapes keep their own launch: not measured there)."""
+        return self.ride_l1 and self.variant in ("ns", "ls") and self._single() and self.D_steps == 1 and \
+            self._batch_gen() and not self._standalone_G and self.pair_dw and self._adam_in_epilogue("G") and \
+            self._gather_rides() and self._fold_head() and self._fold_head_G() and not self._packed_operand() and \
+            2 * self.Bl <= 512 and self._HG_pp[1] is not None
+
+    def _use_hg(self, b):
+        self.HG = self._HG_pp[b]
+        self.Hg, self.Hg2 = self.HG[:self.Bl], self.HG[self.Bl:]
+
+    def _issue_iteration(self, st, it, pos=0, count=1):
         """All segments back to back (one hipGraph when use_graph): single GPU, or data parallel with
-        the in-graph peer exchange."""
-        for run, ar in self._segments():
-            run(st, it)
-            if ar is not None:
-                self._allreduce(ar, st, it)
+        the in-graph peer exchange.  pos / count: this iteration's place in its graph (eager: in its run) -- where layer
+        1 rides (_l1_rides), iteration pos > 0 starts from the H and the batch that iteration pos - 1 formed, into the
+        other HG buffer (parity of pos), and the last one forms nothing ahead."""
+        rides = self._l1_rides()
+        self._l1_in, self._l1_out = rides and pos > 0, rides and pos + 1 < count
+        if rides:
+            self._use_hg(pos & 1)
+            self._l1_next = (pos + 1) & 1
+        try:
+            for run, ar in self._segments():
+                run(st, it)
+                if ar is not None:
+                    self._allreduce(ar, st, it)
+        finally:
+            self._l1_in = self._l1_out = False
 
     def _allreduce(self, ar, st=None, it=0):
         """Gradient exchange after a backward segment.  ar = ("D", j) | ("G", 0)."""
@@ -1213,8 +1244,8 @@ class GANEngine(CriticStep, InfoQStep, GeneratorStep, PenaltySteps):
             def body(k):
                 def fn(st):
                     self._issue_stage_in(st, 0, k)
-                    for _ in range(k):
-                        self._issue_iteration(st, 0)
+                    for i in range(k):
+                        self._issue_iteration(st, 0, i, k)
                 return fn
             self.graph = ops.Graph().capture(body(1))
             self.graphs_by_size = [(1, self.graph)]
@@ -1397,7 +1428,7 @@ class GANEngine(CriticStep, InfoQStep, GeneratorStep, PenaltySteps):
             st = ops.stream_ptr()
             self._issue_stage_in(st, it, k)
             for i in range(k):
-                self._issue_iteration(st, it + i)
+                self._issue_iteration(st, it + i, i, k)
 
     def run(self, n_iters, it_start=0, horizon=None):
         """Run iterations [it_start, it_start+n_iters): the run is cut into power-of-two graph launches

@@ -73,7 +73,9 @@ class CriticStep:
         zD_slot = self._slot(it, d, j, R * d, self.zD_stride)
         zbase = self.zD_base[self.ring_r0 * self.Z:].view(-1, self.Z)
         rows = 2 * Bl if (self._batch_gen() and not self._standalone_G) else Bl
-        if self._gather_rides():
+        if self._l1_in:
+            pass                                    # H and the batch: formed by the previous iteration's launches
+        elif self._gather_rides():
             ops.linear_fwd_gather(zbase, G1.W, G1.b, self.HG, "relu", M=rows, x_slot=zD_slot,
                                   stream=st, **self._gather_args(it, j))
         else:
@@ -363,7 +365,19 @@ class GeneratorStep:
     def _G_sched_slot(self, it):
         return self._slot(it, 1, self.g_off, 0, 1, post=True)
 
+    def _next_slot(self, it, stride):
+        """Ring slot of the NEXT iteration for a consumer behind this iteration's folded tick (one critic step)."""
+        return self._slot(it, 1, 1, self.R, stride, post=True)
+
     def _G_dh(self, st, it):
+        if self._l1_out:
+            # the next iteration's batch gather rides here: this iteration's real rows were last read by the critic's
+            # weight gradient
+            g = self._gather_args(it, 0)
+            g["idx_slot"] = self._next_slot(it, self.ring_B)
+            ops.linear_bwd_dx_gather(self.dXg, self.G2.W, self.dHg, g["data"], g["idx"], g["out"], below=self.Hg2,
+                                     epi="relu", M=self.Bl, B=g["B"], idx_slot=g["idx_slot"], stream=st)
+            return
         ops.linear_bwd_dx(self.dXg, self.G2.W, self.dHg, below=self.Hg2, epi="relu", M=self.Bl,
                           stream=st)
 
@@ -398,10 +412,15 @@ class GeneratorStep:
             adam = self._adam_args("G", self._G_sched_slot(it)) if self._adam_in_epilogue("G") else None
             zbase = self.zG_base[self.ring_r0 * self.Z:].view(-1, self.Z)
             zG_slot = self._slot(it, 1, 0, self.R, self.zG_stride, post=True)
-            ops.linear_bwd_dw_adam_pair(
-                dict(dA=self.dXg, X=self.Hg2, lin=self.G2, adam=adam, M=self.Bl),
-                dict(dA=self.dHg, X=zbase, lin=self.G1, adam=adam, M=self.Bl, x_slot=zG_slot),
-                stream=st)
+            first = dict(dA=self.dXg, X=self.Hg2, lin=self.G2, adam=adam, M=self.Bl)
+            second = dict(dA=self.dHg, X=zbase, lin=self.G1, adam=adam, M=self.Bl, x_slot=zG_slot)
+            if self._l1_out:
+                # ... and the next iteration's G layer 1 on [zD ; zG] of its ring slot, into the other HG buffer
+                zD = self.zD_base[self.ring_r0 * self.Z:].view(-1, self.Z)
+                ops.linear_bwd_dw_adam_pair_l1(first, second, zD, self._HG_pp[self._l1_next], 2 * self.Bl,
+                                               z_slot=self._next_slot(it, self.zD_stride), stream=st)
+                return
+            ops.linear_bwd_dw_adam_pair(first, second, stream=st)
             return
         self._G_dw2(st, it)
         self._G_dw1(st, it)

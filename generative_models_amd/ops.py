@@ -135,6 +135,29 @@ def linear_bwd_dx(dA, W, dX, below=None, epi="id", M=None, add=None, add_scale=1
     return dX
 
 
+def linear_bwd_dx_gather(dA, W, dX, data, idx, out, below=None, epi="id", M=None, B=None, idx_slot=NO_SLOT,
+                         stream=None):
+    """linear_bwd_dx(dA, W, dX, below, epi) and gather_rows(data, idx, out) as ONE launch (the gather workgroups ride in
+    the GEMM's grid; `out` must not be an array of this GEMM).  data: fp32 [N, I] or PackedData (fp32 rows out)."""
+    N, K = W.shape
+    M = dA.shape[0] if M is None else M
+    n_rows, row = data.shape
+    B = out.shape[0] if B is None else B
+    if isinstance(data, PackedData):                 # 1 bit / pixel resident dataset, expanded to fp32 rows
+        _lib.call("gm_linear_bwd_dx_gather_bits", stream or stream_ptr(), _chk(dA, "dA").data_ptr(), _ld(dA),
+                  W.data_ptr(), _chk(dX, "dX").data_ptr(), _ld(dX),
+                  below.data_ptr() if below is not None else None, _ld(below) if below is not None else 0, M, K,
+                  N, ACT[epi] if not isinstance(epi, int) else epi, data.data_ptr(), data.wpr, n_rows,
+                  idx.data_ptr(), idx_slot, out.data_ptr(), _ld(out), B, row)
+        return dX
+    _lib.call("gm_linear_bwd_dx_gather", stream or stream_ptr(), _chk(dA, "dA").data_ptr(), _ld(dA),
+              W.data_ptr(), _chk(dX, "dX").data_ptr(), _ld(dX),
+              below.data_ptr() if below is not None else None, _ld(below) if below is not None else 0, M, K, N,
+              ACT[epi] if not isinstance(epi, int) else epi, _chk(data, "data").data_ptr(), n_rows,
+              idx.data_ptr(), idx_slot, out.data_ptr(), _ld(out), B, row)
+    return dX
+
+
 def linear_bwd_dw(dA, X, dW, db, M=None, accumulate=False, x_slot=NO_SLOT, stream=None):
     """dW[N,K] (+)= dA[M,N]^T @ X[M,K]; db[N] (+)= colsum(dA)."""
     N, K = dW.shape
@@ -210,6 +233,22 @@ def linear_bwd_dw_adam_pair(first, second, betas=(0.9, 0.999), eps=1e-8, weight_
                                  d.get("x_slot", NO_SLOT), betas, eps, weight_decay)
     a, b = mk(first), mk(second)
     _lib.call("gm_linear_bwd_dw_adam_pair", stream or stream_ptr(), ctypes.byref(a), ctypes.byref(b))
+
+
+def linear_bwd_dw_adam_pair_l1(first, second, z, H, rows, z_slot=NO_SLOT, betas=(0.9, 0.999), eps=1e-8,
+                               weight_decay=0.0, stream=None):
+    """linear_bwd_dw_adam_pair(first, second) followed by linear_fwd(z, second's W, second's b, H, "relu", M=rows,
+    x_slot=z_slot) -- the stepped first layer on the next iteration's noise -- as ONE launch where the pair can carry it
+    (the second GEMM's tiles form H from the parameters they just stepped), else as those two launches; same bits."""
+    import ctypes
+    mk = lambda d: _dw_adam_args(d["dA"], d["X"], d["lin"], d.get("adam"), d.get("M"),
+                                 d.get("x_slot", NO_SLOT), betas, eps, weight_decay)
+    if second.get("adam") is None:
+        raise _lib.GMError("linear_bwd_dw_adam_pair_l1: the second GEMM needs its Adam step")
+    a, b = mk(first), mk(second)
+    _lib.call("gm_linear_bwd_dw_adam_pair_l1", stream or stream_ptr(), ctypes.byref(a), ctypes.byref(b),
+              _chk(z, "z").data_ptr(), _ld(z), z_slot, _chk(H, "H").data_ptr(), _ld(H), rows)
+    return H
 
 
 def linear_bwd_dw_adam_pair_finalize(first, second, fin, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,

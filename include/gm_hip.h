@@ -431,6 +431,12 @@ typedef struct gm_dw_adam_args {
 } gm_dw_adam_args;
 int gm_linear_bwd_dw_adam_pair(void* stream, const gm_dw_adam_args* first,
                                const gm_dw_adam_args* second);
+/* The generator's pair carrying the NEXT iteration's first layer: after the pair (second = the first layer's dW1 + Adam,
+ * required), H[rows, second->N] = relu(z W1^T + b1) with the stepped W1, b1 -- z: rows x second->K at z + the slot's
+ * offset, leading dimension ldz.  Bit-identical to gm_linear_bwd_dw_adam_pair followed by gm_linear_fwd, which is what
+ * runs where the pair cannot carry it.  H may be none of the pair's arrays. */
+int gm_linear_bwd_dw_adam_pair_l1(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second,
+                                  const float* z, int64_t ldz, gm_slot z_slot, float* H, int64_t ldh, int rows);
 /* The pair as the LAST launch of a VAE batch (vae.py:162 + the loss sums of :203 / :212): one more workgroup adds up
  * the two partial arrays exactly as gm_sum_finalize2_tick does, and the last workgroup of the launch to finish
  * advances `tick` (every slot of the batch has been resolved by then).  done: one zero-initialised unsigned int the
@@ -448,6 +454,17 @@ int gm_linear_bwd_dw_adam_pair_finalize(void* stream, const gm_dw_adam_args* fir
 int gm_linear_bwd_dx_add(void* stream, const float* dA, int64_t lda, const float* W, float* dX,
                          int64_t ldx, const float* below, int64_t ld_below, int M, int K, int N,
                          int epi, const float* add, int64_t ldadd, float add_scale);
+/* gm_linear_bwd_dx with gm_gather_rows(data, idx, idx_slot, out, ...) riding in the same launch (out: none of the
+ * GEMM's arrays). */
+int gm_linear_bwd_dx_gather(void* stream, const float* dA, int64_t lda, const float* W, float* dX, int64_t ldx,
+                            const float* below, int64_t ld_below, int M, int K, int N, int epi, const float* data,
+                            int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out, int64_t ld_out, int B,
+                            int row_elems);
+/* Same with the bit-packed resident dataset (gm_linear_fwd_gather_bits' layout). */
+int gm_linear_bwd_dx_gather_bits(void* stream, const float* dA, int64_t lda, const float* W, float* dX, int64_t ldx,
+                                 const float* below, int64_t ld_below, int M, int K, int N, int epi,
+                                 const uint32_t* bits, int words_per_row, int64_t n_rows, const int64_t* idx,
+                                 gm_slot idx_slot, float* out, int64_t ld_out, int B, int row_elems);
 
 /* ---- K13: DRAGAN penalty (dra_gan.py:198-223; derivation in SURVEY.md A.3).  std_all: unbiased std
  * of the whole real batch; xhat: delta*x + (1-delta)*(x + C*std*U); rows: per-row norm of the input

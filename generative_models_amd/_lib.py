@@ -94,6 +94,26 @@ class AAEGenArgs(ctypes.Structure):
                 ("loss_part", c_void_p), ("B", c_int), ("Z", c_int), ("H", c_int)]
 
 
+class SghmcSeg(ctypes.Structure):
+    """gm_sghmc_seg (include/gm_hip.h): one tensor of an SGHMC launch."""
+    _fields_ = [("offset", c_int64), ("numel", c_int64), ("stream", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class SghmcArgs(ctypes.Structure):
+    """gm_sghmc_args (include/gm_hip.h): one SGHMC step over a segment table."""
+    _fields_ = [("theta", c_void_p), ("grad", c_void_p), ("mom", c_void_p), ("n_flat", c_int64),
+                ("segs", POINTER(SghmcSeg)), ("nseg", c_int), ("step", c_void_p), ("step_add", c_int64),
+                ("lr", c_void_p), ("friction", c_float), ("prior", c_float), ("noise", c_float),
+                ("seed", ctypes.c_uint64)]
+
+
+class BganHeadArgs(ctypes.Structure):
+    """gm_bgan_head_args (include/gm_hip.h): the Bayesian GAN's critic-ensemble head."""
+    _fields_ = [("h", c_void_p), ("ldh", c_int64), ("w2", c_void_p), ("b2", c_void_p), ("gw2", c_void_p),
+                ("gb2", c_void_p), ("loss_out", c_void_p), ("loss_slot", Slot), ("ws", c_void_p),
+                ("ws_bytes", c_int64), ("mode", c_int), ("B", c_int), ("Jg", c_int), ("Jd", c_int), ("H", c_int)]
+
+
 class Finalize2Args(ctypes.Structure):
     """gm_finalize2_args (include/gm_hip.h): the two loss sums + counter tick that ride in a VAE batch's last launch."""
     _fields_ = [("pa", c_void_p), ("na", c_int), ("scale_a", c_float), ("out_a", c_void_p), ("slot_a", Slot),
@@ -301,6 +321,12 @@ _SIGNATURES = {
     "gm_aae_critic_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "gm_aae_critic_step": (c_int, [_P, POINTER(AAECriticArgs)]),
     "gm_aae_gen_mid": (c_int, [_P, POINTER(AAEGenArgs)]),
+    "gm_philox_raw": (c_int, [_P, _P, _P, _P, c_int64]),
+    "gm_philox_normal": (c_int, [_P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_int, _P, c_int64, _P,
+                                 c_int64]),
+    "gm_sghmc_step": (c_int, [_P, POINTER(SghmcArgs)]),
+    "gm_bgan_head_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "gm_bgan_head": (c_int, [_P, POINTER(BganHeadArgs)]),
     "gm_parzen_ll": (c_int, [_P, _P, c_int64, c_int, _P, c_int64, c_int, c_int, _P, c_int, _P, c_int64, _P,
                              c_int64]),
 }

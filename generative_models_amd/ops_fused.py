@@ -1,4 +1,6 @@
 """Tensor-level wrappers for the variant-specific fused kernels (csrc/gm_fused.hip)."""
+import ctypes
+
 import torch
 
 from . import _lib
@@ -311,3 +313,97 @@ def aae_gen_mid(z, He, W1, b1, w2, b2, Wz, dz, dHe, loss_part, B, stream=None):
     a.loss_part, a.B, a.Z, a.H = loss_part.data_ptr(), B, Z, H
     import ctypes
     _lib.call("gm_aae_gen_mid", stream or stream_ptr(), ctypes.byref(a))
+
+
+# ---- Bayesian GAN (csrc/gm_bgan.hip; bgan.py) ----------------------------------------------------------------------
+def bgan_stream_param(side, k, tensor):
+    """The noise stream word of tensor `tensor` (0 linear.weight, 1 linear.bias, 2 second weight, 3 second bias) of
+    sample k on `side` (0 critics, 1 generators)."""
+    return 0x10000 | (side << 12) | (k << 4) | tensor
+
+
+def bgan_stream_latent(phase, j):
+    """The stream word of generator j's latent draw in phase 0 (critic update) or 1 (generator update)."""
+    return 0x20000 | (phase << 12) | (j << 4)
+
+
+def _u32(t, name):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise _lib.GMError("%s must be a contiguous int32 device tensor" % name)
+    return t
+
+
+def philox_raw(ctr, key, stream=None):
+    """Philox4x32-10 words for n (counter, key) pairs: ctr int32 [n, 4], key int32 [n, 2] (bit patterns) ->
+    int32 [n, 4]."""
+    n = ctr.shape[0]
+    if ctr.shape != (n, 4) or key.shape != (n, 2):
+        raise _lib.GMError("philox_raw: ctr must be [n, 4] and key [n, 2]")
+    out = torch.empty(n, 4, dtype=torch.int32, device=ctr.device)
+    _lib.call("gm_philox_raw", stream or stream_ptr(), _u32(ctr, "ctr").data_ptr(), _u32(key, "key").data_ptr(),
+              out.data_ptr(), n)
+    return out
+
+
+def philox_normal(seed, stream_word, t, n, out=None, nstreams=1, stream_stride=0, step=None, device=None,
+                  stream=None):
+    """nstreams draws of n normals (gm_philox_normal): out[j, e] = Normal(seed, stream_word + j stream_stride,
+    step) element e, with step = (*step if step is a device int64 tensor else 0) + t."""
+    if out is None:
+        out = torch.empty(nstreams, n, device=device or "cuda")
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= nstreams * n):
+        raise _lib.GMError("philox_normal: out must be a contiguous float32 device tensor of >= %d elements"
+                           % (nstreams * n))
+    if step is not None and not (step.is_cuda and step.dtype == torch.int64):
+        raise _lib.GMError("philox_normal: step must be an int64 device tensor")
+    _lib.call("gm_philox_normal", stream or stream_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF, stream_word & 0xFFFFFFFF,
+              stream_stride & 0xFFFFFFFF, nstreams, step.data_ptr() if step is not None else None, int(t),
+              out.data_ptr(), n)
+    return out
+
+
+def sghmc_segments(segs):
+    """A host segment table from (offset, numel, stream word) triples."""
+    arr = (_lib.SghmcSeg * len(segs))()
+    for a, (o, n, s) in zip(arr, segs):
+        a.offset, a.numel, a.stream = int(o), int(n), int(s) & 0xFFFFFFFF
+    return arr
+
+
+def sghmc_step(theta, grad, mom, segs, lr, friction, prior, noise, seed, t=0, step=None, stream=None):
+    """One SGHMC step (gm_sghmc_step) over the flat fp32 buffers theta / grad / mom: segs is a table of
+    sghmc_segments, lr a device float32 tensor (eta in lr[0]), step a device int64 counter (or None) added to t."""
+    for x, nm in ((theta, "theta"), (grad, "grad"), (mom, "mom")):
+        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == theta.numel()):
+            raise _lib.GMError("sghmc_step: %s must be a contiguous float32 device tensor like theta" % nm)
+    if not (lr.is_cuda and lr.dtype == torch.float32):
+        raise _lib.GMError("sghmc_step: lr must be a float32 device tensor")
+    if step is not None and not (step.is_cuda and step.dtype == torch.int64):
+        raise _lib.GMError("sghmc_step: step must be an int64 device tensor")
+    if not isinstance(segs, ctypes.Array):
+        segs = sghmc_segments(segs)
+    a = _lib.SghmcArgs(theta.data_ptr(), grad.data_ptr(), mom.data_ptr(), theta.numel(), segs, len(segs),
+                       step.data_ptr() if step is not None else None, int(t), lr.data_ptr(), friction, prior, noise,
+                       int(seed) & 0xFFFFFFFFFFFFFFFF)
+    _lib.call("gm_sghmc_step", stream or stream_ptr(), ctypes.byref(a))
+
+
+def bgan_head_workspace(mode, B, Jg, Jd, H, device):
+    n = _lib.load().gm_bgan_head_workspace_bytes(mode, B, Jg, Jd, H)
+    if n < 0:
+        raise _lib.GMError("bgan_head: shape (B=%d, Jg=%d, Jd=%d, H=%d) outside the kernel's limits" % (B, Jg, Jd, H))
+    return torch.empty((n + 3) // 4, device=device)
+
+
+def bgan_head(h, w2, b2, mode, B, Jg, Jd, ws, gw2=None, gb2=None, loss_out=None, loss_slot=NO_SLOT, stream=None):
+    """The critic ensemble's head (gm_bgan_head) over h [R, Jd H] (dH written over it): mode 0 = critic update,
+    mode 1 = generator update."""
+    H = w2.numel() // Jd
+    R = (1 + Jg) * B if mode == 0 else Jg * B
+    if h.dim() != 2 or h.shape[0] < R or h.shape[1] != Jd * H or h.stride(1) != 1 or w2.numel() != Jd * H \
+            or b2.numel() != Jd:
+        raise _lib.GMError("bgan_head: h must be [>= %d, %d], w2 [%d, H], b2 [%d]" % (R, Jd * H, Jd, Jd))
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    a = _lib.BganHeadArgs(h.data_ptr(), h.stride(0), w2.data_ptr(), b2.data_ptr(), ptr(gw2), ptr(gb2), ptr(loss_out),
+                          loss_slot, ws.data_ptr(), ws.numel() * 4, mode, B, Jg, Jd, H)
+    _lib.call("gm_bgan_head", stream or stream_ptr(), ctypes.byref(a))

@@ -768,6 +768,58 @@ typedef struct gm_aae_gen_args {
  * ops_fused.aae_gen_mid. */
 int gm_aae_gen_mid(void* stream, const gm_aae_gen_args* a);
 
+/* ---- Bayesian GAN (NEW: the reference's src/bayes_gan.py is a docstring and a TODO; generative_models_amd/bgan.py,
+ * DESIGN.md section 14).  A device-side counter-based generator, the SGHMC update and the critic ensemble's head.
+ *
+ * Normal(seed, stream s, step t), element e: Philox4x32-10 with key (seed mod 2^32, seed >> 32) and counter
+ * (e >> 2, t, s, 0) -> words (x0, x1, x2, x3); u(x) = (2 (x >> 9) + 1) 2^-24; lanes (0, 1) from (x0, x1) and
+ * (2, 3) from (x2, x3) by Box-Muller r = sqrt(-2 ln u_a), phi = 2 pi u_b -> (r cos phi, r sin phi); element e takes
+ * lane e & 3.  The step is t = (step ? *step : 0) + step_add (a device counter, so a replayed graph advances it). */
+#define GM_SGHMC_MAX_SEGS 64
+#define GM_BGAN_MAX_J 16
+/* Philox4x32-10 raw words: out[4i..4i+3] = philox(ctr[4i..4i+3], key[2i..2i+1]) for i < n (known-answer tests). */
+int gm_philox_raw(void* stream, const uint32_t* ctr, const uint32_t* key, uint32_t* out, int64_t n);
+/* nstreams draws of n normals: out[j n + e] = Normal(seed, stream0 + j stream_stride, t) element e. */
+int gm_philox_normal(void* stream, uint64_t seed, uint32_t stream0, uint32_t stream_stride, int nstreams,
+                     const int64_t* step, int64_t step_add, float* out, int64_t n);
+typedef struct gm_sghmc_seg {
+    int64_t offset;           /* first element of the tensor in the flat buffers */
+    int64_t numel;
+    uint32_t stream;          /* the noise stream word of the tensor; elements numbered from 0 within it */
+    uint32_t reserved;
+} gm_sghmc_seg;
+typedef struct gm_sghmc_args {
+    float* theta; const float* grad; float* mom;   /* flat buffers of n_flat floats */
+    int64_t n_flat;
+    const gm_sghmc_seg* segs; int nseg;            /* HOST array of 1..GM_SGHMC_MAX_SEGS disjoint segments */
+    const int64_t* step; int64_t step_add;         /* the noise step t (device counter or NULL) */
+    const float* lr;                               /* device float: the learning rate eta */
+    float friction;                                /* alpha, in [0, 1] */
+    float prior;                                   /* 1 / (sigma^2 N): g <- g + theta prior */
+    float noise;                                   /* 2 alpha / N: the noise std is sqrt(noise eta) */
+    uint64_t seed;
+} gm_sghmc_args;
+/* One SGHMC step (Saatchi & Wilson 2017, Algorithm 1 with gamma-hat = 0) of every segment in ONE launch, one thread
+ * per four elements: v <- (1 - alpha) v - eta (g + theta prior) + sqrt(noise eta) xi, theta <- theta + v, with
+ * xi = Normal(seed, segment stream, t).  No atomics: the same bits on every run. */
+int gm_sghmc_step(void* stream, const gm_sghmc_args* a);
+typedef struct gm_bgan_head_args {
+    float* h; int64_t ldh;          /* [R, Jd H] relu hidden rows of the stacked critics; overwritten by dH */
+    const float* w2; const float* b2;   /* [Jd, H] second-layer weights, [Jd] biases */
+    float* gw2; float* gb2;         /* out (mode 0): [Jd, H], [Jd] */
+    float* loss_out; gm_slot loss_slot; /* out: mode 0 the Jd sums L_D^k, mode 1 the Jg sums L_G^j (or NULL) */
+    float* ws; int64_t ws_bytes;    /* workspace of gm_bgan_head_workspace_bytes bytes */
+    int mode;                       /* 0: critic update, R = (1 + Jg) B rows [x; G_0(z_0); ...]; 1: generator
+                                       update, R = Jg B rows [G_0(z'_0); ...] */
+    int B, Jg, Jd, H;
+} gm_bgan_head_args;
+/* Bytes of gm_bgan_head's workspace, -1 for a shape outside its limits (1 <= Jg, Jd <= 16, H % 4 == 0, H <= 1024). */
+int64_t gm_bgan_head_workspace_bytes(int mode, int B, int Jg, int Jd, int H);
+/* The critic ensemble's head in two launches: per critic k, logit = h[:, kH:(k+1)H] w2_k + b2_k, s = sigmoid; the
+ * contract's loss terms (real rows weight 1/B, fake rows 1/(B Jg) in mode 0; 1/(B Jd) in mode 1, all with the 1e-8
+ * terms); dH = dlogit w2_k [h > 0] in place; gw2, gb2 and the loss sums in a fixed order, no atomics. */
+int gm_bgan_head(void* stream, const gm_bgan_head_args* a);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

@@ -114,6 +114,15 @@ class BganHeadArgs(ctypes.Structure):
                 ("ws_bytes", c_int64), ("mode", c_int), ("B", c_int), ("Jg", c_int), ("Jd", c_int), ("H", c_int)]
 
 
+class CorruptArgs(ctypes.Structure):
+    """gm_corrupt_args (include/gm_hip.h): the denoising VAE's corruption rule, seed, step and first row."""
+    _fields_ = [("kind", c_int), ("level", ctypes.c_double), ("seed", ctypes.c_uint64), ("step_ctr", c_void_p),
+                ("step_base", c_void_p), ("step_add", c_int64), ("row0", c_int64)]
+
+
+NOISE = {"salt_pepper": 1, "gaussian": 2}       # GM_NOISE_SALT_PEPPER, GM_NOISE_GAUSSIAN (GM_NOISE_NONE = 0)
+
+
 class Finalize2Args(ctypes.Structure):
     """gm_finalize2_args (include/gm_hip.h): the two loss sums + counter tick that ride in a VAE batch's last launch."""
     _fields_ = [("pa", c_void_p), ("na", c_int), ("scale_a", c_float), ("out_a", c_void_p), ("slot_a", Slot),
@@ -329,6 +338,17 @@ _SIGNATURES = {
     "gm_bgan_head": (c_int, [_P, POINTER(BganHeadArgs)]),
     "gm_parzen_ll": (c_int, [_P, _P, c_int64, c_int, _P, c_int64, c_int, c_int, _P, c_int, _P, c_int64, _P,
                              c_int64]),
+    "gm_dvae_corrupt": (c_int, [_P, POINTER(CorruptArgs), _P, c_int64, _P, c_int64, c_int64, c_int]),
+    "gm_gather_rows_corrupt": (c_int, [_P, POINTER(CorruptArgs), _P, c_int64, _P, Slot, _P, _P, c_int64, c_int,
+                                       c_int]),
+    "gm_gather_rows_bits_corrupt": (c_int, [_P, POINTER(CorruptArgs), _P, c_int, c_int64, _P, Slot, _P, _P, c_int64,
+                                            c_int, c_int]),
+    "gm_linear_fwd_gather_corrupt": (c_int, [_P, _P, c_int64, Slot, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int,
+                                             _P, c_int64, _P, Slot, _P, c_int64, c_int, c_int, _P,
+                                             POINTER(CorruptArgs)]),
+    "gm_linear_fwd_gather_bits_corrupt": (c_int, [_P, _P, c_int64, Slot, _P, _P, _P, c_int64, c_int, c_int, c_int,
+                                                  c_int, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int, _P,
+                                                  POINTER(CorruptArgs)]),
 }
 
 _lib = None

@@ -33,6 +33,7 @@
 #include "gm_common.h"
 #include "gm_head.h"
 #include "gm_gather.h"
+#include "gm_dvae.h"
 #include "gm_ldsdma.h"
 
 #include <cstdlib>
@@ -1538,6 +1539,20 @@ __global__ __launch_bounds__(1024) void gemm16_fwd_gather_kernel(GemmP p, Gather
     gemm16_body<MODE_FWD, VEC, 16, G, false, MI, NI>(p, red, blockIdx.x, blockIdx.y - grows);
 }
 
+// The same with the denoising VAE's corrupting gather (gm_dvae.h): the gather workgroups also write the corrupted copy of
+// every row.  Its own kernel, so the plain gather kernels above keep their code objects.
+template <bool VEC, int G, int MI, int NI>
+__global__ __launch_bounds__(1024) void gemm16_fwd_gather_corrupt_kernel(GemmP p, GatherP gp, CorruptP cp, int grows,
+                                                                         int gblocks) {
+    __shared__ __attribute__((aligned(16))) float red[16 * 32 * 32];
+    if ((int)blockIdx.y < grows) {                           // workgroup-uniform
+        const int bid = blockIdx.y * gridDim.x + blockIdx.x;
+        if (bid < gblocks) gather_corrupt_body(gp, cp, bid);
+        return;
+    }
+    gemm16_body<MODE_FWD, VEC, 16, G, false, MI, NI>(p, red, blockIdx.x, blockIdx.y - grows);
+}
+
 // The same with an input-gradient GEMM (the generator's dH launch carrying the NEXT iteration's batch gather when the
 // next iteration's first layer rides in the weight-gradient pair: gemm16_dw_pair_l1_kernel).
 template <bool VEC, bool XV, int MI, int NI>
@@ -1800,11 +1815,21 @@ int vec_epi_ok(const GemmP& p) {
 struct Rider {
     const HeadBwdP* head = nullptr;      // MODE_DW: critic-head backward workgroups
     const GatherP* gather = nullptr;     // MODE_FWD / MODE_DX: batch-gather workgroups
+    const CorruptP* corrupt = nullptr;   // MODE_FWD: ... that also write the corrupted rows (gm_dvae.h)
     const GemmP* pair = nullptr;         // MODE_DW: a second weight-gradient GEMM
     bool pair_xvec = false;
     const gm_fin2* fin = nullptr;        // MODE_DW pair: the VAE batch's two loss sums + counter tick
     const L1RideP* l1 = nullptr;         // MODE_DW pair: the next iteration's first layer from the second GEMM's W1, b1
 };
+
+// A rider's batch gather as a launch of its own (4 waves per workgroup), for the configurations that cannot carry it.
+inline void launch_gather_alone(hipStream_t s, const Rider& r) {
+    const GatherP& gp = *r.gather;
+    if (r.corrupt)
+        hipLaunchKernelGGL(gather_rows_corrupt_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp, *r.corrupt);
+    else
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp);
+}
 
 // Tile shapes of the 16-wave kernels, as sub-tiles (16 x 16) per wave: MI x NI
 enum { T22 = 0, T24, T42, T12, T23, T32 };       // 32x32, 32x64, 64x32, 16x32, 32x48, 48x32
@@ -1916,8 +1941,7 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
             const int cfg = lds_cfg_for<MODE>(p, vec, xv);
             if (cfg) {
                 if (head) hipLaunchKernelGGL(head_bwd_kernel, dim3(gm_head_bwd_blocks(*head)), dim3(1024), 0, s, *head);
-                if (rider.gather)
-                    hipLaunchKernelGGL(gather_rows_kernel, dim3(gm_gather_blocks(*rider.gather, 4)), dim3(256), 0, s, *rider.gather);
+                if (rider.gather) launch_gather_alone(s, rider);
                 return launch_lds<MODE>(s, p, cfg);
             }
         }
@@ -1926,7 +1950,11 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
     if constexpr (MODE == MODE_FWD) {
         if (vec && p.K <= 32 && !head && !p.hd_part && !p.sq_part) {
             const dim3 kgrid((p.N + 63) / 64, (p.M + 31) / 32);
-            if (rider.gather) {
+            if (rider.gather && rider.corrupt) {                 // the corrupting gather is not compiled into this kernel
+                launch_gather_alone(s, rider);
+                if (slots) hipLaunchKernelGGL((gemm16_k32_fwd_kernel<true, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0);
+                else hipLaunchKernelGGL((gemm16_k32_fwd_kernel<false, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0);
+            } else if (rider.gather) {
                 const GatherP& gp = *rider.gather;
                 const int gblocks = gm_gather_blocks(gp, 4);
                 const int grows = (gblocks + (int)kgrid.x - 1) / (int)kgrid.x;
@@ -2024,11 +2052,17 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
                 const int gblocks = gm_gather_blocks(gp, 16);
                 const int grows = (gblocks + (int)grid.x - 1) / (int)grid.x;
                 const dim3 ggrid(grid.x, grid.y + grows);
+                if (rider.corrupt) {
+                    const CorruptP& cp = *rider.corrupt;
+                    if (tile == T12) hipLaunchKernelGGL((gemm16_fwd_gather_corrupt_kernel<true, 1, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, cp, grows, gblocks);
+                    else hipLaunchKernelGGL((gemm16_fwd_gather_corrupt_kernel<true, 1, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, cp, grows, gblocks);
+                    GM_LAUNCH_RET();
+                }
                 if (tile == T12) hipLaunchKernelGGL((gemm16_fwd_gather_kernel<true, 1, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
                 else hipLaunchKernelGGL((gemm16_fwd_gather_kernel<true, 1, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
                 GM_LAUNCH_RET();
             }
-            hipLaunchKernelGGL(gather_rows_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp);
+            launch_gather_alone(s, rider);
         }
     }
     if constexpr (MODE == MODE_DW) {
@@ -2243,7 +2277,7 @@ extern "C" int gm_linear_fwd_sqerr(void* stream, const float* X, int64_t ldx, co
 
 static int fwd_gather_impl(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
                            const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                           int K, int N, int act, const GatherP& g, float* out);
+                           int K, int N, int act, const GatherP& g, float* out, const CorruptP* corrupt = nullptr);
 
 extern "C" int gm_linear_fwd_gather(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
                                     const float* W, const float* bias, float* Y, int64_t ldy, int M,
@@ -2278,13 +2312,44 @@ extern "C" int gm_linear_fwd_gather_bits_packed(void* stream, const float* X, in
     return fwd_gather_impl(stream, X, ldx, x_slot, W, bias, Y, ldy, M, K, N, act, g, reinterpret_cast<float*>(out_bits));
 }
 
+extern "C" int gm_linear_fwd_gather_corrupt(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
+                                            const float* W, const float* bias, float* Y, int64_t ldy, int M,
+                                            int K, int N, int act, const float* data, int64_t n_rows,
+                                            const int64_t* idx, gm_slot idx_slot, float* out,
+                                            int64_t ld_out, int B, int row_elems, float* out_c,
+                                            const gm_corrupt_args* a) {
+    GatherP g{};
+    CorruptP c{};
+    int rc = gm_gather_fill(data, n_rows, idx, idx_slot, out, ld_out, B, row_elems, &g);
+    if (rc) return rc;
+    rc = gm_gather_corrupt_fill(a, out_c, &g, &c);
+    if (rc) return rc;
+    return fwd_gather_impl(stream, X, ldx, x_slot, W, bias, Y, ldy, M, K, N, act, g, out, &c);
+}
+
+extern "C" int gm_linear_fwd_gather_bits_corrupt(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
+                                                 const float* W, const float* bias, float* Y, int64_t ldy, int M,
+                                                 int K, int N, int act, const uint32_t* bits, int words_per_row,
+                                                 int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out,
+                                                 int64_t ld_out, int B, int row_elems, float* out_c,
+                                                 const gm_corrupt_args* a) {
+    GatherP g{};
+    CorruptP c{};
+    int rc = gm_gather_fill_bits(bits, words_per_row, n_rows, idx, idx_slot, out, ld_out, B, row_elems, &g);
+    if (rc) return rc;
+    rc = gm_gather_corrupt_fill(a, out_c, &g, &c);
+    if (rc) return rc;
+    return fwd_gather_impl(stream, X, ldx, x_slot, W, bias, Y, ldy, M, K, N, act, g, out, &c);
+}
+
 static int fwd_gather_impl(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
                            const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                           int K, int N, int act, const GatherP& g, float* out) {
+                           int K, int N, int act, const GatherP& g, float* out, const CorruptP* corrupt) {
     GM_CHECK_ARG(X && W && Y && M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= N);
     GM_CHECK_ARG(act >= GM_ACT_ID && act <= GM_ACT_SIGMOID);
     // the gathered rows must not be an operand or the output of this GEMM
     GM_CHECK_ARG(out != Y && out != X);
+    GM_CHECK_ARG(!corrupt || (corrupt->out_c != Y && (const float*)corrupt->out_c != X));
     GemmP p{};
     p.A = X; p.B = W; p.C = Y; p.M = M; p.N = N; p.K = K;
     p.lda = ldx; p.ldb = K; p.ldc = ldy; p.bias = bias; p.epi = act;
@@ -2293,6 +2358,7 @@ static int fwd_gather_impl(void* stream, const float* X, int64_t ldx, gm_slot x_
                      (x_slot.stride % 4 == 0);
     Rider r;
     r.gather = &g;
+    r.corrupt = corrupt;
     return launch<MODE_FWD>((hipStream_t)stream, p, vec, false, r);
 }
 

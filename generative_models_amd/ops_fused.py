@@ -407,3 +407,85 @@ def bgan_head(h, w2, b2, mode, B, Jg, Jd, ws, gw2=None, gb2=None, loss_out=None,
     a = _lib.BganHeadArgs(h.data_ptr(), h.stride(0), w2.data_ptr(), b2.data_ptr(), ptr(gw2), ptr(gb2), ptr(loss_out),
                           loss_slot, ws.data_ptr(), ws.numel() * 4, mode, B, Jg, Jd, H)
     _lib.call("gm_bgan_head", stream or stream_ptr(), ctypes.byref(a))
+
+
+# ---- Denoising VAE (csrc/gm_dvae.hip, gm_dvae.h; dvae.py) ---------------------------------------------------------
+def corrupt_args(noise, level, seed, step=0, step_ctr=None, step_base=None, row0=0):
+    """A gm_corrupt_args block: noise "salt_pepper" / "gaussian" (or a GM_NOISE_* int), its level, the seed
+    (0 <= seed < 2^64) and the training-batch step = *step_ctr + *step_base + step (int64 device tensors, or None for
+    0).  The tensors must outlive every launch (and every captured graph) that reads them."""
+    kind = _lib.NOISE[noise] if isinstance(noise, str) else int(noise)
+    for t, nm in ((step_ctr, "step_ctr"), (step_base, "step_base")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int64):
+            raise _lib.GMError("corrupt_args: %s must be an int64 device tensor" % nm)
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise _lib.GMError("corrupt_args: seed must lie in [0, 2^64)")
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    return _lib.CorruptArgs(kind, float(level), seed, ptr(step_ctr), ptr(step_base), int(step), int(row0))
+
+
+def _rows2d(x, name):
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1):
+        raise _lib.GMError("%s must be a 2-D float32 device tensor with contiguous rows" % name)
+    return x
+
+
+def dvae_corrupt(x, args, out=None, stream=None):
+    """out[r] = the corruption of row r of x (gm_dvae_corrupt; row r is batch position args.row0 + r).  out=None: a
+    new tensor; out may be x itself."""
+    _rows2d(x, "x")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    _rows2d(out, "out")
+    if tuple(out.shape) != tuple(x.shape):
+        raise _lib.GMError("dvae_corrupt: out %s does not match x %s" % (tuple(out.shape), tuple(x.shape)))
+    _lib.call("gm_dvae_corrupt", stream or stream_ptr(), ctypes.byref(args), x.data_ptr(), x.stride(0),
+              out.data_ptr(), out.stride(0), x.shape[0], x.shape[1])
+    return out
+
+
+def _corrupt_out(out, out_c):
+    _rows2d(out_c, "out_c")
+    if _ld(out_c) != _ld(out) or out_c.shape[1] != out.shape[1]:
+        raise _lib.GMError("the corrupted rows must have the clean rows' shape and row stride")
+
+
+def gather_rows_corrupt(data, idx, out, out_c, args, B=None, idx_slot=NO_SLOT, stream=None):
+    """ops.gather_rows(data, idx, out) that also writes the corrupted rows to out_c (gm_gather_rows[_bits]_corrupt)."""
+    from .ops import PackedData
+    n_rows, row = data.shape
+    B = out.shape[0] if B is None else B
+    if not (idx.dtype == torch.int64 and idx.is_cuda):
+        raise _lib.GMError("gather_rows_corrupt: idx must be an int64 device tensor")
+    _rows2d(out, "out")
+    _corrupt_out(out, out_c)
+    if isinstance(data, PackedData):
+        _lib.call("gm_gather_rows_bits_corrupt", stream or stream_ptr(), ctypes.byref(args), data.data_ptr(), data.wpr,
+                  n_rows, idx.data_ptr(), idx_slot, out.data_ptr(), out_c.data_ptr(), _ld(out), B, row)
+    else:
+        _lib.call("gm_gather_rows_corrupt", stream or stream_ptr(), ctypes.byref(args), _rows2d(data, "data").data_ptr(),
+                  n_rows, idx.data_ptr(), idx_slot, out.data_ptr(), out_c.data_ptr(), _ld(out), B, row)
+    return out
+
+
+def linear_fwd_gather_corrupt(x, W, b, y, act, data, idx, out, out_c, args, M=None, B=None, x_slot=NO_SLOT,
+                              idx_slot=NO_SLOT, stream=None):
+    """ops.linear_fwd_gather with the corrupting gather riding in the GEMM's grid (gm_linear_fwd_gather[_bits]_corrupt):
+    out gets the clean rows, out_c their corruption; neither may be an operand of this GEMM."""
+    from .ops import ACT, PackedData, _chk
+    N, K = W.shape
+    M = x.shape[0] if M is None else M
+    n_rows, row = data.shape
+    B = out.shape[0] if B is None else B
+    _rows2d(out, "out")
+    _corrupt_out(out, out_c)
+    head = (stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x), x_slot, _chk(W, "W").data_ptr(),
+            b.data_ptr() if b is not None else None, _chk(y, "y").data_ptr(), _ld(y), M, K, N, ACT[act])
+    if isinstance(data, PackedData):
+        _lib.call("gm_linear_fwd_gather_bits_corrupt", *head, data.data_ptr(), data.wpr, n_rows, idx.data_ptr(),
+                  idx_slot, out.data_ptr(), _ld(out), B, row, out_c.data_ptr(), ctypes.byref(args))
+    else:
+        _lib.call("gm_linear_fwd_gather_corrupt", *head, _rows2d(data, "data").data_ptr(), n_rows, idx.data_ptr(),
+                  idx_slot, out.data_ptr(), _ld(out), B, row, out_c.data_ptr(), ctypes.byref(args))
+    return y

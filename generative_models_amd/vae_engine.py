@@ -161,7 +161,15 @@ class VAEEngine:
         nxt = self.Xb[(pos + 1) % 2] if (self.prefetch_gather and pos + 1 < of) else None
         return X, (pos == 0 or not self.prefetch_gather), nxt
 
-    def _fwd_with_prefetch(self, st, t, lo, b, x, lin, y, act, nxt):
+    def _encoder_rows(self, X, train):
+        """The rows the encoder's first layer reads for the batch whose clean rows are X: X itself."""
+        return X
+
+    def _gather_own(self, st, t, lo, b, X, idx_slot, train):
+        """The batch's own gather launch (the first batch of a graph, or every batch without prefetching)."""
+        ops.gather_rows(self.data, self.idx_ring.view(-1)[lo:], X, B=b, idx_slot=idx_slot, stream=st)
+
+    def _fwd_with_prefetch(self, st, t, lo, b, x, lin, y, act, nxt, train=True):
         """linear_fwd, carrying the gather of the next batch's rows (ring slot t + 1) when asked to."""
         if nxt is None:
             ops.linear_fwd(x, lin.W, lin.b, y, act, M=b, stream=st)
@@ -182,10 +190,11 @@ class VAEEngine:
         lo, hi = self._rows(b)                       # this rank's rows of the batch
         b = hi - lo
         X, own, nxt = self._gather_plan(pos, of)
+        Xe = self._encoder_rows(X, train)            # what the encoder reads (DVAEEngine: the corrupted rows)
         if own:
-            ops.gather_rows(self.data, self.idx_ring.view(-1)[lo:], X, B=b, idx_slot=idx_slot, stream=st)
-        ops.linear_fwd(X, E1.W, E1.b, self.He, "relu", M=b, stream=st)
-        self._fwd_with_prefetch(st, t, lo, b, self.He, ML, self.ml, "id", nxt)
+            self._gather_own(st, t, lo, b, X, idx_slot, train)
+        ops.linear_fwd(Xe, E1.W, E1.b, self.He, "relu", M=b, stream=st)
+        self._fwd_with_prefetch(st, t, lo, b, self.He, ML, self.ml, "id", nxt, train=train)
         eps_base = self.eps_ring.view(-1)[lo * Z:]
         if self.fuse_reparam_fwd and Z <= 32 and Z % 4 == 0:
             # reparameterisation + the decoder's first layer: ONE launch (the GEMM workgroups form z from
@@ -242,12 +251,12 @@ class VAEEngine:
                 # the batch's LAST launch: the encoder's two weight gradients + Adam, both loss sums (vae.py:203, :212)
                 # in one more workgroup of the same grid, the counter tick by the last workgroup to finish
                 ops.linear_bwd_dw_adam_pair_finalize(
-                    dict(dA=self.dHe, X=X, lin=E1, adam=adam, M=b), dict(dA=self.dml, X=self.He, lin=ML, adam=adam, M=b),
+                    dict(dA=self.dHe, X=Xe, lin=E1, adam=adam, M=b), dict(dA=self.dml, X=self.He, lin=ML, adam=adam, M=b),
                     dict(pa=part, na=n_part, out_a=recon_out, slot_a=loss_slot, pb=self.part_kl, nb=n_kl, out_b=kl_out,
                          slot_b=loss_slot, done=self.fin_done, tick=self.ctr if self.use_graph else None),
                     weight_decay=self.wd, stream=st)
                 return
-            dw2((self.dHe, X, E1), (self.dml, self.He, ML))    # (the big GEMM first: its tile shape serves both)
+            dw2((self.dHe, Xe, E1), (self.dml, self.He, ML))    # (the big GEMM first: its tile shape serves both)
             self._optimizer_step(st, sched_slot)
         # both loss sums (vae.py:203, :212) are the step's LAST launch, which also carries the counter tick
         of_.sum_finalize2(part, n_part, recon_out, loss_slot, self.part_kl, n_kl, kl_out, loss_slot,
@@ -719,6 +728,78 @@ class CVAEEngine(VAEEngine):
             dict(pa=part, na=n_part, out_a=recon_out, slot_a=loss_slot, pb=self.part_kl, nb=n_kl, out_b=kl_out,
                  slot_b=loss_slot, done=self.fin_done, tick=self.ctr if self.use_graph else None),
             weight_decay=self.wd, stream=st)
+
+
+class DVAEEngine(VAEEngine):
+    """The denoising VAE (dvae.py) on the VAE engine's batch.  Three differences, training batches only:
+      * the batch's gathers are the corrupting ones (gm_gather_rows[_bits]_corrupt for a graph's first batch, the
+        corrupting gather riding in the [mu | log_var] forward for the others), which write the clean rows to Xb and
+        their corruption to the double-buffered Xcb;
+      * the encoder's first layer reads the corrupted rows, in its forward and in its weight gradient;
+      * nothing else: the reconstruction loss still reads the clean rows.
+    Still 8 launches per batch.  The noise step of a training batch is ctr + nbase (+ 1 for the riding gather, which
+    fills the NEXT batch): ctr is the engine's device counter, nbase a device word configure() writes from the
+    trainer's count of training batches, so a graph captured in one train() call serves the next.  Validation batches
+    are the VAE's, clean.  One GPU only."""
+
+    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
+                 trainer=None):
+        if world_size > 1 or force_dp:
+            raise GMError("the DVAE engine runs on one GPU: data parallelism is not implemented for it")
+        super().__init__(model, device, use_graph=use_graph)
+        self.trainer = trainer                       # noise, level, seed and noise_steps are read from it
+        self.nbase = torch.zeros(1, dtype=torch.int64, device=device)
+
+    def _alloc(self, B):
+        if self._bufB == B:
+            return
+        super()._alloc(B)
+        self.Xcb = (torch.zeros(B, self.I, device=self.device), torch.zeros(B, self.I, device=self.device))
+
+    def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
+        tr = self.trainer
+        now = {"noise": tr.noise, "level": float(tr.level), "seed": int(tr.seed)}
+        if resume is not None and resume.get("config") is not None and not resume.get("lenient", False):
+            saved = resume["config"]
+            diff = {k: (saved[k], now[k]) for k in now if k in saved and saved[k] != now[k]}
+            if diff:
+                raise GMError("checkpoint was written by a run with different settings (saved, now): %s; "
+                              "load_checkpoint(path, strict=False) overrides" % diff)
+        super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
+        self.run_config.update(now)
+        if getattr(self, "_noise_key", None) != tuple(now.values()):
+            self.graphs = {}                         # the rule and the seed are launch arguments of the graphs
+        self._noise_key = tuple(now.values())
+        self.nbase.fill_(int(tr.noise_steps))
+
+    def _xc(self, X):
+        return self.Xcb[0] if X is self.Xb[0] else self.Xcb[1]
+
+    def _cargs(self, t, add):
+        """The corruption of the batch at ring step t (+ add): graphs read ctr + nbase, eager launches t + nbase."""
+        from . import ops_fused as of_
+        tr = self.trainer
+        if self.use_graph:
+            return of_.corrupt_args(tr.noise, tr.level, tr.seed, step=add, step_ctr=self.ctr, step_base=self.nbase)
+        return of_.corrupt_args(tr.noise, tr.level, tr.seed, step=t + add, step_base=self.nbase)
+
+    def _encoder_rows(self, X, train):
+        return self._xc(X) if train else X
+
+    def _gather_own(self, st, t, lo, b, X, idx_slot, train):
+        if not train:
+            return super()._gather_own(st, t, lo, b, X, idx_slot, train)
+        from . import ops_fused as of_
+        of_.gather_rows_corrupt(self.data, self.idx_ring.view(-1)[lo:], X, self._xc(X), self._cargs(t, 0), B=b,
+                                idx_slot=idx_slot, stream=st)
+
+    def _fwd_with_prefetch(self, st, t, lo, b, x, lin, y, act, nxt, train=True):
+        if not train or nxt is None:
+            return super()._fwd_with_prefetch(st, t, lo, b, x, lin, y, act, nxt, train=train)
+        from . import ops_fused as of_
+        of_.linear_fwd_gather_corrupt(x, lin.W, lin.b, y, act, self.data, self.idx_ring.view(-1)[lo:], nxt,
+                                      self._xc(nxt), self._cargs(t, 1), M=b, B=b,
+                                      idx_slot=self._slot(t, 1, 1, self.R, self.B), stream=st)
 
 
 def aae_fused_ok(model):

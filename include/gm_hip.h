@@ -820,6 +820,49 @@ int64_t gm_bgan_head_workspace_bytes(int mode, int B, int Jg, int Jd, int H);
  * terms); dH = dlogit w2_k [h > 0] in place; gw2, gb2 and the loss sums in a fixed order, no atomics. */
 int gm_bgan_head(void* stream, const gm_bgan_head_args* a);
 
+/* ---- Denoising VAE (NEW: the reference's README to-do list "denoising VAE"; generative_models_amd/dvae.py, DESIGN.md
+ * section 15).  Input corruption x~ ~ p(x~ | x) on the device: Philox4x32-10 (the Bayesian GAN's generator) with key
+ * (seed mod 2^32, seed >> 32) and counter (e >> 2, step, row, 0x44564145); pixel e of a row takes word e & 3.
+ *   GM_NOISE_SALT_PEPPER, level p in [0, 1]: T = floor(p 2^31); u < T -> 0, else u - T < T -> 1, else x.
+ *   GM_NOISE_GAUSSIAN, level sigma >= 0: fmaf(sigma, n, x), n the Box-Muller normal of that word (as gm_philox_normal).
+ * Level 0 (or GM_NOISE_NONE) returns x bit for bit.  step = (step_ctr ? *step_ctr : 0) + (step_base ? *step_base : 0)
+ * + step_add (truncated to 32 bits), so a captured graph reads a device counter plus a device base; row = row0 + the
+ * row's position in the call.  A bad kind, a non-finite or negative level or p > 1 returns GM_EINVAL. */
+#define GM_NOISE_NONE 0
+#define GM_NOISE_SALT_PEPPER 1
+#define GM_NOISE_GAUSSIAN 2
+typedef struct gm_corrupt_args {
+    int kind;                                 /* GM_NOISE_* */
+    double level;                             /* p (salt-and-pepper) or sigma (gaussian) */
+    uint64_t seed;
+    const int64_t* step_ctr;                  /* device counter or NULL */
+    const int64_t* step_base;                 /* device base or NULL */
+    int64_t step_add;
+    int64_t row0;                             /* batch position of the first row (>= 0) */
+} gm_corrupt_args;
+/* out[r][e] = corrupt(x[r][e]) for rows r < rows (rows ldx / ldo floats apart; in place when out == x, ldx == ldo). */
+int gm_dvae_corrupt(void* stream, const gm_corrupt_args* a, const float* x, int64_t ldx, float* out, int64_t ldo,
+                    int64_t rows, int row_elems);
+/* gm_gather_rows / gm_gather_rows_bits that also write the corrupted copy of every gathered row to out_c (same ld_out;
+ * out_c must be none of data, out).  out is exactly what the plain gather writes. */
+int gm_gather_rows_corrupt(void* stream, const gm_corrupt_args* a, const float* data, int64_t n_rows,
+                           const int64_t* idx, gm_slot idx_slot, float* out, float* out_c, int64_t ld_out, int B,
+                           int row_elems);
+int gm_gather_rows_bits_corrupt(void* stream, const gm_corrupt_args* a, const uint32_t* bits, int words_per_row,
+                                int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out, float* out_c,
+                                int64_t ld_out, int B, int row_elems);
+/* gm_linear_fwd_gather / gm_linear_fwd_gather_bits with the corrupting gather riding in the GEMM's grid (the VAE
+ * engine's [mu | log_var] forward carrying the NEXT batch's rows; out_c must not be an operand or the output either). */
+int gm_linear_fwd_gather_corrupt(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
+                                 const float* bias, float* Y, int64_t ldy, int M, int K, int N, int act,
+                                 const float* data, int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out,
+                                 int64_t ld_out, int B, int row_elems, float* out_c, const gm_corrupt_args* a);
+int gm_linear_fwd_gather_bits_corrupt(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
+                                      const float* bias, float* Y, int64_t ldy, int M, int K, int N, int act,
+                                      const uint32_t* bits, int words_per_row, int64_t n_rows, const int64_t* idx,
+                                      gm_slot idx_slot, float* out, int64_t ld_out, int B, int row_elems,
+                                      float* out_c, const gm_corrupt_args* a);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

@@ -79,3 +79,11 @@ def host_thread_plan():
                          "torch_intraop": torch.get_num_threads()},
             "busy_threads_on_node": ranks * 2,
             "fits_quota": (q is None) or (ranks * 2 <= q)}
+
+
+def __getattr__(name):
+    """PDWGAN / PDWGANTrainer / PDWGANEngine, imported on first use (importing the package stays free of torch)."""
+    if name in ("PDWGAN", "PDWGANTrainer", "PDWGANEngine"):
+        from . import pdwgan
+        return getattr(pdwgan, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -349,6 +349,10 @@ _SIGNATURES = {
     "gm_linear_fwd_gather_bits_corrupt": (c_int, [_P, _P, c_int64, Slot, _P, _P, _P, c_int64, c_int, c_int, c_int,
                                                   c_int, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int, _P,
                                                   POINTER(CorruptArgs)]),
+    "gm_pdw_couple": (c_int, [_P, _P, c_int64, _P, c_int64, _P, Slot, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64,
+                              c_float, c_int, c_int]),
+    "gm_pdw_dir": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_float, c_float, c_int,
+                           c_int]),
 }
 
 _lib = None

@@ -489,3 +489,37 @@ def linear_fwd_gather_corrupt(x, W, b, y, act, data, idx, out, out_c, args, M=No
         _lib.call("gm_linear_fwd_gather_corrupt", *head, _rows2d(data, "data").data_ptr(), n_rows, idx.data_ptr(),
                   idx_slot, out.data_ptr(), _ld(out), B, row, out_c.data_ptr(), ctypes.byref(args))
     return y
+
+
+# ---- Primal-Dual Wasserstein GAN (csrc/gm_pdw.hip; pdwgan.py) -----------------------------------------------------
+def pdw_couple(x, xr, share, B, inv_b=None, n=None, t=None, t_slot=NO_SLOT, dA=None, xhat=None, xcopy=None,
+               stream=None):
+    """The primal coupling of B image rows x with their reconstructions xr (gm_pdw_couple): share[b] = ||x_b - xr_b||
+    * inv_b (inv_b: 1 / B by default), n[b] the norm itself, dA = d share / d (pre-sigmoid xr), xhat = t x + (1 - t)
+    xr with t the t_slot row of the uniform ring, xcopy = x.  n, dA, xhat (with t) and xcopy are optional."""
+    I = x.shape[1]
+    for a, nm in ((x, "x"), (xr, "xr"), (dA, "dA"), (xhat, "xhat"), (xcopy, "xcopy")):
+        if a is not None and (_rows2d(a, nm).shape[0] < B or a.shape[1] != I):
+            raise _lib.GMError("pdw_couple: %s must be [>= %d, %d], got %s" % (nm, B, I, tuple(a.shape)))
+    if share.numel() < B or (n is not None and n.numel() < B) or (xhat is not None and t is None):
+        raise _lib.GMError("pdw_couple: share / n hold one float per row, and xhat needs t")
+    if inv_b is None:
+        import numpy as np
+        inv_b = float(np.float32(1.0) / np.float32(B))
+    p = lambda a: a.data_ptr() if a is not None else None
+    ld = lambda a: _ld(a) if a is not None else 0
+    _lib.call("gm_pdw_couple", stream or stream_ptr(), x.data_ptr(), _ld(x), xr.data_ptr(), _ld(xr), p(t), t_slot,
+              p(n), share.data_ptr(), p(dA), ld(dA), p(xhat), ld(xhat), p(xcopy), ld(xcopy), inv_b, B, I)
+
+
+def pdw_dir(g, x, xr, n, gamma, pen, lam, inv_b, stream=None):
+    """PD-WGAN's direction penalty in gp_norm's place (gm_pdw_dir): pen[b] = ||g_b - d_b||^2 and gamma_b = lam * inv_b
+    * 2 (g_b - d_b) with d_b = (x_b - xr_b) / n_b (0 where n_b == 0); the row count is g's."""
+    B, I = g.shape
+    for a, nm in ((g, "g"), (x, "x"), (xr, "xr"), (gamma, "gamma")):
+        if _rows2d(a, nm).shape[0] < B or a.shape[1] != I:
+            raise _lib.GMError("pdw_dir: %s must be [>= %d, %d], got %s" % (nm, B, I, tuple(a.shape)))
+    if n.numel() < B or pen.numel() < B:
+        raise _lib.GMError("pdw_dir: n and pen hold one float per row")
+    _lib.call("gm_pdw_dir", stream or stream_ptr(), g.data_ptr(), _ld(g), x.data_ptr(), _ld(x), xr.data_ptr(), _ld(xr),
+              n.data_ptr(), gamma.data_ptr(), _ld(gamma), pen.data_ptr(), lam, inv_b, B, I)

@@ -281,6 +281,7 @@ class VAEEngine:
         self.fp.grad.zero_()
         self.step0 = 0
         self.run_config = {"B": int(B), "lr": float(lr), "weight_decay": float(weight_decay)}
+        self.run_config.update(getattr(self, "_extra_config", {}))    # a subclass's own settings, compared below too
         if resume is not None:                       # see GANEngine.configure
             saved = resume.get("config")
             if saved is not None and not resume.get("lenient", False):

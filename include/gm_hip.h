@@ -863,6 +863,23 @@ int gm_linear_fwd_gather_bits_corrupt(void* stream, const float* X, int64_t ldx,
                                       gm_slot idx_slot, float* out, int64_t ld_out, int B, int row_elems,
                                       float* out_c, const gm_corrupt_args* a);
 
+/* ---- Primal-Dual Wasserstein GAN (csrc/gm_pdw.hip; pdwgan.py).  One wave per row, fixed
+ * reduction order, no atomics.
+ * The primal coupling (pdwgan.PDWGANEngine phase 1, after the decoder's output layer): per row of x [B, I] and its
+ * reconstruction xr, n[b] = ||x_b - xr_b||_2 (n may be NULL), share[b] = n_b * inv_b (the row's share of mean_b n_b),
+ * dA = d share / d (pre-sigmoid xr) = -(d_b * inv_b) xr (1 - xr) with d_b = (x_b - xr_b) / n_b (0 where n_b == 0),
+ * xhat = t_b x + (1 - t_b) xr with t = the slot's row of the uniform ring (two rounded products and an add, as
+ * gm_interp), xcopy = x.  dA / xhat / xcopy may each be NULL (validation passes all three NULL); xhat and xcopy are
+ * row blocks of the critic's stacked input, so no gm_interp launch and no copy is needed. */
+int gm_pdw_couple(void* stream, const float* x, int64_t ldx, const float* xr, int64_t ldr, const float* t,
+                  gm_slot t_slot, float* n, float* share, float* dA, int64_t ldd, float* xhat, int64_t ldh,
+                  float* xcopy, int64_t ldc, float inv_b, int B, int I);
+/* The direction penalty (phase 2, in gm_gp_norm's place and with its conventions): g [B, I] = the critic's input
+ * gradient at xhat, pen[b] = ||g_b - d_b||^2, gamma_b = lambda * inv_b * 2 (g_b - d_b), d_b rebuilt from x, xr and
+ * n (gm_pdw_couple's); a row with x_b == xr_b has d_b = 0. */
+int gm_pdw_dir(void* stream, const float* g, int64_t ldg, const float* x, int64_t ldx, const float* xr, int64_t ldr,
+               const float* n, float* gamma, int64_t ldm, float* pen, float lambda, float inv_b, int B, int I);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

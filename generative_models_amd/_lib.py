@@ -64,13 +64,15 @@ class LabelGradArgs(ctypes.Structure):
 
 
 class DwAdamArgs(ctypes.Structure):
-    """gm_dw_adam_args (include/gm_hip.h): gm_linear_bwd_dw_adam's arguments as one block."""
+    """gm_dw_adam_args (include/gm_hip.h): one weight gradient of gm_linear_bwd_dw_ex (+ Adam, + the riding head)."""
     _fields_ = [("dA", c_void_p), ("lda", c_int64), ("X", c_void_p), ("ldx", c_int64),
                 ("x_slot", Slot), ("dW", c_void_p), ("db", c_void_p), ("M", c_int), ("K", c_int),
                 ("N", c_int), ("pW", c_void_p), ("mW", c_void_p), ("vW", c_void_p),
                 ("pb", c_void_p), ("mb", c_void_p), ("vb", c_void_p), ("sched", c_void_p),
                 ("sched_slot", Slot), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
-                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("clamp", c_float)]
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("clamp", c_float),
+                ("accumulate", c_int), ("ones_from", c_int), ("head", POINTER(HeadBwdArgs)),
+                ("fold", POINTER(HeadFoldArgs)), ("xbits", c_void_p), ("xbits_wpr", c_int), ("xbits_rows", c_int)]
 
 
 class AAECriticArgs(ctypes.Structure):
@@ -130,6 +132,43 @@ class Finalize2Args(ctypes.Structure):
                 ("tick", c_void_p), ("done", c_void_p)]
 
 
+class DwTail(ctypes.Structure):
+    """gm_dw_tail (include/gm_hip.h): what a pair of weight gradients carries -- the next first layer, or the sums."""
+    _fields_ = [("z", c_void_p), ("ldz", c_int64), ("z_slot", Slot), ("H", c_void_p), ("ldh", c_int64),
+                ("rows", c_int), ("fin", POINTER(Finalize2Args))]
+
+
+class GatherArgs(ctypes.Structure):
+    """gm_gather_args (include/gm_hip.h): one batch gather riding in a forward / input-gradient launch."""
+    _fields_ = [("data", c_void_p), ("bits", c_void_p), ("words_per_row", c_int), ("n_rows", c_int64),
+                ("idx", c_void_p), ("idx_slot", Slot), ("out", c_void_p), ("ld_out", c_int64),
+                ("out_bits", c_void_p), ("B", c_int), ("row_elems", c_int), ("corrupt", POINTER(CorruptArgs)),
+                ("out_c", c_void_p)]
+
+
+class FwdArgs(ctypes.Structure):
+    """gm_fwd_args (include/gm_hip.h): gm_linear_fwd_ex -- the base GEMM and at most one optional block."""
+    _fields_ = [("X", c_void_p), ("ldx", c_int64), ("x_slot", Slot), ("W", c_void_p), ("bias", c_void_p),
+                ("Y", c_void_p), ("ldy", c_int64), ("M", c_int), ("K", c_int), ("N", c_int), ("act", c_int),
+                ("ip_eps", c_void_p), ("ip_slot", Slot), ("ip_x", c_void_p), ("ip_ldx", c_int64),
+                ("ip_out", c_void_p), ("ip_ldo", c_int64), ("ip_rows", c_int),
+                ("hd_w2", c_void_p), ("hd_b2", c_void_p), ("hd_part", c_void_p), ("hd_ldp", c_int64),
+                ("hd_snap", c_void_p), ("xbits", c_void_p), ("xbits_wpr", c_int), ("xbits_rows", c_int),
+                ("sq_target", c_void_p), ("sq_ldt", c_int64), ("sq_dA", c_void_p), ("sq_lda", c_int64),
+                ("sq_part", c_void_p), ("sq_ldp", c_int64),
+                ("lb_E", c_void_p), ("lb_C", c_int), ("lb", LabelSrc), ("gather", POINTER(GatherArgs))]
+
+
+class DxArgs(ctypes.Structure):
+    """gm_dx_args (include/gm_hip.h): gm_linear_bwd_dx_ex -- the base GEMM and at most one optional block."""
+    _fields_ = [("dA", c_void_p), ("lda", c_int64), ("W", c_void_p), ("dX", c_void_p), ("ldx", c_int64),
+                ("below", c_void_p), ("ld_below", c_int64), ("M", c_int), ("K", c_int), ("N", c_int), ("epi", c_int),
+                ("add", c_void_p), ("ldadd", c_int64), ("add_scale", c_float),
+                ("head", POINTER(HeadBwdArgs)), ("fold", POINTER(HeadFoldArgs)),
+                ("rp_ml", c_void_p), ("rp_ldml", c_int64), ("rp_eps", c_void_p), ("rp_slot", Slot),
+                ("rp_dml", c_void_p), ("rp_ldd", c_int64), ("gather", POINTER(GatherArgs))]
+
+
 class DrawOp(ctypes.Structure):
     """gm_draw_op (include/gm_hip.h): one draw of the per-iteration host RNG program."""
     _fields_ = [("kind", c_int32), ("n", c_int32), ("a", c_int64), ("b", c_int32), ("c", c_int32),
@@ -161,6 +200,9 @@ _SIGNATURES = {
                                  c_int, c_int]),
     "gm_linear_bwd_dw": (c_int, [_P, _P, c_int64, _P, c_int64, Slot, _P, _P, c_int, c_int, c_int,
                                  c_int]),
+    "gm_linear_fwd_ex": (c_int, [_P, POINTER(FwdArgs)]),
+    "gm_linear_bwd_dx_ex": (c_int, [_P, POINTER(DxArgs)]),
+    "gm_linear_bwd_dw_ex": (c_int, [_P, POINTER(DwAdamArgs), POINTER(DwAdamArgs), POINTER(DwTail)]),
     "gm_gan_loss": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, POINTER(c_float), c_int,
                             c_float, _P, Slot, _P, _P, _P, _P]),
     "gm_gan_loss_phase": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, POINTER(c_float), c_int,
@@ -190,56 +232,8 @@ _SIGNATURES = {
                                c_int, c_int, c_int]),
     "gm_vae_reparam_fwd": (c_int, [_P, _P, c_int64, _P, Slot, _P, c_int64, _P, c_int, c_int, c_int, _P, _P, _P,
                                    c_int64, c_int, c_int]),
-    "gm_linear_bwd_dw_adam": (c_int, [_P, _P, c_int64, _P, c_int64, Slot, _P, _P, c_int, c_int, c_int,
-                                      _P, _P, _P, _P, _P, _P, _P, Slot, ctypes.c_double,
-                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, c_float]),
-    "gm_linear_fwd_interp": (c_int, [_P, _P, c_int64, Slot, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int,
-                                     _P, Slot, _P, c_int64, _P, c_int64, c_int]),
-    "gm_linear_fwd_gather": (c_int, [_P, _P, c_int64, Slot, _P, _P, _P, c_int64, c_int, c_int, c_int,
-                                     c_int, _P, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
-    "gm_linear_fwd_gather_bits": (c_int, [_P, _P, c_int64, Slot, _P, _P, _P, c_int64, c_int, c_int, c_int,
-                                          c_int, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
     "gm_gather_rows_bits": (c_int, [_P, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
-    "gm_linear_bwd_dx_head": (c_int, [_P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int,
-                                      c_int, c_int, POINTER(HeadBwdArgs)]),
-    "gm_linear_bwd_dx_head_fold": (c_int, [_P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int,
-                                           c_int, c_int, POINTER(HeadBwdArgs), POINTER(HeadFoldArgs)]),
-    "gm_linear_fwd_sqerr": (c_int, [_P, _P, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, _P, c_int64,
-                                    _P, c_int64, _P, c_int64]),
-    "gm_linear_bwd_dx_reparam": (c_int, [_P, _P, c_int64, _P, _P, c_int64, c_int, c_int, c_int, _P, c_int64,
-                                         _P, Slot, _P, c_int64]),
-    "gm_linear_fwd_headpart": (c_int, [_P, _P, c_int64, Slot, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int,
-                                       _P, _P, _P, c_int64, _P]),
-    "gm_linear_bwd_dw_adam_head_fold": (c_int, [_P, _P, c_int64, _P, c_int64, Slot, _P, _P, c_int, c_int,
-                                                c_int, _P, _P, _P, _P, _P, _P, _P, Slot, ctypes.c_double,
-                                                ctypes.c_double, ctypes.c_double, ctypes.c_double, c_float,
-                                                POINTER(HeadBwdArgs), POINTER(HeadFoldArgs)]),
     "gm_gather_rows_bits_packed": (c_int, [_P, _P, c_int, c_int64, _P, Slot, _P, c_int]),
-    "gm_linear_fwd_gather_bits_packed": (c_int, [_P, _P, c_int64, Slot, _P, _P, _P, c_int64, c_int, c_int, c_int,
-                                                 c_int, _P, c_int, c_int64, _P, Slot, _P, c_int]),
-    "gm_linear_fwd_headpart_bits": (c_int, [_P, _P, c_int64, Slot, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int,
-                                            _P, _P, _P, c_int64, _P, _P, c_int, c_int]),
-    "gm_linear_bwd_dw_adam_head_fold_bits": (c_int, [_P, _P, c_int64, _P, c_int64, Slot, _P, _P, c_int, c_int,
-                                                     c_int, _P, _P, _P, _P, _P, _P, _P, Slot, ctypes.c_double,
-                                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, c_float,
-                                                     POINTER(HeadBwdArgs), POINTER(HeadFoldArgs), _P, c_int, c_int]),
-    "gm_linear_bwd_dw_adam_pair": (c_int, [_P, POINTER(DwAdamArgs), POINTER(DwAdamArgs)]),
-    "gm_linear_bwd_dw_adam_pair_l1": (c_int, [_P, POINTER(DwAdamArgs), POINTER(DwAdamArgs), _P, c_int64, Slot, _P,
-                                              c_int64, c_int]),
-    "gm_linear_bwd_dx_gather": (c_int, [_P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int, c_int, c_int,
-                                        _P, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
-    "gm_linear_bwd_dx_gather_bits": (c_int, [_P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int, c_int,
-                                             c_int, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
-    "gm_linear_bwd_dw_adam_pair_finalize": (c_int, [_P, POINTER(DwAdamArgs), POINTER(DwAdamArgs),
-                                                    POINTER(Finalize2Args)]),
-    "gm_linear_bwd_dw_adam_head": (c_int, [_P, _P, c_int64, _P, c_int64, Slot, _P, _P, c_int, c_int,
-                                           c_int, _P, _P, _P, _P, _P, _P, _P, Slot, ctypes.c_double,
-                                           ctypes.c_double, ctypes.c_double, ctypes.c_double, c_float,
-                                           POINTER(HeadBwdArgs)]),
-    "gm_linear_bwd_dw_adam_head_ex": (c_int, [_P, _P, c_int64, _P, c_int64, Slot, _P, _P, c_int, c_int,
-                                              c_int, _P, _P, _P, _P, _P, _P, _P, Slot, ctypes.c_double,
-                                              ctypes.c_double, ctypes.c_double, ctypes.c_double, c_float,
-                                              POINTER(HeadBwdArgs), c_int]),
     "gm_gp_dw2_store": (c_int, [_P, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int]),
     "gm_head_gp": (c_int, [_P, _P, c_int64, _P, _P, _P, _P, c_int64, c_int, c_int]),
     "gm_head_bwd_fused": (c_int, [_P, _P, c_int64, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, Slot,
@@ -262,8 +256,6 @@ _SIGNATURES = {
     "gm_began_update": (c_int, [_P, _P, _P, _P, c_float, c_float, c_int64, _P]),
     "gm_adam_scaled": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, Slot, ctypes.c_double, ctypes.c_double,
                                ctypes.c_double, ctypes.c_double, c_float, _P]),
-    "gm_linear_bwd_dx_add": (c_int, [_P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_int, c_int,
-                                     c_int, c_int, _P, c_int64, c_float]),
     "gm_std_all": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P]),
     "gm_dragan_xhat": (c_int, [_P, _P, c_int64, _P, Slot, _P, Slot, _P, c_float, _P, c_int64, c_int,
                                c_int]),
@@ -320,8 +312,6 @@ _SIGNATURES = {
     "gm_event_sync": (c_int, [_P]),
     "gm_event_elapsed_ms": (c_int, [_P, _P, POINTER(c_float)]),
     "gm_event_destroy": (c_int, [_P]),
-    "gm_linear_fwd_label": (c_int, [_P, _P, c_int64, _P, _P, _P, c_int, LabelSrc, _P, c_int64, c_int, c_int, c_int,
-                                    c_int]),
     "gm_vae_reparam_fwd_label": (c_int, [_P, _P, c_int64, _P, Slot, _P, c_int64, _P, c_int, c_int, c_int, _P, _P, _P,
                                          c_int64, c_int, c_int, _P, c_int, LabelSrc]),
     "gm_label_grad_adam": (c_int, [_P, POINTER(LabelGradArgs), c_int, LabelSrc, c_int, c_int, _P, Slot,
@@ -343,12 +333,6 @@ _SIGNATURES = {
                                        c_int]),
     "gm_gather_rows_bits_corrupt": (c_int, [_P, POINTER(CorruptArgs), _P, c_int, c_int64, _P, Slot, _P, _P, c_int64,
                                             c_int, c_int]),
-    "gm_linear_fwd_gather_corrupt": (c_int, [_P, _P, c_int64, Slot, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int,
-                                             _P, c_int64, _P, Slot, _P, c_int64, c_int, c_int, _P,
-                                             POINTER(CorruptArgs)]),
-    "gm_linear_fwd_gather_bits_corrupt": (c_int, [_P, _P, c_int64, Slot, _P, _P, _P, c_int64, c_int, c_int, c_int,
-                                                  c_int, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int, _P,
-                                                  POINTER(CorruptArgs)]),
     "gm_pdw_couple": (c_int, [_P, _P, c_int64, _P, c_int64, _P, Slot, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64,
                               c_float, c_int, c_int]),
     "gm_pdw_dir": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_float, c_float, c_int,

@@ -5,7 +5,7 @@
 //   general path's compute_batch run.
 // gm_gather_rows_corrupt[_bits]: gm_gather_rows[_bits] that also writes the corrupted copy of every gathered row (one
 //   row per wave, 4 waves per workgroup; gather_corrupt_body).  The engine's first batch of a graph; the others get
-//   theirs from the corrupting gather riding in the [mu | log_var] forward (gm_linear_fwd_gather_corrupt, gm_gemm.hip).
+//   theirs from the corrupting gather riding in the [mu | log_var] forward (ops_fused.linear_fwd_gather_corrupt, gm_gemm.hip).
 // No atomics, no reductions: the same bits on every run.
 #include "gm_dvae.h"
 

@@ -1073,7 +1073,7 @@ static int head_fwd_impl(void* stream, int variant, int gen_mode, const float* H
 }
 
 // HeadBwdP, head_bwd_body and head_bwd_kernel live in gm_head.h: the weight-gradient GEMM can
-// co-schedule the head workgroups in its own launch (gm_linear_bwd_dw_adam_head, gm_gemm.hip).
+// co-schedule the head workgroups in its own launch (ops.linear_bwd_dw_adam_head, gm_gemm.hip).
 
 static int head_bwd_launch(void* stream, const gm_head_bwd_args& a) {
     HeadBwdP p{};

@@ -1,7 +1,7 @@
 // K1 gather: out[b,:] = data[idx[b],:]   (process_batch, ns_gan.py:222-226).
 // One 3136-byte image row per wave: 196 float4 -> lanes issue coalesced 16-B loads.  Shared between
 // its own launch (gm_gather_rows, 4 waves per workgroup) and the forward GEMM that can carry the
-// gather workgroups in its grid (gm_linear_fwd_gather, 16 waves per workgroup).
+// gather workgroups in its grid (ops.linear_fwd_gather, 16 waves per workgroup).
 #pragma once
 #include "gm_common.h"
 
@@ -16,7 +16,7 @@ struct GatherP {
     // expands to the fp32 rows the GEMMs consume.
     const uint32_t* bits; int wpr;
     // ... and, instead of expanding, the selected rows copied AS WORDS: out_bits[b * wpr ..) =
-    // the dataset row's wpr words; the consumers (gm_linear_fwd_headpart_bits, gm_linear_bwd_dw_adam_head_fold_bits)
+    // the dataset row's wpr words; the consumers (ops.linear_fwd_headpart(xbits=...), ops.linear_bwd_dw_adam_head_fold(xbits=...))
     // expand in registers.  100 B written per row instead of 3136.
     uint32_t* out_bits;
 };

@@ -151,7 +151,7 @@ struct GemmP {
     // pk_rows % 32 == 0: a forward tile / a 16-row reduction chunk is packed or fp32 as a whole, and each kind gets its own
     // branch-free loop (selecting per fragment inside one loop made hipcc serialise the loads behind s_waitcnt vmcnt(0)).
     const uint32_t* pk_bits; int pk_wpr; int pk_rows;
-    // fwd, class-conditional layer (gm_linear_fwd_label; read only by the LBL instantiations): v += lb_E[n * lb_C + y_m]
+    // fwd, class-conditional layer (gm_fwd_args' label block; read only by the LBL instantiations): v += lb_E[n * lb_C + y_m]
     // before the bias, y_m = row m's class (gm_row_label)
     gm_label_src lb; const float* lb_E; int lb_C;
 #ifdef GM_STAMPS
@@ -1460,7 +1460,7 @@ __global__ __launch_bounds__(WAVES * 64) void gemm16_kernel(GemmP p) {
                                                                                   (int)gridDim.x);
 }
 
-// Class-conditional forward (gm_linear_fwd_label): the plain kernel's body with E[:, y_m] added in the epilogue.  Its own
+// Class-conditional forward (gm_fwd_args' label block): the plain kernel's body with E[:, y_m] added in the epilogue.  Its own
 // instantiations, so that the label term costs the unconditional launches nothing.
 template <bool VEC, int MI, int NI>
 __global__ __launch_bounds__(1024) void gemm16_fwd_label_kernel(GemmP p) {
@@ -2159,35 +2159,111 @@ inline gm_slot no_slot() { gm_slot z; z.ctr = nullptr; z.mul = 0; z.add = 0; z.r
 
 }  // namespace
 
-extern "C" int gm_linear_fwd(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
-                             const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                             int K, int N, int act) {
-    GM_CHECK_ARG(X && W && Y && M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= N);
-    GM_CHECK_ARG(act >= GM_ACT_ID && act <= GM_ACT_SIGMOID);
-    GemmP p{};
-    p.A = X; p.B = W; p.C = Y; p.M = M; p.N = N; p.K = K;
-    p.lda = ldx; p.ldb = K; p.ldc = ldy; p.bias = bias; p.epi = act;
-    p.a_slot = x_slot; p.b_slot = no_slot();
-    const bool vec = aligned16(X) && aligned16(W) && (ldx % 4 == 0) && (K % 4 == 0) &&
-                     (x_slot.stride % 4 == 0);
-    return launch<MODE_FWD>((hipStream_t)stream, p, vec);
+
+// ---- host side of the C ABI: three implementations (forward, input gradient, weight gradient), each reading ONE
+// descriptor.  The plain entry points fill a descriptor with the base fields only; the _ex entry points pass the
+// caller's.  A descriptor's optional blocks are selected by their pointers; a combination no kernel implements is
+// refused here, before anything is launched.
+
+// One batch gather from its descriptor.  *gout: the rows it writes, as the aliasing checks of the carrying GEMM see them.
+static int gather_from_args(const gm_gather_args& a, bool forward, GatherP* g, CorruptP* c, const CorruptP** rider_c,
+                            const float** gout) {
+    GM_CHECK_ARG(!a.data != !a.bits);                        // exactly one source
+    GM_CHECK_ARG(!a.out != !a.out_bits);                     // exactly one destination
+    GM_CHECK_ARG(!a.out_bits || (a.bits && forward));        // packed rows: from the packed dataset, forward only
+    GM_CHECK_ARG(!a.corrupt == !a.out_c);                    // both or neither
+    GM_CHECK_ARG(!a.corrupt || forward);
+    int rc;
+    if (a.data) rc = gm_gather_fill(a.data, a.n_rows, a.idx, a.idx_slot, a.out, a.ld_out, a.B, a.row_elems, g);
+    else if (a.out) rc = gm_gather_fill_bits(a.bits, a.words_per_row, a.n_rows, a.idx, a.idx_slot, a.out, a.ld_out, a.B,
+                                             a.row_elems, g);
+    else rc = gm_gather_fill_bits_packed(a.bits, a.words_per_row, a.n_rows, a.idx, a.idx_slot, a.out_bits, a.B, g);
+    if (rc) return rc;
+    *rider_c = nullptr;
+    if (a.corrupt) {
+        rc = gm_gather_corrupt_fill(a.corrupt, a.out_c, g, c);
+        if (rc) return rc;
+        *rider_c = c;
+    }
+    *gout = a.out ? a.out : reinterpret_cast<const float*>(a.out_bits);
+    return 0;
 }
 
-extern "C" int gm_linear_fwd_label(void* stream, const float* X, int64_t ldx, const float* W, const float* bias,
-                                   const float* E, int C, gm_label_src lab, float* Y, int64_t ldy, int M, int K, int N,
-                                   int act) {
-    GM_CHECK_ARG(X && W && E && lab.labels && Y && M > 0 && K > 0 && N > 0 && C > 0 && C <= 32 && ldx >= K && ldy >= N);
-    GM_CHECK_ARG(act >= GM_ACT_ID && act <= GM_ACT_SIGMOID);
+static bool slot_is_zero(const gm_slot& s) { return !s.ctr && !s.mul && !s.add && !s.ring && !s.stride; }
+
+static int fwd_label_launch(hipStream_t s, const GemmP& p, bool vec);
+
+static int fwd_impl(void* stream, const gm_fwd_args* args) {
+    GM_CHECK_ARG(args);
+    const gm_fwd_args& a = *args;
+    GM_CHECK_ARG(a.X && a.W && a.Y && a.M > 0 && a.K > 0 && a.N > 0 && a.ldx >= a.K && a.ldy >= a.N);
+    GM_CHECK_ARG(a.act >= GM_ACT_ID && a.act <= GM_ACT_SIGMOID);
+    const bool interp = a.ip_eps || a.ip_x || a.ip_out, head = a.hd_w2 || a.hd_b2 || a.hd_part || a.hd_snap,
+               sqerr = a.sq_target || a.sq_dA || a.sq_part, label = a.lb_E || a.lb.labels;
+    if (interp + head + sqerr + label + (a.gather != nullptr) > 1) {
+        gm_set_error("gm_fwd_args: at most one of the interp / head part / sqerr / label / gather blocks");
+        return GM_EINVAL;
+    }
+    if (a.xbits && !head) { gm_set_error("gm_fwd_args: xbits rides with the head part only"); return GM_EINVAL; }
+    if ((sqerr || label) && !slot_is_zero(a.x_slot)) {
+        gm_set_error("gm_fwd_args: the sqerr and label forwards take no ring slot on X");
+        return GM_EINVAL;
+    }
     GemmP p{};
-    p.A = X; p.B = W; p.C = Y; p.M = M; p.N = N; p.K = K;
-    p.lda = ldx; p.ldb = K; p.ldc = ldy; p.bias = bias; p.epi = act;
-    p.a_slot = no_slot(); p.b_slot = no_slot();
-    p.lb = lab; p.lb_E = E; p.lb_C = C;
-    const bool vec = aligned16(X) && aligned16(W) && (ldx % 4 == 0) && (K % 4 == 0);
-    // every shape through the 16-wave split-reduction kernel (its tile choice): the label term lives in its epilogue only
+    p.A = a.X; p.B = a.W; p.C = a.Y; p.M = a.M; p.N = a.N; p.K = a.K;
+    p.lda = a.ldx; p.ldb = a.K; p.ldc = a.ldy; p.bias = a.bias; p.epi = a.act;
+    p.a_slot = a.x_slot; p.b_slot = no_slot();
+    const bool vec = aligned16(a.X) && aligned16(a.W) && (a.ldx % 4 == 0) && (a.K % 4 == 0) &&
+                     (a.x_slot.stride % 4 == 0);
+    Rider r;
+    GatherP g{};
+    CorruptP c{};
+    if (interp) {
+        GM_CHECK_ARG(a.ip_eps && a.ip_x && a.ip_out && a.ip_rows > 0 && a.ip_rows <= a.M && a.ip_ldx >= a.N &&
+                     a.ip_ldo >= a.N);
+        p.ip_eps = a.ip_eps; p.ip_slot = a.ip_slot; p.ip_x = a.ip_x; p.ip_ldx = a.ip_ldx;
+        p.ip_out = a.ip_out; p.ip_ldo = a.ip_ldo; p.ip_rows = a.ip_rows;
+    } else if (head) {
+        GM_CHECK_ARG(a.hd_w2 && a.hd_b2 && a.hd_part && a.hd_snap && a.hd_ldp >= (a.N + 31) / 32 && a.hd_ldp % 4 == 0);
+        GM_CHECK_ARG(a.hd_part != a.Y && a.hd_snap != a.Y && (const float*)a.hd_part != a.X &&
+                     (const float*)a.hd_snap != a.X);
+        p.hd_w2 = a.hd_w2; p.hd_b2 = a.hd_b2; p.hd_part = a.hd_part; p.hd_ldp = a.hd_ldp; p.hd_snap = a.hd_snap;
+        if (a.xbits) {      // the first xbits_rows rows of X are read from the packed copy (gm_gather_args.out_bits)
+            GM_CHECK_ARG(a.xbits_rows > 0 && a.xbits_rows <= a.M && a.xbits_rows % 32 == 0 &&
+                         a.xbits_wpr * 32 >= a.K && a.K % 4 == 0);
+            GM_CHECK_ARG((const void*)a.xbits != (const void*)a.Y && (const void*)a.xbits != (const void*)a.hd_part);
+            p.pk_bits = a.xbits; p.pk_wpr = a.xbits_wpr; p.pk_rows = a.xbits_rows;
+        }
+    } else if (sqerr) {
+        GM_CHECK_ARG(a.act == GM_ACT_SIGMOID);               // the loss gradient is the sigmoid output layer's
+        GM_CHECK_ARG(a.sq_target && a.sq_dA && a.sq_part && a.sq_ldt >= a.N && a.sq_lda >= a.N &&
+                     a.sq_ldp >= (a.N + 31) / 32);
+        GM_CHECK_ARG(a.sq_dA != a.Y && a.sq_part != a.Y && a.sq_part != a.sq_dA && (const float*)a.sq_dA != a.X &&
+                     (const float*)a.sq_part != a.X && (const float*)a.Y != a.sq_target &&
+                     (const float*)a.sq_dA != a.sq_target);
+        p.sq_x = a.sq_target; p.sq_ldx = a.sq_ldt; p.sq_dA = a.sq_dA; p.sq_lda = a.sq_lda; p.sq_part = a.sq_part;
+        p.sq_ldp = a.sq_ldp;
+    } else if (label) {
+        GM_CHECK_ARG(a.lb_E && a.lb.labels && a.lb_C > 0 && a.lb_C <= 32);
+        p.lb = a.lb; p.lb_E = a.lb_E; p.lb_C = a.lb_C;
+        return fwd_label_launch((hipStream_t)stream, p, vec);
+    } else if (a.gather) {
+        const float* gout = nullptr;
+        const int rc = gather_from_args(*a.gather, true, &g, &c, &r.corrupt, &gout);
+        if (rc) return rc;
+        // the gathered rows must not be an operand or the output of this GEMM
+        GM_CHECK_ARG(gout != a.Y && gout != a.X);
+        GM_CHECK_ARG(!r.corrupt || (c.out_c != a.Y && (const float*)c.out_c != a.X));
+        r.gather = &g;
+    }
+    return launch<MODE_FWD>((hipStream_t)stream, p, vec, false, r);
+}
+
+// The class-conditional forward: every shape through the 16-wave split-reduction kernel (its tile choice) -- the label
+// term lives in that kernel's epilogue only.
+static int fwd_label_launch(hipStream_t s, const GemmP& p, bool vec) {
     const int tile = pick_tile<MODE_FWD>(p);
-    const dim3 grid((N + 16 * tile_ni(tile) - 1) / (16 * tile_ni(tile)), (M + 16 * tile_mi(tile) - 1) / (16 * tile_mi(tile)));
-    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((p.N + 16 * tile_ni(tile) - 1) / (16 * tile_ni(tile)), (p.M + 16 * tile_mi(tile) - 1) / (16 * tile_mi(tile)));
 #define GM_LBL(MI_, NI_, D_)                                                                                \
     do {                                                                                                    \
         if (vec) hipLaunchKernelGGL((gemm16_fwd_label_kernel<true, MI_, NI_>), grid, dim3(1024), 0, s, p);  \
@@ -2198,516 +2274,210 @@ extern "C" int gm_linear_fwd_label(void* stream, const float* X, int64_t ldx, co
     GM_LAUNCH_RET();
 }
 
-extern "C" int gm_linear_fwd_interp(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
-                                    const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                                    int K, int N, int act, const float* eps, gm_slot eps_slot,
-                                    const float* x_real, int64_t ld_real, float* x_hat, int64_t ld_hat,
-                                    int rows) {
-    GM_CHECK_ARG(X && W && Y && M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= N);
-    GM_CHECK_ARG(act >= GM_ACT_ID && act <= GM_ACT_SIGMOID);
-    GM_CHECK_ARG(eps && x_real && x_hat && rows > 0 && rows <= M && ld_real >= N && ld_hat >= N);
-    GemmP p{};
-    p.A = X; p.B = W; p.C = Y; p.M = M; p.N = N; p.K = K;
-    p.lda = ldx; p.ldb = K; p.ldc = ldy; p.bias = bias; p.epi = act;
-    p.a_slot = x_slot; p.b_slot = no_slot();
-    p.ip_eps = eps; p.ip_slot = eps_slot; p.ip_x = x_real; p.ip_ldx = ld_real;
-    p.ip_out = x_hat; p.ip_ldo = ld_hat; p.ip_rows = rows;
-    const bool vec = aligned16(X) && aligned16(W) && (ldx % 4 == 0) && (K % 4 == 0) &&
-                     (x_slot.stride % 4 == 0);
-    return launch<MODE_FWD>((hipStream_t)stream, p, vec);
+extern "C" int gm_linear_fwd(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
+                             const float* bias, float* Y, int64_t ldy, int M, int K, int N, int act) {
+    gm_fwd_args a{};
+    a.X = X; a.ldx = ldx; a.x_slot = x_slot; a.W = W; a.bias = bias; a.Y = Y; a.ldy = ldy;
+    a.M = M; a.K = K; a.N = N; a.act = act;
+    return fwd_impl(stream, &a);
 }
 
-extern "C" int gm_linear_fwd_headpart(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
-                                      const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                                      int K, int N, int act, const float* w2, const float* b2,
-                                      float* part, int64_t ldp, float* snap) {
-    GM_CHECK_ARG(X && W && Y && M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= N);
-    GM_CHECK_ARG(act >= GM_ACT_ID && act <= GM_ACT_SIGMOID);
-    GM_CHECK_ARG(w2 && b2 && part && snap && ldp >= (N + 31) / 32 && ldp % 4 == 0);
-    GM_CHECK_ARG(part != Y && snap != Y && (const float*)part != X && (const float*)snap != X);
-    GemmP p{};
-    p.A = X; p.B = W; p.C = Y; p.M = M; p.N = N; p.K = K;
-    p.lda = ldx; p.ldb = K; p.ldc = ldy; p.bias = bias; p.epi = act;
-    p.a_slot = x_slot; p.b_slot = no_slot();
-    p.hd_w2 = w2; p.hd_b2 = b2; p.hd_part = part; p.hd_ldp = ldp; p.hd_snap = snap;
-    const bool vec = aligned16(X) && aligned16(W) && (ldx % 4 == 0) && (K % 4 == 0) &&
-                     (x_slot.stride % 4 == 0);
-    return launch<MODE_FWD>((hipStream_t)stream, p, vec);
-}
+extern "C" int gm_linear_fwd_ex(void* stream, const gm_fwd_args* a) { return fwd_impl(stream, a); }
 
-// gm_linear_fwd_headpart whose first `rows` rows of X are read from the packed copy (gm_gather_rows_bits_packed)
-extern "C" int gm_linear_fwd_headpart_bits(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
-                                           const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                                           int K, int N, int act, const float* w2, const float* b2,
-                                           float* part, int64_t ldp, float* snap, const uint32_t* xbits,
-                                           int words_per_row, int rows) {
-    GM_CHECK_ARG(X && W && Y && M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= N);
-    GM_CHECK_ARG(act >= GM_ACT_ID && act <= GM_ACT_SIGMOID);
-    GM_CHECK_ARG(w2 && b2 && part && snap && ldp >= (N + 31) / 32 && ldp % 4 == 0);
-    GM_CHECK_ARG(part != Y && snap != Y && (const float*)part != X && (const float*)snap != X);
-    GM_CHECK_ARG(xbits && rows > 0 && rows <= M && rows % 32 == 0 && words_per_row * 32 >= K && K % 4 == 0);
-    GM_CHECK_ARG((const void*)xbits != (const void*)Y && (const void*)xbits != (const void*)part);
-    GemmP p{};
-    p.A = X; p.B = W; p.C = Y; p.M = M; p.N = N; p.K = K;
-    p.lda = ldx; p.ldb = K; p.ldc = ldy; p.bias = bias; p.epi = act;
-    p.a_slot = x_slot; p.b_slot = no_slot();
-    p.hd_w2 = w2; p.hd_b2 = b2; p.hd_part = part; p.hd_ldp = ldp; p.hd_snap = snap;
-    p.pk_bits = xbits; p.pk_wpr = words_per_row; p.pk_rows = rows;
-    const bool vec = aligned16(X) && aligned16(W) && (ldx % 4 == 0) && (K % 4 == 0) &&
-                     (x_slot.stride % 4 == 0);
-    return launch<MODE_FWD>((hipStream_t)stream, p, vec);
-}
-
-extern "C" int gm_linear_fwd_sqerr(void* stream, const float* X, int64_t ldx, const float* W,
-                                  const float* bias, float* Y, int64_t ldy, int M, int K, int N,
-                                  const float* target, int64_t ld_target, float* dA, int64_t lda,
-                                  float* part, int64_t ldp) {
-    GM_CHECK_ARG(X && W && Y && M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= N);
-    GM_CHECK_ARG(target && dA && part && ld_target >= N && lda >= N && ldp >= (N + 31) / 32);
-    GM_CHECK_ARG(dA != Y && part != Y && part != dA && (const float*)dA != X && (const float*)part != X &&
-                 (const float*)Y != target && (const float*)dA != target);
-    GemmP p{};
-    p.A = X; p.B = W; p.C = Y; p.M = M; p.N = N; p.K = K;
-    p.lda = ldx; p.ldb = K; p.ldc = ldy; p.bias = bias; p.epi = GM_ACT_SIGMOID;
-    p.a_slot = no_slot(); p.b_slot = no_slot();
-    p.sq_x = target; p.sq_ldx = ld_target; p.sq_dA = dA; p.sq_lda = lda; p.sq_part = part; p.sq_ldp = ldp;
-    const bool vec = aligned16(X) && aligned16(W) && (ldx % 4 == 0) && (K % 4 == 0);
-    return launch<MODE_FWD>((hipStream_t)stream, p, vec);
-}
-
-static int fwd_gather_impl(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
-                           const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                           int K, int N, int act, const GatherP& g, float* out, const CorruptP* corrupt = nullptr);
-
-extern "C" int gm_linear_fwd_gather(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
-                                    const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                                    int K, int N, int act, const float* data, int64_t n_rows,
-                                    const int64_t* idx, gm_slot idx_slot, float* out,
-                                    int64_t ld_out, int B, int row_elems) {
-    GatherP g{};
-    const int rc = gm_gather_fill(data, n_rows, idx, idx_slot, out, ld_out, B, row_elems, &g);
-    if (rc) return rc;
-    return fwd_gather_impl(stream, X, ldx, x_slot, W, bias, Y, ldy, M, K, N, act, g, out);
-}
-
-extern "C" int gm_linear_fwd_gather_bits(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
-                                         const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                                         int K, int N, int act, const uint32_t* bits, int words_per_row,
-                                         int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out,
-                                         int64_t ld_out, int B, int row_elems) {
-    GatherP g{};
-    const int rc = gm_gather_fill_bits(bits, words_per_row, n_rows, idx, idx_slot, out, ld_out, B, row_elems, &g);
-    if (rc) return rc;
-    return fwd_gather_impl(stream, X, ldx, x_slot, W, bias, Y, ldy, M, K, N, act, g, out);
-}
-
-extern "C" int gm_linear_fwd_gather_bits_packed(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
-                                                const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                                                int K, int N, int act, const uint32_t* bits, int words_per_row,
-                                                int64_t n_rows, const int64_t* idx, gm_slot idx_slot,
-                                                uint32_t* out_bits, int B) {
-    GatherP g{};
-    const int rc = gm_gather_fill_bits_packed(bits, words_per_row, n_rows, idx, idx_slot, out_bits, B, &g);
-    if (rc) return rc;
-    return fwd_gather_impl(stream, X, ldx, x_slot, W, bias, Y, ldy, M, K, N, act, g, reinterpret_cast<float*>(out_bits));
-}
-
-extern "C" int gm_linear_fwd_gather_corrupt(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
-                                            const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                                            int K, int N, int act, const float* data, int64_t n_rows,
-                                            const int64_t* idx, gm_slot idx_slot, float* out,
-                                            int64_t ld_out, int B, int row_elems, float* out_c,
-                                            const gm_corrupt_args* a) {
-    GatherP g{};
-    CorruptP c{};
-    int rc = gm_gather_fill(data, n_rows, idx, idx_slot, out, ld_out, B, row_elems, &g);
-    if (rc) return rc;
-    rc = gm_gather_corrupt_fill(a, out_c, &g, &c);
-    if (rc) return rc;
-    return fwd_gather_impl(stream, X, ldx, x_slot, W, bias, Y, ldy, M, K, N, act, g, out, &c);
-}
-
-extern "C" int gm_linear_fwd_gather_bits_corrupt(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
-                                                 const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                                                 int K, int N, int act, const uint32_t* bits, int words_per_row,
-                                                 int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out,
-                                                 int64_t ld_out, int B, int row_elems, float* out_c,
-                                                 const gm_corrupt_args* a) {
-    GatherP g{};
-    CorruptP c{};
-    int rc = gm_gather_fill_bits(bits, words_per_row, n_rows, idx, idx_slot, out, ld_out, B, row_elems, &g);
-    if (rc) return rc;
-    rc = gm_gather_corrupt_fill(a, out_c, &g, &c);
-    if (rc) return rc;
-    return fwd_gather_impl(stream, X, ldx, x_slot, W, bias, Y, ldy, M, K, N, act, g, out, &c);
-}
-
-static int fwd_gather_impl(void* stream, const float* X, int64_t ldx, gm_slot x_slot,
-                           const float* W, const float* bias, float* Y, int64_t ldy, int M,
-                           int K, int N, int act, const GatherP& g, float* out, const CorruptP* corrupt) {
-    GM_CHECK_ARG(X && W && Y && M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= N);
-    GM_CHECK_ARG(act >= GM_ACT_ID && act <= GM_ACT_SIGMOID);
-    // the gathered rows must not be an operand or the output of this GEMM
-    GM_CHECK_ARG(out != Y && out != X);
-    GM_CHECK_ARG(!corrupt || (corrupt->out_c != Y && (const float*)corrupt->out_c != X));
-    GemmP p{};
-    p.A = X; p.B = W; p.C = Y; p.M = M; p.N = N; p.K = K;
-    p.lda = ldx; p.ldb = K; p.ldc = ldy; p.bias = bias; p.epi = act;
-    p.a_slot = x_slot; p.b_slot = no_slot();
-    const bool vec = aligned16(X) && aligned16(W) && (ldx % 4 == 0) && (K % 4 == 0) &&
-                     (x_slot.stride % 4 == 0);
-    Rider r;
-    r.gather = &g;
-    r.corrupt = corrupt;
-    return launch<MODE_FWD>((hipStream_t)stream, p, vec, false, r);
-}
-
-static int dx_impl(void* stream, const float* dA, int64_t lda, const float* W, float* dX, int64_t ldx,
-                   const float* below, int64_t ld_below, int M, int K, int N, int epi,
-                   const float* add, int64_t ldadd, float add_scale, const HeadBwdP* head = nullptr,
-                   const float* fold_w2 = nullptr, const GatherP* gather = nullptr);
-
-extern "C" int gm_linear_bwd_dx_head(void* stream, const float* dA, int64_t lda, const float* W,
-                                     float* dX, int64_t ldx, const float* below, int64_t ld_below,
-                                     int M, int K, int N, int epi, const gm_head_bwd_args* head) {
-    GM_CHECK_ARG(head);
-    // the head workgroups only read dS / rowloss / H: none of them may be this GEMM's output
-    GM_CHECK_ARG((const float*)dX != head->H && (const float*)dX != head->dS &&
-                 (const float*)dX != head->rowloss && dX != head->dH);
-    HeadBwdP hp{};
-    const int rc = gm_head_from_args(*head, &hp);
-    if (rc) return rc;
-    return dx_impl(stream, dA, lda, W, dX, ldx, below, ld_below, M, K, N, epi, nullptr, 0, 0.f, &hp);
-}
-
-extern "C" int gm_linear_bwd_dx_reparam(void* stream, const float* dA, int64_t lda, const float* W,
-                                        float* dZ, int64_t ldz, int M, int Z, int N, const float* ml,
-                                        int64_t ldml, const float* eps, gm_slot eps_slot, float* dml,
-                                        int64_t ldd) {
-    GM_CHECK_ARG(dA && W && dZ && M > 0 && Z > 0 && N > 0 && lda >= N && ldz >= Z);
-    GM_CHECK_ARG(ml && eps && dml && ldml >= 2 * Z && ldd >= 2 * Z && dml != dZ && (const float*)dml != ml &&
-                 (const float*)dml != dA);
-    GemmP p{};
-    p.A = dA; p.B = W; p.C = dZ; p.M = M; p.N = Z; p.K = N;
-    p.lda = lda; p.ldb = Z; p.ldc = ldz; p.epi = GM_ACT_ID;
-    p.a_slot = no_slot(); p.b_slot = no_slot();
-    p.rp_ml = ml; p.rp_ldml = ldml; p.rp_eps = eps; p.rp_slot = eps_slot; p.rp_dml = dml; p.rp_ldd = ldd;
-    p.rp_Z = Z;
-    const bool vec = aligned16(dA) && (lda % 4 == 0) && (N % 4 == 0);
-    const bool xvec = aligned16(W) && (Z % 4 == 0);
-    return launch<MODE_DX>((hipStream_t)stream, p, vec, xvec);
-}
-
-extern "C" int gm_linear_bwd_dx_head_fold(void* stream, const float* H, int64_t ldh, const float* W,
-                                          float* dX, int64_t ldx, const float* below, int64_t ld_below,
-                                          int M, int K, int N, int epi, const gm_head_bwd_args* head,
-                                          const gm_head_fold_args* fold) {
-    GM_CHECK_ARG(head && fold && head->gen_mode && head->H == H && head->B == M && head->Hd == N);
-    GM_CHECK_ARG((const float*)dX != H && dX != fold->S && dX != fold->dS && dX != fold->rowloss);
-    HeadBwdP hp{};
-    const int rc = gm_head_from_args(*head, &hp, fold);
-    if (rc) return rc;
-    return dx_impl(stream, H, ldh, W, dX, ldx, below, ld_below, M, K, N, epi, nullptr, 0, 0.f, &hp, fold->snap);
-}
-
-extern "C" int gm_linear_bwd_dx(void* stream, const float* dA, int64_t lda, const float* W,
-                                float* dX, int64_t ldx, const float* below, int64_t ld_below,
-                                int M, int K, int N, int epi) {
-    return dx_impl(stream, dA, lda, W, dX, ldx, below, ld_below, M, K, N, epi, nullptr, 0, 0.f);
-}
-
-extern "C" int gm_linear_bwd_dx_add(void* stream, const float* dA, int64_t lda, const float* W,
-                                    float* dX, int64_t ldx, const float* below, int64_t ld_below,
-                                    int M, int K, int N, int epi, const float* add, int64_t ldadd,
-                                    float add_scale) {
-    GM_CHECK_ARG(add && ldadd >= K);
-    return dx_impl(stream, dA, lda, W, dX, ldx, below, ld_below, M, K, N, epi, add, ldadd, add_scale);
-}
-
-extern "C" int gm_linear_bwd_dx_gather(void* stream, const float* dA, int64_t lda, const float* W,
-                                       float* dX, int64_t ldx, const float* below, int64_t ld_below,
-                                       int M, int K, int N, int epi, const float* data, int64_t n_rows,
-                                       const int64_t* idx, gm_slot idx_slot, float* out, int64_t ld_out,
-                                       int B, int row_elems) {
-    // the gathered rows must not be an operand or the output of this GEMM
-    GM_CHECK_ARG(out && out != dA && out != W && out != dX && out != below);
-    GatherP g{};
-    const int rc = gm_gather_fill(data, n_rows, idx, idx_slot, out, ld_out, B, row_elems, &g);
-    if (rc) return rc;
-    return dx_impl(stream, dA, lda, W, dX, ldx, below, ld_below, M, K, N, epi, nullptr, 0, 0.f, nullptr, nullptr, &g);
-}
-
-extern "C" int gm_linear_bwd_dx_gather_bits(void* stream, const float* dA, int64_t lda, const float* W,
-                                            float* dX, int64_t ldx, const float* below, int64_t ld_below,
-                                            int M, int K, int N, int epi, const uint32_t* bits, int words_per_row,
-                                            int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out,
-                                            int64_t ld_out, int B, int row_elems) {
-    GM_CHECK_ARG(out && out != dA && out != W && out != dX && out != below);
-    GatherP g{};
-    const int rc = gm_gather_fill_bits(bits, words_per_row, n_rows, idx, idx_slot, out, ld_out, B, row_elems, &g);
-    if (rc) return rc;
-    return dx_impl(stream, dA, lda, W, dX, ldx, below, ld_below, M, K, N, epi, nullptr, 0, 0.f, nullptr, nullptr, &g);
-}
-
-static int dx_impl(void* stream, const float* dA, int64_t lda, const float* W, float* dX, int64_t ldx,
-                   const float* below, int64_t ld_below, int M, int K, int N, int epi,
-                   const float* add, int64_t ldadd, float add_scale, const HeadBwdP* head,
-                   const float* fold_w2, const GatherP* gather) {
-    GM_CHECK_ARG(dA && W && dX && M > 0 && K > 0 && N > 0 && lda >= N && ldx >= K);
-    GM_CHECK_ARG(epi == GM_ACT_ID || (below && ld_below >= K));
+static int dx_impl(void* stream, const gm_dx_args* args) {
+    GM_CHECK_ARG(args);
+    const gm_dx_args& a = *args;
+    GM_CHECK_ARG(a.dA && a.W && a.dX && a.M > 0 && a.K > 0 && a.N > 0 && a.lda >= a.N && a.ldx >= a.K);
+    GM_CHECK_ARG(a.epi == GM_ACT_ID || (a.below && a.ld_below >= a.K));
+    const bool reparam = a.rp_ml || a.rp_eps || a.rp_dml;
+    if ((a.add != nullptr) + (a.head != nullptr) + reparam + (a.gather != nullptr) > 1) {
+        gm_set_error("gm_dx_args: at most one of the add / head / reparam / gather blocks");
+        return GM_EINVAL;
+    }
+    if (a.fold && !a.head) { gm_set_error("gm_dx_args: fold needs head"); return GM_EINVAL; }
+    if (reparam && (a.below || a.ld_below || a.epi != GM_ACT_ID)) {
+        gm_set_error("gm_dx_args: the reparameterisation epilogue takes no activation gradient");
+        return GM_EINVAL;
+    }
     GemmP p{};
     // C[M, K_layer] = sum_{n} dA[m,n] * W[n,k]  => GEMM dims (M, N=K_layer, K=N_layer)
-    p.A = dA; p.B = W; p.C = dX; p.M = M; p.N = K; p.K = N;
-    p.lda = lda; p.ldb = K; p.ldc = ldx; p.aux = below; p.ldaux = ld_below; p.epi = epi;
-    p.add = add; p.ldadd = ldadd; p.add_scale = add_scale;
-    p.fold_w2 = fold_w2;
+    p.A = a.dA; p.B = a.W; p.C = a.dX; p.M = a.M; p.N = a.K; p.K = a.N;
+    p.lda = a.lda; p.ldb = a.K; p.ldc = a.ldx; p.aux = a.below; p.ldaux = a.ld_below; p.epi = a.epi;
     p.a_slot = no_slot(); p.b_slot = no_slot();
-    const bool vec = aligned16(dA) && (lda % 4 == 0) && (N % 4 == 0) && (!fold_w2 || aligned16(fold_w2));
-    const bool xvec = aligned16(W) && (K % 4 == 0);
     Rider r;
-    r.head = head;
-    r.gather = gather;
+    HeadBwdP hp{};
+    GatherP g{};
+    if (a.add) {
+        GM_CHECK_ARG(a.ldadd >= a.K);
+        p.add = a.add; p.ldadd = a.ldadd; p.add_scale = a.add_scale;
+    } else if (a.head && a.fold) {                           // dA is the hidden layer H
+        GM_CHECK_ARG(a.head->gen_mode && a.head->H == a.dA && a.head->B == a.M && a.head->Hd == a.N);
+        GM_CHECK_ARG((const float*)a.dX != a.dA && a.dX != a.fold->S && a.dX != a.fold->dS && a.dX != a.fold->rowloss);
+        const int rc = gm_head_from_args(*a.head, &hp, a.fold);
+        if (rc) return rc;
+        p.fold_w2 = a.fold->snap;
+        r.head = &hp;
+    } else if (a.head) {
+        // the head workgroups only read dS / rowloss / H: none of them may be this GEMM's output
+        GM_CHECK_ARG((const float*)a.dX != a.head->H && (const float*)a.dX != a.head->dS &&
+                     (const float*)a.dX != a.head->rowloss && a.dX != a.head->dH);
+        const int rc = gm_head_from_args(*a.head, &hp);
+        if (rc) return rc;
+        r.head = &hp;
+    } else if (reparam) {                                    // dX is dz (K = Z)
+        GM_CHECK_ARG(a.rp_ml && a.rp_eps && a.rp_dml && a.rp_ldml >= 2 * a.K && a.rp_ldd >= 2 * a.K &&
+                     a.rp_dml != a.dX && (const float*)a.rp_dml != a.rp_ml && (const float*)a.rp_dml != a.dA);
+        p.rp_ml = a.rp_ml; p.rp_ldml = a.rp_ldml; p.rp_eps = a.rp_eps; p.rp_slot = a.rp_slot; p.rp_dml = a.rp_dml;
+        p.rp_ldd = a.rp_ldd; p.rp_Z = a.K;
+    } else if (a.gather) {
+        // the gathered rows must not be an operand or the output of this GEMM
+        const float* out = a.gather->out;
+        GM_CHECK_ARG(out && out != a.dA && out != a.W && out != a.dX && out != a.below);
+        CorruptP c{};
+        const CorruptP* none = nullptr;
+        const int rc = gather_from_args(*a.gather, false, &g, &c, &none, &out);
+        if (rc) return rc;
+        r.gather = &g;
+    }
+    const bool vec = aligned16(a.dA) && (a.lda % 4 == 0) && (a.N % 4 == 0) && (!p.fold_w2 || aligned16(p.fold_w2));
+    const bool xvec = aligned16(a.W) && (a.K % 4 == 0);
     return launch<MODE_DX>((hipStream_t)stream, p, vec, xvec, r);
 }
 
-static int dw_impl(void* stream, const float* dA, int64_t lda, const float* X, int64_t ldx,
-                   gm_slot x_slot, float* dW, float* db, int M, int K, int N, int accumulate,
-                   const gm_adam_epi* adam, const HeadBwdP* head = nullptr, int ones_from = 0,
-                   const float* fold_w2 = nullptr);
-static int dw_fill(const float* dA, int64_t lda, const float* X, int64_t ldx, gm_slot x_slot,
-                   float* dW, float* db, int M, int K, int N, int accumulate,
-                   const gm_adam_epi* adam, GemmP* out, bool* xvec);
-
-extern "C" int gm_linear_bwd_dw(void* stream, const float* dA, int64_t lda, const float* X,
-                                int64_t ldx, gm_slot x_slot, float* dW, float* db, int M, int K,
-                                int N, int accumulate) {
-    return dw_impl(stream, dA, lda, X, ldx, x_slot, dW, db, M, K, N, accumulate, nullptr);
+extern "C" int gm_linear_bwd_dx(void* stream, const float* dA, int64_t lda, const float* W, float* dX, int64_t ldx,
+                                const float* below, int64_t ld_below, int M, int K, int N, int epi) {
+    gm_dx_args a{};
+    a.dA = dA; a.lda = lda; a.W = W; a.dX = dX; a.ldx = ldx; a.below = below; a.ld_below = ld_below;
+    a.M = M; a.K = K; a.N = N; a.epi = epi;
+    return dx_impl(stream, &a);
 }
 
-extern "C" int gm_linear_bwd_dw_adam(void* stream, const float* dA, int64_t lda, const float* X,
-                                     int64_t ldx, gm_slot x_slot, float* dW, float* db, int M,
-                                     int K, int N, float* pW, float* mW, float* vW, float* pb,
-                                     float* mb, float* vb, const float* sched, gm_slot sched_slot,
-                                     double beta1, double beta2, double eps, double weight_decay,
-                                     float clamp) {
-    GM_CHECK_ARG(db && pW && mW && vW && pb && mb && vb && sched);
-    gm_adam_epi a{};
-    a.pW = pW; a.mW = mW; a.vW = vW; a.pb = pb; a.mb = mb; a.vb = vb; a.sched = sched;
-    a.sched_slot = sched_slot; a.omb1 = (float)(1.0 - beta1); a.b2 = (float)beta2;
-    a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps; a.wd = (float)weight_decay; a.clamp = clamp;
-    a.enabled = 1;
-    return dw_impl(stream, dA, lda, X, ldx, x_slot, dW, db, M, K, N, 0, &a);
-}
+extern "C" int gm_linear_bwd_dx_ex(void* stream, const gm_dx_args* a) { return dx_impl(stream, a); }
 
-extern "C" int gm_linear_bwd_dw_adam_head(void* stream, const float* dA, int64_t lda,
-                                          const float* X, int64_t ldx, gm_slot x_slot, float* dW,
-                                          float* db, int M, int K, int N, float* pW, float* mW,
-                                          float* vW, float* pb, float* mb, float* vb,
-                                          const float* sched, gm_slot sched_slot, double beta1,
-                                          double beta2, double eps, double weight_decay, float clamp,
-                                          const gm_head_bwd_args* head) {
-    return gm_linear_bwd_dw_adam_head_ex(stream, dA, lda, X, ldx, x_slot, dW, db, M, K, N, pW, mW, vW, pb, mb,
-                                         vb, sched, sched_slot, beta1, beta2, eps, weight_decay, clamp, head, 0);
-}
-
-extern "C" int gm_linear_bwd_dw_adam_head_ex(void* stream, const float* dA, int64_t lda,
-                                             const float* X, int64_t ldx, gm_slot x_slot, float* dW,
-                                             float* db, int M, int K, int N, float* pW, float* mW,
-                                             float* vW, float* pb, float* mb, float* vb,
-                                             const float* sched, gm_slot sched_slot, double beta1,
-                                             double beta2, double eps, double weight_decay, float clamp,
-                                             const gm_head_bwd_args* head, int ones_from) {
-    GM_CHECK_ARG(head);
-    // sched == NULL: plain gradients (data-parallel runs all-reduce before the optimizer step)
-    GM_CHECK_ARG(!sched || (db && pW && mW && vW && pb && mb && vb));
-    // the head may update (w2, b2) and writes gw2/gb2/loss: none of it may alias the GEMM's operands
-    GM_CHECK_ARG((const float*)head->w2 != pW || !pW);
-    GM_CHECK_ARG(head->gw2 != dW);
-    HeadBwdP hp{};
-    const int rc = gm_head_from_args(*head, &hp);
-    if (rc) return rc;
-    gm_adam_epi a{};
-    if (sched) {
-        a.pW = pW; a.mW = mW; a.vW = vW; a.pb = pb; a.mb = mb; a.vb = vb; a.sched = sched;
-        a.sched_slot = sched_slot; a.omb1 = (float)(1.0 - beta1); a.b2 = (float)beta2;
-        a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps; a.wd = (float)weight_decay; a.clamp = clamp;
-        a.enabled = 1;
-    }
-    return dw_impl(stream, dA, lda, X, ldx, x_slot, dW, db, M, K, N, 0, sched ? &a : nullptr, &hp, ones_from);
-}
-
-extern "C" int gm_linear_bwd_dw_adam_head_fold(void* stream, const float* H, int64_t ldh,
-                                               const float* X, int64_t ldx, gm_slot x_slot, float* dW,
-                                               float* db, int M, int K, int N, float* pW, float* mW,
-                                               float* vW, float* pb, float* mb, float* vb,
-                                               const float* sched, gm_slot sched_slot, double beta1,
-                                               double beta2, double eps, double weight_decay, float clamp,
-                                               const gm_head_bwd_args* head, const gm_head_fold_args* fold) {
-    GM_CHECK_ARG(head && fold && !head->gen_mode && head->H == H && 2 * head->B == M && head->Hd == N);
-    GM_CHECK_ARG(!sched || (db && pW && mW && vW && pb && mb && vb));
-    GM_CHECK_ARG((const float*)head->w2 != pW || !pW);
-    GM_CHECK_ARG(head->gw2 != dW && (const float*)dW != H);
-    // the GEMM workgroups read the SNAPSHOT of (w2, b2): the head workgroups may step the parameters
-    GM_CHECK_ARG(fold->snap != (const float*)head->w2 && fold->snap != (const float*)head->b2);
-    HeadBwdP hp{};
-    const int rc = gm_head_from_args(*head, &hp, fold);
-    if (rc) return rc;
-    gm_adam_epi a{};
-    if (sched) {
-        a.pW = pW; a.mW = mW; a.vW = vW; a.pb = pb; a.mb = mb; a.vb = vb; a.sched = sched;
-        a.sched_slot = sched_slot; a.omb1 = (float)(1.0 - beta1); a.b2 = (float)beta2;
-        a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps; a.wd = (float)weight_decay; a.clamp = clamp;
-        a.enabled = 1;
-    }
-    return dw_impl(stream, H, ldh, X, ldx, x_slot, dW, db, M, K, N, 0, sched ? &a : nullptr, &hp, 0, fold->snap);
-}
-
-// gm_linear_bwd_dw_adam_head_fold whose first `rows` rows of X are read from the packed copy
-extern "C" int gm_linear_bwd_dw_adam_head_fold_bits(void* stream, const float* H, int64_t ldh,
-                                                    const float* X, int64_t ldx, gm_slot x_slot, float* dW,
-                                                    float* db, int M, int K, int N, float* pW, float* mW,
-                                                    float* vW, float* pb, float* mb, float* vb,
-                                                    const float* sched, gm_slot sched_slot, double beta1,
-                                                    double beta2, double eps, double weight_decay, float clamp,
-                                                    const gm_head_bwd_args* head, const gm_head_fold_args* fold,
-                                                    const uint32_t* xbits, int words_per_row, int rows) {
-    GM_CHECK_ARG(head && fold && !head->gen_mode && head->H == H && 2 * head->B == M && head->Hd == N);
-    GM_CHECK_ARG(!sched || (db && pW && mW && vW && pb && mb && vb));
-    GM_CHECK_ARG((const float*)head->w2 != pW || !pW);
-    GM_CHECK_ARG(head->gw2 != dW && (const float*)dW != H);
-    GM_CHECK_ARG(fold->snap != (const float*)head->w2 && fold->snap != (const float*)head->b2);
-    GM_CHECK_ARG(xbits && rows > 0 && rows <= M && rows % 32 == 0 && words_per_row * 32 >= K && K % 4 == 0);
-    GM_CHECK_ARG((const void*)xbits != (const void*)dW && (const void*)xbits != (const void*)pW);
-    HeadBwdP hp{};
-    const int rc = gm_head_from_args(*head, &hp, fold);
-    if (rc) return rc;
-    gm_adam_epi a{};
-    if (sched) {
-        a.pW = pW; a.mW = mW; a.vW = vW; a.pb = pb; a.mb = mb; a.vb = vb; a.sched = sched;
-        a.sched_slot = sched_slot; a.omb1 = (float)(1.0 - beta1); a.b2 = (float)beta2;
-        a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps; a.wd = (float)weight_decay; a.clamp = clamp;
-        a.enabled = 1;
-    }
+// One weight-gradient GEMM from its descriptor (the head / fold / xbits riders are dw_impl's).
+static int dw_fill(const gm_dw_adam_args& a, GemmP* out, bool* xvec_out) {
+    GM_CHECK_ARG(a.dA && a.X && a.dW && a.M > 0 && a.K > 0 && a.N > 0 && a.lda >= a.N && a.ldx >= a.K);
     GemmP p{};
-    bool xvec = false;
-    const int rf = dw_fill(H, ldh, X, ldx, x_slot, dW, db, M, K, N, 0, sched ? &a : nullptr, &p, &xvec);
-    if (rf) return rf;
-    p.fold_w2 = fold->snap;
-    if (!aligned16(fold->snap)) xvec = false;
-    p.pk_bits = xbits; p.pk_wpr = words_per_row; p.pk_rows = rows;
-    Rider r;
-    r.head = &hp;
-    return launch<MODE_DW>((hipStream_t)stream, p, false, xvec, r);
-}
-
-static int dw_adam_fill(const gm_dw_adam_args& a, GemmP* p, bool* xvec) {
-    if (!a.sched)            // plain gradient (no optimizer step in the epilogue)
-        return dw_fill(a.dA, a.lda, a.X, a.ldx, a.x_slot, a.dW, a.db, a.M, a.K, a.N, 0, nullptr, p, xvec);
-    GM_CHECK_ARG(a.db && a.pW && a.mW && a.vW && a.pb && a.mb && a.vb);
-    gm_adam_epi e{};
-    e.pW = a.pW; e.mW = a.mW; e.vW = a.vW; e.pb = a.pb; e.mb = a.mb; e.vb = a.vb; e.sched = a.sched;
-    e.sched_slot = a.sched_slot; e.omb1 = (float)(1.0 - a.beta1); e.b2 = (float)a.beta2;
-    e.omb2 = (float)(1.0 - a.beta2); e.eps = (float)a.eps; e.wd = (float)a.weight_decay;
-    e.clamp = a.clamp; e.enabled = 1;
-    return dw_fill(a.dA, a.lda, a.X, a.ldx, a.x_slot, a.dW, a.db, a.M, a.K, a.N, 0, &e, p, xvec);
-}
-
-static int pair_launch(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second,
-                       const L1RideP* l1);
-
-extern "C" int gm_linear_bwd_dw_adam_pair(void* stream, const gm_dw_adam_args* first,
-                                          const gm_dw_adam_args* second) {
-    return pair_launch(stream, first, second, nullptr);
-}
-
-extern "C" int gm_linear_bwd_dw_adam_pair_l1(void* stream, const gm_dw_adam_args* first,
-                                             const gm_dw_adam_args* second, const float* z, int64_t ldz,
-                                             gm_slot z_slot, float* H, int64_t ldh, int rows) {
-    GM_CHECK_ARG(first && second && second->sched && z && H && rows > 0 && ldz >= second->K && ldh >= second->N);
-    // H is written while the pair runs: it may be none of the pair's operands or outputs
-    const void* pair_arrays[] = {first->dA, first->X, first->dW, first->db, first->pW, first->pb,
-                                 second->dA, second->X, second->dW, second->db, second->pW, second->pb};
-    for (const void* q : pair_arrays) GM_CHECK_ARG(q != (const void*)H);
-    GM_CHECK_ARG((const void*)z != (const void*)H);
-    const L1RideP l{z, ldz, z_slot, H, ldh, rows, (aligned16(H) && ldh % 4 == 0) ? 1 : 0};
-    return pair_launch(stream, first, second, &l);
-}
-
-static int pair_launch(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second,
-                       const L1RideP* l1) {
-    GM_CHECK_ARG(first && second);
-    // neither may consume what the other produces or updates
-    GM_CHECK_ARG(first->dW != second->dW && (first->pW != second->pW || !first->pW));
-    GM_CHECK_ARG(!first->pW || ((const float*)first->pW != second->dA && (const float*)first->pW != second->X));
-    GM_CHECK_ARG(!second->pW || ((const float*)second->pW != first->dA && (const float*)second->pW != first->X));
-    GM_CHECK_ARG(first->dW != second->dA && first->dW != second->X && second->dW != first->dA && second->dW != first->X);
-    GemmP pa{}, pb{};
-    bool xa = false, xb = false;
-    int rc = dw_adam_fill(*first, &pa, &xa);
-    if (rc) return rc;
-    rc = dw_adam_fill(*second, &pb, &xb);
-    if (rc) return rc;
-    Rider r;
-    r.pair = &pb;
-    r.pair_xvec = xb;
-    r.l1 = l1;
-    return launch<MODE_DW>((hipStream_t)stream, pa, false, xa, r);
-}
-
-extern "C" int gm_linear_bwd_dw_adam_pair_finalize(void* stream, const gm_dw_adam_args* first,
-                                                   const gm_dw_adam_args* second, const gm_finalize2_args* fin) {
-    GM_CHECK_ARG(first && second && fin);
-    GM_CHECK_ARG(fin->pa && fin->pb && fin->out_a && fin->out_b && fin->na > 0 && fin->nb > 0 && fin->done);
-    GM_CHECK_ARG(first->dW != second->dW && (first->pW != second->pW || !first->pW));
-    GM_CHECK_ARG(!first->pW || ((const float*)first->pW != second->dA && (const float*)first->pW != second->X));
-    GM_CHECK_ARG(!second->pW || ((const float*)second->pW != first->dA && (const float*)second->pW != first->X));
-    GM_CHECK_ARG(first->dW != second->dA && first->dW != second->X && second->dW != first->dA && second->dW != first->X);
-    GemmP pa{}, pb{};
-    bool xa = false, xb = false;
-    int rc = dw_adam_fill(*first, &pa, &xa);
-    if (rc) return rc;
-    rc = dw_adam_fill(*second, &pb, &xb);
-    if (rc) return rc;
-    const gm_fin2 f{fin->pa, fin->na, fin->scale_a, fin->out_a, fin->slot_a, fin->pb, fin->nb, fin->scale_b,
-                    fin->out_b, fin->slot_b, fin->tick, fin->done};
-    Rider r;
-    r.pair = &pb;
-    r.pair_xvec = xb;
-    r.fin = &f;
-    return launch<MODE_DW>((hipStream_t)stream, pa, false, xa, r);
-}
-
-static int dw_impl(void* stream, const float* dA, int64_t lda, const float* X, int64_t ldx,
-                   gm_slot x_slot, float* dW, float* db, int M, int K, int N, int accumulate,
-                   const gm_adam_epi* adam, const HeadBwdP* head, int ones_from, const float* fold_w2) {
-    GemmP p{};
-    bool xvec = false;
-    const int rc = dw_fill(dA, lda, X, ldx, x_slot, dW, db, M, K, N, accumulate, adam, &p, &xvec);
-    if (rc) return rc;
-    GM_CHECK_ARG(ones_from >= 0 && ones_from <= M && (ones_from == 0 || head));
-    p.ones_from = ones_from;
-    p.fold_w2 = fold_w2;
-    if (fold_w2 && !aligned16(fold_w2)) xvec = false;
-    Rider r;
-    r.head = head;
-    return launch<MODE_DW>((hipStream_t)stream, p, false, xvec, r);
-}
-
-static int dw_fill(const float* dA, int64_t lda, const float* X, int64_t ldx, gm_slot x_slot,
-                   float* dW, float* db, int M, int K, int N, int accumulate,
-                   const gm_adam_epi* adam, GemmP* out, bool* xvec_out) {
-    GM_CHECK_ARG(dA && X && dW && M > 0 && K > 0 && N > 0 && lda >= N && ldx >= K);
-    GemmP p{};
-    if (adam) p.adam = *adam;
+    if (a.sched) {          // else: plain gradient (data-parallel runs all-reduce before the optimizer step)
+        GM_CHECK_ARG(a.db && a.pW && a.mW && a.vW && a.pb && a.mb && a.vb);
+        gm_adam_epi& e = p.adam;
+        e.pW = a.pW; e.mW = a.mW; e.vW = a.vW; e.pb = a.pb; e.mb = a.mb; e.vb = a.vb; e.sched = a.sched;
+        e.sched_slot = a.sched_slot; e.omb1 = (float)(1.0 - a.beta1); e.b2 = (float)a.beta2;
+        e.omb2 = (float)(1.0 - a.beta2); e.eps = (float)a.eps; e.wd = (float)a.weight_decay;
+        e.clamp = a.clamp; e.enabled = 1;
+    }
     // C[N_layer, K_layer(+1)] = sum_{m} dA[m,n] * X[m,k]  => GEMM dims (M=N_layer, N=K_layer(+1), K=batch)
-    p.A = dA; p.B = X; p.C = dW; p.M = N; p.N = K + (db ? 1 : 0); p.K = M;
-    p.lda = lda; p.ldb = ldx; p.ldc = K; p.db = db; p.n_real = K; p.accumulate = accumulate;
-    p.a_slot = no_slot(); p.b_slot = x_slot;
+    p.A = a.dA; p.B = a.X; p.C = a.dW; p.M = a.N; p.N = a.K + (a.db ? 1 : 0); p.K = a.M;
+    p.lda = a.lda; p.ldb = a.ldx; p.ldc = a.K; p.db = a.db; p.n_real = a.K; p.accumulate = a.accumulate;
+    p.a_slot = no_slot(); p.b_slot = a.x_slot;
     // both operands are x-contiguous; the 16-byte + quad-transpose path needs every row start and
     // the tile edges on 4-element boundaries (the virtual ones-column sits at x == K, K % 4 == 0)
-    const bool xvec = aligned16(dA) && aligned16(X) && (lda % 4 == 0) && (ldx % 4 == 0) &&
-                      (N % 4 == 0) && (K % 4 == 0) && (x_slot.stride % 4 == 0) && N >= 4 && K >= 4;
+    *xvec_out = aligned16(a.dA) && aligned16(a.X) && (a.lda % 4 == 0) && (a.ldx % 4 == 0) && (a.N % 4 == 0) &&
+                (a.K % 4 == 0) && (a.x_slot.stride % 4 == 0) && a.N >= 4 && a.K >= 4;
     *out = p;
-    *xvec_out = xvec;
     return 0;
+}
+
+static int dw_impl(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second, const gm_dw_tail* tail) {
+    GM_CHECK_ARG(first);
+    const gm_dw_adam_args& a = *first;
+    if (second && (a.head || second->head)) {
+        gm_set_error("gm_dw_adam_args: the head rides in a single weight gradient, not in a pair");
+        return GM_EINVAL;
+    }
+    for (const gm_dw_adam_args* q : {first, second}) {
+        if (!q) continue;
+        if (!q->head && (q->ones_from > 0 || q->fold)) { gm_set_error("gm_dw_adam_args: ones_from / fold need head"); return GM_EINVAL; }
+        if (q->xbits && !q->fold) { gm_set_error("gm_dw_adam_args: xbits needs fold"); return GM_EINVAL; }
+        if (q->accumulate && (q->sched || q->head || second)) {
+            gm_set_error("gm_dw_adam_args: accumulate is the plain single weight gradient's");
+            return GM_EINVAL;
+        }
+    }
+    const bool tail_l1 = tail && (tail->z || tail->H);
+    if (tail && (!second || tail_l1 == (tail->fin != nullptr))) {
+        gm_set_error("gm_dw_tail: rides in a pair, with either the layer-1 fields or fin");
+        return GM_EINVAL;
+    }
+    GemmP pa{}, pb{};
+    bool xa = false, xb = false;
+    Rider r;
+    if (!second) {
+        HeadBwdP hp{};
+        if (a.head) {
+            // sched == NULL: plain gradients (data-parallel runs all-reduce before the optimizer step)
+            GM_CHECK_ARG(!a.sched || (a.db && a.pW && a.mW && a.vW && a.pb && a.mb && a.vb));
+            // the head may update (w2, b2) and writes gw2/gb2/loss: none of it may alias the GEMM's operands
+            GM_CHECK_ARG((const float*)a.head->w2 != a.pW || !a.pW);
+            GM_CHECK_ARG(a.head->gw2 != a.dW);
+            if (a.fold) {                                    // dA is the hidden layer H
+                GM_CHECK_ARG(!a.head->gen_mode && a.head->H == a.dA && 2 * a.head->B == a.M && a.head->Hd == a.N);
+                GM_CHECK_ARG((const float*)a.dW != a.dA && a.ones_from == 0);
+                // the GEMM workgroups read the SNAPSHOT of (w2, b2): the head workgroups may step the parameters
+                GM_CHECK_ARG(a.fold->snap != (const float*)a.head->w2 && a.fold->snap != (const float*)a.head->b2);
+            }
+            if (a.xbits) {  // the first xbits_rows rows of X are read from the packed copy (gm_gather_args.out_bits)
+                GM_CHECK_ARG(a.xbits_rows > 0 && a.xbits_rows <= a.M && a.xbits_rows % 32 == 0 &&
+                             a.xbits_wpr * 32 >= a.K && a.K % 4 == 0);
+                GM_CHECK_ARG((const void*)a.xbits != (const void*)a.dW && (const void*)a.xbits != (const void*)a.pW);
+            }
+            const int rc = gm_head_from_args(*a.head, &hp, a.fold);
+            if (rc) return rc;
+            r.head = &hp;
+        }
+        const int rc = dw_fill(a, &pa, &xa);
+        if (rc) return rc;
+        GM_CHECK_ARG(a.ones_from >= 0 && a.ones_from <= a.M);
+        pa.ones_from = a.ones_from;
+        if (a.fold) {
+            pa.fold_w2 = a.fold->snap;
+            if (!aligned16(a.fold->snap)) xa = false;
+        }
+        pa.pk_bits = a.xbits; pa.pk_wpr = a.xbits ? a.xbits_wpr : 0; pa.pk_rows = a.xbits ? a.xbits_rows : 0;
+        return launch<MODE_DW>((hipStream_t)stream, pa, false, xa, r);
+    }
+    const gm_dw_adam_args& b = *second;
+    L1RideP l{};
+    gm_fin2 f{};
+    if (tail_l1) {
+        GM_CHECK_ARG(b.sched && tail->z && tail->H && tail->rows > 0 && tail->ldz >= b.K && tail->ldh >= b.N);
+        // H is written while the pair runs: it may be none of the pair's operands or outputs
+        const void* pair_arrays[] = {a.dA, a.X, a.dW, a.db, a.pW, a.pb, b.dA, b.X, b.dW, b.db, b.pW, b.pb};
+        for (const void* q : pair_arrays) GM_CHECK_ARG(q != (const void*)tail->H);
+        GM_CHECK_ARG((const void*)tail->z != (const void*)tail->H);
+        l = L1RideP{tail->z, tail->ldz, tail->z_slot, tail->H, tail->ldh, tail->rows,
+                    (aligned16(tail->H) && tail->ldh % 4 == 0) ? 1 : 0};
+        r.l1 = &l;
+    } else if (tail) {
+        const gm_finalize2_args* fin = tail->fin;
+        GM_CHECK_ARG(fin->pa && fin->pb && fin->out_a && fin->out_b && fin->na > 0 && fin->nb > 0 && fin->done);
+        f = gm_fin2{fin->pa, fin->na, fin->scale_a, fin->out_a, fin->slot_a, fin->pb, fin->nb, fin->scale_b,
+                    fin->out_b, fin->slot_b, fin->tick, fin->done};
+        r.fin = &f;
+    }
+    // neither may consume what the other produces or updates
+    GM_CHECK_ARG(a.dW != b.dW && (a.pW != b.pW || !a.pW));
+    GM_CHECK_ARG(!a.pW || ((const float*)a.pW != b.dA && (const float*)a.pW != b.X));
+    GM_CHECK_ARG(!b.pW || ((const float*)b.pW != a.dA && (const float*)b.pW != a.X));
+    GM_CHECK_ARG(a.dW != b.dA && a.dW != b.X && b.dW != a.dA && b.dW != a.X);
+    int rc = dw_fill(a, &pa, &xa);
+    if (rc) return rc;
+    rc = dw_fill(b, &pb, &xb);
+    if (rc) return rc;
+    r.pair = &pb;
+    r.pair_xvec = xb;
+    return launch<MODE_DW>((hipStream_t)stream, pa, false, xa, r);
+}
+
+extern "C" int gm_linear_bwd_dw(void* stream, const float* dA, int64_t lda, const float* X, int64_t ldx,
+                                gm_slot x_slot, float* dW, float* db, int M, int K, int N, int accumulate) {
+    gm_dw_adam_args a{};
+    a.dA = dA; a.lda = lda; a.X = X; a.ldx = ldx; a.x_slot = x_slot; a.dW = dW; a.db = db;
+    a.M = M; a.K = K; a.N = N; a.accumulate = accumulate;
+    return dw_impl(stream, &a, nullptr, nullptr);
+}
+
+extern "C" int gm_linear_bwd_dw_ex(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second,
+                                   const gm_dw_tail* tail) {
+    return dw_impl(stream, first, second, tail);
 }

@@ -1,6 +1,6 @@
 // Backward half of the fused critic head (see gm_fused.hip for the forward half and the C-ABI):
 // shared between its own launch (gm_head_bwd*) and the weight-gradient GEMM that can carry the
-// head workgroups in its grid (gm_linear_bwd_dw_adam_head) -- the two are independent once
+// head workgroups in its grid (ops.linear_bwd_dw_adam_head) -- the two are independent once
 // head_fwd_loss has produced dH, so one launch does both.
 #pragma once
 #include "gm_common.h"

@@ -105,7 +105,7 @@ extern "C" int gm_host_device_ptr(void* host_ptr, void** dev_ptr_out) {
 // One 3136-byte image row per wave: 196 float4 -> lanes issue coalesced 16-B loads.
 // ------------------------------------------------------------------------------------------
 // The body lives in gm_gather.h: the generator's first forward GEMM can carry the gather workgroups
-// in its own grid (gm_linear_fwd_gather, gm_gemm.hip).
+// in its own grid (ops.linear_fwd_gather, gm_gemm.hip).
 extern "C" int gm_gather_rows(void* stream, const float* data, int64_t n_rows, const int64_t* idx,
                               gm_slot idx_slot, float* out, int64_t ld_out, int B, int row_elems) {
     GatherP g{};

@@ -674,7 +674,7 @@ class GANEngine(CriticStep, InfoQStep, GeneratorStep, PenaltySteps):
 
     def _l1_rides(self):
         """The next iteration's generator layer 1 rides in this iteration's generator weight-gradient pair
-        (gm_linear_bwd_dw_adam_pair_l1: its W1 tiles form H from the parameters they just stepped) and the next batch
+        (ops.linear_bwd_dw_adam_pair_l1: its W1 tiles form H from the parameters they just stepped) and the next batch
         gather in this iteration's dH launch (the real rows are last read by the critic's weight gradient).  One GPU,
         one critic step, NSGAN / LSGAN with the batched generator forward, the paired weight gradients with Adam in
         their epilogue; up to 512 generator rows (the bs = 1024 shapes keep their own launch: not measured there)."""

@@ -24,7 +24,7 @@ class CriticStep:
         """The critic step reads its real rows as BITS: the gather copies the selected rows of the
         1-bit resident dataset as words (100 B per MNIST row instead of 3136 B of fp32) and the folded step's two
         launches -- hidden layer forward, layer-1 weight gradient -- expand them in registers
-        (gm_linear_fwd_headpart_bits, gm_linear_bwd_dw_adam_head_fold_bits).  Bit-identical losses and parameters
+        (ops.linear_fwd_headpart(xbits=...), ops.linear_bwd_dw_adam_head_fold(xbits=...)).  Bit-identical losses and parameters
         (tests/test_gpu_trainers.py); GM_PACKED_OPERAND=1 turns it on -- measured neither faster nor slower than the
         fp32 rows on one MI355X (profiles/r05_experiments.md section 9), so the default stays the path every other
         variant shares.  Needs the folded step of a separable loss and a batch of whole 32-row tiles."""

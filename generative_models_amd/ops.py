@@ -31,15 +31,56 @@ def _ld(t):
     return t.stride(0)
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _act(a):
+    return a if isinstance(a, int) else ACT[a]
+
+
 # ---- raw ops (pointers may be offset views; M/K/N given explicitly) -------------------------
 def linear_fwd(x, W, b, y, act, M=None, x_slot=NO_SLOT, stream=None):
     """y[M,N] = act(x[M,K] @ W[N,K]^T + b).  ns_gan.py:44-45,58-59."""
     N, K = W.shape
     M = x.shape[0] if M is None else M
     _lib.call("gm_linear_fwd", stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x), x_slot,
-              _chk(W, "W").data_ptr(), b.data_ptr() if b is not None else None,
-              _chk(y, "y").data_ptr(), _ld(y), M, K, N, ACT[act] if not isinstance(act, int) else act)
+              _chk(W, "W").data_ptr(), _ptr(b), _chk(y, "y").data_ptr(), _ld(y), M, K, N, _act(act))
     return y
+
+
+def _fwd_args(x, W, b, y, act, M=None, x_slot=NO_SLOT):
+    """gm_fwd_args with the base GEMM filled in; the caller sets at most one optional block."""
+    a = _lib.FwdArgs()
+    a.N, a.K = W.shape
+    a.M = x.shape[0] if M is None else M
+    a.X, a.ldx, a.x_slot = _chk(x, "x").data_ptr(), _ld(x), x_slot
+    a.W, a.bias = _chk(W, "W").data_ptr(), _ptr(b)
+    a.Y, a.ldy, a.act = _chk(y, "y").data_ptr(), _ld(y), _act(act)
+    return a
+
+
+def _fwd_ex(a, stream):
+    _lib.call("gm_linear_fwd_ex", stream or stream_ptr(), ctypes.byref(a))
+
+
+def _gather_args(data, idx, out, B=None, idx_slot=NO_SLOT):
+    """gm_gather_args: out[b, :] = data[idx[b], :].  data: fp32 [N, I] or PackedData; an int32 `out` [B, wpr] keeps a
+    PackedData's rows packed."""
+    g = _lib.GatherArgs()
+    g.n_rows, g.row_elems = data.shape
+    g.B = out.shape[0] if B is None else B
+    g.idx, g.idx_slot = idx.data_ptr(), idx_slot
+    if isinstance(data, PackedData):                 # 1 bit / pixel resident dataset
+        g.bits, g.words_per_row = data.data_ptr(), data.wpr
+    else:
+        g.data = _chk(data, "data").data_ptr()
+    if isinstance(data, PackedData) and out.dtype == torch.int32:     # ... and the rows stay packed
+        assert out.is_contiguous() and out.shape[1] == data.wpr
+        g.out_bits = out.data_ptr()
+    else:
+        g.out, g.ld_out = out.data_ptr(), _ld(out)
+    return g
 
 
 def label_src(labels, idx=None, idx_slot=NO_SLOT):
@@ -72,9 +113,9 @@ def linear_fwd_label(x, W, b, E, lab, y, act, M=None, stream=None):
         raise _lib.GMError("linear_fwd_label: x %s / y %s do not fit M=%d, K=%d, N=%d"
                            % (tuple(x.shape), tuple(y.shape), M, K, N))
     _check_labels(lab, M)
-    _lib.call("gm_linear_fwd_label", stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x), _chk(W, "W").data_ptr(),
-              b.data_ptr() if b is not None else None, _chk(E, "E").data_ptr(), E.shape[1], lab,
-              _chk(y, "y").data_ptr(), _ld(y), M, K, N, ACT[act] if not isinstance(act, int) else act)
+    a = _fwd_args(x, W, b, y, act, M)
+    a.lb_E, a.lb_C, a.lb = _chk(E, "E").data_ptr(), E.shape[1], lab
+    _fwd_ex(a, stream)
     return y
 
 
@@ -83,7 +124,6 @@ def label_grad_adam(layers, lab, M, C, adam=None, betas=(0.9, 0.999), eps=1e-8, 
     layers: dicts(dPre, gE=None, E=None, mE=None, vE=None); with E given, Adam steps (E, mE, vE) in the same
     launch with the schedule row of adam = dict(sched, sched_slot)."""
     arr = (_lib.LabelGradArgs * len(layers))()
-    ptr = lambda t: t.data_ptr() if t is not None else None
     _check_labels(lab, M)
     for a, d in zip(arr, layers):
         dp = _chk(d["dPre"], "dPre")
@@ -96,7 +136,7 @@ def label_grad_adam(layers, lab, M, C, adam=None, betas=(0.9, 0.999), eps=1e-8, 
                 raise _lib.GMError("%s must be a contiguous float32 device tensor [N=%d, C=%d], got %s"
                                    % (k, dp.shape[1], C, tuple(t.shape)))
         a.dPre, a.ld, a.N = dp.data_ptr(), _ld(dp), dp.shape[1]
-        a.gE, a.E, a.mE, a.vE = ptr(d.get("gE")), ptr(d.get("E")), ptr(d.get("mE")), ptr(d.get("vE"))
+        a.gE, a.E, a.mE, a.vE = _ptr(d.get("gE")), _ptr(d.get("E")), _ptr(d.get("mE")), _ptr(d.get("vE"))
     _lib.call("gm_label_grad_adam", stream or stream_ptr(), arr, len(layers), lab, M, C,
               adam["sched"].data_ptr() if adam else None, adam["sched_slot"] if adam else NO_SLOT,
               betas[0], betas[1], eps, weight_decay)
@@ -106,32 +146,42 @@ def linear_fwd_interp(x, W, b, y, act, eps, eps_slot, x_real, x_hat, rows, M=Non
                       stream=None):
     """linear_fwd + WGAN-GP's x_hat = eps*x_real + (1-eps)*y for the first `rows` output rows
     (w_gp_gan.py:197-201), written by the same launch."""
-    N, K = W.shape
-    M = x.shape[0] if M is None else M
-    _lib.call("gm_linear_fwd_interp", stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x), x_slot,
-              _chk(W, "W").data_ptr(), b.data_ptr() if b is not None else None,
-              _chk(y, "y").data_ptr(), _ld(y), M, K, N, ACT[act] if not isinstance(act, int) else act,
-              eps.data_ptr(), eps_slot, _chk(x_real, "x_real").data_ptr(), _ld(x_real),
-              _chk(x_hat, "x_hat").data_ptr(), _ld(x_hat), rows)
+    a = _fwd_args(x, W, b, y, act, M, x_slot)
+    a.ip_eps, a.ip_slot, a.ip_rows = eps.data_ptr(), eps_slot, rows
+    a.ip_x, a.ip_ldx = _chk(x_real, "x_real").data_ptr(), _ld(x_real)
+    a.ip_out, a.ip_ldo = _chk(x_hat, "x_hat").data_ptr(), _ld(x_hat)
+    _fwd_ex(a, stream)
     return y
+
+
+def _dx_args(dA, W, dX, below=None, epi="id", M=None):
+    """gm_dx_args with the base GEMM filled in; the caller sets at most one optional block."""
+    a = _lib.DxArgs()
+    a.N, a.K = W.shape
+    a.M = dA.shape[0] if M is None else M
+    a.dA, a.lda, a.W = _chk(dA, "dA").data_ptr(), _ld(dA), _chk(W, "W").data_ptr()
+    a.dX, a.ldx, a.epi = _chk(dX, "dX").data_ptr(), _ld(dX), _act(epi)
+    if below is not None:
+        a.below, a.ld_below = below.data_ptr(), _ld(below)
+    return a
+
+
+def _dx_ex(a, stream):
+    _lib.call("gm_linear_bwd_dx_ex", stream or stream_ptr(), ctypes.byref(a))
 
 
 def linear_bwd_dx(dA, W, dX, below=None, epi="id", M=None, add=None, add_scale=1.0, stream=None):
     """dX[M,K] = (dA[M,N] @ W[N,K] + add_scale*add) (* act'(below))."""
+    if add is not None:
+        a = _dx_args(dA, W, dX, below, epi, M)
+        a.add, a.ldadd, a.add_scale = add.data_ptr(), _ld(add), add_scale
+        _dx_ex(a, stream)
+        return dX
     N, K = W.shape
     M = dA.shape[0] if M is None else M
-    if add is not None:
-        _lib.call("gm_linear_bwd_dx_add", stream or stream_ptr(), _chk(dA, "dA").data_ptr(), _ld(dA),
-                  W.data_ptr(), _chk(dX, "dX").data_ptr(), _ld(dX),
-                  below.data_ptr() if below is not None else None,
-                  _ld(below) if below is not None else 0, M, K, N,
-                  ACT[epi] if not isinstance(epi, int) else epi, add.data_ptr(), _ld(add), add_scale)
-        return dX
     _lib.call("gm_linear_bwd_dx", stream or stream_ptr(), _chk(dA, "dA").data_ptr(), _ld(dA),
-              W.data_ptr(), _chk(dX, "dX").data_ptr(), _ld(dX),
-              below.data_ptr() if below is not None else None,
-              _ld(below) if below is not None else 0, M, K, N,
-              ACT[epi] if not isinstance(epi, int) else epi)
+              W.data_ptr(), _chk(dX, "dX").data_ptr(), _ld(dX), _ptr(below),
+              _ld(below) if below is not None else 0, M, K, N, _act(epi))
     return dX
 
 
@@ -139,22 +189,10 @@ def linear_bwd_dx_gather(dA, W, dX, data, idx, out, below=None, epi="id", M=None
                          stream=None):
     """linear_bwd_dx(dA, W, dX, below, epi) and gather_rows(data, idx, out) as ONE launch (the gather workgroups ride in
     the GEMM's grid; `out` must not be an array of this GEMM).  data: fp32 [N, I] or PackedData (fp32 rows out)."""
-    N, K = W.shape
-    M = dA.shape[0] if M is None else M
-    n_rows, row = data.shape
-    B = out.shape[0] if B is None else B
-    if isinstance(data, PackedData):                 # 1 bit / pixel resident dataset, expanded to fp32 rows
-        _lib.call("gm_linear_bwd_dx_gather_bits", stream or stream_ptr(), _chk(dA, "dA").data_ptr(), _ld(dA),
-                  W.data_ptr(), _chk(dX, "dX").data_ptr(), _ld(dX),
-                  below.data_ptr() if below is not None else None, _ld(below) if below is not None else 0, M, K,
-                  N, ACT[epi] if not isinstance(epi, int) else epi, data.data_ptr(), data.wpr, n_rows,
-                  idx.data_ptr(), idx_slot, out.data_ptr(), _ld(out), B, row)
-        return dX
-    _lib.call("gm_linear_bwd_dx_gather", stream or stream_ptr(), _chk(dA, "dA").data_ptr(), _ld(dA),
-              W.data_ptr(), _chk(dX, "dX").data_ptr(), _ld(dX),
-              below.data_ptr() if below is not None else None, _ld(below) if below is not None else 0, M, K, N,
-              ACT[epi] if not isinstance(epi, int) else epi, _chk(data, "data").data_ptr(), n_rows,
-              idx.data_ptr(), idx_slot, out.data_ptr(), _ld(out), B, row)
+    a = _dx_args(dA, W, dX, below, epi, M)
+    g = _gather_args(data, idx, out, B, idx_slot)
+    a.gather = ctypes.pointer(g)
+    _dx_ex(a, stream)
     return dX
 
 
@@ -163,59 +201,17 @@ def linear_bwd_dw(dA, X, dW, db, M=None, accumulate=False, x_slot=NO_SLOT, strea
     N, K = dW.shape
     M = dA.shape[0] if M is None else M
     _lib.call("gm_linear_bwd_dw", stream or stream_ptr(), _chk(dA, "dA").data_ptr(), _ld(dA),
-              _chk(X, "X").data_ptr(), _ld(X), x_slot, dW.data_ptr(),
-              db.data_ptr() if db is not None else None, M, K, N, 1 if accumulate else 0)
-
-
-def linear_bwd_dw_adam(dA, X, lin, adam, M=None, x_slot=NO_SLOT, betas=(0.9, 0.999), eps=1e-8,
-                       weight_decay=0.0, stream=None):
-    """dW/db as linear_bwd_dw (written into lin.gW/lin.gb) with Adam applied to the layer's
-    parameters in the same kernel.  lin: engine._Linear (W, b, gW, gb, mW, vW, mb, vb views);
-    adam: dict(sched, sched_slot, clamp)."""
-    N, K = lin.gW.shape
-    M = dA.shape[0] if M is None else M
-    _lib.call("gm_linear_bwd_dw_adam", stream or stream_ptr(), _chk(dA, "dA").data_ptr(), _ld(dA),
-              _chk(X, "X").data_ptr(), _ld(X), x_slot, lin.gW.data_ptr(), lin.gb.data_ptr(), M, K, N,
-              lin.W.data_ptr(), lin.mW.data_ptr(), lin.vW.data_ptr(), lin.b.data_ptr(),
-              lin.mb.data_ptr(), lin.vb.data_ptr(), adam["sched"].data_ptr(), adam["sched_slot"],
-              betas[0], betas[1], eps, weight_decay, adam.get("clamp", 0.0))
-
-
-def linear_fwd_gather(x, W, b, y, act, data, idx, out, M=None, B=None, x_slot=NO_SLOT,
-                      idx_slot=NO_SLOT, stream=None):
-    """linear_fwd(x, W, b, y, act) and gather_rows(data, idx, out) as ONE launch (the gather
-    workgroups ride in the GEMM's grid; `out` must not be an operand of this GEMM)."""
-    N, K = W.shape
-    M = x.shape[0] if M is None else M
-    n_rows, row = data.shape
-    B = out.shape[0] if B is None else B
-    if isinstance(data, PackedData) and out.dtype == torch.int32:     # ... and the rows stay packed (out: [B, wpr] words)
-        assert out.is_contiguous() and out.shape[1] == data.wpr
-        _lib.call("gm_linear_fwd_gather_bits_packed", stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x),
-                  x_slot, _chk(W, "W").data_ptr(), b.data_ptr() if b is not None else None,
-                  _chk(y, "y").data_ptr(), _ld(y), M, K, N, ACT[act], data.data_ptr(), data.wpr,
-                  n_rows, idx.data_ptr(), idx_slot, out.data_ptr(), B)
-        return y
-    if isinstance(data, PackedData):                 # 1 bit / pixel resident dataset
-        _lib.call("gm_linear_fwd_gather_bits", stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x),
-                  x_slot, _chk(W, "W").data_ptr(), b.data_ptr() if b is not None else None,
-                  _chk(y, "y").data_ptr(), _ld(y), M, K, N, ACT[act], data.data_ptr(), data.wpr,
-                  n_rows, idx.data_ptr(), idx_slot, out.data_ptr(), _ld(out), B, row)
-        return y
-    _lib.call("gm_linear_fwd_gather", stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x),
-              x_slot, _chk(W, "W").data_ptr(), b.data_ptr() if b is not None else None,
-              _chk(y, "y").data_ptr(), _ld(y), M, K, N, ACT[act], _chk(data, "data").data_ptr(),
-              n_rows, idx.data_ptr(), idx_slot, out.data_ptr(), _ld(out), B, row)
-    return y
+              _chk(X, "X").data_ptr(), _ld(X), x_slot, dW.data_ptr(), _ptr(db), M, K, N, 1 if accumulate else 0)
 
 
 def _dw_adam_args(dA, X, lin, adam, M, x_slot, betas, eps, weight_decay):
-    from ._lib import DwAdamArgs
+    """gm_dw_adam_args: one weight gradient into lin.gW / lin.gb; adam = dict(sched, sched_slot, clamp) steps the
+    layer's parameters in the same kernel, None leaves the Adam fields zero (plain gradients, no optimizer step)."""
     N, K = lin.gW.shape
-    a = DwAdamArgs()
+    a = _lib.DwAdamArgs()
     a.dA, a.lda, a.X, a.ldx, a.x_slot = _chk(dA, "dA").data_ptr(), _ld(dA), _chk(X, "X").data_ptr(), _ld(X), x_slot
     a.dW, a.db, a.M, a.K, a.N = lin.gW.data_ptr(), lin.gb.data_ptr(), (dA.shape[0] if M is None else M), K, N
-    if adam is not None:                        # None: plain gradients, no optimizer step
+    if adam is not None:
         a.pW, a.mW, a.vW = lin.W.data_ptr(), lin.mW.data_ptr(), lin.vW.data_ptr()
         a.pb, a.mb, a.vb = lin.b.data_ptr(), lin.mb.data_ptr(), lin.vb.data_ptr()
         a.sched, a.sched_slot = adam["sched"].data_ptr(), adam["sched_slot"]
@@ -224,15 +220,42 @@ def _dw_adam_args(dA, X, lin, adam, M, x_slot, betas, eps, weight_decay):
     return a
 
 
+def _dw_ex(first, second, tail, stream):
+    _lib.call("gm_linear_bwd_dw_ex", stream or stream_ptr(), ctypes.byref(first),
+              ctypes.byref(second) if second is not None else None, ctypes.byref(tail) if tail is not None else None)
+
+
+def linear_bwd_dw_adam(dA, X, lin, adam, M=None, x_slot=NO_SLOT, betas=(0.9, 0.999), eps=1e-8,
+                       weight_decay=0.0, stream=None):
+    """dW/db as linear_bwd_dw (written into lin.gW/lin.gb) with Adam applied to the layer's
+    parameters in the same kernel.  lin: engine._Linear (W, b, gW, gb, mW, vW, mb, vb views);
+    adam: dict(sched, sched_slot, clamp)."""
+    _dw_ex(_dw_adam_args(dA, X, lin, adam, M, x_slot, betas, eps, weight_decay), None, None, stream)
+
+
+def linear_fwd_gather(x, W, b, y, act, data, idx, out, M=None, B=None, x_slot=NO_SLOT,
+                      idx_slot=NO_SLOT, stream=None):
+    """linear_fwd(x, W, b, y, act) and gather_rows(data, idx, out) as ONE launch (the gather
+    workgroups ride in the GEMM's grid; `out` must not be an operand of this GEMM)."""
+    a = _fwd_args(x, W, b, y, act, M, x_slot)
+    g = _gather_args(data, idx, out, B, idx_slot)
+    a.gather = ctypes.pointer(g)
+    _fwd_ex(a, stream)
+    return y
+
+
+def _pair_args(first, second, betas, eps, weight_decay):
+    mk = lambda d: _dw_adam_args(d["dA"], d["X"], d["lin"], d.get("adam"), d.get("M"),
+                                 d.get("x_slot", NO_SLOT), betas, eps, weight_decay)
+    return mk(first), mk(second)
+
+
 def linear_bwd_dw_adam_pair(first, second, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                             stream=None):
     """Two linear_bwd_dw_adam calls over the same batch rows as ONE launch.  first / second:
     dict(dA, X, lin, adam, M=None, x_slot=NO_SLOT)."""
-    import ctypes
-    mk = lambda d: _dw_adam_args(d["dA"], d["X"], d["lin"], d.get("adam"), d.get("M"),
-                                 d.get("x_slot", NO_SLOT), betas, eps, weight_decay)
-    a, b = mk(first), mk(second)
-    _lib.call("gm_linear_bwd_dw_adam_pair", stream or stream_ptr(), ctypes.byref(a), ctypes.byref(b))
+    a, b = _pair_args(first, second, betas, eps, weight_decay)
+    _dw_ex(a, b, None, stream)
 
 
 def linear_bwd_dw_adam_pair_l1(first, second, z, H, rows, z_slot=NO_SLOT, betas=(0.9, 0.999), eps=1e-8,
@@ -240,14 +263,13 @@ def linear_bwd_dw_adam_pair_l1(first, second, z, H, rows, z_slot=NO_SLOT, betas=
     """linear_bwd_dw_adam_pair(first, second) followed by linear_fwd(z, second's W, second's b, H, "relu", M=rows,
     x_slot=z_slot) -- the stepped first layer on the next iteration's noise -- as ONE launch where the pair can carry it
     (the second GEMM's tiles form H from the parameters they just stepped), else as those two launches; same bits."""
-    import ctypes
-    mk = lambda d: _dw_adam_args(d["dA"], d["X"], d["lin"], d.get("adam"), d.get("M"),
-                                 d.get("x_slot", NO_SLOT), betas, eps, weight_decay)
     if second.get("adam") is None:
         raise _lib.GMError("linear_bwd_dw_adam_pair_l1: the second GEMM needs its Adam step")
-    a, b = mk(first), mk(second)
-    _lib.call("gm_linear_bwd_dw_adam_pair_l1", stream or stream_ptr(), ctypes.byref(a), ctypes.byref(b),
-              _chk(z, "z").data_ptr(), _ld(z), z_slot, _chk(H, "H").data_ptr(), _ld(H), rows)
+    a, b = _pair_args(first, second, betas, eps, weight_decay)
+    t = _lib.DwTail()
+    t.z, t.ldz, t.z_slot = _chk(z, "z").data_ptr(), _ld(z), z_slot
+    t.H, t.ldh, t.rows = _chk(H, "H").data_ptr(), _ld(H), rows
+    _dw_ex(a, b, t, stream)
     return H
 
 
@@ -256,35 +278,29 @@ def linear_bwd_dw_adam_pair_finalize(first, second, fin, betas=(0.9, 0.999), eps
     """linear_bwd_dw_adam_pair as the LAST launch of a VAE batch: one more workgroup runs sum_finalize2's two sums and
     the last workgroup to finish advances the step counter.  fin: dict(pa, na, out_a, slot_a, pb, nb, out_b, slot_b,
     done (one zeroed int32 the launch counts its workgroups on), tick=None, scale_a=1.0, scale_b=1.0)."""
-    import ctypes
-    from ._lib import Finalize2Args
-    mk = lambda d: _dw_adam_args(d["dA"], d["X"], d["lin"], d.get("adam"), d.get("M"),
-                                 d.get("x_slot", NO_SLOT), betas, eps, weight_decay)
-    a, b = mk(first), mk(second)
-    f = Finalize2Args()
+    a, b = _pair_args(first, second, betas, eps, weight_decay)
+    f = _lib.Finalize2Args()
     f.pa, f.na, f.scale_a, f.out_a, f.slot_a = fin["pa"].data_ptr(), fin["na"], fin.get("scale_a", 1.0), \
         fin["out_a"].data_ptr(), fin["slot_a"]
     f.pb, f.nb, f.scale_b, f.out_b, f.slot_b = fin["pb"].data_ptr(), fin["nb"], fin.get("scale_b", 1.0), \
         fin["out_b"].data_ptr(), fin["slot_b"]
-    tick = fin.get("tick")
-    f.tick = tick.data_ptr() if tick is not None else None
+    f.tick = _ptr(fin.get("tick"))
     assert fin["done"].dtype == torch.int32 and fin["done"].numel() >= 1
     f.done = fin["done"].data_ptr()
-    _lib.call("gm_linear_bwd_dw_adam_pair_finalize", stream or stream_ptr(), ctypes.byref(a), ctypes.byref(b),
-              ctypes.byref(f))
+    t = _lib.DwTail()
+    t.fin = ctypes.pointer(f)
+    _dw_ex(a, b, t, stream)
 
 
 def _head_args(head, betas=(0.9, 0.999), eps=1e-8):
     """gm_head_bwd_args from dict(H, dS, lin (head _Linear), rowloss, loss_out, loss_slot, inv_b, B,
     gen_mode=False, adam=None (dict(sched, sched_slot, clamp)), tick=None, grads=True).  dS / rowloss
     may be None for the folded head (they are rebuilt from the forward's partial dots)."""
-    from ._lib import HeadBwdArgs
     hl, ha, H = head["lin"], head.get("adam"), head["H"]
     gen = bool(head.get("gen_mode", False))
-    a = HeadBwdArgs()
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    a.H, a.ldh, a.dS = H.data_ptr(), _ld(H), ptr(head.get("dS"))
-    a.w2, a.b2, a.rowloss = hl.W.data_ptr(), hl.b.data_ptr(), ptr(head.get("rowloss"))
+    a = _lib.HeadBwdArgs()
+    a.H, a.ldh, a.dS = H.data_ptr(), _ld(H), _ptr(head.get("dS"))
+    a.w2, a.b2, a.rowloss = hl.W.data_ptr(), hl.b.data_ptr(), _ptr(head.get("rowloss"))
     a.dH, a.lddh = None, 0                      # written by head_fwd_loss
     if not gen:
         a.gw2, a.gb2 = hl.gW.data_ptr(), hl.gb.data_ptr()
@@ -296,12 +312,7 @@ def _head_args(head, betas=(0.9, 0.999), eps=1e-8):
         a.sched, a.sched_slot = ha["sched"].data_ptr(), ha["sched_slot"]
         a.clamp = ha.get("clamp", 0.0)
     a.beta1, a.beta2, a.eps, a.weight_decay = betas[0], betas[1], eps, 0.0
-    tick = head.get("tick")
-    a.tick = tick.data_ptr() if tick is not None else None
-    add = head.get("gw2_add")
-    a.gw2_add = add.data_ptr() if add is not None else None
-    addb = head.get("gb2_add")
-    a.gb2_add = addb.data_ptr() if addb is not None else None
+    a.tick, a.gw2_add, a.gb2_add = _ptr(head.get("tick")), _ptr(head.get("gw2_add")), _ptr(head.get("gb2_add"))
     pen = head.get("pen")                       # dict(s=[rows], h=[rows, Hd], t=[rows, Hd]): see gm_hip.h
     if pen is not None:
         a.pen_s, a.pen_h, a.pen_ldh = pen["s"].data_ptr(), pen["h"].data_ptr(), _ld(pen["h"])
@@ -313,24 +324,22 @@ def linear_fwd_sqerr(x, W, b, y, target, dA, part, M=None, stream=None):
     """Sigmoid output layer + the reconstruction loss in its epilogue (vae.py:203): y = sigmoid(xW^T+b),
     dA = d sum((target - y)^2) / d (pre-sigmoid), part[m, j] = the row's squared error inside 32-column
     tile j (part: [>= M, >= ceil(N/32)], zero-initialised; sum it with ops_fused.sum_finalize*)."""
-    N, K = W.shape
-    M = x.shape[0] if M is None else M
-    assert part.dim() == 2 and part.shape[0] >= M and part.shape[1] >= (N + 31) // 32
-    _lib.call("gm_linear_fwd_sqerr", stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x),
-              _chk(W, "W").data_ptr(), b.data_ptr() if b is not None else None, _chk(y, "y").data_ptr(), _ld(y),
-              M, K, N, _chk(target, "target").data_ptr(), _ld(target), _chk(dA, "dA").data_ptr(), _ld(dA),
-              part.data_ptr(), part.shape[1])
+    a = _fwd_args(x, W, b, y, "sigmoid", M)
+    assert part.dim() == 2 and part.shape[0] >= a.M and part.shape[1] >= (a.N + 31) // 32
+    a.sq_target, a.sq_ldt = _chk(target, "target").data_ptr(), _ld(target)
+    a.sq_dA, a.sq_lda = _chk(dA, "dA").data_ptr(), _ld(dA)
+    a.sq_part, a.sq_ldp = part.data_ptr(), part.shape[1]
+    _fwd_ex(a, stream)
     return y
 
 
 def linear_bwd_dx_reparam(dA, W, dZ, ml, eps, dml, M=None, eps_slot=NO_SLOT, stream=None):
     """dZ = dA W through the decoder's first layer (W: [N, Z]) + the reparameterisation / KL backward in
     the epilogue: dml = [dZ + mu | dZ*eps*exp(lv/2)/2 + (exp(lv)-1)/2]   (vae.py:100-106,210-212)."""
-    N, Z = W.shape
-    M = dA.shape[0] if M is None else M
-    _lib.call("gm_linear_bwd_dx_reparam", stream or stream_ptr(), _chk(dA, "dA").data_ptr(), _ld(dA),
-              _chk(W, "W").data_ptr(), _chk(dZ, "dZ").data_ptr(), _ld(dZ), M, Z, N, ml.data_ptr(), _ld(ml),
-              eps.data_ptr(), eps_slot, dml.data_ptr(), _ld(dml))
+    a = _dx_args(dA, W, dZ, M=M)
+    a.rp_ml, a.rp_ldml, a.rp_eps, a.rp_slot = ml.data_ptr(), _ld(ml), eps.data_ptr(), eps_slot
+    a.rp_dml, a.rp_ldd = dml.data_ptr(), _ld(dml)
+    _dx_ex(a, stream)
     return dZ
 
 
@@ -355,18 +364,16 @@ class HeadFold:
         self.hidden = hidden
 
     def args(self, variant, out_act, hyper=(), pen=None, S=None, dS=None, rowloss=None):
-        from ._lib import HeadFoldArgs
-        a = HeadFoldArgs()
+        a = _lib.HeadFoldArgs()
         a.part, a.ldp, a.nparts, a.snap = self.part.data_ptr(), self.part.shape[1], self.nparts, self.snap.data_ptr()   # ldp = row stride
         a.variant = LOSS[variant] if not isinstance(variant, int) else variant
-        a.out_act = ACT[out_act] if not isinstance(out_act, int) else out_act
+        a.out_act = _act(out_act)
         hy = tuple(hyper)
         assert len(hy) <= 8
         for i, h in enumerate(hy):
             a.hyper[i] = float(h)
         a.n_hyper = len(hy)
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        a.pen, a.S, a.dS, a.rowloss = ptr(pen), ptr(S), ptr(dS), ptr(rowloss)
+        a.pen, a.S, a.dS, a.rowloss = _ptr(pen), _ptr(S), _ptr(dS), _ptr(rowloss)
         return a
 
 
@@ -378,71 +385,44 @@ def linear_fwd_headpart(x, W, b, y, act, head_lin, fold, M=None, x_slot=NO_SLOT,
     """linear_fwd of the critic's hidden layer that also leaves the folded head's partial dots and
     the (w2, b2) snapshot in `fold` (HeadFold).  xbits = (words, words_per_row, rows): the first `rows` rows of x
     are read from the packed copy (gather_rows_packed) instead."""
-    N, K = W.shape
-    M = x.shape[0] if M is None else M
-    assert fold.hidden == N and fold.part.shape[0] >= M
+    a = _fwd_args(x, W, b, y, act, M, x_slot)
+    assert fold.hidden == a.N and fold.part.shape[0] >= a.M
+    a.hd_w2, a.hd_b2, a.hd_snap = head_lin.W.data_ptr(), head_lin.b.data_ptr(), fold.snap.data_ptr()
+    a.hd_part, a.hd_ldp = fold.part.data_ptr(), fold.part.shape[1]
     if xbits is not None:
-        _lib.call("gm_linear_fwd_headpart_bits", stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x), x_slot,
-                  _chk(W, "W").data_ptr(), b.data_ptr() if b is not None else None, _chk(y, "y").data_ptr(),
-                  _ld(y), M, K, N, ACT[act] if not isinstance(act, int) else act, head_lin.W.data_ptr(),
-                  head_lin.b.data_ptr(), fold.part.data_ptr(), fold.part.shape[1], fold.snap.data_ptr(),
-                  xbits[0].data_ptr(), xbits[1], xbits[2])
-        return y
-    _lib.call("gm_linear_fwd_headpart", stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x), x_slot,
-              _chk(W, "W").data_ptr(), b.data_ptr() if b is not None else None, _chk(y, "y").data_ptr(),
-              _ld(y), M, K, N, ACT[act] if not isinstance(act, int) else act, head_lin.W.data_ptr(),
-              head_lin.b.data_ptr(), fold.part.data_ptr(), fold.part.shape[1], fold.snap.data_ptr())
+        a.xbits, a.xbits_wpr, a.xbits_rows = xbits[0].data_ptr(), xbits[1], xbits[2]
+    _fwd_ex(a, stream)
     return y
 
 
 def linear_bwd_dx_head_fold(H, W, dX, head, fold_args, below=None, epi="id", M=None, stream=None):
     """linear_bwd_dx_head in the folded form: A operand = the hidden activations H (dH is formed in
     registers from the rows' dS and the snapshot of w2); head: see _head_args (dS / rowloss unused)."""
-    import ctypes
-    N, K = W.shape
-    M = H.shape[0] if M is None else M
-    a = _head_args(head)
-    _lib.call("gm_linear_bwd_dx_head_fold", stream or stream_ptr(), _chk(H, "H").data_ptr(), _ld(H),
-              _chk(W, "W").data_ptr(), _chk(dX, "dX").data_ptr(), _ld(dX),
-              below.data_ptr() if below is not None else None, _ld(below) if below is not None else 0,
-              M, K, N, ACT[epi] if not isinstance(epi, int) else epi, ctypes.byref(a), ctypes.byref(fold_args))
+    a = _dx_args(H, W, dX, below, epi, M)
+    h = _head_args(head)
+    a.head, a.fold = ctypes.pointer(h), ctypes.pointer(fold_args)
+    _dx_ex(a, stream)
     return dX
 
 
 def linear_bwd_dw_adam_head_fold(H, X, lin, adam, head, fold_args, M=None, x_slot=NO_SLOT,
                                  betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, stream=None, xbits=None):
     """linear_bwd_dw_adam_head in the folded form (see linear_bwd_dx_head_fold).  xbits: as linear_fwd_headpart."""
-    import ctypes
-    N, K = lin.gW.shape
-    M = H.shape[0] if M is None else M
-    a = _head_args(head, betas, eps)
-    name = "gm_linear_bwd_dw_adam_head_fold" + ("_bits" if xbits is not None else "")
-    tail = (xbits[0].data_ptr(), xbits[1], xbits[2]) if xbits is not None else ()
-    if adam is None:
-        _lib.call(name, stream or stream_ptr(), _chk(H, "H").data_ptr(),
-                  _ld(H), _chk(X, "X").data_ptr(), _ld(X), x_slot, lin.gW.data_ptr(),
-                  lin.gb.data_ptr(), M, K, N, None, None, None, None, None, None, None, NO_SLOT,
-                  betas[0], betas[1], eps, weight_decay, 0.0, ctypes.byref(a), ctypes.byref(fold_args), *tail)
-        return
-    _lib.call(name, stream or stream_ptr(), _chk(H, "H").data_ptr(),
-              _ld(H), _chk(X, "X").data_ptr(), _ld(X), x_slot, lin.gW.data_ptr(),
-              lin.gb.data_ptr(), M, K, N, lin.W.data_ptr(), lin.mW.data_ptr(), lin.vW.data_ptr(),
-              lin.b.data_ptr(), lin.mb.data_ptr(), lin.vb.data_ptr(), adam["sched"].data_ptr(),
-              adam["sched_slot"], betas[0], betas[1], eps, weight_decay, adam.get("clamp", 0.0),
-              ctypes.byref(a), ctypes.byref(fold_args), *tail)
+    a = _dw_adam_args(H, X, lin, adam, M, x_slot, betas, eps, weight_decay)
+    h = _head_args(head, betas, eps)
+    a.head, a.fold = ctypes.pointer(h), ctypes.pointer(fold_args)
+    if xbits is not None:
+        a.xbits, a.xbits_wpr, a.xbits_rows = xbits[0].data_ptr(), xbits[1], xbits[2]
+    _dw_ex(a, None, None, stream)
 
 
 def linear_bwd_dx_head(dA, W, dX, head, below=None, epi="id", M=None, stream=None):
     """linear_bwd_dx with the head's backward workgroups riding in the launch (generator step: the
     scalar workgroup that writes the loss and ticks).  head: see _head_args."""
-    import ctypes
-    N, K = W.shape
-    M = dA.shape[0] if M is None else M
-    a = _head_args(head)
-    _lib.call("gm_linear_bwd_dx_head", stream or stream_ptr(), _chk(dA, "dA").data_ptr(), _ld(dA),
-              _chk(W, "W").data_ptr(), _chk(dX, "dX").data_ptr(), _ld(dX),
-              below.data_ptr() if below is not None else None, _ld(below) if below is not None else 0,
-              M, K, N, ACT[epi] if not isinstance(epi, int) else epi, ctypes.byref(a))
+    a = _dx_args(dA, W, dX, below, epi, M)
+    h = _head_args(head)
+    a.head = ctypes.pointer(h)
+    _dx_ex(a, stream)
     return dX
 
 
@@ -451,23 +431,12 @@ def linear_bwd_dw_adam_head(dA, X, lin, adam, head, M=None, x_slot=NO_SLOT, beta
     """linear_bwd_dw_adam and the critic head's backward (ops_fused.head_bwd with Adam on the head
     layer) as ONE launch.  head: dict(H, dS, lin (head _Linear), rowloss, loss_out, loss_slot,
     inv_b, B, adam (dict(sched, sched_slot, clamp)), gw2_add=None); dH must already be written by
-    head_fwd_loss.  ones_from: the first rows of the (stacked) reduction that do not reach db."""
-    import ctypes
-    N, K = lin.gW.shape
-    M = dA.shape[0] if M is None else M
-    a = _head_args(head, betas, eps)
-    if adam is None:                            # plain gradients (the head's dict has adam=None too)
-        _lib.call("gm_linear_bwd_dw_adam_head_ex", stream or stream_ptr(), _chk(dA, "dA").data_ptr(),
-                  _ld(dA), _chk(X, "X").data_ptr(), _ld(X), x_slot, lin.gW.data_ptr(),
-                  lin.gb.data_ptr(), M, K, N, None, None, None, None, None, None, None, NO_SLOT,
-                  betas[0], betas[1], eps, weight_decay, 0.0, ctypes.byref(a), ones_from)
-        return
-    _lib.call("gm_linear_bwd_dw_adam_head_ex", stream or stream_ptr(), _chk(dA, "dA").data_ptr(),
-              _ld(dA), _chk(X, "X").data_ptr(), _ld(X), x_slot, lin.gW.data_ptr(),
-              lin.gb.data_ptr(), M, K, N, lin.W.data_ptr(), lin.mW.data_ptr(), lin.vW.data_ptr(),
-              lin.b.data_ptr(), lin.mb.data_ptr(), lin.vb.data_ptr(), adam["sched"].data_ptr(),
-              adam["sched_slot"], betas[0], betas[1], eps, weight_decay, adam.get("clamp", 0.0),
-              ctypes.byref(a), ones_from)
+    head_fwd_loss.  ones_from: the first rows of the (stacked) reduction that do not reach db.
+    adam=None: plain gradients (the head's dict has adam=None too)."""
+    a = _dw_adam_args(dA, X, lin, adam, M, x_slot, betas, eps, weight_decay)
+    h = _head_args(head, betas, eps)
+    a.head, a.ones_from = ctypes.pointer(h), ones_from
+    _dw_ex(a, None, None, stream)
 
 
 class PackedData:

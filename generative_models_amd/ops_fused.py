@@ -471,23 +471,18 @@ def gather_rows_corrupt(data, idx, out, out_c, args, B=None, idx_slot=NO_SLOT, s
 
 def linear_fwd_gather_corrupt(x, W, b, y, act, data, idx, out, out_c, args, M=None, B=None, x_slot=NO_SLOT,
                               idx_slot=NO_SLOT, stream=None):
-    """ops.linear_fwd_gather with the corrupting gather riding in the GEMM's grid (gm_linear_fwd_gather[_bits]_corrupt):
+    """ops.linear_fwd_gather with the corrupting gather riding in the GEMM's grid (gm_gather_args.corrupt / out_c):
     out gets the clean rows, out_c their corruption; neither may be an operand of this GEMM."""
-    from .ops import ACT, PackedData, _chk
-    N, K = W.shape
-    M = x.shape[0] if M is None else M
-    n_rows, row = data.shape
-    B = out.shape[0] if B is None else B
+    from .ops import PackedData, _fwd_args, _fwd_ex, _gather_args
     _rows2d(out, "out")
     _corrupt_out(out, out_c)
-    head = (stream or stream_ptr(), _chk(x, "x").data_ptr(), _ld(x), x_slot, _chk(W, "W").data_ptr(),
-            b.data_ptr() if b is not None else None, _chk(y, "y").data_ptr(), _ld(y), M, K, N, ACT[act])
-    if isinstance(data, PackedData):
-        _lib.call("gm_linear_fwd_gather_bits_corrupt", *head, data.data_ptr(), data.wpr, n_rows, idx.data_ptr(),
-                  idx_slot, out.data_ptr(), _ld(out), B, row, out_c.data_ptr(), ctypes.byref(args))
-    else:
-        _lib.call("gm_linear_fwd_gather_corrupt", *head, _rows2d(data, "data").data_ptr(), n_rows, idx.data_ptr(),
-                  idx_slot, out.data_ptr(), _ld(out), B, row, out_c.data_ptr(), ctypes.byref(args))
+    if not isinstance(data, PackedData):
+        _rows2d(data, "data")
+    a = _fwd_args(x, W, b, y, act, M, x_slot)
+    g = _gather_args(data, idx, out, B, idx_slot)
+    g.corrupt, g.out_c = ctypes.pointer(args), out_c.data_ptr()
+    a.gather = ctypes.pointer(g)
+    _fwd_ex(a, stream)
     return y
 
 

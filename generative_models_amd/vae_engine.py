@@ -155,7 +155,7 @@ class VAEEngine:
     def _gather_plan(self, pos, of):
         """Batch `pos` of a graph of `of` equal-size batches: (its image buffer, whether it gathers its
         own rows, the buffer the NEXT batch's rows are prefetched into or None).  Inside a multi-batch
-        graph the gather of batch i+1 rides in a small forward GEMM of batch i (gm_linear_fwd_gather:
+        graph the gather of batch i+1 rides in a small forward GEMM of batch i (ops.linear_fwd_gather:
         extra workgroups of that launch), so only the graph's first batch pays a gather launch."""
         X = self.Xb[pos % 2]
         nxt = self.Xb[(pos + 1) % 2] if (self.prefetch_gather and pos + 1 < of) else None
@@ -605,7 +605,7 @@ def validate_labels(labels, num_classes, error=GMError):
 
 class CVAEEngine(VAEEngine):
     """The class-conditional VAE (cvae.py) on the VAE engine's batch: the encoder's and the decoder's first layers take
-    E[:, y_m] in their forward epilogues (gm_linear_fwd_label, gm_vae_reparam_fwd_label), row m's class read through
+    E[:, y_m] in their forward epilogues (ops.linear_fwd_label, gm_vae_reparam_fwd_label), row m's class read through
     the batch's row of the index ring -- no gather of its own -- and one more launch (gm_label_grad_adam) forms both
     label weights' gradients by class and steps them with Adam.  9 launches per batch (the VAE's 8 + that one).
     One GPU only; the fused form of the VAE batch only (configure() refuses the toggles that would turn off fused

@@ -90,16 +90,9 @@ int gm_linear_bwd_dx(void* stream, const float* dA, int64_t lda, const float* W,
 int gm_linear_bwd_dw(void* stream, const float* dA, int64_t lda, const float* X, int64_t ldx,
                      gm_slot x_slot, float* dW, float* db, int M, int K, int N, int accumulate);
 
-/* gm_linear_bwd_dw with the optimizer folded into the gradient epilogue: dW/db are written as
- * usual and Adam (same arithmetic as gm_adam) is applied to (pW,mW,vW)/(pb,mb,vb)
- * by the thread that produced the gradient element -- optim.Adam.step (ns_gan.py:139,156) without
- * its own launch.  Single-GPU fast path only (under data parallelism the all-reduce sits between
- * gradient and optimizer). */
-int gm_linear_bwd_dw_adam(void* stream, const float* dA, int64_t lda, const float* X, int64_t ldx,
-                          gm_slot x_slot, float* dW, float* db, int M, int K, int N, float* pW,
-                          float* mW, float* vW, float* pb, float* mb, float* vb, const float* sched,
-                          gm_slot sched_slot, double beta1, double beta2, double eps,
-                          double weight_decay, float clamp);
+/* The three launches above with work riding in them (an epilogue term, the optimizer step, a batch gather, the critic
+ * head, a second GEMM): gm_linear_fwd_ex / gm_linear_bwd_dx_ex / gm_linear_bwd_dw_ex further down, one descriptor each.
+ * The plain entry points are those calls with only the base fields of the descriptor set. */
 
 /* ---- K4: adversarial loss + its gradient w.r.t. the critic's PRE-activation output.
  * sx,sg: [B] post-activation scores D(x), D(G(z)) (sx NULL in generator mode).
@@ -191,9 +184,9 @@ int gm_vae_reparam_fwd(void* stream, const float* ml, int64_t ldml, const float*
                        float* z, int64_t ldz, float* kl_part, int n_part, int B, int Z, const float* W,
                        const float* bias, float* H, int64_t ldh, int N, int act);
 /* The two narrow GEMMs in the middle of the VAE's backward pass as ONE launch (round 4): dz = dHdec W_d1
- * (W_d1: [Hd, Z], decoder layer 1), d loss / d [mu | log_var] from dz exactly as gm_linear_bwd_dx_reparam's epilogue
+ * (W_d1: [Hd, Z], decoder layer 1), d loss / d [mu | log_var] from dz exactly as gm_dx_args' reparam epilogue
  * forms it (dml: [B, 2Z], written), dHe = (dml W_ml) . [He > 0] (W_ml: [2Z, Hd], the encoder's mu / log_var layer).
- * One workgroup per 16 rows; same summation orders as gm_linear_bwd_dx_reparam followed by gm_linear_bwd_dx.
+ * One workgroup per 16 rows; same summation orders as that launch followed by gm_linear_bwd_dx.
  * Z <= 32, Hd % 4 == 0.  dz itself is not stored. */
 int gm_vae_bwd_mid(void* stream, const float* dHdec, int64_t lddh, const float* Wd1, const float* ml,
                    int64_t ldml, const float* eps, gm_slot eps_slot, float* dml, int64_t lddml,
@@ -270,11 +263,11 @@ int gm_adam_scaled(void* stream, float* p, const float* g, float* m, float* v, i
                    const float* sched, gm_slot sched_slot, double beta1, double beta2, double eps,
                    double weight_decay, float clamp, const float* lr_scale);
 /* The critic head's backward and the first layer's weight gradient are independent once
- * gm_head_fwd_loss has written dH: this entry point runs gm_linear_bwd_dw_adam AND gm_head_bwd_fused
+ * gm_head_fwd_loss has written dH: gm_dw_adam_args.head runs the weight gradient (+ Adam) AND gm_head_bwd_fused
  * as ONE launch (the head workgroups ride in the GEMM's grid; 25 + 169 workgroups for the 784-400-1
- * critic at B = 256 -- one round of the 256 CUs).  `head` mirrors gm_head_bwd_fused's arguments.
- * sched == NULL (and head->with_adam == 0): plain gradients, no optimizer step (data-parallel runs
- * all-reduce the gradients first). */
+ * critic at B = 256 -- one round of the 256 CUs); gm_dx_args.head carries them in an input-gradient launch.
+ * This block mirrors gm_head_bwd_fused's arguments.  with_adam == 0: plain gradients, no optimizer step
+ * (data-parallel runs all-reduce the gradients first). */
 typedef struct gm_head_bwd_args {
     const float* H; int64_t ldh;
     const float* dS; float* w2; float* b2; const float* rowloss;
@@ -294,30 +287,10 @@ typedef struct gm_head_bwd_args {
     const float* gb2_add;                 /* optional [1]: added to gb2 before it is stored / stepped (DRAGAN's sigma''
                                            * path reaches the head bias, dra_gan.py:207-223; gm_dragan_head_bwd_store) */
 } gm_head_bwd_args;
-int gm_linear_bwd_dw_adam_head(void* stream, const float* dA, int64_t lda, const float* X,
-                               int64_t ldx, gm_slot x_slot, float* dW, float* db, int M, int K, int N,
-                               float* pW, float* mW, float* vW, float* pb, float* mb, float* vb,
-                               const float* sched, gm_slot sched_slot, double beta1, double beta2,
-                               double eps, double weight_decay, float clamp,
-                               const gm_head_bwd_args* head);
-/* Same with a STACKED reduction: the first `ones_from` rows of dA / X contribute to dW but not to db
- * (WGAN-GP, w_gp_gan.py:207-218: dW1 = [u ; dH]^T [gamma ; X] in one GEMM -- the penalty's second
- * backward has no bias term). */
-int gm_linear_bwd_dw_adam_head_ex(void* stream, const float* dA, int64_t lda, const float* X,
-                                  int64_t ldx, gm_slot x_slot, float* dW, float* db, int M, int K, int N,
-                                  float* pW, float* mW, float* vW, float* pb, float* mb, float* vb,
-                                  const float* sched, gm_slot sched_slot, double beta1, double beta2,
-                                  double eps, double weight_decay, float clamp,
-                                  const gm_head_bwd_args* head, int ones_from);
-/* gm_linear_bwd_dx carrying the head's backward workgroups (generator step: the single scalar
- * workgroup that writes the loss and ticks the iteration counter). */
-int gm_linear_bwd_dx_head(void* stream, const float* dA, int64_t lda, const float* W, float* dX,
-                          int64_t ldx, const float* below, int64_t ld_below, int M, int K, int N,
-                          int epi, const gm_head_bwd_args* head);
 /* ---- FOLDED critic head (round 3): no launch for the N = 1 layer at all.
  * Discriminator.forward's second layer (ns_gan.py:59: `discrimination = sigmoid(self.discriminate(
  * activated))`, a [R, 400] x [400] product) is split over the launches on either side of it:
- *  - gm_linear_fwd_headpart = gm_linear_fwd of the hidden layer whose epilogue also leaves, per
+ *  - the head part of gm_fwd_args = gm_linear_fwd of the hidden layer whose epilogue also leaves, per
  *    32-column tile j of the hidden layer, part[r * ldp + j] = sum_{n in tile j} Y[r, n] * w2[n]
  *    (nparts = ceil(N / 32) <= 16 entries per row, rows ldp floats apart, ldp % 4 == 0, the unused
  *    entries of a row stay zero) and a snapshot snap[0..N) = w2, snap[N] = b2[0] of the head
@@ -325,10 +298,10 @@ int gm_linear_bwd_dx_head(void* stream, const float* dA, int64_t lda, const floa
  *  - the consumers rebuild, per row, score = act(sum_j part[r][j] + b2), the row's loss term and
  *    dS (the train_D / train_G loss lines: ns_gan.py:191-192,214 and the siblings gm_head_fwd_loss
  *    lists) in a prologue, and form dH[r, n] = dS_r * w2[n] * [Y[r, n] > 0] in registers while loading
- *    their A operand: gm_linear_bwd_dw_adam_head_fold (critic step: layer-1 weight gradient + Adam,
- *    head backward workgroups riding: gw2, gb2, loss, Adam on (w2, b2)) and gm_linear_bwd_dx_head_fold
+ *    their A operand: gm_dw_adam_args.head + fold (critic step: layer-1 weight gradient + Adam,
+ *    head backward workgroups riding: gw2, gb2, loss, Adam on (w2, b2)) and gm_dx_args.head + fold
  *    (generator step: dX through layer 1 + the loss / tick workgroup).  Both take the hidden
- *    activations H where the unfolded entry points take dH; head->dS / head->rowloss are not read.
+ *    activations H as dA where the unfolded form takes dH; head->dS / head->rowloss are not read.
  * Summation order of a score: 32-lane butterfly inside a tile, then tiles j = 0, 1, ... : fixed, so
  * results are bitwise reproducible run to run (they differ from gm_head_fwd_loss's order in the last
  * bits).  fold->S / dS / rowloss (optional, [R]) receive the per-row values for inspection. */
@@ -340,131 +313,21 @@ typedef struct gm_head_fold_args {
     const float* pen;                     /* optional penalty rows added to the x rows' loss terms */
     float* S; float* dS; float* rowloss;  /* optional outputs */
 } gm_head_fold_args;
-int gm_linear_fwd_headpart(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
-                           const float* bias, float* Y, int64_t ldy, int M, int K, int N, int act,
-                           const float* w2, const float* b2, float* part, int64_t ldp, float* snap);
-int gm_linear_bwd_dw_adam_head_fold(void* stream, const float* H, int64_t ldh, const float* X,
-                                    int64_t ldx, gm_slot x_slot, float* dW, float* db, int M, int K, int N,
-                                    float* pW, float* mW, float* vW, float* pb, float* mb, float* vb,
-                                    const float* sched, gm_slot sched_slot, double beta1, double beta2,
-                                    double eps, double weight_decay, float clamp,
-                                    const gm_head_bwd_args* head, const gm_head_fold_args* fold);
-int gm_linear_bwd_dx_head_fold(void* stream, const float* H, int64_t ldh, const float* W, float* dX,
-                               int64_t ldx, const float* below, int64_t ld_below, int M, int K, int N,
-                               int epi, const gm_head_bwd_args* head, const gm_head_fold_args* fold);
-/* VAE / AE reconstruction loss where the reconstruction is produced (vae.py:196-203: `recon_loss =
- * torch.sum((images - outputs)**2)` behind Decoder.forward's sigmoid, vae.py:75-77; ae.py:147-160):
- * gm_linear_fwd of the decoder's last layer (sigmoid) whose epilogue also writes
- *   dA[m][n] = d loss / d (pre-sigmoid output) = (-2 (x - x_hat) (1 - x_hat)) x_hat   (as gm_sqerr_sigmoid_bwd)
- *   part[m * ldp + j] = sum_{n in 32-column tile j} (x[m][n] - x_hat[m][n])^2,  j < ceil(N / 32) <= ldp
- * (entries j >= ceil(N / 32) of a row are not written; gm_sum_finalize* over the whole `part` array adds
- * them up in a fixed order).  Replaces the separate gm_sqerr_sigmoid_bwd launch. */
-int gm_linear_fwd_sqerr(void* stream, const float* X, int64_t ldx, const float* W, const float* bias,
-                        float* Y, int64_t ldy, int M, int K, int N, const float* target,
-                        int64_t ld_target, float* dA, int64_t lda, float* part, int64_t ldp);
-/* VAE reparameterisation backward where dz is produced (vae.py:100-106 `z = mu + eps * exp(log_var/2)`
- * and kl_divergence :210-212, autograd of both): gm_linear_bwd_dx through the decoder's first layer
- * (dZ = dA W, W: [N, Z]) whose epilogue also writes, with the expressions of gm_vae_reparam_bwd,
- *   dml[m][c] = dz + mu,   dml[m][Z + c] = dz eps exp(lv/2) / 2 + (exp(lv) - 1) / 2.
- * Replaces the separate gm_vae_reparam_bwd launch (bit-identical results). */
-int gm_linear_bwd_dx_reparam(void* stream, const float* dA, int64_t lda, const float* W, float* dZ,
-                             int64_t ldz, int M, int Z, int N, const float* ml, int64_t ldml,
-                             const float* eps, gm_slot eps_slot, float* dml, int64_t ldd);
-/* gm_linear_fwd that also writes WGAN-GP's interpolate for its first `rows` output rows
- * (w_gp_gan.py:197-201: x_hat = eps * x + (1 - eps) * G(z), computed where G(z) is produced):
- *   x_hat[m][n] = eps[m] * x_real[m][n] + (1 - eps[m]) * Y[m][n],  m < rows
- * eps: per-row uniforms (ring base + eps_slot).  Saves the separate gm_interp launch. */
-int gm_linear_fwd_interp(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
-                         const float* bias, float* Y, int64_t ldy, int M, int K, int N, int act,
-                         const float* eps, gm_slot eps_slot, const float* x_real, int64_t ld_real,
-                         float* x_hat, int64_t ld_hat, int rows);
-/* gm_linear_fwd and gm_gather_rows as ONE launch: the gather workgroups ride in the GEMM's grid.  The
- * gather only reads the index ring and the resident dataset, so any forward launch that does not
- * touch `out` can carry it (the engine uses the generator's first layer, ns_gan.py:44 + :222-226). */
-int gm_linear_fwd_gather(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
-                         const float* bias, float* Y, int64_t ldy, int M, int K, int N, int act,
-                         const float* data, int64_t n_rows, const int64_t* idx, gm_slot idx_slot,
-                         float* out, int64_t ld_out, int B, int row_elems);
-/* Same with the BIT-PACKED resident dataset (utils.py:31 binarises MNIST): row r
+/* gm_gather_rows with the BIT-PACKED resident dataset (utils.py:31 binarises MNIST): row r
  * = bits[r*words_per_row ...], pixel i = bit (i & 31) of word i >> 5; the gather expands to fp32 rows. */
-int gm_linear_fwd_gather_bits(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
-                              const float* bias, float* Y, int64_t ldy, int M, int K, int N, int act,
-                              const uint32_t* bits, int words_per_row, int64_t n_rows, const int64_t* idx,
-                              gm_slot idx_slot, float* out, int64_t ld_out, int B, int row_elems);
 int gm_gather_rows_bits(void* stream, const uint32_t* bits, int words_per_row, int64_t n_rows,
                         const int64_t* idx, gm_slot idx_slot, float* out, int64_t ld_out, int B,
                         int row_elems);
 /* Bit-packed rows AS A GEMM OPERAND (the data is process_batch's, ns_gan.py:222-226, binarised by
  * utils.py:31): the gather copies the selected rows as WORDS (out_bits[b * words_per_row ..), 100 B per MNIST row
- * instead of 3136), and the folded critic step's two launches read rows [0, rows) of X from that copy, expanding to
- * 0.0f / 1.0f in registers -- the fp32 rows X[0 .. rows) are neither written nor read.  Same MFMA sequence on the same
- * values: results are bit-identical to the fp32-operand entry points.  rows % 32 == 0, K % 4 == 0 (a forward tile /
- * reduction chunk is packed as a whole); one tile shape per launch (32x32 forward, 32x48 weight gradient, operands
- * through registers); anything else returns GM_EINVAL -- there is no fp32 copy to fall back to. */
+ * instead of 3136), and the folded critic step's two launches (the xbits fields of gm_fwd_args and gm_dw_adam_args)
+ * read rows [0, rows) of X from that copy, expanding to 0.0f / 1.0f in registers -- the fp32 rows X[0 .. rows) are
+ * neither written nor read.  Same MFMA sequence on the same values: results are bit-identical to the fp32-operand
+ * launches.  rows % 32 == 0, K % 4 == 0 (a forward tile / reduction chunk is packed as a whole); one tile shape per
+ * launch (32x32 forward, 32x48 weight gradient, operands through registers); anything else returns GM_EINVAL -- there
+ * is no fp32 copy to fall back to. */
 int gm_gather_rows_bits_packed(void* stream, const uint32_t* bits, int words_per_row, int64_t n_rows,
                                const int64_t* idx, gm_slot idx_slot, uint32_t* out_bits, int B);
-int gm_linear_fwd_gather_bits_packed(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
-                                     const float* bias, float* Y, int64_t ldy, int M, int K, int N, int act,
-                                     const uint32_t* bits, int words_per_row, int64_t n_rows, const int64_t* idx,
-                                     gm_slot idx_slot, uint32_t* out_bits, int B);
-int gm_linear_fwd_headpart_bits(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
-                                const float* bias, float* Y, int64_t ldy, int M, int K, int N, int act,
-                                const float* w2, const float* b2, float* part, int64_t ldp, float* snap,
-                                const uint32_t* xbits, int words_per_row, int rows);
-int gm_linear_bwd_dw_adam_head_fold_bits(void* stream, const float* H, int64_t ldh, const float* X,
-                                         int64_t ldx, gm_slot x_slot, float* dW, float* db, int M, int K, int N,
-                                         float* pW, float* mW, float* vW, float* pb, float* mb, float* vb,
-                                         const float* sched, gm_slot sched_slot, double beta1, double beta2,
-                                         double eps, double weight_decay, float clamp,
-                                         const gm_head_bwd_args* head, const gm_head_fold_args* fold,
-                                         const uint32_t* xbits, int words_per_row, int rows);
-/* Two gm_linear_bwd_dw_adam calls over the same batch rows as ONE launch (the generator step's two
- * weight gradients are independent once d loss / d hidden is known).  Falls back to two launches
- * when the pair cannot share a tile configuration.  sched == NULL in an argument block: plain
- * gradient for that GEMM (no optimizer step). */
-typedef struct gm_dw_adam_args {
-    const float* dA; int64_t lda; const float* X; int64_t ldx; gm_slot x_slot;
-    float* dW; float* db; int M, K, N;
-    float* pW; float* mW; float* vW; float* pb; float* mb; float* vb;
-    const float* sched; gm_slot sched_slot;
-    double beta1, beta2, eps, weight_decay; float clamp;
-} gm_dw_adam_args;
-int gm_linear_bwd_dw_adam_pair(void* stream, const gm_dw_adam_args* first,
-                               const gm_dw_adam_args* second);
-/* The generator's pair carrying the NEXT iteration's first layer: after the pair (second = the first layer's dW1 + Adam,
- * required), H[rows, second->N] = relu(z W1^T + b1) with the stepped W1, b1 -- z: rows x second->K at z + the slot's
- * offset, leading dimension ldz.  Bit-identical to gm_linear_bwd_dw_adam_pair followed by gm_linear_fwd, which is what
- * runs where the pair cannot carry it.  H may be none of the pair's arrays. */
-int gm_linear_bwd_dw_adam_pair_l1(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second,
-                                  const float* z, int64_t ldz, gm_slot z_slot, float* H, int64_t ldh, int rows);
-/* The pair as the LAST launch of a VAE batch (vae.py:162 + the loss sums of :203 / :212): one more workgroup adds up
- * the two partial arrays exactly as gm_sum_finalize2_tick does, and the last workgroup of the launch to finish
- * advances `tick` (every slot of the batch has been resolved by then).  done: one zero-initialised unsigned int the
- * launch counts its workgroups on and re-arms.  Falls back to separate launches when the pair cannot share a tile. */
-typedef struct gm_finalize2_args {
-    const float* pa; int na; float scale_a; float* out_a; gm_slot slot_a;
-    const float* pb; int nb; float scale_b; float* out_b; gm_slot slot_b;
-    int64_t* tick; unsigned int* done;
-} gm_finalize2_args;
-int gm_linear_bwd_dw_adam_pair_finalize(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second,
-                                        const gm_finalize2_args* fin);
-/* gm_linear_bwd_dx with an additive term before the activation gradient:
- * dX = (dA*W + add_scale*add) * act'(below)   (BEGAN's generator sees G(z) both through D and
- * directly in |D(G(z)) - G(z)|, be_gan.py:256). */
-int gm_linear_bwd_dx_add(void* stream, const float* dA, int64_t lda, const float* W, float* dX,
-                         int64_t ldx, const float* below, int64_t ld_below, int M, int K, int N,
-                         int epi, const float* add, int64_t ldadd, float add_scale);
-/* gm_linear_bwd_dx with gm_gather_rows(data, idx, idx_slot, out, ...) riding in the same launch (out: none of the
- * GEMM's arrays). */
-int gm_linear_bwd_dx_gather(void* stream, const float* dA, int64_t lda, const float* W, float* dX, int64_t ldx,
-                            const float* below, int64_t ld_below, int M, int K, int N, int epi, const float* data,
-                            int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out, int64_t ld_out, int B,
-                            int row_elems);
-/* Same with the bit-packed resident dataset (gm_linear_fwd_gather_bits' layout). */
-int gm_linear_bwd_dx_gather_bits(void* stream, const float* dA, int64_t lda, const float* W, float* dX, int64_t ldx,
-                                 const float* below, int64_t ld_below, int M, int K, int N, int epi,
-                                 const uint32_t* bits, int words_per_row, int64_t n_rows, const int64_t* idx,
-                                 gm_slot idx_slot, float* out, int64_t ld_out, int B, int row_elems);
 
 /* ---- K13: DRAGAN penalty (dra_gan.py:198-223; derivation in SURVEY.md A.3).  std_all: unbiased std
  * of the whole real batch; xhat: delta*x + (1-delta)*(x + C*std*U); rows: per-row norm of the input
@@ -487,7 +350,7 @@ int gm_dragan_rows(void* stream, const float* s, const float* V, int64_t ldv, fl
 int gm_dragan_head_bwd(void* stream, const float* H, int64_t ldh, const float* T, int64_t ldt,
                        const float* da2, const float* w2, float* gw2, float* gb2, float* dA1,
                        int64_t ldd, int B, int Hd);
-/* Fisher GAN (fisher_gan.py:155-156) on the folded critic head: gm_linear_bwd_dw_adam_head_fold with variant
+/* Fisher GAN (fisher_gan.py:155-156) on the folded critic head: gm_linear_bwd_dw_ex (head + fold) with variant
  * GM_LOSS_FISHER reads lambda = aux[0] in every workgroup and leaves lambda + rho * d loss / d lambda in aux[5]
  * (and the four moments in aux[1..4]); this launch makes it lambda.  aux: 8 floats. */
 int gm_fisher_commit(void* stream, float* aux);
@@ -700,12 +563,6 @@ typedef struct gm_label_src {
     const int64_t* idx;       /* NULL: row m reads labels[m] */
     gm_slot idx_slot;
 } gm_label_src;
-/* Y = act(X W^T + b + E[:, y_m]), 1 <= C <= 32: the first layers of CVAE Encoder.forward / Decoder.forward
- * (cvae.py), called from vae_engine.CVAEEngine._issue (encoder; decoder when Z > 32 or Z % 4 != 0) and from
- * ops._LabelLinear (the autograd path). */
-int gm_linear_fwd_label(void* stream, const float* X, int64_t ldx, const float* W, const float* bias,
-                        const float* E, int C, gm_label_src lab, float* Y, int64_t ldy, int M, int K, int N,
-                        int act);
 /* gm_vae_reparam_fwd whose decoder-layer workgroups add E[:, y_m] before the activation: CVAE.forward's
  * reparameterisation + Decoder.linear/label (cvae.py), called from vae_engine.CVAEEngine._issue. */
 int gm_vae_reparam_fwd_label(void* stream, const float* ml, int64_t ldml, const float* eps, gm_slot eps_slot,
@@ -851,17 +708,131 @@ int gm_gather_rows_corrupt(void* stream, const gm_corrupt_args* a, const float* 
 int gm_gather_rows_bits_corrupt(void* stream, const gm_corrupt_args* a, const uint32_t* bits, int words_per_row,
                                 int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out, float* out_c,
                                 int64_t ld_out, int B, int row_elems);
-/* gm_linear_fwd_gather / gm_linear_fwd_gather_bits with the corrupting gather riding in the GEMM's grid (the VAE
- * engine's [mu | log_var] forward carrying the NEXT batch's rows; out_c must not be an operand or the output either). */
-int gm_linear_fwd_gather_corrupt(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
-                                 const float* bias, float* Y, int64_t ldy, int M, int K, int N, int act,
-                                 const float* data, int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out,
-                                 int64_t ld_out, int B, int row_elems, float* out_c, const gm_corrupt_args* a);
-int gm_linear_fwd_gather_bits_corrupt(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
-                                      const float* bias, float* Y, int64_t ldy, int M, int K, int N, int act,
-                                      const uint32_t* bits, int words_per_row, int64_t n_rows, const int64_t* idx,
-                                      gm_slot idx_slot, float* out, int64_t ld_out, int B, int row_elems,
-                                      float* out_c, const gm_corrupt_args* a);
+
+/* ---- the linear layers' launches with work riding in them: gm_linear_fwd / gm_linear_bwd_dx / gm_linear_bwd_dw taking
+ * ONE descriptor each.  A zero-initialised descriptor with only its base fields set is the plain entry point.  The
+ * optional blocks are selected by their pointers (all NULL / 0: block absent), and a descriptor offers exactly the
+ * combinations a kernel implements: AT MOST ONE optional block per launch (plus the sub-fields a block names as its
+ * own); anything else returns GM_EINVAL before a launch.  Descriptors are read on the host during the call only. */
+
+/* One batch gather (gm_gather_rows and its siblings) riding in a GEMM's grid, or launched next to it where the GEMM's
+ * tile configuration cannot carry it.  The gather only reads the index ring and the resident dataset, so any launch
+ * that does not touch the gathered rows can carry it: they must be none of the GEMM's operands or outputs. */
+typedef struct gm_gather_args {
+    const float* data;                    /* fp32 dataset [n_rows, row_elems] ... */
+    const uint32_t* bits; int words_per_row;  /* ... or the bit-packed one (gm_gather_rows_bits' layout): exactly one */
+    int64_t n_rows; const int64_t* idx; gm_slot idx_slot;
+    float* out; int64_t ld_out;           /* fp32 rows out[b, :] = data[idx[b], :] ... */
+    uint32_t* out_bits;                   /* ... or the rows as words (gm_gather_rows_bits_packed; bits, forward only;
+                                           * ld_out / row_elems unused): exactly one */
+    int B, row_elems;
+    /* forward only, both or neither: the gather also writes the corrupted copy of every row to out_c (same ld_out;
+     * gm_gather_rows_corrupt / gm_gather_rows_bits_corrupt -- the VAE engine's [mu | log_var] forward carrying the NEXT
+     * batch's rows); out_c must be none of data, out, the GEMM's operands or its output */
+    const gm_corrupt_args* corrupt; float* out_c;
+} gm_gather_args;
+
+/* Y[M,N] = act(X W^T + bias) as gm_linear_fwd, and at most one of the blocks below. */
+typedef struct gm_fwd_args {
+    const float* X; int64_t ldx; gm_slot x_slot; const float* W; const float* bias;
+    float* Y; int64_t ldy; int M, K, N, act;
+    /* interp: the launch also writes WGAN-GP's interpolate for its first ip_rows output rows (w_gp_gan.py:197-201:
+     * x_hat = eps * x + (1 - eps) * G(z), computed where G(z) is produced):
+     *   ip_out[m][n] = ip_eps[m] * ip_x[m][n] + (1 - ip_eps[m]) * Y[m][n],  m < ip_rows
+     * ip_eps: per-row uniforms (ring base + ip_slot).  Saves the separate gm_interp launch. */
+    const float* ip_eps; gm_slot ip_slot; const float* ip_x; int64_t ip_ldx; float* ip_out; int64_t ip_ldo; int ip_rows;
+    /* head part: the folded critic head's partial dots hd_part (rows hd_ldp floats apart) and parameter snapshot
+     * hd_snap (gm_head_fold_args above); hd_part / hd_snap are neither X nor Y.  With xbits: the first xbits_rows rows
+     * of X are read from the packed copy (gm_gather_rows_bits_packed's output, xbits_wpr words per row). */
+    const float* hd_w2; const float* hd_b2; float* hd_part; int64_t hd_ldp; float* hd_snap;
+    const uint32_t* xbits; int xbits_wpr, xbits_rows;
+    /* sqerr (act == GM_ACT_SIGMOID, no x_slot): VAE / AE reconstruction loss where the reconstruction is produced
+     * (vae.py:196-203: `recon_loss = torch.sum((images - outputs)**2)` behind Decoder.forward's sigmoid, vae.py:75-77;
+     * ae.py:147-160).  The decoder's last layer also writes
+     *   sq_dA[m][n] = d loss / d (pre-sigmoid output) = (-2 (x - x_hat) (1 - x_hat)) x_hat   (as gm_sqerr_sigmoid_bwd)
+     *   sq_part[m * sq_ldp + j] = sum_{n in 32-column tile j} (x[m][n] - x_hat[m][n])^2,  j < ceil(N / 32) <= sq_ldp
+     * with x = sq_target (entries j >= ceil(N / 32) of a row are not written; gm_sum_finalize* over the whole array
+     * adds them up in a fixed order).  Replaces the separate gm_sqerr_sigmoid_bwd launch. */
+    const float* sq_target; int64_t sq_ldt; float* sq_dA; int64_t sq_lda; float* sq_part; int64_t sq_ldp;
+    /* label (no x_slot): Y = act(X W^T + b + lb_E[:, y_m]), lb_E [N, lb_C], 1 <= lb_C <= 32, y_m through lb
+     * (gm_label_src): the first layers of CVAE Encoder.forward / Decoder.forward (cvae.py), called from
+     * vae_engine.CVAEEngine._issue (encoder; decoder when Z > 32 or Z % 4 != 0) and ops._LabelLinear. */
+    const float* lb_E; int lb_C; gm_label_src lb;
+    /* gather: gm_linear_fwd and a batch gather as ONE launch (the engine uses the generator's first layer,
+     * ns_gan.py:44 + :222-226) */
+    const gm_gather_args* gather;
+} gm_fwd_args;
+int gm_linear_fwd_ex(void* stream, const gm_fwd_args* a);
+
+/* dX[M,K] = (dA W) . act'(below) as gm_linear_bwd_dx, and at most one of the blocks below. */
+typedef struct gm_dx_args {
+    const float* dA; int64_t lda; const float* W; float* dX; int64_t ldx;
+    const float* below; int64_t ld_below; int M, K, N, epi;
+    /* add: an additive term before the activation gradient, dX = (dA*W + add_scale*add) * act'(below) (BEGAN's
+     * generator sees G(z) both through D and directly in |D(G(z)) - G(z)|, be_gan.py:256) */
+    const float* add; int64_t ldadd; float add_scale;
+    /* head: the critic head's backward workgroups ride along (generator step: the single scalar workgroup that
+     * writes the loss and ticks the iteration counter).  fold (with head only): the folded form, dA = the hidden
+     * activations H (gm_head_fold_args above). */
+    const gm_head_bwd_args* head; const gm_head_fold_args* fold;
+    /* reparam (below == NULL, epi == GM_ACT_ID): VAE reparameterisation backward where dz is produced (vae.py:100-106
+     * `z = mu + eps * exp(log_var/2)` and kl_divergence :210-212, autograd of both).  The GEMM runs through the
+     * decoder's first layer (dX = dz = dA W, W: [N, Z], K = Z) and its epilogue also writes, with the expressions of
+     * gm_vae_reparam_bwd,
+     *   rp_dml[m][c] = dz + mu,   rp_dml[m][Z + c] = dz eps exp(lv/2) / 2 + (exp(lv) - 1) / 2
+     * from rp_ml = [mu | log_var] and the noise rp_eps (+ rp_slot).  Replaces the separate gm_vae_reparam_bwd launch
+     * (bit-identical results). */
+    const float* rp_ml; int64_t rp_ldml; const float* rp_eps; gm_slot rp_slot; float* rp_dml; int64_t rp_ldd;
+    /* gather: a batch gather to fp32 rows rides in the same launch (no out_bits, no corrupt) */
+    const gm_gather_args* gather;
+} gm_dx_args;
+int gm_linear_bwd_dx_ex(void* stream, const gm_dx_args* a);
+
+/* One weight gradient dW[N,K] = dA^T X, db = colsum(dA) as gm_linear_bwd_dw. */
+typedef struct gm_dw_adam_args {
+    const float* dA; int64_t lda; const float* X; int64_t ldx; gm_slot x_slot;
+    float* dW; float* db; int M, K, N;
+    /* sched != NULL: the optimizer folded into the gradient epilogue.  dW/db are written as usual and Adam (same
+     * arithmetic as gm_adam) is applied to (pW,mW,vW)/(pb,mb,vb) by the thread that produced the
+     * gradient element -- optim.Adam.step (ns_gan.py:139,156) without its own launch.  Single-GPU fast path only (under
+     * data parallelism the all-reduce sits between gradient and optimizer).  sched == NULL: plain gradient. */
+    float* pW; float* mW; float* vW; float* pb; float* mb; float* vb;
+    const float* sched; gm_slot sched_slot;
+    double beta1, beta2, eps, weight_decay; float clamp;
+    int accumulate;                       /* dW / db += instead of = (plain single gradient only: no sched, head, pair) */
+    int ones_from;                        /* with head, see below */
+    /* head (single gradient only): gm_head_bwd_fused rides in the launch (gm_head_bwd_args above).  ones_from: a
+     * STACKED reduction, the first ones_from rows of dA / X contribute to dW but not to db (WGAN-GP,
+     * w_gp_gan.py:207-218: dW1 = [u ; dH]^T [gamma ; X] in one GEMM -- the penalty's second backward has no bias
+     * term).  fold: the folded head, dA = the hidden activations H (ones_from == 0); with xbits the first xbits_rows
+     * rows of X are read from the packed copy, as in gm_fwd_args. */
+    const gm_head_bwd_args* head; const gm_head_fold_args* fold;
+    const uint32_t* xbits; int xbits_wpr, xbits_rows;
+} gm_dw_adam_args;
+typedef struct gm_finalize2_args {
+    const float* pa; int na; float scale_a; float* out_a; gm_slot slot_a;
+    const float* pb; int nb; float scale_b; float* out_b; gm_slot slot_b;
+    int64_t* tick; unsigned int* done;
+} gm_finalize2_args;
+/* What a PAIR of weight gradients may carry: either the layer-1 fields or fin. */
+typedef struct gm_dw_tail {
+    /* The generator's pair carrying the NEXT iteration's first layer: after the pair (second = the first layer's
+     * dW1 + Adam, required), H[rows, second->N] = relu(z W1^T + b1) with the stepped W1, b1 -- z: rows x second->K at
+     * z + the slot's offset, leading dimension ldz.  Bit-identical to the pair followed by gm_linear_fwd, which is what
+     * runs where the pair cannot carry it.  H may be none of the pair's arrays. */
+    const float* z; int64_t ldz; gm_slot z_slot; float* H; int64_t ldh; int rows;
+    /* The pair as the LAST launch of a VAE batch (vae.py:162 + the loss sums of :203 / :212): one more workgroup adds
+     * up the two partial arrays exactly as gm_sum_finalize2_tick does, and the last workgroup of the launch to finish
+     * advances `tick` (every slot of the batch has been resolved by then).  done: one zero-initialised unsigned int
+     * the launch counts its workgroups on and re-arms.  Falls back to separate launches when the pair cannot share a
+     * tile. */
+    const gm_finalize2_args* fin;
+} gm_dw_tail;
+/* second != NULL: two weight gradients over the same batch rows as ONE launch (the generator step's two weight
+ * gradients are independent once d loss / d hidden is known; neither may consume what the other produces or updates).
+ * Falls back to two launches when the pair cannot share a tile configuration.  tail (pair only) may be NULL. */
+int gm_linear_bwd_dw_ex(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second,
+                        const gm_dw_tail* tail);
 
 /* ---- Primal-Dual Wasserstein GAN (csrc/gm_pdw.hip; pdwgan.py).  One wave per row, fixed
  * reduction order, no atomics.

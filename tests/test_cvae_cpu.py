@@ -16,7 +16,8 @@ import cvae  # noqa: E402
 from generative_models_amd import _lib  # noqa: E402
 from generative_models_amd._lib import GMError  # noqa: E402
 
-NEW = ("gm_linear_fwd_label", "gm_vae_reparam_fwd_label", "gm_label_grad_adam")
+# (the conditioned forward is the label block of gm_linear_fwd_ex)
+NEW = ("gm_linear_fwd_ex", "gm_vae_reparam_fwd_label", "gm_label_grad_adam")
 
 
 def _loaders(n=40, C=3, batch=8):
@@ -110,11 +111,16 @@ def test_new_symbols_declared_bound_and_reject_bad_arguments():
     okl = _lib.LabelSrc(p, None, _lib.NO_SLOT)
     E = _lib.GM_EINVAL
     # null pointers, non-positive sizes, C out of [1, 32]
-    assert lib.gm_linear_fwd_label(None, p, 4, p, p, p, 3, src, p, 4, 2, 4, 4, 1) == E
-    assert lib.gm_linear_fwd_label(None, None, 4, p, p, p, 3, okl, p, 4, 2, 4, 4, 1) == E
-    assert lib.gm_linear_fwd_label(None, p, 4, p, p, None, 3, okl, p, 4, 2, 4, 4, 1) == E
+    import ctypes
+
+    def fwd_label(X, Em, C, lab, M=2, K=4, N=4):
+        a = _lib.FwdArgs(X=X, ldx=4, W=p, bias=p, Y=p, ldy=4, M=M, K=K, N=N, act=1, lb_E=Em, lb_C=C, lb=lab)
+        return lib.gm_linear_fwd_ex(None, ctypes.byref(a))
+    assert fwd_label(p, p, 3, src) == E
+    assert fwd_label(None, p, 3, okl) == E
+    assert fwd_label(p, None, 3, okl) == E
     for M, K, N, C in ((0, 4, 4, 3), (2, 0, 4, 3), (2, 4, 0, 3), (2, 4, 4, 0), (2, 4, 4, 33)):
-        assert lib.gm_linear_fwd_label(None, p, 4, p, p, p, C, okl, p, 4, M, K, N, 1) == E
+        assert fwd_label(p, p, C, okl, M, K, N) == E
     for B, Z, N, C in ((0, 4, 4, 3), (2, 0, 4, 3), (2, 4, 0, 3), (2, 4, 4, 0), (2, 4, 4, 33)):
         assert lib.gm_vae_reparam_fwd_label(None, p, 8, p, _lib.NO_SLOT, p, 4, p, 4, B, Z, p, p, p, 4, N, 1,
                                             p, C, okl) == E

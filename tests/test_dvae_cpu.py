@@ -18,8 +18,8 @@ import vae  # noqa: E402
 from generative_models_amd import _lib, ops_fused  # noqa: E402
 from generative_models_amd import dvae as gdvae  # noqa: E402
 
-NEW = ("gm_dvae_corrupt", "gm_gather_rows_corrupt", "gm_gather_rows_bits_corrupt", "gm_linear_fwd_gather_corrupt",
-       "gm_linear_fwd_gather_bits_corrupt")
+# (the riding forms are the gather block of gm_linear_fwd_ex: gm_gather_args.corrupt / out_c)
+NEW = ("gm_dvae_corrupt", "gm_gather_rows_corrupt", "gm_gather_rows_bits_corrupt", "gm_linear_fwd_ex")
 M32 = 0xFFFFFFFF
 
 
@@ -190,13 +190,22 @@ def test_new_symbols_declared_bound_and_reject_bad_arguments():
     assert lib.gm_gather_rows_bits_corrupt(None, None, p, 1, 16, p, S, 2 * p, 3 * p, 8, 4, 8) == E
     # the riding forms: the gather's refusals, and out_c may not be an operand or the output of the GEMM
     X, W, Y = 5 * p, 6 * p, 7 * p
-    gemm = (X, 8, S, W, None, Y, 8, 4, 8, 8, 1)
+    def ride(out_c, corrupt, bits=False, ld_out=8):
+        g = _lib.GatherArgs(n_rows=16, idx=p, idx_slot=S, out=2 * p, ld_out=ld_out, B=4, row_elems=8, out_c=out_c)
+        if bits:
+            g.bits, g.words_per_row = p, 1
+        else:
+            g.data = p
+        if corrupt is not None:
+            g.corrupt = corrupt
+        a = _lib.FwdArgs(X=X, ldx=8, x_slot=S, W=W, Y=Y, ldy=8, M=4, K=8, N=8, act=1, gather=_ptr(g))
+        return lib.gm_linear_fwd_ex(None, _ptr(a))
     for out_c in (None, X, Y, 2 * p):
-        assert lib.gm_linear_fwd_gather_corrupt(None, *gemm, p, 16, p, S, 2 * p, 8, 4, 8, out_c, c) == E, out_c
-        assert lib.gm_linear_fwd_gather_bits_corrupt(None, *gemm, p, 1, 16, p, S, 2 * p, 8, 4, 8, out_c, c) == E
-    assert lib.gm_linear_fwd_gather_corrupt(None, *gemm, p, 16, p, S, 2 * p, 8, 4, 8, 3 * p, None) == E
-    assert lib.gm_linear_fwd_gather_corrupt(None, *gemm, p, 16, p, S, 2 * p, 8, 4, 8, 3 * p, _ptr(args(kind=9))) == E
-    assert lib.gm_linear_fwd_gather_corrupt(None, *gemm, p, 16, p, S, 2 * p, 4, 4, 8, 3 * p, c) == E   # ld < row
+        assert ride(out_c, c) == E, out_c
+        assert ride(out_c, c, bits=True) == E
+    assert ride(3 * p, None) == E
+    assert ride(3 * p, _ptr(args(kind=9))) == E
+    assert ride(3 * p, c, ld_out=4) == E   # ld < row
 
 
 def _ptr(a):

@@ -124,7 +124,7 @@ def lclose(got, ref, tol=1e-5):
 
 SMALL = dict(I=64, H=48, Z=8, C=3, side=8, batch=32, n_train=200, n_val=48, n_test=48, epochs=2)
 FULL = dict(I=784, H=400, Z=20, C=10, side=28, batch=512, n_train=3 * 512 + 336, n_val=512, n_test=64, epochs=1)
-# outside the fused launches' limits: Z % 4 != 0 (decoder layer 1 as vae_reparam_wide + gm_linear_fwd_label), and
+# outside the fused launches' limits: Z % 4 != 0 (decoder layer 1 as vae_reparam_wide + ops.linear_fwd_label), and
 # Z > 32 with a hidden width > 512 (that, plus the two generic dX launches instead of gm_vae_bwd_mid)
 ODD_Z = dict(I=64, H=48, Z=6, C=3, side=8, batch=32, n_train=200, n_val=48, n_test=48, epochs=2)
 WIDE = dict(I=64, H=520, Z=40, C=5, side=8, batch=32, n_train=80, n_val=32, n_test=32, epochs=1)

@@ -145,7 +145,7 @@ def test_sqerr_sigmoid_backward(B, I):
 
 @pytest.mark.parametrize("B,H,I", [(512, 400, 784), (336, 400, 784), (16, 48, 64), (40, 32, 36), (1024, 400, 784)])
 def test_reconstruction_loss_in_the_decoder_forward_epilogue(B, H, I):
-    """gm_linear_fwd_sqerr (vae.py:75-77 + :203): x_hat and dA bit-identical to gm_linear_fwd(sigmoid)
+    """ops.linear_fwd_sqerr (vae.py:75-77 + :203): x_hat and dA bit-identical to gm_linear_fwd(sigmoid)
     followed by gm_sqerr_sigmoid_bwd, the row-tile partials add up to sum (x - x_hat)^2, stale entries
     of the partial array beyond this batch's rows are not read, and a relaunch reproduces every bit."""
     torch.manual_seed(B + I)
@@ -178,7 +178,7 @@ def test_reconstruction_loss_in_the_decoder_forward_epilogue(B, H, I):
 
 @pytest.mark.parametrize("B,Z,H", [(512, 20, 400), (336, 20, 400), (16, 8, 48), (37, 4, 20)])
 def test_reparam_backward_in_the_dx_epilogue(B, Z, H):
-    """gm_linear_bwd_dx_reparam (autograd of vae.py:100-106,210-212 behind the decoder's first layer):
+    """ops.linear_bwd_dx_reparam (autograd of vae.py:100-106,210-212 behind the decoder's first layer):
     dz and d loss / d [mu | log_var] bit-identical to gm_linear_bwd_dx + gm_vae_reparam_bwd, reading the
     noise through a ring slot."""
     torch.manual_seed(B + Z)
@@ -430,7 +430,7 @@ def test_vae_reparam_and_first_decoder_layer_in_one_launch(B, Z, N):
 @pytest.mark.parametrize("B,Z,H", [(512, 20, 400), (336, 20, 400), (100, 20, 400), (37, 8, 52), (64, 32, 128),
                                     (17, 4, 20)])
 def test_vae_backward_mid_chain_in_one_launch(B, Z, H):
-    """gm_vae_bwd_mid == gm_linear_bwd_dx_reparam (dz, d loss / d [mu | log_var]) followed by gm_linear_bwd_dx
+    """gm_vae_bwd_mid == ops.linear_bwd_dx_reparam (dz, d loss / d [mu | log_var]) followed by gm_linear_bwd_dx
     (dHe = (dml W_ml) . [He > 0]): vae.py:93-113 backwards between the two wide layers.  The summation orders are the
     separate launches' (asserted: bit-identical dml and dHe), and both against fp64 autograd."""
     torch.manual_seed(B + Z)

@@ -1,5 +1,5 @@
-"""The generator's first layer riding in the previous iteration's weight-gradient pair (gm_linear_bwd_dw_adam_pair_l1)
-and the batch gather riding in the dH launch (gm_linear_bwd_dx_gather[_bits]): bit for bit what the separate launches
+"""The generator's first layer riding in the previous iteration's weight-gradient pair (ops.linear_bwd_dw_adam_pair_l1)
+and the batch gather riding in the dH launch (ops.linear_bwd_dx_gather): bit for bit what the separate launches
 compute, at the op level and over whole training runs."""
 import os
 import sys
@@ -46,7 +46,7 @@ def _case(B, hid, Z, rows, I=784, seed=0):
 @pytest.mark.parametrize("Z", [4, 20, 32])
 @pytest.mark.parametrize("B,rows", [(64, 128), (100, 100), (256, 512), (1024, 256)])
 def test_pair_l1_equals_pair_then_forward(hid, Z, B, rows):
-    """gm_linear_bwd_dw_adam_pair_l1 == gm_linear_bwd_dw_adam_pair, then gm_linear_fwd (the k32 kernel) on the next
+    """ops.linear_bwd_dw_adam_pair_l1 == ops.linear_bwd_dw_adam_pair, then gm_linear_fwd (the k32 kernel) on the next
     slot of the noise ring with the stepped W1, b1: H, both layers' parameters, gradients and Adam moments."""
     G2, G1, dXg, Hg2, dHg, zring, sched, R = _case(B, hid, Z, rows, seed=B + hid + Z)
     ctr = torch.tensor([1], dtype=torch.int64, device=DEV)
@@ -79,7 +79,7 @@ def test_pair_l1_equals_pair_then_forward(hid, Z, B, rows):
 @pytest.mark.parametrize("B,Hd,I", [(256, 400, 784), (100, 390, 784), (64, 33, 36)])
 @pytest.mark.parametrize("packed", [True, False])
 def test_dx_with_gather_riding(B, Hd, I, packed):
-    """gm_linear_bwd_dx_gather(_bits) == gm_gather_rows(_bits) + gm_linear_bwd_dx, bit for bit."""
+    """ops.linear_bwd_dx_gather == gm_gather_rows(_bits) + gm_linear_bwd_dx, bit for bit."""
     g = torch.Generator().manual_seed(B + Hd)
     dA = torch.randn(B, I, generator=g).to(DEV)
     W = torch.randn(I, Hd, generator=g).to(DEV)

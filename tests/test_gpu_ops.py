@@ -455,7 +455,7 @@ def test_head_fwd_loss_final(B, Hd):
 
 @pytest.mark.parametrize("B,I,Hd", [(256, 784, 400), (24, 36, 20), (512, 784, 400)])
 def test_dw_adam_with_head_in_one_launch(B, I, Hd):
-    """gm_linear_bwd_dw_adam_head == gm_head_bwd_fused followed by gm_linear_bwd_dw_adam, bit for
+    """ops.linear_bwd_dw_adam_head == gm_head_bwd_fused followed by ops.linear_bwd_dw_adam, bit for
     bit (the head workgroups only ride in the GEMM's grid; the arithmetic is the same code)."""
     import torch.nn as nn
     from generative_models_amd import ops_fused as of
@@ -528,7 +528,7 @@ def test_short_reduction_forward_equals_the_16_wave_kernel_bit_for_bit(M, K, N, 
 @pytest.mark.parametrize("M,K,N,B,I", [(512, 20, 400, 256, 784), (256, 20, 400, 256, 784),
                                        (33, 13, 31, 7, 10), (64, 20, 400, 100, 36)])
 def test_linear_fwd_with_gather_riding(M, K, N, B, I):
-    """gm_linear_fwd_gather == gm_linear_fwd + gm_gather_rows, bit for bit (aligned shapes ride
+    """ops.linear_fwd_gather == gm_linear_fwd + gm_gather_rows, bit for bit (aligned shapes ride
     in the GEMM's grid, the ragged case takes the two-launch fallback inside the library)."""
     torch.manual_seed(M + B)
     x, W, b = torch.randn(M, K).to(DEV), (torch.randn(N, K) / K ** 0.5).to(DEV), torch.randn(N).to(DEV)
@@ -548,7 +548,7 @@ def test_linear_fwd_with_gather_riding(M, K, N, B, I):
 @pytest.mark.parametrize("B,H,I,Z", [(256, 400, 784, 20), (1024, 400, 784, 20), (24, 20, 36, 8),
                                      (32, 31, 33, 5)])
 def test_dw_adam_pair_in_one_launch(B, H, I, Z):
-    """gm_linear_bwd_dw_adam_pair == two gm_linear_bwd_dw_adam launches, bit for bit below 1024 rows (incl. the
+    """ops.linear_bwd_dw_adam_pair == two ops.linear_bwd_dw_adam launches, bit for bit below 1024 rows (incl. the
     unaligned two-launch fallback), to rounding at B = 1024 (wide tiles, interleaved fragments)."""
     import torch.nn as nn
     from generative_models_amd.engine import FlatParams, _Linear
@@ -586,7 +586,7 @@ def test_dw_adam_pair_in_one_launch(B, H, I, Z):
 @pytest.mark.parametrize("B,H,I,Z", [(512, 400, 784, 20), (336, 400, 784, 20), (1024, 400, 784, 20), (24, 20, 36, 8),
                                      (32, 31, 33, 5)])
 def test_dw_adam_pair_closing_a_vae_batch(B, H, I, Z):
-    """gm_linear_bwd_dw_adam_pair_finalize == gm_linear_bwd_dw_adam_pair followed by gm_sum_finalize2_tick, bit for
+    """ops.linear_bwd_dw_adam_pair_finalize == ops.linear_bwd_dw_adam_pair followed by gm_sum_finalize2_tick, bit for
     bit (incl. the unaligned fallback to separate launches): parameters, gradients, both Adam moments, both sums at
     the slot the counter named BEFORE the launch, counter advanced exactly once per launch, arrival counter re-armed.
     The Adam schedule is read through the same counter the launch advances -- a tick ahead of a late workgroup's
@@ -633,7 +633,7 @@ def test_dw_adam_pair_closing_a_vae_batch(B, H, I, Z):
 
 @pytest.mark.parametrize("B,I,Hd", [(256, 784, 400), (24, 36, 20), (33, 30, 17)])
 def test_dx_with_scalar_head_riding(B, I, Hd):
-    """gm_linear_bwd_dx_head == gm_head_bwd (generator mode: loss scalar + tick) followed by
+    """ops.linear_bwd_dx_head == gm_head_bwd (generator mode: loss scalar + tick) followed by
     gm_linear_bwd_dx, bit for bit; the counter advances exactly once per launch."""
     from types import SimpleNamespace
     from generative_models_amd import ops_fused as of
@@ -678,7 +678,7 @@ def _oracle_tail_loss(variant, s, B, gen_mode):
 
 @pytest.mark.parametrize("M,I,Hd", [(512, 784, 400), (256, 784, 400), (48, 36, 20), (33, 30, 17), (2048, 784, 400)])
 def test_folded_head_forward_leaves_partial_dots_and_snapshot(M, I, Hd):
-    """gm_linear_fwd_headpart: the hidden layer is bit-identical to gm_linear_fwd's, the per-tile
+    """ops.linear_fwd_headpart: the hidden layer is bit-identical to gm_linear_fwd's, the per-tile
     partial dots add up to h . w2 (fp64 reference), the snapshot holds (w2, b2), and a second launch
     reproduces every bit."""
     from types import SimpleNamespace
@@ -840,7 +840,7 @@ def test_packed_dataset_gather_equals_fp32_gather(N, I, B):
     ops.gather_rows(data, idx, a)
     ops.gather_rows(packed, idx, b)
     assert torch.equal(a, data[idx]) and torch.equal(b, a)
-    # riding in the generator's first forward launch (engine: gm_linear_fwd_gather_bits)
+    # riding in the generator's first forward launch (engine: ops.linear_fwd_gather)
     x, W, bias = torch.randn(2 * B, 20, device="cuda"), torch.randn(48, 20, device="cuda"), torch.zeros(48, device="cuda")
     y1, y2 = torch.empty(2 * B, 48, device="cuda"), torch.empty(2 * B, 48, device="cuda")
     o1, o2 = torch.empty(B, I, device="cuda"), torch.full((B, I), -1.0, device="cuda")
@@ -875,7 +875,7 @@ def test_packed_gather_copies_the_rows_as_words(N, I, B):
 @pytest.mark.parametrize("B,I,Hd,rows", [(256, 784, 400, 256), (64, 784, 400, 64), (64, 36, 20, 64), (32, 64, 48, 32),
                                          (352, 784, 400, 352), (96, 100, 72, 32), (256, 784, 400, 128)])
 def test_folded_critic_step_reads_packed_rows_bit_identically(variant, out_act, B, I, Hd, rows):
-    """gm_linear_fwd_headpart_bits / gm_linear_bwd_dw_adam_head_fold_bits: the first `rows` rows of [x ; G(z)] come
+    """ops.linear_fwd_headpart(xbits=...) / ops.linear_bwd_dw_adam_head_fold(xbits=...): the first `rows` rows of [x ; G(z)] come
     from the packed copy, the fp32 rows behind them hold garbage -- hidden layer, partial dots, gradients, Adam'd
     parameters, moments and loss must equal the fp32-row launches bit for bit (same MFMA sequence on the same values)."""
     import torch.nn as nn
@@ -1004,7 +1004,7 @@ def test_stage_in_strided_pieces_copy_only_the_ranks_rows(B, Bl, w, dtype):
 
 @pytest.mark.parametrize("M,K,N,rows", [(512, 400, 784, 256), (96, 48, 64, 40), (2048, 400, 784, 1024)])
 def test_linear_fwd_with_interp_epilogue_equals_separate_launches(M, K, N, rows):
-    """gm_linear_fwd_interp: the generator's last layer also writes WGAN-GP's x_hat for its first
+    """ops.linear_fwd_interp: the generator's last layer also writes WGAN-GP's x_hat for its first
     `rows` rows -- bit-identical to gm_linear_fwd followed by gm_interp (w_gp_gan.py:197-201), for the
     split-reduction kernel and the LDS macro-tile kernel (M >= 1024) alike."""
     from generative_models_amd import ops_fused as of

@@ -207,18 +207,28 @@ def test_flat_params_pack_and_alias():
 
 
 def test_ctypes_structs_match_the_c_header(tmp_path):
-    """The argument blocks passed by pointer (gm_slot, gm_head_bwd_args, gm_dw_adam_args) must have
-    the same size and field offsets in ctypes as in include/gm_hip.h compiled by the host C
-    compiler (the header is plain C)."""
+    """Every ctypes.Structure of _lib (the argument blocks passed by value or by pointer: gm_slot, gm_fwd_args,
+    gm_dx_args, gm_dw_adam_args, gm_head_bwd_args, ...) must have the same size and field offsets as its struct in
+    include/gm_hip.h compiled by the host C compiler (the header is plain C).  The structures are found by walking
+    _lib, so one added later without an entry in the name map below fails here."""
     import shutil
     import subprocess
     gcc = shutil.which("gcc") or shutil.which("cc")
     if gcc is None:
         pytest.skip("no host C compiler")
     root = os.path.dirname(HERE)
-    structs = {"gm_slot": _lib.Slot, "gm_head_bwd_args": _lib.HeadBwdArgs,
-               "gm_dw_adam_args": _lib.DwAdamArgs, "gm_stage_seg": _lib.StageSeg,
-               "gm_draw_op": _lib.DrawOp}
+    import ctypes
+    c_names = {"Slot": "gm_slot", "HeadBwdArgs": "gm_head_bwd_args", "HeadFoldArgs": "gm_head_fold_args",
+               "LabelSrc": "gm_label_src", "LabelGradArgs": "gm_label_grad_args", "DwAdamArgs": "gm_dw_adam_args",
+               "AAECriticArgs": "gm_aae_critic_args", "AAEGenArgs": "gm_aae_gen_args", "SghmcSeg": "gm_sghmc_seg",
+               "SghmcArgs": "gm_sghmc_args", "BganHeadArgs": "gm_bgan_head_args", "CorruptArgs": "gm_corrupt_args",
+               "Finalize2Args": "gm_finalize2_args", "DwTail": "gm_dw_tail", "GatherArgs": "gm_gather_args",
+               "FwdArgs": "gm_fwd_args", "DxArgs": "gm_dx_args", "DrawOp": "gm_draw_op", "StageSeg": "gm_stage_seg"}
+    found = {n: v for n, v in vars(_lib).items()
+             if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure}
+    assert set(found) == set(c_names), set(found) ^ set(c_names)
+    structs = {c_names[n]: ct for n, ct in found.items()}
+    assert len(structs) == len(c_names) >= 19
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "gm_hip.h"', 'int main(void) {']
     for cname, ct in structs.items():
         lines.append('printf("%s size %%zu\\n", sizeof(%s));' % (cname, cname))

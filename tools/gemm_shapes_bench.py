@@ -22,7 +22,7 @@ def time_shape(kind, M, K, N, reps=50):
     dW, db, b = torch.empty(N, K, device=dev), torch.empty(N, device=dev), torch.zeros(N, device=dev)
     st = [ops.stream_ptr()]
     if kind == "dwadam":
-        # weight gradient with the optimizer in its epilogue (gm_linear_bwd_dw_adam), as the training steps launch it
+        # weight gradient with the optimizer in its epilogue (ops.linear_bwd_dw_adam), as the training steps launch it
         import torch.nn as nn
         from generative_models_amd.engine import FlatParams, _Linear
         net = nn.Sequential(nn.Linear(K, N))

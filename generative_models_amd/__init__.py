@@ -82,8 +82,15 @@ def host_thread_plan():
 
 
 def __getattr__(name):
-    """PDWGAN / PDWGANTrainer / PDWGANEngine, imported on first use (importing the package stays free of torch)."""
+    """PDWGAN / PDWGANTrainer / PDWGANEngine and IWAE / IWAETrainer / IWAEEngine, imported on first use (importing
+    the package stays free of torch)."""
     if name in ("PDWGAN", "PDWGANTrainer", "PDWGANEngine"):
         from . import pdwgan
         return getattr(pdwgan, name)
+    if name in ("IWAE", "IWAETrainer"):
+        from . import iwae
+        return getattr(iwae, name)
+    if name == "IWAEEngine":
+        from . import engine
+        return engine.IWAEEngine
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -122,6 +122,10 @@ class CorruptArgs(ctypes.Structure):
                 ("step_base", c_void_p), ("step_add", c_int64), ("row0", c_int64)]
 
 
+IWAE_TAG_TRAIN, IWAE_TAG_EVAL = 0x49574145, 0x49574556      # GM_IWAE_TAG_TRAIN / GM_IWAE_TAG_EVAL
+IWAE_MAX_K, IWAE_MAX_Z = 64, 32                             # GM_IWAE_MAX_K / GM_IWAE_MAX_Z
+# (gm_iwae_noise travels by pointer; its ctypes form, IwaeNoise, lives in ops_fused beside iwae_noise())
+
 NOISE = {"salt_pepper": 1, "gaussian": 2}       # GM_NOISE_SALT_PEPPER, GM_NOISE_GAUSSIAN (GM_NOISE_NONE = 0)
 
 
@@ -337,6 +341,10 @@ _SIGNATURES = {
                               c_float, c_int, c_int]),
     "gm_pdw_dir": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_float, c_float, c_int,
                            c_int]),
+    "gm_iwae_sample": (c_int, [_P, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int]),
+    "gm_iwae_weights": (c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int]),
+    "gm_iwae_reduce": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, c_int,
+                               c_int, c_int]),
 }
 
 _lib = None

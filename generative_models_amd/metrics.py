@@ -20,6 +20,8 @@ from ._lib import GMError
 MAX_SIGMAS = 16
 
 ParzenResult = collections.namedtuple("ParzenResult", "sigma ll_mean ll_stderr val_means")
+# VAETrainer.log_likelihood (iwae.py): the importance-weighted estimate of log p(x) over n rows from k samples each
+IWAEResult = collections.namedtuple("IWAEResult", "ll_mean ll_stderr k n")
 
 
 def default_sigmas():

@@ -518,3 +518,82 @@ def pdw_dir(g, x, xr, n, gamma, pen, lam, inv_b, stream=None):
         raise _lib.GMError("pdw_dir: n and pen hold one float per row")
     _lib.call("gm_pdw_dir", stream or stream_ptr(), g.data_ptr(), _ld(g), x.data_ptr(), _ld(x), xr.data_ptr(), _ld(xr),
               n.data_ptr(), gamma.data_ptr(), _ld(gamma), pen.data_ptr(), lam, inv_b, B, I)
+
+
+# ---- Importance-weighted autoencoder (csrc/gm_iwae.hip; iwae.py) ---------------------------------------------------
+class IwaeNoise(ctypes.Structure):
+    """gm_iwae_noise (include/gm_hip.h): the IWAE's noise stream -- seed, tag, step and the sample rows of the call."""
+    _fields_ = [("seed", ctypes.c_uint64), ("tag", ctypes.c_uint32), ("step_ctr", ctypes.c_void_p),
+                ("step_base", ctypes.c_void_p), ("step_add", ctypes.c_int64), ("k_total", ctypes.c_int64),
+                ("j0", ctypes.c_int64), ("q0", ctypes.c_int64)]
+
+
+def iwae_noise(seed, tag, k_total, j0=0, step=0, step_ctr=None, step_base=None, q0=0):
+    """A gm_iwae_noise block: the stream (seed, tag) at step = *step_ctr + *step_base + step (int64 device tensors, or
+    None for 0); the call's sample j of image b draws noise row b * k_total + j0 + j.  The tensors must outlive every
+    launch (and every captured graph) that reads them."""
+    for t, nm in ((step_ctr, "step_ctr"), (step_base, "step_base")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int64):
+            raise _lib.GMError("iwae_noise: %s must be an int64 device tensor" % nm)
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise _lib.GMError("iwae_noise: seed must lie in [0, 2^64)")
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    return IwaeNoise(seed, int(tag) & 0xFFFFFFFF, ptr(step_ctr), ptr(step_base), int(step), int(k_total), int(j0), int(q0))
+
+
+def iwae_sample(ml, z, lp, noise, B, k, Z, stream=None):
+    """z [B k, Z] and lp [B k] of the k samples of each of B images from ml [B, 2Z] (gm_iwae_sample)."""
+    if _rows2d(ml, "ml").shape[0] < B or ml.shape[1] < 2 * Z or _rows2d(z, "z").shape[0] < B * k or z.shape[1] < Z \
+            or lp.numel() < B * k or not lp.is_contiguous():
+        raise _lib.GMError("iwae_sample: ml %s / z %s / lp %s do not fit B=%d, k=%d, Z=%d"
+                           % (tuple(ml.shape), tuple(z.shape), tuple(lp.shape), B, k, Z))
+    _lib.call("gm_iwae_sample", stream or stream_ptr(), ctypes.byref(noise), ml.data_ptr(), _ld(ml), z.data_ptr(),
+              _ld(z), lp.data_ptr(), B, k, Z)
+
+
+def iwae_weights(x, xr, lp, negL, ess, wn, B, k, dA=None, ms=None, stream=None):
+    """Per image: -L_k, ess, the normalised weights wn [B k] and, with dA [B k, I], the weighted gradient at the
+    decoder's pre-sigmoid output; ms [B, 2] takes (max, sum) of exp(log w - max) (gm_iwae_weights)."""
+    I = x.shape[1]
+    if _rows2d(x, "x").shape[0] < B or _rows2d(xr, "xr").shape[0] < B * k or xr.shape[1] != I \
+            or min(lp.numel(), wn.numel()) < B * k or min(negL.numel(), ess.numel()) < B \
+            or (dA is not None and (_rows2d(dA, "dA").shape[0] < B * k or dA.shape[1] != I)) \
+            or (ms is not None and (ms.numel() < 2 * B or not ms.is_contiguous())):
+        raise _lib.GMError("iwae_weights: the arrays do not fit B=%d, k=%d, I=%d" % (B, k, I))
+    for t in (lp, negL, ess, wn):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise _lib.GMError("iwae_weights: lp, negL, ess and wn must be contiguous float32 device tensors")
+    _lib.call("gm_iwae_weights", stream or stream_ptr(), x.data_ptr(), _ld(x), xr.data_ptr(), _ld(xr), lp.data_ptr(),
+              negL.data_ptr(), ess.data_ptr(), wn.data_ptr(), dA.data_ptr() if dA is not None else None,
+              _ld(dA) if dA is not None else 0, ms.data_ptr() if ms is not None else None, B, k, I)
+
+
+def iwae_reduce(ml, wn, dzdec, dml, noise, B, k, Z, dZ=None, stream=None):
+    """d loss / d [mu | lv] -> dml [B, 2Z] from dzdec [B k, Z] = dHdec Wd1 and the weights (gm_iwae_reduce); dZ [B k, Z]
+    takes d loss / d z when given."""
+    if _rows2d(ml, "ml").shape[0] < B or ml.shape[1] < 2 * Z or _rows2d(dzdec, "dzdec").shape[0] < B * k \
+            or dzdec.shape[1] < Z or _rows2d(dml, "dml").shape[0] < B or dml.shape[1] < 2 * Z or wn.numel() < B * k \
+            or (dZ is not None and (_rows2d(dZ, "dZ").shape[0] < B * k or dZ.shape[1] < Z)):
+        raise _lib.GMError("iwae_reduce: the arrays do not fit B=%d, k=%d, Z=%d" % (B, k, Z))
+    _lib.call("gm_iwae_reduce", stream or stream_ptr(), ctypes.byref(noise), ml.data_ptr(), _ld(ml), wn.data_ptr(),
+              dzdec.data_ptr(), _ld(dzdec), dml.data_ptr(), _ld(dml), dZ.data_ptr() if dZ is not None else None,
+              _ld(dZ) if dZ is not None else 0, B, k, Z)
+
+
+def iwae_normals(n_images, k, Z, seed, step, tag, device="cuda"):
+    """eps [n_images k, Z]: the normals gm_iwae_sample draws for (seed, step, tag), through gm_iwae_sample itself
+    on mu = 0, log_var = 0 (z = 0 + eps * exp(0) = eps, bit for bit).  k or Z above the fused limits go in pieces of 64
+    samples by 32 latents.  What the general path's compute_batch feeds its reparameterisation."""
+    MK, MZ = _lib.IWAE_MAX_K, _lib.IWAE_MAX_Z
+    ml = torch.zeros(n_images, 2 * min(Z, MZ), device=device)
+    out = torch.empty(n_images, k, Z, device=device)
+    for j0 in range(0, k, MK):
+        kc = min(MK, k - j0)
+        for c0 in range(0, Z, MZ):
+            zc = min(MZ, Z - c0)
+            z = torch.empty(n_images * kc, zc, device=device)
+            lp = torch.empty(n_images * kc, device=device)
+            iwae_sample(ml[:, :2 * zc], z, lp, iwae_noise(seed, tag, k, j0=j0, step=step, q0=c0 // 4), n_images, kc, zc)
+            out[:, j0:j0 + kc, c0:c0 + zc] = z.view(n_images, kc, zc)
+    return out.view(n_images * k, Z)

@@ -946,6 +946,13 @@ class VAETrainer:
         the first n_val validation images (metrics.parzen_evaluate) -> metrics.ParzenResult."""
         return _parzen(self, n_samples, sigmas, n_val, seed)
 
+    def log_likelihood(self, images=None, k=500, seed=0):
+        """Importance-weighted estimate of log p(x) from k samples per image (iwae.log_likelihood; images=None: the
+        whole test_iter) -> metrics.IWAEResult.  For models built of vae.py's Encoder and Decoder unchanged (VAE, DVAE,
+        IWAE); the other trainers of this family raise GMError."""
+        from . import iwae
+        return iwae.log_likelihood(self, images, k, seed)
+
     def sample_images(self, epoch=-100, num_images=36, save=True):
         from . import viz
         return viz.vae_sample_images(self, epoch, num_images, save, self.viz_dir)

@@ -803,6 +803,117 @@ class DVAEEngine(VAEEngine):
                                       idx_slot=self._slot(t, 1, 1, self.R, self.B), stream=st)
 
 
+class IWAEEngine(VAEEngine):
+    """The importance-weighted autoencoder (iwae.py holds the contract) on the VAE engine's batch: the encoder runs on
+    the batch's B rows, the decoder on its B k sample rows (image-major).  12 launches per training batch:
+      1. encoder layer 1;  2. [mu | log_var], carrying the next batch's gather;  3. gm_iwae_sample (z, lp);
+      4. decoder layer 1 on B k rows;  5. decoder output, sigmoid;  6. gm_iwae_weights (-L_k, ess, wn, weighted dA);
+      7. decoder dX with relu;  8. dzdec = dHdec Wd1;  9. the decoder's paired dW + Adam with M = B k;
+      10. gm_iwae_reduce (dml);  11. dX through [mu | log_var];  12. the encoder's paired dW + Adam, whose finalize
+      block sums the per-image -L_k (-> `recon`) and ess / b (-> `kl`) and ticks the counter.
+    A validation batch is launches 1-6 in evaluation mode and the two sums.  The noise step of a training batch is
+    ctr + nbase (DVAEEngine's scheme), of a validation batch ctr (the batch's index in the pass).  One GPU only."""
+
+    has_eps = False              # the noise is drawn on the device: no host eps ring traffic
+
+    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
+                 trainer=None):
+        if world_size > 1 or force_dp:
+            raise GMError("the IWAE engine runs on one GPU: data parallelism is not implemented for it")
+        from ._lib import IWAE_MAX_K, IWAE_MAX_Z
+        k, Z = int(trainer.k), model.encoder.mu.weight.shape[0]
+        if not (1 <= k <= IWAE_MAX_K and 1 <= Z <= IWAE_MAX_Z):
+            raise GMError("IWAEEngine: 1 <= k <= %d and 1 <= z_dim <= %d (got k=%d, z_dim=%d); IWAETrainer trains "
+                          "these on the general path" % (IWAE_MAX_K, IWAE_MAX_Z, k, Z))
+        super().__init__(model, device, use_graph=use_graph)
+        self.trainer, self.k = trainer, k            # seed and noise_steps are read from the trainer
+        self.nbase = torch.zeros(1, dtype=torch.int64, device=device)
+
+    def _alloc(self, B):
+        if self._bufB == B:
+            return
+        dev, I, H, Z, k = self.device, self.I, self.H, self.Z, self.k
+        Hd = self.D1.W.shape[0]
+        z = lambda *s: torch.zeros(*s, device=dev)
+        self.X, self.He, self.ml = z(B, I), z(B, H), z(B, 2 * Z)
+        self.Xb = (self.X, z(B, I))
+        self.Zs, self.lp, self.wn = z(B * k, Z), z(B * k), z(B * k)
+        self.Hdec, self.Xr, self.dA = z(B * k, Hd), z(B * k, I), z(B * k, I)
+        self.dHdec, self.dzdec = z(B * k, Hd), z(B * k, Z)
+        self.negL, self.essb = z(B), z(B)
+        self.dml, self.dHe = z(B, 2 * Z), z(B, H)
+        self._bufB = B
+        self.graphs = {}
+
+    def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
+        tr = self.trainer
+        if int(tr.k) != self.k:
+            raise GMError("IWAETrainer.k changed after the engine was built (%d -> %d)" % (self.k, int(tr.k)))
+        now = {"k": self.k, "seed": int(tr.seed)}
+        if resume is not None and resume.get("config") is not None and not resume.get("lenient", False):
+            saved = resume["config"]
+            diff = {n: (saved[n], now[n]) for n in now if n in saved and saved[n] != now[n]}
+            if diff:
+                raise GMError("checkpoint was written by a run with different settings (saved, now): %s; "
+                              "load_checkpoint(path, strict=False) overrides" % diff)
+        super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
+        self.run_config.update(now)
+        if getattr(self, "_noise_key", None) != tuple(now.values()):
+            self.graphs = {}                         # the seed is a launch argument of the graphs
+        self._noise_key = tuple(now.values())
+        self.nbase.fill_(int(tr.noise_steps))
+
+    def _noise(self, t, train):
+        """The batch's noise stream: training batches read ctr + nbase (eager: t + nbase) under the training tag,
+        validation batches their index in the pass under the evaluation tag."""
+        from . import ops_fused as of_
+        from ._lib import IWAE_TAG_EVAL, IWAE_TAG_TRAIN
+        tag, base = (IWAE_TAG_TRAIN, self.nbase) if train else (IWAE_TAG_EVAL, None)
+        if self.use_graph:
+            return of_.iwae_noise(self.trainer.seed, tag, self.k, step_ctr=self.ctr, step_base=base)
+        return of_.iwae_noise(self.trainer.seed, tag, self.k, step=t, step_base=base)
+
+    def _issue(self, st, t, b, train, pos=0, of=1):
+        """One batch of size b: forward on b k sample rows + -L_k, ess (+ backward + Adam when train)."""
+        from . import ops_fused as of_
+        of = max(1, of)
+        R, B, Z, k = self.R, self.B, self.Z, self.k
+        E1, ML, D1, D2 = self.E1, self.ML, self.D1, self.D2
+        idx_slot = self._slot(t, 1, 0, R, B)
+        loss_slot = self._slot(t, 1, 0, 0, 1)
+        loss_out, ess_out = (self.recon, self.kl) if train else (self.vrecon, self.vkl)
+        tick = self.ctr if self.use_graph else None
+        X, own, nxt = self._gather_plan(pos, of)
+        if own:
+            self._gather_own(st, t, 0, b, X, idx_slot, train)
+        ops.linear_fwd(X, E1.W, E1.b, self.He, "relu", M=b, stream=st)
+        self._fwd_with_prefetch(st, t, 0, b, self.He, ML, self.ml, "id", nxt, train=train)
+        nz = self._noise(t, train)
+        of_.iwae_sample(self.ml, self.Zs, self.lp, nz, b, k, Z, stream=st)
+        ops.linear_fwd(self.Zs, D1.W, D1.b, self.Hdec, "relu", M=b * k, stream=st)
+        ops.linear_fwd(self.Hdec, D2.W, D2.b, self.Xr, "sigmoid", M=b * k, stream=st)
+        of_.iwae_weights(X, self.Xr, self.lp, self.negL, self.essb, self.wn, b, k, dA=self.dA if train else None,
+                         stream=st)
+        if not train:
+            of_.sum_finalize2(self.negL, b, loss_out, loss_slot, self.essb, b, ess_out, loss_slot, scale_b=1.0 / b,
+                              tick=tick, stream=st)
+            return
+        adam = dict(sched=self.sched, sched_slot=self._slot(t, 1, 0, 0, 1))
+        # every dX reads a layer's weights BEFORE that layer's dW(+Adam) launch updates them
+        ops.linear_bwd_dx(self.dA, D2.W, self.dHdec, below=self.Hdec, epi="relu", M=b * k, stream=st)
+        ops.linear_bwd_dx(self.dHdec, D1.W, self.dzdec, M=b * k, stream=st)
+        ops.linear_bwd_dw_adam_pair(dict(dA=self.dA, X=self.Hdec, lin=D2, adam=adam, M=b * k),
+                                    dict(dA=self.dHdec, X=self.Zs, lin=D1, adam=adam, M=b * k),
+                                    weight_decay=self.wd, stream=st)
+        of_.iwae_reduce(self.ml, self.wn, self.dzdec, self.dml, nz, b, k, Z, stream=st)
+        ops.linear_bwd_dx(self.dml, ML.W, self.dHe, below=self.He, epi="relu", M=b, stream=st)
+        ops.linear_bwd_dw_adam_pair_finalize(
+            dict(dA=self.dHe, X=X, lin=E1, adam=adam, M=b), dict(dA=self.dml, X=self.He, lin=ML, adam=adam, M=b),
+            dict(pa=self.negL, na=b, out_a=loss_out, slot_a=loss_slot, pb=self.essb, nb=b, scale_b=1.0 / b,
+                 out_b=ess_out, slot_b=loss_slot, done=self.fin_done, tick=tick),
+            weight_decay=self.wd, stream=st)
+
+
 def aae_fused_ok(model):
     """True iff an AAE's shapes fit the fused kernels (gm_aae.hip): 1 <= Z <= 32 with Z % 4 == 0, hidden width <= 512,
     the decoder's and the discriminator's hidden widths equal to the encoder's, one discriminator output."""

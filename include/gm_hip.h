@@ -851,6 +851,47 @@ int gm_pdw_couple(void* stream, const float* x, int64_t ldx, const float* xr, in
 int gm_pdw_dir(void* stream, const float* g, int64_t ldg, const float* x, int64_t ldx, const float* xr, int64_t ldr,
                const float* n, float* gamma, int64_t ldm, float* pen, float lambda, float inv_b, int B, int I);
 
+/* ---- Importance-weighted autoencoder (csrc/gm_iwae.hip; iwae.py holds the contract).  k samples
+ * per image, rows image-major: sample j of image b is row b * k + j of every [B*k, .] array.  Fixed reduction order, no
+ * atomics.  Noise: Philox4x32-10 with key (seed mod 2^32, seed >> 32) and counter (c >> 2, step, row, tag) gives word
+ * c & 3 (through gm_philox_normal's Box-Muller mapping) to latent c of noise row `row` = b * k_total + j0 + j, step =
+ * (step_ctr ? *step_ctr : 0) + (step_base ? *step_base : 0) + step_add truncated to 32 bits.  k_total >= j0 + k lets
+ * a caller run the samples of an image in chunks of k that draw what one call over k_total samples would.
+ * Limits: 1 <= k <= 64, 1 <= Z <= 32; outside them, or with a NULL array, every entry point returns GM_EINVAL before
+ * any launch. */
+#define GM_IWAE_TAG_TRAIN 0x49574145u          /* "IWAE" */
+#define GM_IWAE_TAG_EVAL 0x49574556u           /* "IWEV" */
+#define GM_IWAE_MAX_K 64
+#define GM_IWAE_MAX_Z 32
+typedef struct gm_iwae_noise {
+    uint64_t seed;
+    uint32_t tag;                             /* the fourth counter word */
+    const int64_t* step_ctr;                  /* device counter or NULL */
+    const int64_t* step_base;                 /* device base or NULL */
+    int64_t step_add;
+    int64_t k_total;                          /* samples per image of the whole draw (>= j0 + k) */
+    int64_t j0;                               /* first sample of this call (>= 0) */
+    int64_t q0;                               /* first latent quad of this call (>= 0): its latent c is latent 4 q0 + c
+                                               * of the row, so a row wider than the limit can be drawn in pieces */
+} gm_iwae_noise;
+/* z[b k + j] = mu_b + eps_j exp(lv_b / 2) (gm_reparam_z's roundings) from ml [B, 2Z] = [mu | lv], and
+ * lp[b k + j] = 1/2 sum_c (eps_jc^2 - z_jc^2 + lv_bc): the part of log w_j that does not need the decoder. */
+int gm_iwae_sample(void* stream, const gm_iwae_noise* n, const float* ml, int64_t ldml, float* z, int64_t ldz,
+                   float* lp, int B, int k, int Z);
+/* One workgroup per image: sq_j = ||x_b - xr_j||^2 over the image's k rows of xr [B*k, I] (the sigmoid output),
+ * log w_j = lp_j - sq_j, m = max_j log w_j, s = sum_j exp(log w_j - m), wn_j = exp(log w_j - m) / s;
+ * negL[b] = -(m + log s - log k), ess[b] = s^2 / sum_j exp(log w_j - m)^2 (= 1 / sum_j wn_j^2), wn [B*k];
+ * dA [B*k, I] (training; NULL in evaluation) = wn_j * (-2 (x - xr_j) (1 - xr_j) xr_j), the gradient of sum_b negL
+ * with respect to the pre-sigmoid output; ms [B, 2] (evaluation; may be NULL) = (m, s), so that chunks of samples
+ * combine.  The image's k rows stay in LDS between the two passes while they fit in 64 KB, else they are re-read. */
+int gm_iwae_weights(void* stream, const float* x, int64_t ldx, const float* xr, int64_t ldr, const float* lp,
+                    float* negL, float* ess, float* wn, float* dA, int64_t lda, float* ms, int B, int k, int I);
+/* dz_j = dzdec_j + wn_j z_j (z and eps rebuilt from ml and the counter, never read), dml [B, 2Z] = [sum_j dz_j |
+ * sum_j dz_j eps_j exp(lv / 2) / 2 - 1/2], j ascending; dZ [B*k, Z] = dz when not NULL. */
+int gm_iwae_reduce(void* stream, const gm_iwae_noise* n, const float* ml, int64_t ldml, const float* wn,
+                   const float* dzdec, int64_t lddz, float* dml, int64_t lddml, float* dZ, int64_t lddZ, int B, int k,
+                   int Z);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

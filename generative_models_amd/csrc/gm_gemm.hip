@@ -372,15 +372,23 @@ __device__ __forceinline__ int red_idx(int w, int row, int col) {
     return (w * 32 + row) * 32 + (col ^ ((((row >> 2) ^ row) & 1) << 4));
 }
 
+// The same buffer under the strided-set operand path (raw_xs): a lane's columns are NI i16 + f -- one parity per store
+// -- and the two lane groups of a half-wave sit on rows 4 (dX) or 4 MI (dW) apart: the same bank either way.  flip: the
+// writing lane group's parity (g4 & 1), which swaps each column pair; readers recompute it from the row.
+__device__ __forceinline__ int red_idx_sx(int w, int row, int col, int flip) {
+    return (w * 32 + row) * 32 + (col ^ flip);
+}
+
 // Sum the per-wave partial tiles (red[w][32][32]) and apply the epilogue of the mode.
 // ncap: columns >= ncap are not this block's to store (the 16-column last block of a 48-wide tile);
 // rcap: rows of the block that belong to the tile (16 for the last block of a 48-row tile)
 // kept: row-major copy of the block's stepped parameters, row stride KEEP_LD (weight gradient with Adam; see store_element)
 constexpr int KEEP_LD = 68;
-template <int MODE, int WAVES, int ROWS = 32, bool LBL = false>
+// SXD > 0: partial tiles of the strided-set operand path (red_idx_sx, flip = ((srow0 + row) / SXD) & 1)
+template <int MODE, int WAVES, int ROWS = 32, bool LBL = false, int SXD = 0>
 __device__ __forceinline__ void reduce_and_store(const GemmP& p, const float* red, int t, int m0,
                                                  int n0, int ncap = 0x7fffffff, int rcap = 32,
-                                                 float* kept = nullptr) {
+                                                 float* kept = nullptr, int srow0 = 0) {
     if (MODE == MODE_FWD && p.hd_part) {                     // kernel-argument uniform
         // Folded critic head: every row of this 32-column block also leaves its partial dot with w2.
         // The 32 lanes that hold a row (one half of a wave) sum their products in a fixed butterfly;
@@ -453,7 +461,8 @@ __device__ __forceinline__ void reduce_and_store(const GemmP& p, const float* re
         if ((ROWS < 32 && row >= ROWS) || row >= rcap) continue;   // 16-row tiles / blocks: half the threads idle
         float v = 0.f;
 #pragma unroll
-        for (int ww = 0; ww < WAVES; ++ww) v += red[red_idx(ww, row, col)];
+        for (int ww = 0; ww < WAVES; ++ww)
+            v += red[SXD > 0 ? red_idx_sx(ww, row, col, ((srow0 + row) / (SXD > 0 ? SXD : 1)) & 1) : red_idx(ww, row, col)];
         const int m = m0 + row, n = n0 + col;
         if (m >= p.M || n >= p.N || n >= ncap) continue;
         store_element<MODE, LBL>(p, v, m, n, kept ? kept + row * KEEP_LD + col : nullptr);
@@ -874,6 +883,45 @@ __device__ __forceinline__ float4 lane48_transpose(float4 v, int lane) {
 // W consecutive floats as one load (interleaved fragments of the LDS-DMA weight gradient below)
 template <int W> struct __attribute__((aligned(4))) ILV { float v[W]; };
 
+// ---- strided-set x-contiguous fragment loads --------------------------------------------------------------------
+// The 16x16x4 MFMA does not care WHICH 16 rows its operand covers.  Lane (i16, g4) issues four loads t = 0..3; load t
+// reads, in k-row 16c + 4 g4 + t, the W = (tile width / 16) consecutive floats x0 + W i16 .. + W - 1.  Component s of
+// load t is then already the MFMA operand of the strided 16-row set {x0 + W i + s : i = 0..15}, and accumulator
+// [s_a][s_b] takes the MFMAs t = 0, 1, 2, 3 in that order: MFMA t covers k = 16c + 4g + t, g = 0..3 -- the k set of the
+// transpose path's t-th MFMA, so every output is the same fmaf chain in the same order.  No lane transpose; the price
+// is 4 load instructions per operand (instead of W), each over 4 rows of 64 W contiguous bytes.  The lane ends up
+// with output x0 + W i + s of sub-tile s: the interleaved accumulator layout of gemm16_dw_dma, undone in the epilogues.
+// Which instantiations take this path: sx_feed below.  Measured (profiles/xfeed_ns_b256.md): NSGAN bs=256 step 61.4 ->
+// 59.8 us; layer-1 weight gradient + head 14.15 -> 13.36 us, generator pair 10.56 -> 10.15, dH + gather 7.24 -> 6.76.
+template <int W> struct __attribute__((aligned(W == 4 ? 16 : W == 2 ? 8 : 4))) XSV { float v[W]; };
+
+// X % 4 == 0 and X >= 4 (the 16-byte paths' condition): a lane's group is whole or absent for W = 1, 2, 4; for W = 3 it
+// may straddle X, and the load clamped to X - 3 then holds the lane's elements d = xl - (X - 3) components further on
+template <int W>
+__device__ __forceinline__ XSV<W> raw_xs(const float* __restrict__ P, int64_t ld, int xl, int X, int k, int K) {
+    return *reinterpret_cast<const XSV<W>*>(P + (int64_t)min(k, K - 1) * ld + min(xl, X - W));
+}
+// the W operands of one loaded fragment (k-row k, kin = k < K): fix_xc's values per component.  FOLD: the fragment is
+// h[k][x]; the operand is dH = (h > 0) ? ds * w2[x] : 0 (fold_dh4's arithmetic per element)
+template <int W, bool FOLD>
+__device__ __forceinline__ void fix_xs(const XSV<W>& r, float (&o)[W], int xl, int X, bool kin, int ones_col, float one,
+                                       float ds, const float* fw) {
+    float c[W];
+#pragma unroll
+    for (int s = 0; s < W; ++s) c[s] = r.v[s];
+    if constexpr (W == 3) {
+        const int d = xl - min(xl, X - 3);
+        c[0] = (d == 0) ? r.v[0] : ((d == 1) ? r.v[1] : r.v[2]);
+        c[1] = (d == 0) ? r.v[1] : r.v[2];
+    }
+#pragma unroll
+    for (int s = 0; s < W; ++s) {
+        float v = c[s];
+        if constexpr (FOLD) v = (v > 0.f) ? ds * fw[s] : 0.f;
+        o[s] = kin ? ((xl + s < X) ? v : ((xl + s == ones_col) ? one : 0.f)) : 0.f;
+    }
+}
+
 // Two consecutive weight-gradient outputs C(m, n), C(m, n + 1), n even, both real columns: store_element's arithmetic
 // per element, 8-byte accesses (p.vec_epi: C and the Adam arrays are 16-byte aligned, ldc % 4 == 0).
 __device__ __forceinline__ void store2_dw(const GemmP& p, float2 v, int m, int n) {
@@ -900,11 +948,19 @@ __device__ __forceinline__ void store2_dw(const GemmP& p, float2 v, int m, int n
 // the epilogue once.  The block-by-block form (reduce_and_store) makes two or three trips -- barrier, sum, Adam state
 // in, parameters out -- one behind the other, and each trip is a memory round trip.  ILO: interleaved accumulator
 // layout of gemm16_dw_dma.
-template <int MI, int NI, bool ILO, bool XMAP = false>
+// SX: strided-set accumulators (raw_xs): register r of accumulator (e, f) in lane (i16, g4) is output (row MI (4 g4 + r)
+// + e, column NI i16 + f) of the tile.  The image keeps that row at LDS row 16 e + 4 r + g4 -- the two lane groups of a
+// half-wave on NEIGHBOURING rows, as the transpose path has them: 48-column images put them 16 banks apart (the lanes'
+// 3 i16 + f cover 16 banks that do not meet their own shift by 16); images of 32 / 64 columns swap each odd row's column
+// pairs (the lanes' even-NI strides leave every other bank free) and, at 64 columns, move the upper 32 columns by one pair
+// (lanes 8 apart would share a bank).  Conflict-free writes; the readers take whole rows as before.
+template <int MI, int NI, bool ILO, bool XMAP = false, bool SX = false>
 __device__ __forceinline__ void dw_reduce_onepass(const GemmP& p, float* red, f32x4 (&acc)[MI][NI], int m0, int n0,
                                                   bool sync_first) {
     constexpr int RT = 16 * MI, CT = 16 * NI, IMG = RT * CT, G = IMG / 2;
-    constexpr bool SWZ = !ILO && XMAP && (CT % 32 == 0);
+    constexpr bool SWZ = !ILO && !SX && XMAP && (CT % 32 == 0);
+    constexpr bool SXZ = SX && (NI % 2 == 0);
+    static_assert(!SX || !ILO, "one accumulator layout");
     static_assert(G <= 1024, "one pair of columns per thread");
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int i16 = lane & 15, g4 = lane >> 4;
@@ -917,11 +973,13 @@ __device__ __forceinline__ void dw_reduce_onepass(const GemmP& p, float* red, f3
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 // XMAP: the coalesced x-contiguous loads leave output index sigma16(.) of each 16-wide sub-tile in a lane
-                const int row = ILO ? MI * (4 * g4 + r) + e : 16 * e + (XMAP ? sigma16(4 * g4 + r) : 4 * g4 + r);
-                const int col = ILO ? NI * i16 + f : 16 * f + (XMAP ? sigma16(i16) : i16);
+                const int row = SX ? 16 * e + 4 * r + g4
+                                   : ILO ? MI * (4 * g4 + r) + e : 16 * e + (XMAP ? sigma16(4 * g4 + r) : 4 * g4 + r);
+                const int col = (SX || ILO) ? NI * i16 + f : 16 * f + (XMAP ? sigma16(i16) : i16);
                 // SWZ (images whose rows are a whole number of 32-bank turns, e.g. the generator's 48 x 32 tiles): the two
                 // lane groups of a half-wave sit on neighbouring rows = the same banks; flip column bit 4 on odd rows
-                img[row * CT + (SWZ ? col ^ ((row & 1) << 4) : col)] = acc[e][f][r];
+                const int cs = SXZ ? col ^ (((col >> 5) & 1) << 1) ^ (row & 1) : SWZ ? col ^ ((row & 1) << 4) : col;
+                img[row * CT + cs] = acc[e][f][r];
             }
     __syncthreads();
 #ifdef GM_STAMPS
@@ -929,15 +987,18 @@ __device__ __forceinline__ void dw_reduce_onepass(const GemmP& p, float* red, f3
 #endif
     GM_STAMP(p.stamp, st_tile, 10);                      // partial tiles of all waves in LDS
     if (t >= G) return;
-    const int row = t / (CT / 2), c2 = t % (CT / 2);
+    const int lrow = t / (CT / 2), c2 = t % (CT / 2);
+    const int cr = SXZ ? (2 * c2) ^ (((c2 >> 4) & 1) << 1) : SWZ ? (2 * c2) ^ ((lrow & 1) << 4) : 2 * c2;
     float2 v = make_float2(0.f, 0.f);
 #pragma unroll
     for (int ww = 0; ww < 16; ++ww) {
-        const float2 x = *reinterpret_cast<const float2*>(&red[ww * IMG + row * CT + (SWZ ? (2 * c2) ^ ((row & 1) << 4) : 2 * c2)]);
+        const float2 x = *reinterpret_cast<const float2*>(&red[ww * IMG + lrow * CT + cr]);
         v.x += x.x; v.y += x.y;
     }
+    if (SXZ && (lrow & 1)) v = make_float2(v.y, v.x);        // odd rows keep their pairs swapped
     GM_STAMP_AFTER(v.x);
     GM_STAMP(p.stamp, st_tile, 11);                      // sixteen images summed; the epilogue's round trips follow
+    const int row = SX ? MI * sigma16(lrow & 15) + (lrow >> 4) : lrow;
     const int m = m0 + row, n = n0 + 2 * c2;
     if (m >= p.M) return;
     if (n + 1 < p.n_real) { store2_dw(p, v, m, n); return; }
@@ -1123,6 +1184,51 @@ __device__ __forceinline__ void gemm16_dw_dma(const GemmP& p, float* red, int bx
     GM_STAMP_EDGE(p, true, st_tile, MODE_DW + 20);
 }
 
+// Which instantiations feed their x-contiguous operands as strided sets (raw_xs) instead of through the lane transpose
+// (raw_xc4_16 / lane48_transpose): decided per (MODE, MI, NI) by measurement, profiles/xfeed_ns_b256.md.
+template <int MODE, int MI, int NI>
+constexpr bool sx_feed() {
+    // (weight-gradient tiles 16 rows tall and 48 / 64 wide exist only as the second body of gemm16_dw_pair_l1_kernel<., 3 / 4>,
+    // which no configuration launches: they keep the transpose path, whose scalar-register count is the committed one)
+    return (MODE == MODE_DW && !(MI == 1 && NI > 2)) || MODE == MODE_DX;
+}
+
+// Cross-wave reduction + epilogue of the strided-set operand path, one 32 x 32 block of the tile at a time through the
+// first 64 KB of `red`: accumulator (e, f) register r of lane (i16, g4) is output column NI i16 + f and output row
+// MI (4 g4 + r) + e (ILA: weight gradient, both operands strided) or 16 e + 4 g4 + r (input gradient: A in fragment
+// layout).  Same sums in the same wave order as the transpose path's blocks.
+template <int MODE, int MI, int NI, bool ILA>
+__device__ __forceinline__ void sx_block_reduce(const GemmP& p, float* red, f32x4 (&acc)[MI][NI], int m0, int n0,
+                                                float* kept) {
+    const int t = threadIdx.x;
+    const int lane = t & 63, w = t >> 6;
+    const int i16 = lane & 15, g4 = lane >> 4;
+    constexpr int SXD = ILA ? 4 * MI : 4;                    // rows per lane group
+#pragma unroll
+    for (int bm = 0; bm < (MI + 1) / 2; ++bm)
+#pragma unroll
+        for (int bn = 0; bn < (NI + 1) / 2; ++bn) {
+            if (bm + bn > 0) __syncthreads();                // previous block fully consumed
+#pragma unroll
+            for (int e = 0; e < MI; ++e)
+#pragma unroll
+                for (int f = 0; f < NI; ++f)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = ILA ? MI * (4 * g4 + r) + e : 16 * e + 4 * g4 + r, col = NI * i16 + f;
+                        const bool rin = ILA ? (MI <= 2 || (row >> 5) == bm) : (e >> 1) == bm;
+                        if (rin && (NI <= 2 || (col >> 5) == bn))
+                            red[red_idx_sx(w, row & 31, col & 31, g4 & 1)] = acc[e][f][r];
+                    }
+            __syncthreads();
+            reduce_and_store<MODE, 16, (MI > 1 ? 32 : 16), false, SXD>(p, red, t, m0 + 32 * bm, n0 + 32 * bn,
+                                                                       (2 * bn + 1 < NI) ? 0x7fffffff : n0 + 32 * bn + 16,
+                                                                       (2 * bm + 1 < MI) ? 32 : 16,
+                                                                       kept ? kept + 32 * bm * KEEP_LD + 32 * bn : nullptr,
+                                                                       ILA ? 32 * bm : 0);
+        }
+}
+
 // LDS floats of the 16-wave kernels: the 64 KB block-by-block reduction buffer; for weight gradients of multi-block
 // tiles the sixteen whole-tile images of dw_reduce_onepass; the DMA form's sixteen chunk buffers
 template <int MODE, bool DMA, int MI, int NI> struct RedSize {
@@ -1178,35 +1284,54 @@ __device__ __forceinline__ void gemm16_body(const GemmP& p, float* red, int bx, 
     GM_STAMP_AFTER(A); GM_STAMP_AFTER(B); GM_STAMP_AFTER(nchunks);
     GM_STAMP(st_slot, st_tile, 16);                           // operand bases resolved (kernel arguments + slot counters read)
 
+    // strided-set feed of the x-contiguous operands (raw_xs): both operands of the weight gradient, B of the input gradient
+    constexpr bool SX = XV && WAVES == 16 && !PK && (MODE == MODE_DW || MODE == MODE_DX) && sx_feed<MODE, MI, NI>();
+    constexpr bool SXA = SX && MODE == MODE_DW;
+    using FragA = std::conditional_t<SXA, XSV<MI>, float4>;
+    using FragB = std::conditional_t<SX, XSV<NI>, float4>;
+    constexpr int NA = SXA ? 4 : MI, NB = SX ? 4 : NI;       // loads per chunk: one per k-row / one per sub-tile
+    const int xla = m0 + MI * i16, xlb = n0 + NI * i16;      // SX: this lane's first A / B column
+
     // folded head: what stays fixed per lane across the reduction
     float4 fw[FOLD == 1 ? MI : 1];
+    float fws[FOLD == 1 ? MI : 1];                           // SX: w2 of this lane's own A columns
     float fds[FOLD == 2 ? MI : 1];
     // x-contiguous 16-byte operands: which x-quad / which of its lane-group's four k-rows this lane LOADS
     const int xq_ld = lane & 3, xe_ld = (lane >> 2) & 3;
     // ... and which output index of the 16-wide sub-tile it then HOLDS (XMAP: sigma16)
     constexpr bool XMAP_A = MODE == MODE_DW && XV, XMAP_B = MODE != MODE_FWD && XV;
     const int ia = XMAP_A ? sigma16(i16) : i16, ib = XMAP_B ? sigma16(i16) : i16;
-    if constexpr (FOLD == 1) {
+    if constexpr (FOLD == 1 && SX) {
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) fws[mi] = p.fold_w2[min(xla + mi, p.M - 1)];
+    } else if constexpr (FOLD == 1) {
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)                       // w2 of this lane's four A columns
             fw[mi] = *reinterpret_cast<const float4*>(
                 p.fold_w2 + min(m0 + 16 * mi + 4 * xq_ld, p.M - 4));
     }
-    auto load_a = [&](int c, int mi) -> float4 {
+    // (SX operands: `mi` / `ni` is the load's index t, k-row 16c + 4 g4 + t)
+    auto load_a = [&](int c, int mi) -> FragA {
         const int kb = 16 * c + 4 * g4, x0 = m0 + 16 * mi;
-        if (MODE == MODE_DW) {
-            if (XV) return raw_xc4_16(A, p.lda, x0, p.M, c, p.K, lane);
-            return raw_xc(A, p.lda, x0 + i16, p.M, kb, p.K);
+        if constexpr (SXA) return raw_xs<MI>(A, p.lda, xla, p.M, kb + mi, p.K);
+        else {
+            if (MODE == MODE_DW) {
+                if (XV) return raw_xc4_16(A, p.lda, x0, p.M, c, p.K, lane);
+                return raw_xc(A, p.lda, x0 + i16, p.M, kb, p.K);
+            }
+            return raw_kc<VEC>(A, p.lda, x0 + i16, p.M, kb, p.K);
         }
-        return raw_kc<VEC>(A, p.lda, x0 + i16, p.M, kb, p.K);
     };
-    auto load_b = [&](int c, int ni) -> float4 {
+    auto load_b = [&](int c, int ni) -> FragB {
         const int kb = 16 * c + 4 * g4, x0 = n0 + 16 * ni;
-        if (MODE == MODE_FWD) return raw_kc<VEC>(B, p.ldb, x0 + i16, p.N, kb, p.K);
-        if (XV) return raw_xc4_16(B, p.ldb, x0, b_cols, c, p.K, lane);
-        return raw_xc(B, p.ldb, x0 + i16, b_cols, kb, p.K);
+        if constexpr (SX) return raw_xs<NI>(B, p.ldb, xlb, b_cols, kb + ni, p.K);
+        else {
+            if (MODE == MODE_FWD) return raw_kc<VEC>(B, p.ldb, x0 + i16, p.N, kb, p.K);
+            if (XV) return raw_xc4_16(B, p.ldb, x0, b_cols, c, p.K, lane);
+            return raw_xc(B, p.ldb, x0 + i16, b_cols, kb, p.K);
+        }
     };
-    auto fix_a = [&](float4 v, int c, int mi, float4 wk) -> float4 {
+    auto fix_a = [&](float4 v, int c, int mi, float4 wk) -> float4 {  // (fragment layout / transpose path)
         const int kb = 16 * c + 4 * g4, x = m0 + 16 * mi + ia;
         if constexpr (FOLD == 1)                              // the loaded row is k = 16c + 4g + e (clamped)
             v = fold_dh4(v, sds[min(16 * c + 4 * g4 + xe_ld, p.K - 1)], fw[mi]);
@@ -1237,8 +1362,44 @@ __device__ __forceinline__ void gemm16_body(const GemmP& p, float* red, int bx, 
     // (profiles/r01 .. r03_experiments.md): batches of G chunks of loads ahead of their MFMAs (waves in lockstep:
     // fwd 512x784x400 G=4 8.8 us, G=2 7.7, G=1 7.4-7.6), a rolling prefetch of the next chunk (step 71.7 -> 76.3 us),
     // k-steps outermost in the MFMA block, a fast path for interior tiles, spreading the reduction's tail over waves.
-    auto consume = [&](const float4 (&ra)[MI], const float4 (&rb)[NI], float4 wk, int q) {
+    auto consume = [&](const FragA (&ra)[NA], const FragB (&rb)[NB], float4 wk, int q) {
         const int cq = w + q * WAVES;
+        if constexpr (SX) {
+            // fa[t][s] / fb[t][s]: component s of k-row 16 cq + 4 g4 + t; accumulator [s_a][s_b] takes t = 0..3 in order
+            float fa[4][MI], fb[4][NI];
+            if constexpr (!SXA) {
+#pragma unroll
+                for (int mi = 0; mi < MI; ++mi) {
+                    const float4 v = fix_a(ra[mi], cq, mi, wk);
+                    fa[0][mi] = v.x; fa[1][mi] = v.y; fa[2][mi] = v.z; fa[3][mi] = v.w;
+                }
+            }
+#pragma unroll
+            for (int t4 = 0; t4 < 4; ++t4) {
+                const int k = 16 * cq + 4 * g4 + t4;
+                const bool kin = k < p.K;
+                if constexpr (SXA) {
+                    float ds = 0.f;
+                    if constexpr (FOLD == 1) ds = sds[min(k, p.K - 1)];
+                    fix_xs<MI, FOLD == 1>(ra[t4], fa[t4], xla, p.M, kin, -1, 0.f, ds, fws);
+                }
+                float one = 1.f;
+                if constexpr (OF) one = (k >= p.ones_from) ? 1.f : 0.f;
+                fix_xs<NI, false>(rb[t4], fb[t4], xlb, b_cols, kin, ones_col, one, 0.f, nullptr);
+            }
+            GM_STAMP_AFTER(fa[3][MI - 1]); GM_STAMP_AFTER(fb[3][NI - 1]);
+            if (q < 4) GM_STAMP(st_slot, st_tile, 1 + 2 * q);
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < NI; ++ni) {
+                    f32x4 c4 = acc[mi][ni];
+#pragma unroll
+                    for (int t4 = 0; t4 < 4; ++t4)
+                        c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[t4][mi], fb[t4][ni], c4, 0, 0, 0);
+                    acc[mi][ni] = c4;
+                }
+        } else {
         float4 fa[MI], fb[NI];
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) fa[mi] = fix_a(ra[mi], cq, mi, wk);
@@ -1257,6 +1418,7 @@ __device__ __forceinline__ void gemm16_body(const GemmP& p, float* red, int bx, 
                 c4 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[mi].w, fb[ni].w, c4, 0, 0, 0);
                 acc[mi][ni] = c4;
             }
+        }
         GM_STAMP_AFTER(acc[MI - 1][NI - 1][0]);
         if (q < 4) GM_STAMP(st_slot, st_tile, 2 + 2 * q);     // chunk q: last MFMA retired
     };
@@ -1322,7 +1484,7 @@ __device__ __forceinline__ void gemm16_body(const GemmP& p, float* red, int bx, 
         else q_pk = min(nq_s, max(0, ((p.pk_rows >> 4) - __builtin_amdgcn_readfirstlane(w) + WAVES - 1) / WAVES));
         auto do_chunk = [&](auto is_pk, auto with_prologue, int q) {
             constexpr bool P = decltype(is_pk)::value;
-            float4 ra[MI], rb[NI];
+            float4 ra[MI], rb[NI];                            // (PK: never SX)
             uint32_t pw[PN];
             const int cc = w + q * WAVES;
 #pragma unroll
@@ -1359,7 +1521,7 @@ __device__ __forceinline__ void gemm16_body(const GemmP& p, float* red, int bx, 
     } else {
     int q_first = 0;
     if constexpr (FOLD != 0) {
-        float4 ra[MI], rb[NI];
+        FragA ra[NA]; FragB rb[NB];
         float4 wk = make_float4(0.f, 0.f, 0.f, 0.f);
         const bool have = nq > 0;
         // folded weight gradient: this thread's row of partial dots is requested FIRST (gm_head.h fold_part_load)
@@ -1375,9 +1537,9 @@ __device__ __forceinline__ void gemm16_body(const GemmP& p, float* red, int bx, 
         }
         if (have) {
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi) ra[mi] = load_a(w, mi);
+            for (int mi = 0; mi < NA; ++mi) ra[mi] = load_a(w, mi);
 #pragma unroll
-            for (int ni = 0; ni < NI; ++ni) rb[ni] = load_b(w, ni);
+            for (int ni = 0; ni < NB; ++ni) rb[ni] = load_b(w, ni);
             wk = load_wk(w);
         }
         GM_STAMP(st_slot, st_tile, 17);                       // first chunk's operand loads issued
@@ -1399,17 +1561,31 @@ __device__ __forceinline__ void gemm16_body(const GemmP& p, float* red, int bx, 
         q_first = 1;
     }
     for (int q = q_first; q < nq; ++q) {
-        float4 ra[MI], rb[NI];
+        FragA ra[NA]; FragB rb[NB];
         const int cc = w + q * WAVES;
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) ra[mi] = load_a(cc, mi);
+        for (int mi = 0; mi < NA; ++mi) ra[mi] = load_a(cc, mi);
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni) rb[ni] = load_b(cc, ni);
+        for (int ni = 0; ni < NB; ++ni) rb[ni] = load_b(cc, ni);
         const float4 wk = load_wk(cc);
         consume(ra, rb, wk, q);
     }
     }
     GM_STAMP(st_slot, st_tile, 9);                            // reduction loop done (this wave)
+    if constexpr (SX) {
+        if constexpr (MODE == MODE_DW && MI * NI > 4) {
+            if (p.vec_epi) {                                 // kernel-argument uniform
+                dw_reduce_onepass<MI, NI, false, false, true>(p, red, acc, m0, n0, false);
+                GM_STAMP(st_slot, st_tile, 12);
+                GM_STAMP_EDGE(p, true, st_tile, MODE);
+                return;
+            }
+        }
+        sx_block_reduce<MODE, MI, NI, SXA>(p, red, acc, m0, n0, kept);
+        GM_STAMP(st_slot, st_tile, 12);
+        GM_STAMP_EDGE(p, true, st_tile, MODE);
+        return;
+    }
     if constexpr (MODE == MODE_DW && WAVES == 16 && MI * NI > 4) {
         if (p.vec_epi) {                                     // kernel-argument uniform
             dw_reduce_onepass<MI, NI, false, XMAP_A>(p, red, acc, m0, n0, false);

@@ -124,7 +124,8 @@ class CorruptArgs(ctypes.Structure):
 
 IWAE_TAG_TRAIN, IWAE_TAG_EVAL = 0x49574145, 0x49574556      # GM_IWAE_TAG_TRAIN / GM_IWAE_TAG_EVAL
 IWAE_MAX_K, IWAE_MAX_Z = 64, 32                             # GM_IWAE_MAX_K / GM_IWAE_MAX_Z
-# (gm_iwae_noise travels by pointer; its ctypes form, IwaeNoise, lives in ops_fused beside iwae_noise())
+# (gm_iwae_noise and gm_acgan_heads_args travel by pointer; their ctypes forms, IwaeNoise and ACGANHeadsArgs, live in
+# ops_fused beside their wrappers)
 
 NOISE = {"salt_pepper": 1, "gaussian": 2}       # GM_NOISE_SALT_PEPPER, GM_NOISE_GAUSSIAN (GM_NOISE_NONE = 0)
 
@@ -324,6 +325,9 @@ _SIGNATURES = {
     "gm_aae_critic_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "gm_aae_critic_step": (c_int, [_P, POINTER(AAECriticArgs)]),
     "gm_aae_gen_mid": (c_int, [_P, POINTER(AAEGenArgs)]),
+    "gm_acgan_heads_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "gm_acgan_heads_fwd": (c_int, [_P, _P]),
+    "gm_acgan_heads_bwd": (c_int, [_P, _P]),
     "gm_philox_raw": (c_int, [_P, _P, _P, _P, c_int64]),
     "gm_philox_normal": (c_int, [_P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_int, _P, c_int64, _P,
                                  c_int64]),

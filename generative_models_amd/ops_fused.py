@@ -315,6 +315,93 @@ def aae_gen_mid(z, He, W1, b1, w2, b2, Wz, dz, dHe, loss_part, B, stream=None):
     _lib.call("gm_aae_gen_mid", stream or stream_ptr(), ctypes.byref(a))
 
 
+# ---- auxiliary-classifier GAN (csrc/gm_acgan.hip; acgan.py) ---------------------------------------------------------
+class ACGANHeadsArgs(ctypes.Structure):
+    """gm_acgan_heads_args (include/gm_hip.h): the AC-GAN critic's two heads, forward and backward."""
+    _fields_ = [("H", ctypes.c_void_p), ("ldh", ctypes.c_int64), ("rows", ctypes.c_int), ("B", ctypes.c_int), ("Hd", ctypes.c_int), ("C", ctypes.c_int),
+                ("gen_mode", ctypes.c_int), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p), ("Wc", ctypes.c_void_p), ("bc", ctypes.c_void_p),
+                ("lab", _lib.LabelSrc), ("class_weight", ctypes.c_float), ("da2", ctypes.c_void_p), ("dq", ctypes.c_void_p), ("lddq", ctypes.c_int64),
+                ("loss_out", ctypes.c_void_p), ("loss_slot", _lib.Slot), ("ce_out", ctypes.c_void_p), ("ce_slot", _lib.Slot),
+                ("acc_out", ctypes.c_void_p), ("acc_slot", _lib.Slot), ("dPre", ctypes.c_void_p), ("ldp", ctypes.c_int64),
+                ("gw2", ctypes.c_void_p), ("gb2", ctypes.c_void_p), ("gWc", ctypes.c_void_p), ("gbc", ctypes.c_void_p),
+                ("mw2", ctypes.c_void_p), ("vw2", ctypes.c_void_p), ("mb2", ctypes.c_void_p), ("vb2", ctypes.c_void_p),
+                ("mWc", ctypes.c_void_p), ("vWc", ctypes.c_void_p), ("mbc", ctypes.c_void_p), ("vbc", ctypes.c_void_p),
+                ("sched", ctypes.c_void_p), ("sched_slot", _lib.Slot), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_int64)]
+
+
+def _acgan_shape(rows, Hd, C):
+    if not (rows >= 1 and 1 <= C <= 32 and 4 <= Hd <= 1024 and Hd % 4 == 0):
+        raise _lib.GMError("the AC-GAN head kernels take 1 <= C <= 32 and 4 <= Hd <= 1024 with Hd %% 4 == 0 (got "
+                           "rows=%d, Hd=%d, C=%d); other shapes train on the general path" % (rows, Hd, C))
+
+
+def acgan_heads_workspace(rows, Hd, C, device):
+    """A zeroed workspace for acgan_heads_fwd / acgan_heads_bwd at this shape (float32 device tensor)."""
+    _acgan_shape(rows, Hd, C)
+    n = _lib.load().gm_acgan_heads_workspace_bytes(rows, Hd, C)
+    return torch.zeros((n + 3) // 4, device=device)
+
+
+def _acgan_args(H, w2, b2, Wc, bc, B, gen_mode, class_weight, da2, dq, ws, rows):
+    C, Hd = Wc.shape
+    rows = (B if gen_mode else 2 * B) if rows is None else rows
+    _acgan_shape(rows, Hd, C)
+    if (H.dim() != 2 or H.shape[0] < rows or H.shape[1] != Hd or w2.numel() != Hd or b2.numel() != 1
+            or bc.numel() != C or da2.numel() < rows or dq.dim() != 2 or dq.shape[0] < rows or dq.shape[1] != C
+            or not Wc.is_contiguous()):
+        raise _lib.GMError("acgan heads: H must be [>= rows, Hd], w2 [1, Hd], b2 [1], Wc [C, Hd] contiguous, bc [C], "
+                           "da2 [>= rows] and dq [>= rows, C]")
+    if ws.numel() * 4 < _lib.load().gm_acgan_heads_workspace_bytes(rows, Hd, C):
+        raise _lib.GMError("acgan heads: workspace too small (use acgan_heads_workspace)")
+    a = ACGANHeadsArgs()
+    a.H, a.ldh, a.rows, a.B, a.Hd, a.C, a.gen_mode = H.data_ptr(), _ld(H), rows, B, Hd, C, 1 if gen_mode else 0
+    a.w2, a.b2, a.Wc, a.bc = w2.data_ptr(), b2.data_ptr(), Wc.data_ptr(), bc.data_ptr()
+    a.class_weight = float(class_weight)
+    a.da2, a.dq, a.lddq = da2.data_ptr(), dq.data_ptr(), _ld(dq)
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    return a
+
+
+def acgan_heads_fwd(H, w2, b2, Wc, bc, lab, B, gen_mode, class_weight, da2, dq, ws, loss_out=None, loss_slot=NO_SLOT,
+                    ce_out=None, ce_slot=NO_SLOT, acc_out=None, acc_slot=NO_SLOT, rows=None, stream=None):
+    """Both AC-GAN critic heads on the hidden rows H (gm_acgan_heads_fwd): critic mode on 2B stacked rows [x; G(z, y)],
+    generator mode on B generated rows; row m (and fake row B + m) has class lab[m] (ops.label_src).  Writes da2
+    [rows] and dq [rows, C]; loss_out[loss_slot] = the total loss, ce_out[ce_slot] = CE of rows [0, B), acc_out[acc_slot]
+    = the number of correctly classified real rows (critic mode)."""
+    import ctypes
+    from .ops import _check_labels
+    a = _acgan_args(H, w2, b2, Wc, bc, B, gen_mode, class_weight, da2, dq, ws, rows)
+    _check_labels(lab, B)
+    a.lab = lab
+    p = lambda t: t.data_ptr() if t is not None else None
+    a.loss_out, a.loss_slot, a.ce_out, a.ce_slot = p(loss_out), loss_slot, p(ce_out), ce_slot
+    a.acc_out, a.acc_slot = p(acc_out), acc_slot
+    _lib.call("gm_acgan_heads_fwd", stream or stream_ptr(), ctypes.byref(a))
+
+
+def acgan_heads_bwd(H, w2, b2, Wc, bc, B, gen_mode, da2, dq, dPre, ws, grads=None, adam=None, moments=None, rows=None,
+                    betas=(0.9, 0.999), eps=1e-8, stream=None):
+    """Both heads' backward (gm_acgan_heads_bwd): dPre = (da2 w2 + dq Wc) . [H > 0]; critic mode: grads = (gw2, gb2,
+    gWc, gbc) receive the heads' gradients, and with adam = dict(sched, sched_slot) and moments = (mw2, vw2, mb2, vb2,
+    mWc, vWc, mbc, vbc) Adam steps the four tensors in the same call."""
+    import ctypes
+    a = _acgan_args(H, w2, b2, Wc, bc, B, gen_mode, 0.0, da2, dq, ws, rows)
+    if dPre.dim() != 2 or dPre.shape[0] < a.rows or dPre.shape[1] != a.Hd:
+        raise _lib.GMError("acgan_heads_bwd: dPre must be [>= rows, Hd]")
+    a.dPre, a.ldp = dPre.data_ptr(), _ld(dPre)
+    if grads is not None:
+        for g, ref in zip(grads, (w2, b2, Wc, bc)):
+            if g.numel() != ref.numel() or not g.is_contiguous():
+                raise _lib.GMError("acgan_heads_bwd: a gradient output does not match its parameter")
+        a.gw2, a.gb2, a.gWc, a.gbc = (g.data_ptr() for g in grads)
+    if adam is not None:
+        a.mw2, a.vw2, a.mb2, a.vb2, a.mWc, a.vWc, a.mbc, a.vbc = (m.data_ptr() for m in moments)
+        a.sched, a.sched_slot = adam["sched"].data_ptr(), adam["sched_slot"]
+    a.beta1, a.beta2, a.eps = betas[0], betas[1], eps
+    _lib.call("gm_acgan_heads_bwd", stream or stream_ptr(), ctypes.byref(a))
+
+
 # ---- Bayesian GAN (csrc/gm_bgan.hip; bgan.py) ----------------------------------------------------------------------
 def bgan_stream_param(side, k, tensor):
     """The noise stream word of tensor `tensor` (0 linear.weight, 1 linear.bias, 2 second weight, 3 second bias) of

@@ -625,6 +625,51 @@ typedef struct gm_aae_gen_args {
  * ops_fused.aae_gen_mid. */
 int gm_aae_gen_mid(void* stream, const gm_aae_gen_args* a);
 
+/* ---- auxiliary-classifier GAN (NEW: Odena, Olah & Shlens, arXiv 1610.09585; generative_models_amd/acgan.py).  The
+ * critic D: x -> h = relu(W1 x + b1) (Hd) carries two heads on the same h: the source head sigmoid(w2 . h + b2) with
+ * ns_gan.py's loss, and a class head Wc h + bc (C logits) with a softmax cross-entropy against the row's label.
+ * Critic mode (gen_mode 0): rows = 2B stacked [x; G(z, y)], rows [0, B) real and [B, 2B) fake, fake row B + m has
+ * the class of row m;  loss = -mean(log(s_real + 1e-8) + log(1 - s_fake + 1e-8)) + class_weight (CE_real + CE_fake).
+ * Generator mode (gen_mode 1): rows = B generated rows;  loss = -mean(log(s + 1e-8)) + class_weight CE.
+ * Both CEs are means over B.  Row m's class comes through lab (gm_label_src) at row m mod B.
+ * Limits: 1 <= C <= 32, Hd % 4 == 0, 4 <= Hd <= 1024, rows >= 1; H, w2, Wc and ws 16-byte aligned, ldh % 4 == 0.
+ * Outside them, or with a NULL array, both entry points return GM_EINVAL before any launch.  No floating-point
+ * atomics: the same bits on every run, in a graph or not. */
+typedef struct gm_acgan_heads_args {
+    const float* H; int64_t ldh;              /* the critic's hidden rows [rows, Hd] (after relu) */
+    int rows, B, Hd, C, gen_mode;
+    float* w2; float* b2;                     /* D.discriminate [1, Hd], [1] */
+    float* Wc; float* bc;                     /* D.classify [C, Hd], [C] */
+    gm_label_src lab;                         /* forward: the batch's classes */
+    float class_weight;
+    float* da2;                               /* [rows] d loss / d source logit: out of fwd, in of bwd */
+    float* dq; int64_t lddq;                  /* [rows, C] class_weight (softmax - onehot) / B: out of fwd, in of bwd */
+    /* forward: the iteration's loss values (loss_out NULL: none are written) */
+    float* loss_out; gm_slot loss_slot;       /* the total above */
+    float* ce_out; gm_slot ce_slot;           /* CE of rows [0, B) (or NULL) */
+    float* acc_out; gm_slot acc_slot;         /* critic mode: how many real rows' first maximal logit is the label */
+    /* backward */
+    float* dPre; int64_t ldp;                 /* out [rows, Hd]: (da2 w2 + dq Wc) . [H > 0] */
+    float* gw2; float* gb2; float* gWc; float* gbc;      /* critic mode: gradient outputs (all four, or none) */
+    float* mw2; float* vw2; float* mb2; float* vb2;      /* Adam moments (with sched) */
+    float* mWc; float* vWc; float* mbc; float* vbc;
+    const float* sched; gm_slot sched_slot;   /* critic mode; NULL: gradients only, parameters untouched */
+    double beta1, beta2, eps;
+    float* ws; int64_t ws_bytes;              /* gm_acgan_heads_workspace_bytes(rows, Hd, C) bytes, zeroed once */
+} gm_acgan_heads_args;
+/* Bytes of the heads' workspace (shared by both directions), -1 for a shape outside the limits. */
+int64_t gm_acgan_heads_workspace_bytes(int rows, int Hd, int C);
+/* Both heads' forward and losses from one read of H, ONE launch: da2, dq and (loss_out given) the loss slots, the
+ * rows' terms added in a fixed order by the last workgroup to finish.  Called from acgan.ACGANEngine._issue and
+ * ops_fused.acgan_heads_fwd. */
+int gm_acgan_heads_fwd(void* stream, const gm_acgan_heads_args* a);
+/* Both heads' backward from one read of H: dPre in gm_head_bwd's place (consumed by gm_linear_bwd_dw_ex /
+ * gm_linear_bwd_dx_ex unchanged); in critic mode a second launch adds the row blocks' partial gw2 / gb2 / gWc / gbc
+ * in block order, writes them and steps Adam on the four tensors with sched[2 * slot .. +1].  Generator mode
+ * refuses gradient outputs and a schedule (the critic is frozen).  Called from acgan.ACGANEngine._issue and
+ * ops_fused.acgan_heads_bwd. */
+int gm_acgan_heads_bwd(void* stream, const gm_acgan_heads_args* a);
+
 /* ---- Bayesian GAN (NEW: the reference's src/bayes_gan.py is a docstring and a TODO; generative_models_amd/bgan.py,
  * DESIGN.md section 14).  A device-side counter-based generator, the SGHMC update and the critic ensemble's head.
  *

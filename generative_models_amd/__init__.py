@@ -82,8 +82,11 @@ def host_thread_plan():
 
 
 def __getattr__(name):
-    """PDWGAN / PDWGANTrainer / PDWGANEngine and IWAE / IWAETrainer / IWAEEngine, imported on first use (importing
-    the package stays free of torch)."""
+    """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine and SNGAN / SNGANTrainer / SNGANEngine,
+    imported on first use (importing the package stays free of torch)."""
+    if name in ("SNGAN", "SNGANTrainer", "SNGANEngine"):
+        from . import sngan
+        return getattr(sngan, name)
     if name in ("PDWGAN", "PDWGANTrainer", "PDWGANEngine"):
         from . import pdwgan
         return getattr(pdwgan, name)

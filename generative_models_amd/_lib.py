@@ -124,8 +124,8 @@ class CorruptArgs(ctypes.Structure):
 
 IWAE_TAG_TRAIN, IWAE_TAG_EVAL = 0x49574145, 0x49574556      # GM_IWAE_TAG_TRAIN / GM_IWAE_TAG_EVAL
 IWAE_MAX_K, IWAE_MAX_Z = 64, 32                             # GM_IWAE_MAX_K / GM_IWAE_MAX_Z
-# (gm_iwae_noise and gm_acgan_heads_args travel by pointer; their ctypes forms, IwaeNoise and ACGANHeadsArgs, live in
-# ops_fused beside their wrappers)
+# (gm_iwae_noise, gm_acgan_heads_args and the gm_sn_*_args travel by pointer; their ctypes forms, IwaeNoise,
+# ACGANHeadsArgs and SNPowerArgs / SNHeadArgs / SNGradArgs, live in ops_fused beside their wrappers)
 
 NOISE = {"salt_pepper": 1, "gaussian": 2}       # GM_NOISE_SALT_PEPPER, GM_NOISE_GAUSSIAN (GM_NOISE_NONE = 0)
 
@@ -328,6 +328,13 @@ _SIGNATURES = {
     "gm_acgan_heads_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "gm_acgan_heads_fwd": (c_int, [_P, _P]),
     "gm_acgan_heads_bwd": (c_int, [_P, _P]),
+    "gm_sn_power_workspace_bytes": (c_int64, [c_int, c_int]),
+    "gm_sn_power_iter": (c_int, [_P, _P]),
+    "gm_sn_head_workspace_bytes": (c_int64, [c_int, c_int]),
+    "gm_sn_head_fwd": (c_int, [_P, _P]),
+    "gm_sn_head_bwd": (c_int, [_P, _P]),
+    "gm_sn_grad_workspace_bytes": (c_int64, [c_int]),
+    "gm_sn_grad": (c_int, [_P, _P]),
     "gm_philox_raw": (c_int, [_P, _P, _P, _P, c_int64]),
     "gm_philox_normal": (c_int, [_P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_int, _P, c_int64, _P,
                                  c_int64]),

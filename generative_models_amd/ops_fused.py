@@ -402,6 +402,132 @@ def acgan_heads_bwd(H, w2, b2, Wc, bc, B, gen_mode, da2, dq, dPre, ws, grads=Non
     _lib.call("gm_acgan_heads_bwd", stream or stream_ptr(), ctypes.byref(a))
 
 
+# ---- spectrally normalised hinge GAN (csrc/gm_sn.hip; sngan.py) -----------------------------------------------------
+SN_MAX_H, SN_MAX_I = 1024, 8192                     # GM_SN_MAX_H / GM_SN_MAX_I
+SN_SIGMA, SN_NW2, SN_NT, SN_NR = 0, 1, 2, 3        # GM_SN_STAT_*
+
+
+class SNPowerArgs(ctypes.Structure):
+    """gm_sn_power_args (include/gm_hip.h): the power-iteration stage in front of a critic forward."""
+    _fields_ = [("W", ctypes.c_void_p), ("H", ctypes.c_int), ("I", ctypes.c_int), ("u", ctypes.c_void_p),
+                ("v", ctypes.c_void_p), ("Wbar", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("w2bar", ctypes.c_void_p),
+                ("stats", ctypes.c_void_p), ("update_u", ctypes.c_int), ("ws", ctypes.c_void_p),
+                ("ws_bytes", ctypes.c_int64)]
+
+
+class SNHeadArgs(ctypes.Structure):
+    """gm_sn_head_args (include/gm_hip.h): the hinge head on the normalised w2, forward and backward."""
+    _fields_ = [("H", ctypes.c_void_p), ("ldh", ctypes.c_int64), ("rows", ctypes.c_int), ("B", ctypes.c_int),
+                ("Hd", ctypes.c_int), ("gen_mode", ctypes.c_int), ("w2bar", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("s", ctypes.c_void_p), ("ds", ctypes.c_void_p), ("loss_out", ctypes.c_void_p), ("loss_slot", _lib.Slot),
+                ("dPre", ctypes.c_void_p), ("ldp", ctypes.c_int64), ("stats", ctypes.c_void_p), ("gw2", ctypes.c_void_p),
+                ("gb2", ctypes.c_void_p), ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_int64)]
+
+
+class SNGradArgs(ctypes.Structure):
+    """gm_sn_grad_args (include/gm_hip.h): d loss / d Wbar carried back to W."""
+    _fields_ = [("G", ctypes.c_void_p), ("Wbar", ctypes.c_void_p), ("H", ctypes.c_int), ("I", ctypes.c_int),
+                ("u", ctypes.c_void_p), ("v", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("gW", ctypes.c_void_p),
+                ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_int64)]
+
+
+def _sn_w_shape(H, I):
+    if not (4 <= H <= SN_MAX_H and H % 4 == 0 and 1 <= I <= SN_MAX_I):
+        raise _lib.GMError("the spectral-norm kernels take 4 <= H <= 1024 with H %% 4 == 0 and 1 <= I <= 8192 (got "
+                           "H=%d, I=%d); other shapes train on the general path" % (H, I))
+
+
+def _sn_ws(nbytes, device):
+    return torch.zeros((nbytes + 3) // 4, device=device)
+
+
+def sn_power_workspace(H, I, device):
+    _sn_w_shape(H, I)
+    return _sn_ws(_lib.load().gm_sn_power_workspace_bytes(H, I), device)
+
+
+def sn_head_workspace(rows, Hd, device):
+    """A zeroed workspace for sn_head_fwd / sn_head_bwd at this shape (float32 device tensor)."""
+    _sn_w_shape(Hd, 1)
+    if rows < 1:
+        raise _lib.GMError("sn head: rows must be >= 1")
+    return _sn_ws(_lib.load().gm_sn_head_workspace_bytes(rows, Hd), device)
+
+
+def sn_grad_workspace(H, device):
+    _sn_w_shape(H, 1)
+    return _sn_ws(_lib.load().gm_sn_grad_workspace_bytes(H), device)
+
+
+def sn_power_iter(W, u, v, Wbar, w2, w2bar, stats, ws, update_u=True, stream=None):
+    """One power-iteration step on W [H, I] (gm_sn_power_iter, three launches): v = normalize(W^T u), u' = normalize(W v),
+    sigma = u'^T W v; writes v [I], Wbar = W / sigma, w2bar = w2 / ||w2||, stats [4] = (sigma, ||w2||, ||W^T u||,
+    ||W v||) and, with update_u, u' over u.  update_u=False (eval mode): sigma = u^T W v with the stored u."""
+    H, I = W.shape
+    _sn_w_shape(H, I)
+    if (not (W.is_contiguous() and Wbar.is_contiguous()) or tuple(Wbar.shape) != (H, I) or u.numel() != H
+            or v.numel() != I or w2.numel() != H or w2bar.numel() != H or stats.numel() < 4):
+        raise _lib.GMError("sn_power_iter: W and Wbar must be contiguous [H, I], u, w2, w2bar [H], v [I], stats [4]")
+    a = SNPowerArgs()
+    a.W, a.H, a.I, a.u, a.v, a.Wbar = W.data_ptr(), H, I, u.data_ptr(), v.data_ptr(), Wbar.data_ptr()
+    a.w2, a.w2bar, a.stats, a.update_u = w2.data_ptr(), w2bar.data_ptr(), stats.data_ptr(), 1 if update_u else 0
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    _lib.call("gm_sn_power_iter", stream or stream_ptr(), ctypes.byref(a))
+
+
+def _sn_head_args(H, w2bar, B, gen_mode, ds, ws, rows):
+    Hd = w2bar.numel()
+    rows = (B if gen_mode else 2 * B) if rows is None else rows
+    _sn_w_shape(Hd, 1)
+    if H.dim() != 2 or H.shape[0] < rows or H.shape[1] != Hd or ds.numel() < rows or rows < 1:
+        raise _lib.GMError("sn head: H must be [>= rows, Hd], w2bar [Hd] and ds [>= rows]")
+    a = SNHeadArgs()
+    a.H, a.ldh, a.rows, a.B, a.Hd, a.gen_mode = H.data_ptr(), _ld(H), rows, B, Hd, 1 if gen_mode else 0
+    a.w2bar, a.ds = w2bar.data_ptr(), ds.data_ptr()
+    a.ws, a.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    return a
+
+
+def sn_head_fwd(H, w2bar, b2, B, gen_mode, s, ds, ws, loss_out=None, loss_slot=NO_SLOT, rows=None, stream=None):
+    """The hinge head on the hidden rows H (gm_sn_head_fwd): s = H w2bar + b2, ds = d loss / d s, and loss_out[loss_slot]
+    = mean relu(1 - s_real) + mean relu(1 + s_fake) on 2B stacked rows (critic mode) or -mean s on B rows."""
+    a = _sn_head_args(H, w2bar, B, gen_mode, ds, ws, rows)
+    if s.numel() < a.rows or b2.numel() != 1:
+        raise _lib.GMError("sn_head_fwd: s must be [>= rows] and b2 [1]")
+    a.b2, a.s = b2.data_ptr(), s.data_ptr()
+    if loss_out is not None:
+        a.loss_out, a.loss_slot = loss_out.data_ptr(), loss_slot
+    _lib.call("gm_sn_head_fwd", stream or stream_ptr(), ctypes.byref(a))
+
+
+def sn_head_bwd(H, w2bar, B, gen_mode, ds, dPre, ws, stats=None, grads=None, rows=None, stream=None):
+    """The head's backward (gm_sn_head_bwd): dPre = ds w2bar . [H > 0]; critic mode: grads = (gw2, gb2) receive d loss / d
+    w2 = (g - <g, w2bar> w2bar) / ||w2|| with g = sum ds h, and d loss / d b2 (stats: sn_power_iter's)."""
+    a = _sn_head_args(H, w2bar, B, gen_mode, ds, ws, rows)
+    if dPre.dim() != 2 or dPre.shape[0] < a.rows or dPre.shape[1] != a.Hd:
+        raise _lib.GMError("sn_head_bwd: dPre must be [>= rows, Hd]")
+    a.dPre, a.ldp = dPre.data_ptr(), _ld(dPre)
+    if grads is not None:
+        gw2, gb2 = grads
+        if gw2.numel() != a.Hd or gb2.numel() != 1 or not gw2.is_contiguous() or stats is None:
+            raise _lib.GMError("sn_head_bwd: grads must be (gw2 [Hd], gb2 [1]) with the power stage's stats")
+        a.gw2, a.gb2, a.stats = gw2.data_ptr(), gb2.data_ptr(), stats.data_ptr()
+    _lib.call("gm_sn_head_bwd", stream or stream_ptr(), ctypes.byref(a))
+
+
+def sn_grad(G, Wbar, u, v, stats, gW, ws, stream=None):
+    """gW = (G - <G, Wbar> u v^T) / sigma (gm_sn_grad, two launches): G = d loss / d Wbar, u / v / stats the forward's."""
+    H, I = Wbar.shape
+    _sn_w_shape(H, I)
+    if (tuple(G.shape) != (H, I) or gW.numel() != H * I or u.numel() != H or v.numel() != I
+            or not (G.is_contiguous() and Wbar.is_contiguous() and gW.is_contiguous())):
+        raise _lib.GMError("sn_grad: G, Wbar and gW must be contiguous [H, I], u [H], v [I]")
+    a = SNGradArgs()
+    a.G, a.Wbar, a.H, a.I, a.u, a.v = G.data_ptr(), Wbar.data_ptr(), H, I, u.data_ptr(), v.data_ptr()
+    a.stats, a.gW, a.ws, a.ws_bytes = stats.data_ptr(), gW.data_ptr(), ws.data_ptr(), ws.numel() * 4
+    _lib.call("gm_sn_grad", stream or stream_ptr(), ctypes.byref(a))
+
+
 # ---- Bayesian GAN (csrc/gm_bgan.hip; bgan.py) ----------------------------------------------------------------------
 def bgan_stream_param(side, k, tensor):
     """The noise stream word of tensor `tensor` (0 linear.weight, 1 linear.bias, 2 second weight, 3 second bias) of

@@ -152,10 +152,10 @@ class FlatAdam(torch.optim.Optimizer):
     handled by keeping one (flat, step) pair per "has grad" pattern is overkill here -- the
     reference never mixes patterns within one optimizer, so a None grad means "all None"."""
 
-    def __init__(self, params, lr, weight_decay=0.0, clamp=0.0):
+    def __init__(self, params, lr, weight_decay=0.0, clamp=0.0, betas=(0.9, 0.999)):
         params = [p for p in params if p.requires_grad]
         super().__init__(params, dict(lr=lr))
-        self.wd, self.clamp = weight_decay, clamp
+        self.wd, self.clamp, self.betas = weight_decay, clamp, (float(betas[0]), float(betas[1]))
         self._ps = params
         dev = params[0].device
         n = sum((p.numel() + 3) // 4 * 4 for p in params)
@@ -199,8 +199,8 @@ class FlatAdam(torch.optim.Optimizer):
             while j + 1 < n and active[j + 1] and self.steps[j + 1] == self.steps[i]:
                 j += 1
             lo, hi = self.offs[i], ends[j]
-            sched = torch.from_numpy(ops.adam_schedule(lr, 1, start=self.steps[i])).to(self.flat.device)
-            ops.adam(self.flat[lo:hi], self.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], sched,
+            sched = torch.from_numpy(ops.adam_schedule(lr, 1, betas=self.betas, start=self.steps[i])).to(self.flat.device)
+            ops.adam(self.flat[lo:hi], self.grad[lo:hi], self.m[lo:hi], self.v[lo:hi], sched, betas=self.betas,
                      weight_decay=self.wd, clamp=self.clamp)
             i = j + 1
         self.t = max(self.steps)

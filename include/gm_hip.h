@@ -670,6 +670,76 @@ int gm_acgan_heads_fwd(void* stream, const gm_acgan_heads_args* a);
  * ops_fused.acgan_heads_bwd. */
 int gm_acgan_heads_bwd(void* stream, const gm_acgan_heads_args* a);
 
+/* ---- spectrally normalised hinge GAN (NEW: Miyato et al., arXiv 1802.05957; the hinge loss and two-time-scale Adam of
+ * arXiv 1805.08318; generative_models_amd/sngan.py).  The critic D: x -> h = relu(Wbar x + b) -> s = w2bar . h + b2 with
+ * Wbar = W / sigma and w2bar = w2 / ||w2||; sigma comes from ONE power-iteration step on W [H, I] per forward:
+ *   v = W^T u / max(||W^T u||, 1e-12);  u' = W v / max(||W v||, 1e-12);  sigma = u'^T W v  (u', v constants of the backward).
+ * Limits of all gm_sn_* calls: H % 4 == 0, 4 <= H <= 1024 (the head's float4 lanes; u and W v held in LDS), 1 <= I <= 8192
+ * (W^T u, 32 KiB, held in one workgroup's LDS), rows >= 1; W, Wbar, G, gW contiguous [H, I]; H-row arrays and every
+ * workspace 16-byte aligned, ldh % 4 == 0.  Outside them, or with a NULL array, every entry point returns GM_EINVAL before
+ * any launch.  Sums are accumulated in fp64 in a fixed order; no floating-point atomics: the same bits on every run, in a
+ * graph or not.  Workgroups exchange data only across kernel boundaries (the loss slot's arrival counter excepted). */
+#define GM_SN_MAX_H 1024
+#define GM_SN_MAX_I 8192
+#define GM_SN_STAT_SIGMA 0      /* stats[4]: sigma, ||w2||, ||W^T u||, ||W v|| */
+#define GM_SN_STAT_NW2 1
+#define GM_SN_STAT_NT 2
+#define GM_SN_STAT_NR 3
+typedef struct gm_sn_power_args {
+    const float* W; int H, I;                 /* D.linear.weight [H, I] */
+    float* u;                                 /* [H] in; out (u') when update_u */
+    float* v;                                 /* [I] out */
+    float* Wbar;                              /* [H, I] out: W / sigma */
+    const float* w2; float* w2bar;            /* D.discriminate.weight [H] in, w2 / ||w2|| out */
+    float* stats;                             /* [4] out (GM_SN_STAT_*) */
+    int update_u;                             /* 0 (eval mode): sigma = u^T W v with the stored u, u is not written */
+    float* ws; int64_t ws_bytes;              /* gm_sn_power_workspace_bytes(H, I) */
+} gm_sn_power_args;
+int64_t gm_sn_power_workspace_bytes(int H, int I);      /* -1 for a shape outside the limits */
+/* The power-iteration stage, three launches: t = W^T u (a workgroup per 16 columns walks all rows); W v = W t / ||t|| (a
+ * wave per row, every workgroup re-derives ||t|| from t); then every workgroup re-derives ||W v||, u' and sigma and
+ * writes its 8 rows of Wbar, workgroup 0 also u (update_u), v, w2bar and stats.  Called from sngan.SNGANEngine._power and
+ * ops_fused.sn_power_iter. */
+int gm_sn_power_iter(void* stream, const gm_sn_power_args* a);
+
+typedef struct gm_sn_head_args {
+    const float* H; int64_t ldh;              /* the critic's hidden rows [rows, Hd] (after relu) */
+    int rows, B, Hd, gen_mode;                /* critic mode: rows = 2B stacked [x; G(z)]; generator mode: rows = B */
+    const float* w2bar; const float* b2;      /* the normalised head [Hd], D.discriminate.bias [1] */
+    float* s;                                 /* [rows] out of fwd: the logits */
+    float* ds;                                /* [rows] d loss / d logit: out of fwd, in of bwd */
+    float* loss_out; gm_slot loss_slot;       /* fwd: the hinge loss (or NULL) */
+    float* dPre; int64_t ldp;                 /* bwd out [rows, Hd]: ds w2bar . [H > 0] */
+    const float* stats;                       /* bwd, critic mode: the power stage's stats (||w2||) */
+    float* gw2; float* gb2;                   /* bwd, critic mode: d loss / d w2 [Hd] (projected), d loss / d b2 [1] */
+    float* ws; int64_t ws_bytes;              /* gm_sn_head_workspace_bytes(rows, Hd), zeroed once */
+} gm_sn_head_args;
+int64_t gm_sn_head_workspace_bytes(int rows, int Hd);   /* -1 for a shape outside the limits */
+/* One launch: per row s = w2bar . h + b2, the hinge term and ds -- critic mode -[1 - s > 0] / B on real rows [0, B) and
+ * +[1 + s > 0] / B on fake rows [B, 2B), loss = (sum relu(1 - s_real) + sum relu(1 + s_fake)) / B; generator mode
+ * ds = -1 / B, loss = -sum s / B.  The rows' terms are added in fp64 in a fixed order by the last workgroup to finish.
+ * Called from sngan.SNGANEngine._issue_D / _issue_G and ops_fused.sn_head_fwd. */
+int gm_sn_head_fwd(void* stream, const gm_sn_head_args* a);
+/* dPre in gm_head_bwd's place (consumed by gm_linear_bwd_dw / gm_linear_bwd_dx unchanged), one launch; in critic mode
+ * each workgroup also writes its 8 rows' partial g = sum ds h and gb2, and a second one-workgroup launch adds them in
+ * workgroup order and writes gw2 = (g - <g, w2bar> w2bar) / ||w2|| and gb2.  Generator mode refuses gw2 / gb2.  Called
+ * from sngan.SNGANEngine._issue_D / _issue_G and ops_fused.sn_head_bwd. */
+int gm_sn_head_bwd(void* stream, const gm_sn_head_args* a);
+
+typedef struct gm_sn_grad_args {
+    const float* G;                           /* d loss / d Wbar [H, I] (gm_linear_bwd_dw's output) */
+    const float* Wbar; int H, I;
+    const float* u; const float* v;           /* the forward's u' [H] and v [I] */
+    const float* stats;                       /* the power stage's stats (sigma) */
+    float* gW;                                /* out [H, I]: (G - <G, Wbar> u v^T) / sigma; may be G itself */
+    float* ws; int64_t ws_bytes;              /* gm_sn_grad_workspace_bytes(H) */
+} gm_sn_grad_args;
+int64_t gm_sn_grad_workspace_bytes(int H);              /* -1 for a shape outside the limits */
+/* The weight gradient's projection, two launches: per 8 rows a partial of c = <G, Wbar>; then every workgroup adds the
+ * partials in workgroup order and writes its rows of gW.  Called from sngan.SNGANEngine._issue_D and
+ * ops_fused.sn_grad. */
+int gm_sn_grad(void* stream, const gm_sn_grad_args* a);
+
 /* ---- Bayesian GAN (NEW: the reference's src/bayes_gan.py is a docstring and a TODO; generative_models_amd/bgan.py,
  * DESIGN.md section 14).  A device-side counter-based generator, the SGHMC update and the critic ensemble's head.
  *

@@ -82,8 +82,11 @@ def host_thread_plan():
 
 
 def __getattr__(name):
-    """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine and SNGAN / SNGANTrainer / SNGANEngine,
-    imported on first use (importing the package stays free of torch)."""
+    """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine, SNGAN / SNGANTrainer / SNGANEngine and
+    DDPM / DDPMTrainer / DDPMEngine, imported on first use (importing the package stays free of torch)."""
+    if name in ("DDPM", "DDPMTrainer", "DDPMEngine"):
+        from . import ddpm
+        return getattr(ddpm, name)
     if name in ("SNGAN", "SNGANTrainer", "SNGANEngine"):
         from . import sngan
         return getattr(sngan, name)

@@ -127,6 +127,10 @@ IWAE_MAX_K, IWAE_MAX_Z = 64, 32                             # GM_IWAE_MAX_K / GM
 # (gm_iwae_noise, gm_acgan_heads_args and the gm_sn_*_args travel by pointer; their ctypes forms, IwaeNoise,
 # ACGANHeadsArgs and SNPowerArgs / SNHeadArgs / SNGradArgs, live in ops_fused beside their wrappers)
 
+DDPM_TAG_T, DDPM_TAG_E, DDPM_TAG_V, DDPM_TAG_VE, DDPM_TAG_S = 0x44445054, 0x4444504D, 0x44445056, 0x44445057, 0x44445053
+DDPM_MAX_I, DDPM_MIN_E, DDPM_MAX_E, DDPM_MAX_T = 8192, 4, 128, 4096      # GM_DDPM_* (include/gm_hip.h)
+# (gm_ddpm_noise / _tables / _out / _reverse_args travel by pointer; their ctypes forms live in ops_fused)
+
 NOISE = {"salt_pepper": 1, "gaussian": 2}       # GM_NOISE_SALT_PEPPER, GM_NOISE_GAUSSIAN (GM_NOISE_NONE = 0)
 
 
@@ -356,6 +360,12 @@ _SIGNATURES = {
     "gm_iwae_weights": (c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int]),
     "gm_iwae_reduce": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, c_int,
                                c_int, c_int]),
+    "gm_ddpm_qsample": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int]),
+    "gm_gather_rows_qsample": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
+    "gm_gather_rows_bits_qsample": (c_int, [_P, _P, _P, _P, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
+    "gm_ddpm_loss": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_float, c_int, c_int]),
+    "gm_ddpm_reverse": (c_int, [_P, _P]),
+    "gm_ddpm_prior": (c_int, [_P, _P, c_int64, _P, ctypes.c_uint64, c_int64, c_int, _P, c_int, c_int, c_int, c_int]),
 }
 
 _lib = None

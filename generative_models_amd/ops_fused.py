@@ -810,3 +810,157 @@ def iwae_normals(n_images, k, Z, seed, step, tag, device="cuda"):
             iwae_sample(ml[:, :2 * zc], z, lp, iwae_noise(seed, tag, k, j0=j0, step=step, q0=c0 // 4), n_images, kc, zc)
             out[:, j0:j0 + kc, c0:c0 + zc] = z.view(n_images, kc, zc)
     return out.view(n_images * k, Z)
+
+
+# ---- Denoising diffusion (csrc/gm_ddpm.hip, gm_ddpm.h; ddpm.py) ----------------------------------------------------
+class DdpmNoise(ctypes.Structure):
+    """gm_ddpm_noise (include/gm_hip.h): seed, the two tags, the step and the first row's batch position."""
+    _fields_ = [("seed", ctypes.c_uint64), ("tag_t", ctypes.c_uint32), ("tag_e", ctypes.c_uint32),
+                ("step_ctr", ctypes.c_void_p), ("step_base", ctypes.c_void_p), ("step_add", ctypes.c_int64),
+                ("row0", ctypes.c_int64)]
+
+
+class DdpmTables(ctypes.Structure):
+    """gm_ddpm_tables (include/gm_hip.h): the schedule and embedding tables on the device."""
+    _fields_ = [("sa", ctypes.c_void_p), ("s1", ctypes.c_void_p), ("temb", ctypes.c_void_p), ("T", ctypes.c_int),
+                ("E", ctypes.c_int)]
+
+
+class DdpmOut(ctypes.Structure):
+    """gm_ddpm_out (include/gm_hip.h): where a q-sample writes."""
+    _fields_ = [("xin", ctypes.c_void_p), ("ldin", ctypes.c_int64), ("eps", ctypes.c_void_p), ("lde", ctypes.c_int64),
+                ("t", ctypes.c_void_p)]
+
+
+class DdpmReverseArgs(ctypes.Structure):
+    """gm_ddpm_reverse_args (include/gm_hip.h): one sampler step."""
+    _fields_ = [("xin", ctypes.c_void_p), ("ldin", ctypes.c_int64), ("eps", ctypes.c_void_p), ("lde", ctypes.c_int64),
+                ("coef", ctypes.c_void_p), ("slot", _lib.Slot), ("temb", ctypes.c_void_p), ("traj", ctypes.c_void_p),
+                ("traj_stride", ctypes.c_int64), ("seed", ctypes.c_uint64), ("tick", ctypes.c_void_p),
+                ("done", ctypes.c_void_p), ("rows", ctypes.c_int), ("I", ctypes.c_int), ("E", ctypes.c_int),
+                ("T", ctypes.c_int), ("S", ctypes.c_int), ("clip", ctypes.c_int)]
+
+
+def ddpm_noise(seed, train=True, step=0, step_ctr=None, step_base=None, row0=0):
+    """A gm_ddpm_noise block: the training stream (tags DDPT / DDPM) or the validation one (DDPV / DDPW) at step =
+    *step_ctr + *step_base + step (int64 device tensors, or None for 0).  The tensors must outlive every launch (and
+    every captured graph) that reads them."""
+    for t, nm in ((step_ctr, "step_ctr"), (step_base, "step_base")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int64):
+            raise _lib.GMError("ddpm_noise: %s must be an int64 device tensor" % nm)
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise _lib.GMError("ddpm_noise: seed must lie in [0, 2^64)")
+    tags = (_lib.DDPM_TAG_T, _lib.DDPM_TAG_E) if train else (_lib.DDPM_TAG_V, _lib.DDPM_TAG_VE)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    return DdpmNoise(seed, tags[0], tags[1], ptr(step_ctr), ptr(step_base), int(step), int(row0))
+
+
+def ddpm_tables(sa, s1, temb):
+    """A gm_ddpm_tables block over the model's fp32 device buffers sa [T], s1 [T], temb [T, E]."""
+    for t, nm in ((sa, "sa"), (s1, "s1"), (temb, "temb")):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise _lib.GMError("ddpm_tables: %s must be a contiguous float32 device tensor" % nm)
+    T, E = temb.shape
+    if sa.numel() != T or s1.numel() != T:
+        raise _lib.GMError("ddpm_tables: sa and s1 hold one float per timestep")
+    tab = DdpmTables(sa.data_ptr(), s1.data_ptr(), temb.data_ptr(), T, E)
+    tab.keep = (sa, s1, temb)
+    return tab
+
+
+def _ddpm_out(xin, eps, t, rows, I, E):
+    if _rows2d(xin, "xin").shape[0] < rows or xin.shape[1] < I + E or _rows2d(eps, "eps").shape[0] < rows \
+            or eps.shape[1] < I or (t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+                                                           and t.numel() >= rows)):
+        raise _lib.GMError("ddpm q-sample: xin %s / eps %s / t do not fit %d rows of %d + %d"
+                           % (tuple(xin.shape), tuple(eps.shape), rows, I, E))
+    return DdpmOut(xin.data_ptr(), _ld(xin), eps.data_ptr(), _ld(eps), t.data_ptr() if t is not None else None)
+
+
+def ddpm_qsample(x, noise, tables, xin=None, eps=None, t=None, stream=None):
+    """(xin, eps, t) of the image rows x [n, I] in [0, 1] (gm_ddpm_qsample): xin [n, I + E] = [x_t | temb[t]], eps
+    [n, I] the noise, t [n] int32.  Missing outputs are allocated."""
+    n, I = _rows2d(x, "x").shape
+    E = tables.E
+    xin = torch.empty(n, I + E, device=x.device) if xin is None else xin
+    eps = torch.empty(n, I, device=x.device) if eps is None else eps
+    t = torch.empty(n, dtype=torch.int32, device=x.device) if t is None else t
+    if n:
+        o = _ddpm_out(xin, eps, t, n, I, E)
+        _lib.call("gm_ddpm_qsample", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(tables), ctypes.byref(o),
+                  x.data_ptr(), x.stride(0), n, I)
+    return xin, eps, t
+
+
+def gather_rows_qsample(data, idx, out, xin, eps, t, noise, tables, B=None, idx_slot=NO_SLOT, stream=None):
+    """ops.gather_rows(data, idx, out) and the q-sample of every gathered row in one launch
+    (gm_gather_rows[_bits]_qsample)."""
+    from .ops import PackedData
+    n_rows, row = data.shape
+    B = out.shape[0] if B is None else B
+    if not (idx.dtype == torch.int64 and idx.is_cuda):
+        raise _lib.GMError("gather_rows_qsample: idx must be an int64 device tensor")
+    if _rows2d(out, "out").shape[0] < B or out.shape[1] < row:
+        raise _lib.GMError("gather_rows_qsample: out %s does not fit %d rows of %d" % (tuple(out.shape), B, row))
+    o = _ddpm_out(xin, eps, t, B, row, tables.E)
+    if isinstance(data, PackedData):
+        _lib.call("gm_gather_rows_bits_qsample", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(tables),
+                  ctypes.byref(o), data.data_ptr(), data.wpr, n_rows, idx.data_ptr(), idx_slot, out.data_ptr(),
+                  _ld(out), B, row)
+    else:
+        _lib.call("gm_gather_rows_qsample", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(tables),
+                  ctypes.byref(o), _rows2d(data, "data").data_ptr(), n_rows, idx.data_ptr(), idx_slot, out.data_ptr(),
+                  _ld(out), B, row)
+    return out
+
+
+def ddpm_loss(out, eps, part, B, scale, dA=None, stream=None):
+    """part[b] = sum_e (out - eps)^2 of row b and, with dA, dA = 2 scale (out - eps) (gm_ddpm_loss)."""
+    I = out.shape[1]
+    if _rows2d(out, "out").shape[0] < B or _rows2d(eps, "eps").shape[0] < B or eps.shape[1] < I or part.numel() < B \
+            or not part.is_contiguous() or (dA is not None and (_rows2d(dA, "dA").shape[0] < B or dA.shape[1] != I)):
+        raise _lib.GMError("ddpm_loss: the arrays do not fit B=%d, I=%d" % (B, I))
+    _lib.call("gm_ddpm_loss", stream or stream_ptr(), out.data_ptr(), _ld(out), eps.data_ptr(), _ld(eps),
+              dA.data_ptr() if dA is not None else None, _ld(dA) if dA is not None else 0, part.data_ptr(), scale, B, I)
+
+
+def ddpm_reverse(xin, eps, coef, temb, I, seed, clip=True, slot=None, step=0, traj=None, tick=None, done=None,
+                 rows=None, stream=None):
+    """One sampler step in place on xin [n, >= I + E] with the denoiser's output eps [n, I] (gm_ddpm_reverse): the
+    coefficients are row `slot` (a gm_slot of stride 8 over a device counter) or row `step` of coef [S, 8]; traj
+    [S + 1, n, I] takes x_prev at index step + 1; tick (with done, one zeroed int32) is advanced by the launch."""
+    T, E = temb.shape
+    S = coef.shape[0]
+    rows = xin.shape[0] if rows is None else rows
+    if _rows2d(xin, "xin").shape[0] < rows or xin.shape[1] < I + E or _rows2d(eps, "eps").shape[0] < rows \
+            or eps.shape[1] < I or tuple(coef.shape) != (S, 8) or not coef.is_contiguous() or not temb.is_contiguous():
+        raise _lib.GMError("ddpm_reverse: xin %s / eps %s / coef %s do not fit %d rows of %d + %d"
+                           % (tuple(xin.shape), tuple(eps.shape), tuple(coef.shape), rows, I, E))
+    if traj is not None and not (traj.is_contiguous() and tuple(traj.shape) == (S + 1, rows, I)):
+        raise _lib.GMError("ddpm_reverse: traj must be a contiguous [%d, %d, %d] tensor" % (S + 1, rows, I))
+    if done is not None and not (done.dtype == torch.int32 and done.is_cuda):
+        raise _lib.GMError("ddpm_reverse: done must be an int32 device tensor")
+    a = DdpmReverseArgs()
+    a.xin, a.ldin, a.eps, a.lde = xin.data_ptr(), _ld(xin), eps.data_ptr(), _ld(eps)
+    a.coef, a.slot, a.temb = coef.data_ptr(), (slot if slot is not None else _lib.slot(0, 0, int(step), 0, 8)), \
+        temb.data_ptr()
+    if traj is not None:
+        a.traj, a.traj_stride = traj.data_ptr(), rows * I
+    a.seed = int(seed)
+    a.tick = tick.data_ptr() if tick is not None else None
+    a.done = done.data_ptr() if done is not None else None
+    a.rows, a.I, a.E, a.T, a.S, a.clip = rows, I, E, T, S, 1 if clip else 0
+    _lib.call("gm_ddpm_reverse", stream or stream_ptr(), ctypes.byref(a))
+
+
+def ddpm_prior(xin, temb, I, seed, step, t, traj=None, rows=None, stream=None):
+    """xin[:, :I] = the sampler's starting normals (counter step `step`), tails temb[t] (gm_ddpm_prior); traj [n, I]
+    takes the same rows."""
+    T, E = temb.shape
+    rows = xin.shape[0] if rows is None else rows
+    if _rows2d(xin, "xin").shape[0] < rows or xin.shape[1] < I + E or not temb.is_contiguous() \
+            or (traj is not None and not (traj.is_contiguous() and traj.numel() >= rows * I)):
+        raise _lib.GMError("ddpm_prior: xin %s does not fit %d rows of %d + %d" % (tuple(xin.shape), rows, I, E))
+    _lib.call("gm_ddpm_prior", stream or stream_ptr(), xin.data_ptr(), _ld(xin), temb.data_ptr(), int(seed), int(step),
+              int(t), traj.data_ptr() if traj is not None else None, rows, I, E, T)

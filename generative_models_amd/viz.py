@@ -161,3 +161,14 @@ def vae_viz_loss(trainer, second="kl_loss"):
         plt.legend(["Reconstruction"])
     plt.title(trainer.name)
     plt.show()
+
+
+def ddpm_sample_images(trainer, epoch=-100, num_images=36, save=True, outdir=None, steps=None):
+    """A grid of trainer.sample(num_images, seed=max(epoch, 0), steps) -- drawn on the device from the sampler's own
+    counter stream, so the global CPU generator stays where it is -- written as ../viz/<name>/sample_<epoch>.png."""
+    sample = trainer.sample(num_images, seed=max(int(epoch), 0), steps=steps)
+    images = _to_host_images(sample, trainer.model.shape)
+    if save:
+        write_png_gray(os.path.join(_outdir(trainer, outdir), "sample_%d.png" % epoch),
+                       make_grid(images, int(num_images ** 0.5)))
+    return images

@@ -1007,6 +1007,84 @@ int gm_iwae_reduce(void* stream, const gm_iwae_noise* n, const float* ml, int64_
                    const float* dzdec, int64_t lddz, float* dml, int64_t lddml, float* dZ, int64_t lddZ, int B, int k,
                    int Z);
 
+/* ---- Denoising diffusion (csrc/gm_ddpm.hip, gm_ddpm.h; ddpm.py holds the contract).  One
+ * 256-thread workgroup per row, fixed reduction orders, no floating-point atomics.  Noise: Philox4x32-10 with key
+ * (seed mod 2^32, seed >> 32); batch row `row` = row0 + the row's position in the call, step = (step_ctr ? *step_ctr :
+ * 0) + (step_base ? *step_base : 0) + step_add truncated to 32 bits.
+ *   timestep: word 0 of counter (0, step, row, tag_t), t = mulhi(word, T);
+ *   noise of pixels 4q .. 4q + 3: counter (q, step, row, tag_e) through gm_philox_normal's Box-Muller mapping;
+ *   x_t = fmaf(s1[t], n, sa[t] * fmaf(2, x, -1)) for an image pixel x in [0, 1].
+ * Training draws under (GM_DDPM_TAG_T, GM_DDPM_TAG_E), validation under (GM_DDPM_TAG_V, GM_DDPM_TAG_VE), the sampler's
+ * z under GM_DDPM_TAG_S with counter (q, sampler step, sample row, GM_DDPM_TAG_S).
+ * Limits: 1 <= I <= 8192, 4 <= E <= 128 with E % 4 == 0, 2 <= T <= 4096; outside them, or with a NULL array, every
+ * entry point returns GM_EINVAL before any launch.  Rows that are not 16-byte aligned multiples of 4 floats take an
+ * element-by-element path in the same kernels. */
+#define GM_DDPM_TAG_T 0x44445054u              /* "DDPT" */
+#define GM_DDPM_TAG_E 0x4444504Du              /* "DDPM" */
+#define GM_DDPM_TAG_V 0x44445056u              /* "DDPV" */
+#define GM_DDPM_TAG_VE 0x44445057u             /* "DDPW" */
+#define GM_DDPM_TAG_S 0x44445053u              /* "DDPS" */
+#define GM_DDPM_MAX_I 8192
+#define GM_DDPM_MIN_E 4
+#define GM_DDPM_MAX_E 128
+#define GM_DDPM_MAX_T 4096
+typedef struct gm_ddpm_noise {
+    uint64_t seed;
+    uint32_t tag_t, tag_e;                    /* the fourth counter word of the timestep draw and of the noise draw */
+    const int64_t* step_ctr;                  /* device counter or NULL */
+    const int64_t* step_base;                 /* device base or NULL */
+    int64_t step_add;
+    int64_t row0;                             /* batch position of the first row (>= 0) */
+} gm_ddpm_noise;
+typedef struct gm_ddpm_tables {               /* fp32 device tables, built on the host in fp64 and rounded once */
+    const float* sa; const float* s1;         /* [T]: sqrt(alpha_bar_t), sqrt(1 - alpha_bar_t) */
+    const float* temb;                        /* [T, E]: the sinusoidal embedding of t */
+    int T, E;
+} gm_ddpm_tables;
+typedef struct gm_ddpm_out {
+    float* xin; int64_t ldin;                 /* [rows, >= I + E]: row = [x_t | temb[t]], the denoiser's input */
+    float* eps; int64_t lde;                  /* [rows, >= I]: the noise */
+    int32_t* t;                               /* [rows]: the timestep (may be NULL) */
+} gm_ddpm_out;
+/* The forward process of `rows` image rows x (ldx floats apart). */
+int gm_ddpm_qsample(void* stream, const gm_ddpm_noise* n, const gm_ddpm_tables* s, const gm_ddpm_out* o,
+                    const float* x, int64_t ldx, int64_t rows, int I);
+/* gm_gather_rows / gm_gather_rows_bits and the forward process of every gathered row in one launch: out is exactly what
+ * the plain gather writes, o what gm_ddpm_qsample writes for those rows (o's arrays are none of data, out). */
+int gm_gather_rows_qsample(void* stream, const gm_ddpm_noise* n, const gm_ddpm_tables* s, const gm_ddpm_out* o,
+                           const float* data, int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out,
+                           int64_t ld_out, int B, int row_elems);
+int gm_gather_rows_bits_qsample(void* stream, const gm_ddpm_noise* n, const gm_ddpm_tables* s, const gm_ddpm_out* o,
+                                const uint32_t* bits, int words_per_row, int64_t n_rows, const int64_t* idx,
+                                gm_slot idx_slot, float* out, int64_t ld_out, int B, int row_elems);
+/* L_simple (Ho et al., arXiv 2006.11239 eq. 14) of one batch: part[b] = sum_e (out - eps)^2 of row b (fp32, fixed
+ * order; gm_sum_finalize* scales and adds them up) and, when dA is not NULL, dA = (2 scale) (out - eps) -- with scale =
+ * 1 / (B I) the gradient of the batch's mean squared error. */
+int gm_ddpm_loss(void* stream, const float* out, int64_t ldo, const float* eps, int64_t lde, float* dA, int64_t lda,
+                 float* part, float scale, int B, int I);
+/* One sampler step in place on xin, generalised form of Song et al., arXiv 2010.02502 eq. 12, with the coefficients of
+ * row s = slot's index of the table coef [S, 8] = (s1_t, sa_t, sa_prev, dir, sigma, t_next, t, 0):
+ *   x0 = (x_t - s1_t eps) / sa_t (clamped to [-1, 1] when clip);  eps' = (x_t - sa_t x0) / s1_t;
+ *   x_prev = sa_prev x0 + dir eps' + sigma z,  z from counter (q, s, row, GM_DDPM_TAG_S); sigma == 0 draws nothing.
+ * temb[t_next] goes into the rows' tails (t_next < 0: the tail stays).  traj (may be NULL): x_prev also to traj +
+ * (s + 1) traj_stride, rows I floats apart.  done (may be NULL): one zero-initialised unsigned int the launch counts its
+ * workgroups on and re-arms; the last workgroup to arrive advances tick (may be NULL; needs done). */
+typedef struct gm_ddpm_reverse_args {
+    float* xin; int64_t ldin;
+    const float* eps; int64_t lde;            /* the denoiser's output [rows, >= I] */
+    const float* coef; gm_slot slot;          /* slot.stride == 8 */
+    const float* temb;
+    float* traj; int64_t traj_stride;
+    uint64_t seed;
+    int64_t* tick; unsigned int* done;
+    int rows, I, E, T, S, clip;
+} gm_ddpm_reverse_args;
+int gm_ddpm_reverse(void* stream, const gm_ddpm_reverse_args* a);
+/* The sampler's start: xin[:, :I] = z from counter (q, step, row, GM_DDPM_TAG_S), tails temb[t]; traj (may be NULL)
+ * takes the same rows, I floats apart. */
+int gm_ddpm_prior(void* stream, float* xin, int64_t ldin, const float* temb, uint64_t seed, int64_t step, int t,
+                  float* traj, int rows, int I, int E, int T);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

@@ -30,7 +30,8 @@ from ._lib import GMError, slot
 from .trainers import (EPS, FlatAdam, GANTrainer, _dataset_rows, _lin, _parzen, _save_checkpoint, _stock_module, stock,
                        stock_model, to_cuda)
 from .cvae import LabelError, _labels_arg, _layer
-from .engine import FlatParams, _Linear, draw_sampler_indices, validate_labels
+from .engine import FlatParams, _Linear, validate_labels
+from .ring_engine import TwoAdamRingEngine, reference_loader_ok
 
 HISTORY = ("Glosses", "Dlosses", "class_losses", "num_epochs")
 MAX_C, MAX_H = 32, 1024
@@ -98,7 +99,7 @@ def acgan_fused_ok(model):
             and G.label.bias is None and tuple(G.generate.weight.shape) == (I, H))
 
 
-class ACGANEngine:
+class ACGANEngine(TwoAdamRingEngine):
     """The fused path.  Batch rows and both steps' noise come from the sampler / randn protocol replayed on the host
     (draw_sampler_indices, normal_ on the global generator) into rings of `graph_iters` iterations, uploaded per chunk;
     whole iterations are captured as hipGraphs of `graph_iters` iterations (and of 1 for the tail), each launch reading
@@ -110,7 +111,6 @@ class ACGANEngine:
     through D.linear (sigmoid epilogue) and through G.generate (relu epilogue); G's paired weight gradients + Adam;
     gm_label_grad_adam for G.label; the tick.  One GPU only."""
 
-    graph_iters = 16
     fused_ok = staticmethod(acgan_fused_ok)
 
     def __init__(self, model, data, labels, B, device, use_graph=True, world_size=1):
@@ -139,8 +139,6 @@ class ACGANEngine:
         self.ws = ops_fused.acgan_heads_workspace(2 * B, H, C, device)
         self.ctr = torch.zeros(2, dtype=torch.int64, device=device)      # D steps, G steps of this train() call
         self.inv_b = float(np.float32(1.0) / np.float32(B))
-        self.graphs, self._graph_key = {}, None
-        self.steps_planned = None
 
     # ---- one iteration's launches -------------------------------------------------------------------------------
     def _heads(self):
@@ -189,137 +187,21 @@ class ACGANEngine:
                             adam=adam, stream=s)
         ops.tick(self.ctr[1:2], stream=s)
 
-    def _issue(self, s, i):
-        """Iteration i of a chunk."""
-        d = self.D_steps
-        for j in range(d):
-            self._issue_D(s, i * d + j)
-        self._issue_G(s, i, i * d + d - 1)
-
     launches_per_iteration = staticmethod(lambda D_steps=1: 10 * D_steps + 10)
 
-    # ---- run settings, host draws, replay ----------------------------------------------------------------------
-    def configure(self, n_iters, G_lr, D_lr, D_steps, class_weight, resume=None):
-        """Once per train(): fresh Adam state (the reference's optimizers are locals of train()), schedules, loss
-        buffers, rings.  resume: a checkpoint's optim_state() -- moments restored, schedules continued."""
-        dev, B, Z = self.dev, self.B, self.Z
-        self.D_steps, self.class_weight = int(D_steps), float(class_weight)
-        self.run_config = {"B": int(B), "D_steps": int(D_steps), "G_lr": float(G_lr), "D_lr": float(D_lr),
-                           "class_weight": float(class_weight)}
-        self.step0 = {"G": 0, "D": 0}
-        for fp in (self.fG, self.fD):
-            fp.rebind(); fp.reset_state(); fp.grad.zero_()
-        if resume is not None:
-            saved = resume.get("config")
-            if saved is not None and not resume.get("lenient", False):
-                diff = {k: (saved[k], v) for k, v in self.run_config.items() if k in saved and saved[k] != v}
-                if diff:
-                    raise GMError("checkpoint was written by a run with different settings (saved, now): %s -- "
-                                  "load_checkpoint(path, strict=False) overrides" % diff)
-            for net, fp in (("G", self.fG), ("D", self.fD)):
-                st = resume[net]
-                if st["m"].numel() != fp.m.numel():
-                    raise GMError("checkpoint optimizer state does not match this model")
-                fp.m.copy_(st["m"]); fp.v.copy_(st["v"])
-                self.step0[net] = int(st["step"])
-        nD, nG = max(1, n_iters * self.D_steps), max(1, n_iters)
-        self.steps_planned = {"G": n_iters, "D": n_iters * self.D_steps}
-        sched = lambda lr, n, net: torch.from_numpy(ops.adam_schedule(lr, n, start=self.step0[net] + 1)).to(dev)
-        self.schedD, self.schedG = sched(D_lr, nD, "D"), sched(G_lr, nG, "G")
-        self.dloss, self.closs, self.dacc = (torch.zeros(nD, device=dev) for _ in range(3))
-        self.gloss = torch.zeros(nG, device=dev)
-        self.ctr.zero_()
-        K = max(1, self.graph_iters)
-        R = K * self.D_steps
-        self.idx = torch.zeros(R, B, dtype=torch.int64, device=dev)
-        self.zD, self.zG = torch.zeros(R, B, Z, device=dev), torch.zeros(K, B, Z, device=dev)
-        self.host = [(torch.zeros(R, B, dtype=torch.int64).pin_memory(), torch.zeros(R, B, Z).pin_memory(),
-                      torch.zeros(K, B, Z).pin_memory()) for _ in range(2)]
-        self.host_ev, self.buf = [None, None], 0
-        self.graphs = {}                               # (the buffers above are this call's: captured addresses)
-        self.done = 0
+    # ---- run settings, losses -----------------------------------------------------------------------------------
+    d_step_losses = ("closs", "dacc")
 
-    def optim_state(self):
-        torch.cuda.synchronize()
-        cpu = lambda t: t.detach().cpu().clone()
-        st = {net: {"m": cpu(fp.m), "v": cpu(fp.v), "step": self.step0[net] + self.steps_planned[net]}
-              for net, fp in (("G", self.fG), ("D", self.fD))}
-        st["config"] = dict(self.run_config)
-        return st
-
-    def _host_draws(self, k):
-        """The global generator's draws of k iterations in NSGANTrainer's order: per critic step the sampler's
-        (draw_sampler_indices) and compute_noise's randn(B, Z), then the generator step's randn(B, Z)."""
-        b = self.buf
-        if self.host_ev[b] is not None:
-            self.host_ev[b].synchronize()              # the copies that last read these pinned buffers have finished
-        hi, hd, hg = self.host[b]
-        n, d = self.data.shape[0], self.D_steps
-        for i in range(k):
-            for j in range(d):
-                draw_sampler_indices(n, self.B, hi[i * d + j].numpy())
-                hd[i * d + j].normal_()
-            hg[i].normal_()
-        self.idx[:k * d].copy_(hi[:k * d], non_blocking=True)
-        self.zD[:k * d].copy_(hd[:k * d], non_blocking=True)
-        self.zG[:k].copy_(hg[:k], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.host_ev[b] = ev
-        self.buf = 1 - b
-
-    def _graph(self, k):
-        g = self.graphs.get(k)
-        if g is None:
-            def body(s):
-                for i in range(k):
-                    self._issue(s, i)
-            g = self.graphs[k] = ops.Graph().capture(body)
-        return g
-
-    def run(self, n_iters):
-        done, K = 0, max(1, self.graph_iters)
-        while done < n_iters:
-            k = K if n_iters - done >= K else 1
-            self._host_draws(k)
-            if self.use_graph:
-                self._graph(k).launch()
-            else:
-                s = ops.stream_ptr()
-                for i in range(k):
-                    self._issue(s, i)
-            done += k
-        self.done += n_iters
+    def _configure_extra(self, class_weight):
+        self.class_weight = float(class_weight)
+        return {"class_weight": self.class_weight}
 
     def losses(self, it0, it1):
         """(G losses, D losses, class losses) of iterations [it0, it1) of this train() call: the totals, D's as the
-        mean over the iteration's critic steps, and CE(c(x), y) of its last critic step (one read-back)."""
-        d = self.D_steps
-        dl, cl = self.dloss.cpu().numpy(), self.closs.cpu().numpy()
-        gl = self.gloss.cpu().numpy()
-        G = [float(gl[it]) for it in range(it0, it1)]
-        D = [np.mean([float(dl[it * d + j]) for j in range(d)]) for it in range(it0, it1)]
-        Cl = [float(cl[it * d + d - 1]) for it in range(it0, it1)]
-        return G, D, Cl
-
-    def phase_grads(self):
-        """The last critic step's and the last generator step's gradients: {"d": 6 tensors, "g": 5}, keyed by the
-        model's state_dict names (views of the flat gradient buffers)."""
-        names = {id(p): n for n, p in self.model.named_parameters()}
-        out = {"d": {}, "g": {}}
-        for key, fp in (("d", self.fD), ("g", self.fG)):
-            for p, gv in zip(fp.params, fp.gviews):
-                out[key][names[id(p)]] = gv
-        return out
-
-
-def _loader_ok(it):
-    return bool(isinstance(it, torch.utils.data.DataLoader)
-                and isinstance(it.dataset, torch.utils.data.TensorDataset) and len(it.dataset.tensors) >= 2
-                and isinstance(it.sampler, torch.utils.data.RandomSampler)
-                and it.sampler.generator is None and it.generator is None
-                and not it.sampler.replacement and it.num_workers == 0
-                and it.batch_size is not None and it.batch_size <= len(it.dataset))
+        mean over the iteration's critic steps, and CE(c(x), y) of its last critic step."""
+        G, D = super().losses(it0, it1)
+        d, cl = self.D_steps, self.closs.cpu().numpy()
+        return G, D, [float(cl[it * d + d - 1]) for it in range(it0, it1)]
 
 
 @stock
@@ -358,18 +240,16 @@ class ACGANTrainer(GANTrainer):
 
     # ---- path selection ---------------------------------------------------------------------------------------
     def _stock(self):
-        if not all(self._hook_is_stock(n) for n in self._STOCK):
+        if not self._stock_prefix():
             return False
         m = self.model
-        if not type(m).__dict__.get("_gm_stock_model", False):
-            return False                               # a subclass may have changed the model
         G, D = getattr(m, "G", None), getattr(m, "D", None)
         if not (type(G) is Generator and type(D) is Discriminator and _stock_module(G, 3) and _stock_module(D, 3)
                 and G.label.bias is None):
             return False                               # edited / subclassed networks: general path
         if not acgan_fused_ok(m):
             return False                               # outside the fused heads' limits: general path
-        return _loader_ok(self.train_iter)
+        return reference_loader_ok(self.train_iter, labelled=True)
 
     def _device_labels(self, loader):
         """The dataset's classes as an int32 device tensor, validated on the host once per dataset."""
@@ -380,18 +260,9 @@ class ACGANTrainer(GANTrainer):
             cache[key] = y if not torch.cuda.is_available() else y.to(next(self.model.parameters()).device)
         return cache[key]
 
-    def _get_engine(self):
-        it = self.train_iter
-        key = (id(it.dataset), it.batch_size)
-        if self._engine is None or self._engine_key != key:
-            dev = next(self.model.parameters()).device
-            imgs = it.dataset.tensors[0]
-            data = imgs.reshape(imgs.shape[0], -1).to(dev, torch.float32).contiguous()
-            self._engine = ACGANEngine(self.model, data, self._device_labels(it), it.batch_size, dev,
-                                       use_graph=self.use_graph)
-            self._engine_key = key
-        self._engine.use_graph = self.use_graph
-        return self._engine
+    def _make_engine(self, data, loader, dev):
+        return ACGANEngine(self.model, data, self._device_labels(loader), loader.batch_size, dev,
+                           use_graph=self.use_graph)
 
     # ---- the loop -------------------------------------------------------------------------------------------------
     def train(self, num_epochs, G_lr=2e-4, D_lr=2e-4, D_steps=1, class_weight=1.0):
@@ -403,10 +274,9 @@ class ACGANTrainer(GANTrainer):
         epoch_steps = int(np.ceil(len(self.train_iter) / D_steps))
         if self._stock():
             self._device_labels(self.train_iter)       # bad labels raise here, before anything is launched
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
             eng = self._get_engine()
-            eng.configure(num_epochs * epoch_steps, G_lr, D_lr, D_steps, class_weight,
+            eng.use_graph = self.use_graph
+            eng.configure(num_epochs * epoch_steps, G_lr, D_lr, D_steps, class_weight=class_weight,
                           resume=self.__dict__.pop("_resume_optim", None))
             for epoch in range(1, num_epochs + 1):
                 self.model.train()
@@ -421,7 +291,7 @@ class ACGANTrainer(GANTrainer):
         if self.__dict__.get("_resume_optim") is not None:
             raise GMError("load_checkpoint() restored optimizer state, but this trainer runs the general path "
                           "(overridden hooks / edited networks), whose optimizers start fresh")
-        if _loader_ok(self.train_iter):
+        if reference_loader_ok(self.train_iter, labelled=True):
             validate_labels(self.train_iter.dataset.tensors[1], self.model.num_classes)
         m = self.model
         G_opt, D_opt = FlatAdam(m.G.parameters(), G_lr), FlatAdam(m.D.parameters(), D_lr)

@@ -22,6 +22,7 @@ import torch.nn as nn
 from . import ops, ops_fused
 from ._lib import GMError, slot
 from .ops_fused import bgan_stream_latent, bgan_stream_param
+from .ring_engine import ChunkedReplay, reference_loader_ok
 from .trainers import (CHECKPOINT_VERSION, EPS, Discriminator, GANTrainer, Generator, _decode_rows, _load_checkpoint,
                        _parzen, _plain, _stock_module, stock, stock_model)
 
@@ -97,7 +98,7 @@ class FlatSGHMC:
         return [self.v[o:o + p.numel()].view(p.shape).detach().cpu().clone() for p, o in zip(self.params, self.offs)]
 
 
-class BayesGANEngine:
+class BayesGANEngine(ChunkedReplay):
     """The fused path.  Critics stacked: their linear.weight / .bias are one [J_d H, I] matrix and one [J_d H] vector,
     their second layers one [J_d, H] and one [J_d] (FlatParams groups, the modules' parameters stay views), so the
     critic forward over the (1 + J_g) b rows [x; x~_0; ...] is one linear_fwd, dW1 of every critic one linear_bwd_dw
@@ -106,8 +107,6 @@ class BayesGANEngine:
     the step counters t_D / t_G on the device; batch rows through the sampler protocol replayed on the host
     (draw_sampler_indices) into an index ring read by gather_rows.  Whole iterations are captured as hipGraphs of
     `graph_iters` iterations (and of 1 for the tail)."""
-
-    graph_iters = 16
 
     @staticmethod
     def fused_ok(model):
@@ -159,7 +158,6 @@ class BayesGANEngine:
         self.wsG = ops_fused.bgan_head_workspace(1, B, Jg, Jd, H, device)
         self.ctr = torch.zeros(2, dtype=torch.int64, device=device)      # t_D, t_G
         self.lr = z(2)                                                  # D_lr, G_lr
-        self.graphs = {}
         self.steps_planned = 0
 
     # ---- one iteration's launches -------------------------------------------------------------------------------
@@ -170,7 +168,8 @@ class BayesGANEngine:
             ops.linear_fwd(self.Zb[r], l1.W, l1.b, self.HG[r], "relu", stream=s)
             ops.linear_fwd(self.HG[r], l2.W, l2.b, Xf[r], "sigmoid", stream=s)
 
-    def _issue(self, s):
+    def _issue(self, s, i):
+        """One iteration; its place i in the chunk is not read (the ring rows are addressed by t_D on the device)."""
         B, Jg, Jd, Z = self.B, self.Jg, self.Jd, self.Z
         tD, tG = self.ctr[0:1], self.ctr[1:2]
         Xf = self.X[B:]
@@ -224,10 +223,7 @@ class BayesGANEngine:
         self.gloss = torch.zeros(max(1, n_iters), self.Jg, device=self.dev)
         self.ring = max(1, self.graph_iters) * self.D_steps
         self.idx = torch.zeros(self.ring, self.B, dtype=torch.int64, device=self.dev)
-        self.idx_host = [torch.zeros(self.ring, self.B, dtype=torch.int64).pin_memory() for _ in range(2)]
-        self.idx_ev = [None, None]
-        self.buf = 0
-        self.graphs = {}
+        self._new_rings(self.idx)
         self.t_D0, self.t_G0 = self.t_D, self.t_G
         self.steps_planned = n_iters
 
@@ -252,48 +248,20 @@ class BayesGANEngine:
         (draw_sampler_indices, into the index ring) and the b x Z normals NSGAN's compute_noise takes, then the
         generator update's b x Z -- the latter are advanced past, never used."""
         from .engine import draw_sampler_indices
-        b = self.buf
-        if self.idx_ev[b] is not None:
-            self.idx_ev[b].synchronize()           # the copy that last read this pinned buffer has finished
-        host = self.idx_host[b]
         n = self.data.shape[0]
         t = self.t_D
-        for _ in range(k):
-            for _ in range(self.D_steps):
-                draw_sampler_indices(n, self.B, host[t % self.ring].numpy())
+        with self._staging() as (host,):
+            for _ in range(k):
+                for _ in range(self.D_steps):
+                    draw_sampler_indices(n, self.B, host[t % self.ring].numpy())
+                    torch.randn(self.B, self.Z)
+                    t += 1
                 torch.randn(self.B, self.Z)
-                t += 1
-            torch.randn(self.B, self.Z)
-        self.idx.copy_(host, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.idx_ev[b] = ev
-        self.buf = 1 - b
+            self.idx.copy_(host, non_blocking=True)
 
-    def _graph(self, k):
-        g = self.graphs.get(k)
-        if g is None:
-            def body(s):
-                for _ in range(k):
-                    self._issue(s)
-            g = self.graphs[k] = ops.Graph().capture(body)
-        return g
-
-    def run(self, n_iters):
-        done = 0
-        K = max(1, self.graph_iters)
-        while done < n_iters:
-            k = K if n_iters - done >= K else 1
-            self._host_draws(k)
-            if self.use_graph:
-                self._graph(k).launch()
-            else:
-                s = ops.stream_ptr()
-                for _ in range(k):
-                    self._issue(s)
-            self.t_D += k * self.D_steps
-            self.t_G += k
-            done += k
+    def _after_chunk(self, k):
+        self.t_D += k * self.D_steps
+        self.t_G += k
 
     def losses(self, it0, it1):
         """(G losses, D losses) of iterations [it0, it1) of this train() call: mean_j L_G^j, and per iteration the
@@ -355,11 +323,9 @@ class BayesGANTrainer(GANTrainer):
 
     # ---- path selection ---------------------------------------------------------------------------------------
     def _stock(self):
-        if not all(self._hook_is_stock(n) for n in self._STOCK):
+        if not self._stock_prefix():
             return False
         m = self.model
-        if not type(m).__dict__.get("_gm_stock_model", False):
-            return False                               # a subclass may have changed the model
         G, D = getattr(m, "G", None), getattr(m, "D", None)
         if not (type(G) is nn.ModuleList and type(D) is nn.ModuleList and len(G) and len(D)):
             return False
@@ -368,27 +334,10 @@ class BayesGANTrainer(GANTrainer):
             return False                               # edited / subclassed networks: general path
         if not BayesGANEngine.fused_ok(m):
             return False
-        it = self.train_iter
-        return bool(isinstance(it, torch.utils.data.DataLoader)
-                    and isinstance(it.dataset, torch.utils.data.TensorDataset)
-                    and isinstance(it.sampler, torch.utils.data.RandomSampler)
-                    and it.sampler.generator is None and it.generator is None
-                    and not it.sampler.replacement and it.num_workers == 0
-                    and it.batch_size is not None and it.batch_size <= len(it.dataset))
+        return reference_loader_ok(self.train_iter)
 
-    def _get_engine(self):
-        it = self.train_iter
-        key = (id(it.dataset), it.batch_size)
-        if self._engine is None or self._engine_key != key:
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            dev = next(self.model.parameters()).device
-            imgs = it.dataset.tensors[0]
-            data = imgs.reshape(imgs.shape[0], -1).to(dev, torch.float32).contiguous()
-            self._engine = BayesGANEngine(self.model, data, it.batch_size, dev, use_graph=self.use_graph)
-            self._engine_key = key
-        self._engine.use_graph = self.use_graph
-        return self._engine
+    def _make_engine(self, data, loader, dev):
+        return BayesGANEngine(self.model, data, loader.batch_size, dev, use_graph=self.use_graph)
 
     def _nsgan_noise_cursor(self, b):
         """Advance the global generator past the b x z_dim normals NSGANTrainer's compute_noise takes at this point of
@@ -409,6 +358,7 @@ class BayesGANTrainer(GANTrainer):
         momenta = None if resume is None else {"vD": resume["vD"], "vG": resume["vG"]}
         if self._stock():
             eng = self._get_engine()
+            eng.use_graph = self.use_graph
             eng.configure(num_epochs * epoch_steps, G_lr, D_lr, D_steps, friction, prior_std, N, self.seed,
                           self.t_D, self.t_G, momenta)
             self._state = eng

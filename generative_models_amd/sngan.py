@@ -36,7 +36,8 @@ import torch.nn.functional as F
 from . import ops, ops_fused
 from ._lib import GMError, slot
 from .trainers import FlatAdam, GANTrainer, Generator, _stock_module, stock, stock_model, to_cuda
-from .engine import FlatParams, _Linear, draw_sampler_indices
+from .engine import FlatParams, _Linear
+from .ring_engine import TwoAdamRingEngine, reference_loader_ok
 
 MAX_H, MAX_I = ops_fused.SN_MAX_H, ops_fused.SN_MAX_I
 NORM_EPS = 1e-12
@@ -91,7 +92,7 @@ def sngan_fused_ok(model):
             and tuple(G.linear.weight.shape) == (H, Z) and tuple(G.generate.weight.shape) == (I, H))
 
 
-class SNGANEngine:
+class SNGANEngine(TwoAdamRingEngine):
     """The fused path.  Batch rows and both steps' noise come from the sampler / randn protocol replayed on the host
     (draw_sampler_indices, normal_ on the global generator) into rings of `graph_iters` iterations, uploaded per chunk;
     whole iterations are captured as hipGraphs of `graph_iters` iterations (and of 1 for the tail), each launch reading
@@ -104,7 +105,6 @@ class SNGANEngine:
     generator mode; dX through Wbar (sigmoid epilogue) and through G.generate (relu epilogue); G's paired weight
     gradients + Adam; the tick.  One GPU only."""
 
-    graph_iters = 16
     fused_ok = staticmethod(sngan_fused_ok)
 
     def __init__(self, model, data, B, device, use_graph=True, world_size=1):
@@ -131,8 +131,6 @@ class SNGANEngine:
         self.ws_h = ops_fused.sn_head_workspace(2 * B, H, device)
         self.ws_g = ops_fused.sn_grad_workspace(H, device)
         self.ctr = torch.zeros(2, dtype=torch.int64, device=device)      # D steps, G steps of this train() call
-        self.graphs = {}
-        self.steps_planned = None
 
     # ---- one iteration's launches -------------------------------------------------------------------------------
     def _power(self, s, update_u=True):
@@ -158,8 +156,8 @@ class SNGANEngine:
         ops.adam(fD.flat, fD.grad, fD.m, fD.v, self.schedD, sched_slot=sl, betas=self.betas, stream=s)
         ops.tick(self.ctr[0:1], stream=s)
 
-    def _issue_G(self, s, k):
-        """The generator step on noise row k."""
+    def _issue_G(self, s, k, kd):
+        """The generator step on noise row k (the critic's row kd is not read: the generator is unconditioned)."""
         B, G1, G2, D1, D2 = self.B, self.G1, self.G2, self.D1, self.D2
         sl = slot(self.ctr[1:2].data_ptr(), 1, 0, 0, 1)
         z, Xg, Hd, dPre = self.zG[k], self.X[B:], self.Hd[:B], self.dPre[:B]
@@ -177,138 +175,15 @@ class SNGANEngine:
                                     dict(dA=self.dHg, X=z, lin=G1, adam=adam), betas=self.betas, stream=s)
         ops.tick(self.ctr[1:2], stream=s)
 
-    def _issue(self, s, i):
-        """Iteration i of a chunk."""
-        d = self.D_steps
-        for j in range(d):
-            self._issue_D(s, i * d + j)
-        self._issue_G(s, i)
-
     launches_per_iteration = staticmethod(lambda D_steps=1: 15 * D_steps + 12)
 
-    # ---- run settings, host draws, replay ----------------------------------------------------------------------
-    def configure(self, n_iters, G_lr, D_lr, D_steps, betas, resume=None):
-        """Once per train(): fresh Adam state (the reference's optimizers are locals of train()), schedules, loss
-        buffers, rings.  resume: a checkpoint's optim_state() -- moments restored, schedules continued."""
-        dev, B, Z = self.dev, self.B, self.Z
-        self.D_steps, self.betas = int(D_steps), (float(betas[0]), float(betas[1]))
-        self.run_config = {"B": int(B), "D_steps": int(D_steps), "G_lr": float(G_lr), "D_lr": float(D_lr),
-                           "beta1": self.betas[0], "beta2": self.betas[1]}
-        self.step0 = {"G": 0, "D": 0}
-        for fp in (self.fG, self.fD):
-            fp.rebind(); fp.reset_state(); fp.grad.zero_()
+    # ---- run settings ---------------------------------------------------------------------------------------------
+    def _configure_extra(self, betas):
+        self.betas = (float(betas[0]), float(betas[1]))
         self.u = self.model.D.u                        # (load_state_dict keeps the buffer; .to() may have moved it)
         if not (self.u.is_cuda and self.u.is_contiguous() and self.u.dtype == torch.float32):
             raise GMError("SNGANEngine: D.u must be a contiguous float32 device buffer")
-        if resume is not None:
-            saved = resume.get("config")
-            if saved is not None and not resume.get("lenient", False):
-                diff = {k: (saved[k], v) for k, v in self.run_config.items() if k in saved and saved[k] != v}
-                if diff:
-                    raise GMError("checkpoint was written by a run with different settings (saved, now): %s -- "
-                                  "load_checkpoint(path, strict=False) overrides" % diff)
-            for net, fp in (("G", self.fG), ("D", self.fD)):
-                st = resume[net]
-                if st["m"].numel() != fp.m.numel():
-                    raise GMError("checkpoint optimizer state does not match this model")
-                fp.m.copy_(st["m"]); fp.v.copy_(st["v"])
-                self.step0[net] = int(st["step"])
-        nD, nG = max(1, n_iters * self.D_steps), max(1, n_iters)
-        self.steps_planned = {"G": n_iters, "D": n_iters * self.D_steps}
-        sched = lambda lr, n, net: torch.from_numpy(
-            ops.adam_schedule(lr, n, betas=self.betas, start=self.step0[net] + 1)).to(dev)
-        self.schedD, self.schedG = sched(D_lr, nD, "D"), sched(G_lr, nG, "G")
-        self.dloss, self.gloss = torch.zeros(nD, device=dev), torch.zeros(nG, device=dev)
-        self.ctr.zero_()
-        K = max(1, self.graph_iters)
-        R = K * self.D_steps
-        self.idx = torch.zeros(R, B, dtype=torch.int64, device=dev)
-        self.zD, self.zG = torch.zeros(R, B, Z, device=dev), torch.zeros(K, B, Z, device=dev)
-        self.host = [(torch.zeros(R, B, dtype=torch.int64).pin_memory(), torch.zeros(R, B, Z).pin_memory(),
-                      torch.zeros(K, B, Z).pin_memory()) for _ in range(2)]
-        self.host_ev, self.buf = [None, None], 0
-        self.graphs = {}                               # (the buffers above are this call's: captured addresses)
-        self.done = 0
-
-    def optim_state(self):
-        torch.cuda.synchronize()
-        cpu = lambda t: t.detach().cpu().clone()
-        st = {net: {"m": cpu(fp.m), "v": cpu(fp.v), "step": self.step0[net] + self.steps_planned[net]}
-              for net, fp in (("G", self.fG), ("D", self.fD))}
-        st["config"] = dict(self.run_config)
-        return st
-
-    def _host_draws(self, k):
-        """The global generator's draws of k iterations in NSGANTrainer's order: per critic step the sampler's
-        (draw_sampler_indices) and compute_noise's randn(B, Z), then the generator step's randn(B, Z)."""
-        b = self.buf
-        if self.host_ev[b] is not None:
-            self.host_ev[b].synchronize()              # the copies that last read these pinned buffers have finished
-        hi, hd, hg = self.host[b]
-        n, d = self.data.shape[0], self.D_steps
-        for i in range(k):
-            for j in range(d):
-                draw_sampler_indices(n, self.B, hi[i * d + j].numpy())
-                hd[i * d + j].normal_()
-            hg[i].normal_()
-        self.idx[:k * d].copy_(hi[:k * d], non_blocking=True)
-        self.zD[:k * d].copy_(hd[:k * d], non_blocking=True)
-        self.zG[:k].copy_(hg[:k], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.host_ev[b] = ev
-        self.buf = 1 - b
-
-    def _graph(self, k):
-        g = self.graphs.get(k)
-        if g is None:
-            def body(s):
-                for i in range(k):
-                    self._issue(s, i)
-            g = self.graphs[k] = ops.Graph().capture(body)
-        return g
-
-    def run(self, n_iters):
-        done, K = 0, max(1, self.graph_iters)
-        while done < n_iters:
-            k = K if n_iters - done >= K else 1
-            self._host_draws(k)
-            if self.use_graph:
-                self._graph(k).launch()
-            else:
-                s = ops.stream_ptr()
-                for i in range(k):
-                    self._issue(s, i)
-            done += k
-        self.done += n_iters
-
-    def losses(self, it0, it1):
-        """(G losses, D losses) of iterations [it0, it1) of this train() call, D's as the mean over the iteration's
-        critic steps (one read-back)."""
-        d = self.D_steps
-        dl, gl = self.dloss.cpu().numpy(), self.gloss.cpu().numpy()
-        G = [float(gl[it]) for it in range(it0, it1)]
-        D = [np.mean([float(dl[it * d + j]) for j in range(d)]) for it in range(it0, it1)]
-        return G, D
-
-    def phase_grads(self):
-        """The last critic step's and the last generator step's gradients: {"d": 4 tensors, "g": 4}, keyed by the
-        model's state_dict names (views of the flat gradient buffers)."""
-        names = {id(p): n for n, p in self.model.named_parameters()}
-        out = {"d": {}, "g": {}}
-        for key, fp in (("d", self.fD), ("g", self.fG)):
-            for p, gv in zip(fp.params, fp.gviews):
-                out[key][names[id(p)]] = gv
-        return out
-
-
-def _loader_ok(it):
-    return bool(isinstance(it, torch.utils.data.DataLoader)
-                and isinstance(it.dataset, torch.utils.data.TensorDataset)
-                and isinstance(it.sampler, torch.utils.data.RandomSampler)
-                and it.sampler.generator is None and it.generator is None
-                and not it.sampler.replacement and it.num_workers == 0
-                and it.batch_size is not None and it.batch_size <= len(it.dataset))
+        return {"beta1": self.betas[0], "beta2": self.betas[1]}
 
 
 @stock
@@ -334,29 +209,18 @@ class SNGANTrainer(GANTrainer):
 
     # ---- path selection ---------------------------------------------------------------------------------------
     def _stock(self):
-        if not all(self._hook_is_stock(n) for n in self._STOCK):
+        if not self._stock_prefix():
             return False
         m = self.model
-        if not type(m).__dict__.get("_gm_stock_model", False):
-            return False                               # a subclass may have changed the model
         G, D = getattr(m, "G", None), getattr(m, "D", None)
         if not (type(G) is Generator and type(D) is Discriminator and _stock_module(G, 2) and _stock_module(D, 2)):
             return False                               # edited / subclassed networks: general path
         if not sngan_fused_ok(m):
             return False                               # outside the kernels' limits: general path
-        return _loader_ok(self.train_iter)
+        return reference_loader_ok(self.train_iter)
 
-    def _get_engine(self):
-        it = self.train_iter
-        key = (id(it.dataset), it.batch_size)
-        if self._engine is None or self._engine_key != key:
-            dev = next(self.model.parameters()).device
-            imgs = it.dataset.tensors[0]
-            data = imgs.reshape(imgs.shape[0], -1).to(dev, torch.float32).contiguous()
-            self._engine = SNGANEngine(self.model, data, it.batch_size, dev, use_graph=self.use_graph)
-            self._engine_key = key
-        self._engine.use_graph = self.use_graph
-        return self._engine
+    def _make_engine(self, data, loader, dev):
+        return SNGANEngine(self.model, data, loader.batch_size, dev, use_graph=self.use_graph)
 
     # ---- the loop -------------------------------------------------------------------------------------------------
     def train(self, num_epochs, G_lr=1e-4, D_lr=4e-4, D_steps=1, betas=(0.0, 0.9)):
@@ -366,10 +230,9 @@ class SNGANTrainer(GANTrainer):
             raise GMError("SNGANTrainer runs on one GPU: data parallelism is not implemented for it")
         epoch_steps = int(np.ceil(len(self.train_iter) / D_steps))
         if self._stock():
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
             eng = self._get_engine()
-            eng.configure(num_epochs * epoch_steps, G_lr, D_lr, D_steps, betas,
+            eng.use_graph = self.use_graph
+            eng.configure(num_epochs * epoch_steps, G_lr, D_lr, D_steps, betas=betas,
                           resume=self.__dict__.pop("_resume_optim", None))
             for epoch in range(1, num_epochs + 1):
                 self.model.train()

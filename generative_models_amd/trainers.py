@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import GMError
+from .ring_engine import device_rows, reference_loader_ok
 
 EPS = 1e-8
 
@@ -344,6 +345,12 @@ class GANTrainer:
                 return bool(base.__dict__.get("_gm_stock_class", False))
         return True
 
+    def _stock_prefix(self):
+        """What every stand-alone trainer's _stock() starts with: all _STOCK hooks the shipped ones, and the model's
+        class one this package ships (a subclass may have changed the model)."""
+        return bool(all(self._hook_is_stock(n) for n in self._STOCK)
+                    and type(self.model).__dict__.get("_gm_stock_model", False))
+
     def _stock(self):
         from .engine import GANEngine
         if self.variant not in GANEngine.SUPPORTED:
@@ -356,14 +363,7 @@ class GANTrainer:
             return False                               # edited / subclassed networks: general path
         if self.variant == "info" and not _stock_module(getattr(m, "Q", None)):
             return False
-        it = self.train_iter
-        ok = (isinstance(it, torch.utils.data.DataLoader)
-              and isinstance(it.dataset, torch.utils.data.TensorDataset)
-              and isinstance(it.sampler, torch.utils.data.RandomSampler)
-              and it.sampler.generator is None and it.generator is None
-              and not it.sampler.replacement and it.num_workers == 0
-              and it.batch_size is not None and it.batch_size <= len(it.dataset))
-        return bool(ok)
+        return reference_loader_ok(self.train_iter)
 
     def _captured_general_ok(self):
         """Only train_D / train_G differ from the stock trainer (README.md:29-65): stock process_batch / compute_noise
@@ -385,12 +385,7 @@ class GANTrainer:
         it = self.train_iter
         if not HostReplay.available() or (it.batch_size or 0) * m.z_dim < 16:
             return False
-        return bool(isinstance(it, torch.utils.data.DataLoader)
-                    and isinstance(it.dataset, torch.utils.data.TensorDataset)
-                    and isinstance(it.sampler, torch.utils.data.RandomSampler)
-                    and it.sampler.generator is None and it.generator is None
-                    and not it.sampler.replacement and it.num_workers == 0
-                    and it.batch_size is not None and it.batch_size <= len(it.dataset))
+        return reference_loader_ok(it)
 
     def _get_captured(self):
         from .captured import CapturedLoop
@@ -399,8 +394,7 @@ class GANTrainer:
         if getattr(self, "_captured", None) is None or self._captured_key != key:
             import os
             dev = next(self.model.parameters()).device
-            imgs = it.dataset.tensors[0]
-            data = imgs.reshape(imgs.shape[0], -1).to(dev, torch.float32).contiguous()
+            data = device_rows(it, dev)
             if os.environ.get("GM_PACKED", "1") != "0" and ops.PackedData.is_binary(data):
                 data = ops.PackedData(data)
             self._captured = CapturedLoop(self, data, it.batch_size, dev)
@@ -408,23 +402,26 @@ class GANTrainer:
         return self._captured
 
     def _get_engine(self):
-        from .engine import GANEngine
+        """The trainer's step engine, kept for as long as the dataset, the batch size and `method` stay the same."""
+        if not torch.cuda.is_available():
+            raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
         it = self.train_iter
         key = (id(it.dataset), it.batch_size, self.method)
         if self._engine is None or self._engine_key != key:
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
             dev = next(self.model.parameters()).device
-            imgs = it.dataset.tensors[0]
-            data = imgs.reshape(imgs.shape[0], -1).to(dev, torch.float32).contiguous()
-            from . import dp
-            world, rank, group = dp.current()
-            self._engine = GANEngine(self.variant, self.model, data, it.batch_size, dev,
-                                     method=self.method, use_graph=self.use_graph,
-                                     world_size=world, rank=rank, process_group=group,
-                                     force_dp=getattr(self, "force_dp", False))
+            self._engine = self._make_engine(device_rows(it, dev), it, dev)
             self._engine_key = key
         return self._engine
+
+    def _make_engine(self, data, loader, dev):
+        """A new engine over the dataset's rows `data` on `dev`: the one thing a trainer with an engine of its own
+        overrides."""
+        from . import dp
+        from .engine import GANEngine
+        world, rank, group = dp.current()
+        return GANEngine(self.variant, self.model, data, loader.batch_size, dev, method=self.method,
+                         use_graph=self.use_graph, world_size=world, rank=rank, process_group=group,
+                         force_dp=getattr(self, "force_dp", False))
 
     # ---- the step loop (ns_gan.py:94-170) --------------------------------------------------
     def _train(self, num_epochs, G_lr, D_lr, D_steps, clip=0.0, hyper=(), G_init=0, quiet=False,
@@ -1417,23 +1414,12 @@ class BEGANTrainerBase(GANTrainer):
     variant = "be"
     _gm_stock_class = True
 
-    def _get_engine(self):
+    def _make_engine(self, data, loader, dev):
+        from . import dp
         from .engine import BEGANEngine
-        it = self.train_iter
-        key = (id(it.dataset), it.batch_size)
-        if self._engine is None or self._engine_key != key:
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            from . import dp
-            world, rank, group = dp.current()
-            dev = next(self.model.parameters()).device
-            imgs = it.dataset.tensors[0]
-            data = imgs.reshape(imgs.shape[0], -1).to(dev, torch.float32).contiguous()
-            self._engine = BEGANEngine(self.model, data, it.batch_size, dev, use_graph=self.use_graph,
-                                       world_size=world, rank=rank, process_group=group,
-                                       force_dp=getattr(self, "force_dp", False))
-            self._engine_key = key
-        return self._engine
+        world, rank, group = dp.current()
+        return BEGANEngine(self.model, data, loader.batch_size, dev, use_graph=self.use_graph, world_size=world,
+                           rank=rank, process_group=group, force_dp=getattr(self, "force_dp", False))
 
     def train_D(self, images, K):
         """be_gan.py:212-238."""

@@ -363,28 +363,30 @@ def _same(a, b):
         assert torch.equal(a[3][k], b[3][k]), k
 
 
-def test_bitwise_runs_graph_eager_and_resume(tmp_path):
-    cfg = SMALL
+@pytest.mark.parametrize("D_steps", [1, 2])
+def test_bitwise_runs_graph_eager_and_resume(tmp_path, D_steps):
+    """Ring rows i * D_steps + j across the boundary between the graph of 16 and the tail, and across a resume."""
+    cfg = dict(SMALL, n_train=32 * 18 * D_steps)             # 18 iterations an epoch: a graph of 16 and two of 1
     runs = []
     for use_graph in (True, True, False):
-        tr, m, _ = product_run(cfg, use_graph=use_graph)
+        tr, m, _ = product_run(cfg, use_graph=use_graph, D_steps=D_steps)
         runs.append(_snapshot(tr, m))
     _same(runs[0], runs[1])
     _same(runs[0], runs[2])
     # train(1) + save + load into a fresh trainer + train(1) == train(2)
-    tr, m, its = product_run(dict(cfg, epochs=1))
+    tr, m, its = product_run(dict(cfg, epochs=1), D_steps=D_steps)
     path = str(tmp_path / "ck.pt")
     tr.save_checkpoint(path)
     ck = torch.load(path, weights_only=True)
     assert set(ck["history"]) == {"Glosses", "Dlosses", "class_losses", "num_epochs"}
-    assert ck["optim"]["G"]["step"] == 7 and ck["optim"]["D"]["step"] == 7
+    assert ck["optim"]["G"]["step"] == 18 and ck["optim"]["D"]["step"] == 18 * D_steps
     state = torch.get_rng_state()
     m2 = ac_gan.ACGAN(cfg["I"], cfg["H"], cfg["Z"], cfg["C"]).to(DEV)
     tr2 = ac_gan.ACGANTrainer(m2, *its)
     tr2.load_checkpoint(path)
     assert torch.equal(torch.get_rng_state(), state)
     with contextlib.redirect_stdout(io.StringIO()):
-        tr2.train(1)
+        tr2.train(1, D_steps=D_steps)
     torch.cuda.synchronize()
     _same(runs[0], _snapshot(tr2, m2))
 

@@ -415,21 +415,23 @@ def _same(a, b):
         assert torch.equal(a[2][k], b[2][k]), k
 
 
-def test_bitwise_runs_graph_eager_and_resume(tmp_path):
-    cfg = dict(SMALL, n_train=8 * 18, epochs=2)          # 18 iterations an epoch: a graph of 16 and two of 1
+@pytest.mark.parametrize("D_steps", [1, 2])
+def test_bitwise_runs_graph_eager_and_resume(tmp_path, D_steps):
+    """Ring rows i * D_steps + j across the boundary between the graph of 16 and the tail, and across a resume."""
+    cfg = dict(SMALL, n_train=8 * 18 * D_steps, epochs=2)    # 18 iterations an epoch: a graph of 16 and two of 1
     runs = []
     for use_graph in (True, True, False):
-        tr, m, _ = product_run(cfg, use_graph=use_graph)
+        tr, m, _ = product_run(cfg, use_graph=use_graph, D_steps=D_steps)
         runs.append(_snapshot(tr, m))
     _same(runs[0], runs[1])
     _same(runs[0], runs[2])
     # train(1) + save + load into a fresh trainer + train(1) == train(2)
-    tr, m, its = product_run(dict(cfg, epochs=1))
+    tr, m, its = product_run(dict(cfg, epochs=1), D_steps=D_steps)
     path = str(tmp_path / "ck.pt")
     tr.save_checkpoint(path)
     ck = torch.load(path, weights_only=True)
     assert set(ck["history"]) == {"Glosses", "Dlosses", "num_epochs"} and "D.u" in ck["model"]
-    assert ck["optim"]["G"]["step"] == 18 and ck["optim"]["D"]["step"] == 18
+    assert ck["optim"]["G"]["step"] == 18 and ck["optim"]["D"]["step"] == 18 * D_steps
     assert ck["optim"]["config"]["beta1"] == 0.0 and ck["optim"]["config"]["beta2"] == 0.9
     state = torch.get_rng_state()
     m2 = sn_gan.SNGAN(cfg["I"], cfg["H"], cfg["Z"]).to(DEV)
@@ -437,7 +439,7 @@ def test_bitwise_runs_graph_eager_and_resume(tmp_path):
     tr2.load_checkpoint(path)
     assert torch.equal(torch.get_rng_state(), state)
     with contextlib.redirect_stdout(io.StringIO()):
-        tr2.train(1)
+        tr2.train(1, D_steps=D_steps)
     torch.cuda.synchronize()
     _same(runs[0], _snapshot(tr2, m2))
 

@@ -63,6 +63,35 @@ def test_sampler_protocol_matches_dataloader_bit_exact():
     assert torch.equal(ref_state, torch.get_rng_state())
 
 
+@pytest.mark.parametrize("seed", [0, 11])
+@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("D_steps", [1, 2])
+def test_nsgan_order_draws_match_the_reference_loop_bit_exact(D_steps, k, seed):
+    """ring_engine.nsgan_order_draws == what ns_gan.py's loop takes from the global generator in k iterations: per
+    critic step next(iter(loader)) and randn(B, Z), then the generator step's randn(B, Z); ring rows i * D_steps + j
+    and i, rows past the k iterations untouched, and the generator left in the same state."""
+    from generative_models_amd import ring_engine
+    n, B, Z = 40, 8, 4
+    loader = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(torch.arange(n), torch.arange(n)),
+                                         batch_size=B, shuffle=True)
+    torch.manual_seed(seed)
+    ref_idx, ref_zD, ref_zG = [], [], []
+    for _ in range(k):
+        for _ in range(D_steps):
+            ref_idx.append(next(iter(loader))[0])
+            ref_zD.append(torch.randn(B, Z))
+        ref_zG.append(torch.randn(B, Z))
+    ref_state = torch.get_rng_state()
+    torch.manual_seed(seed)
+    idx = torch.full((k * D_steps + 1, B), -1, dtype=torch.int64)
+    zD, zG = torch.full((k * D_steps + 1, B, Z), -9.0), torch.full((k + 1, B, Z), -9.0)
+    ring_engine.nsgan_order_draws(n, B, D_steps, k, idx, zD, zG)
+    assert torch.equal(idx[:-1], torch.stack(ref_idx)) and bool((idx[-1] == -1).all())
+    assert torch.equal(zD[:-1], torch.stack(ref_zD)) and bool((zD[-1] == -9).all())
+    assert torch.equal(zG[:-1], torch.stack(ref_zG)) and bool((zG[-1] == -9).all())
+    assert torch.equal(ref_state, torch.get_rng_state())
+
+
 def test_epoch_order_matches_dataloader():
     data = torch.arange(100, dtype=torch.float32).reshape(100, 1)
     loader = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(data, torch.zeros(100)),
@@ -426,7 +455,7 @@ def test_no_function_of_the_package_reads_a_name_its_module_does_not_define():
     import sys
     root = os.path.dirname(HERE)
     mods = ["generative_models_amd." + m for m in ("engine", "gan_steps", "vae_engine", "began_engine", "trainers", "ops",
-                                                   "ops_fused", "dp", "viz", "_lib", "_build")]
+                                                   "ops_fused", "dp", "viz", "_lib", "_build", "ring_engine")]
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "undefined_names.py")] + mods,
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr

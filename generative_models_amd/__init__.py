@@ -82,8 +82,12 @@ def host_thread_plan():
 
 
 def __getattr__(name):
-    """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine, SNGAN / SNGANTrainer / SNGANEngine and
-    DDPM / DDPMTrainer / DDPMEngine, imported on first use (importing the package stays free of torch)."""
+    """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine, SNGAN / SNGANTrainer / SNGANEngine,
+    DDPM / DDPMTrainer / DDPMEngine and MADE / MADETrainer / MADEEngine, imported on first use (importing the package
+    stays free of torch)."""
+    if name in ("MADE", "MADETrainer", "MADEEngine"):
+        from . import made
+        return getattr(made, name)
     if name in ("DDPM", "DDPMTrainer", "DDPMEngine"):
         from . import ddpm
         return getattr(ddpm, name)

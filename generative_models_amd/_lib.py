@@ -131,6 +131,10 @@ DDPM_TAG_T, DDPM_TAG_E, DDPM_TAG_V, DDPM_TAG_VE, DDPM_TAG_S = 0x44445054, 0x4444
 DDPM_MAX_I, DDPM_MIN_E, DDPM_MAX_E, DDPM_MAX_T = 8192, 4, 128, 4096      # GM_DDPM_* (include/gm_hip.h)
 # (gm_ddpm_noise / _tables / _out / _reverse_args travel by pointer; their ctypes forms live in ops_fused)
 
+MADE_TAG_S = 0x4D414453                                     # GM_MADE_TAG_S ("MADS")
+MADE_MIN_I, MADE_MAX_I, MADE_MAX_H = 2, 8192, 1024          # GM_MADE_* (include/gm_hip.h)
+# (gm_made_mask_args / gm_made_sample_args travel by pointer; their ctypes forms live in ops_fused)
+
 NOISE = {"salt_pepper": 1, "gaussian": 2}       # GM_NOISE_SALT_PEPPER, GM_NOISE_GAUSSIAN (GM_NOISE_NONE = 0)
 
 
@@ -366,6 +370,10 @@ _SIGNATURES = {
     "gm_ddpm_loss": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_float, c_int, c_int]),
     "gm_ddpm_reverse": (c_int, [_P, _P]),
     "gm_ddpm_prior": (c_int, [_P, _P, c_int64, _P, ctypes.c_uint64, c_int64, c_int, _P, c_int, c_int, c_int, c_int]),
+    "gm_made_bce": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_float, c_int, c_int]),
+    "gm_made_mask": (c_int, [_P, _P]),
+    "gm_made_sample": (c_int, [_P, _P]),
+    "gm_made_uniform": (c_int, [_P, _P, c_int64, ctypes.c_uint64, c_int64, c_int64, c_int]),
 }
 
 _lib = None

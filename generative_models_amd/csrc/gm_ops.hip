@@ -287,7 +287,9 @@ __global__ __launch_bounds__(256) void gan_loss_kernel(LossP p) {
         // (w_gp_gan.py:215-218; rows produced by gm_gp_norm)
         // (DRAGAN carries the same kind of penalty rows on the NS loss, dra_gan.py:220-223: any
         // separable variant with aux rows gets the term, like the fused head kernel)
-        if (D && p.aux) lx += p.hyper[7] * p.aux[i];
+        // (a caller without a penalty leaves hyper[7] at 0 and may pass an aux of another meaning and length -- Fisher's
+        // 8 state words, say: aux is then not read at all, never B floats of it)
+        if (D && p.aux && p.hyper[7] != 0.f) lx += p.hyper[7] * p.aux[i];
         acc += (double)lx + (double)lg;
         if (D && p.dax) { const float ax = act_grad(dx, x, p.out_act); p.dax[i] = ax; sbx += (double)ax; }
         if (p.dag) { const float ag = act_grad(dg, g, p.out_act); p.dag[i] = ag; sbg += (double)ag; }

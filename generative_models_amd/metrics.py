@@ -22,6 +22,8 @@ MAX_SIGMAS = 16
 ParzenResult = collections.namedtuple("ParzenResult", "sigma ll_mean ll_stderr val_means")
 # VAETrainer.log_likelihood (iwae.py): the importance-weighted estimate of log p(x) over n rows from k samples each
 IWAEResult = collections.namedtuple("IWAEResult", "ll_mean ll_stderr k n")
+# the exact log-likelihood of a model with a tractable one (made.MADETrainer.log_likelihood), nats per image
+NLLResult = collections.namedtuple("NLLResult", "ll_mean ll_stderr n")
 
 
 def default_sigmas():

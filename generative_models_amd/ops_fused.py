@@ -964,3 +964,87 @@ def ddpm_prior(xin, temb, I, seed, step, t, traj=None, rows=None, stream=None):
         raise _lib.GMError("ddpm_prior: xin %s does not fit %d rows of %d + %d" % (tuple(xin.shape), rows, I, E))
     _lib.call("gm_ddpm_prior", stream or stream_ptr(), xin.data_ptr(), _ld(xin), temb.data_ptr(), int(seed), int(step),
               int(t), traj.data_ptr() if traj is not None else None, rows, I, E, T)
+
+
+# ---- Masked autoregressive model (csrc/gm_made.hip, gm_made.h; made.py) ----------------------------------------------
+class MadeMaskArgs(ctypes.Structure):
+    """gm_made_mask_args (include/gm_hip.h): both masked layers, their moments and the degree vectors."""
+    _fields_ = [("W1", ctypes.c_void_p), ("m1", ctypes.c_void_p), ("v1", ctypes.c_void_p), ("W2", ctypes.c_void_p),
+                ("m2", ctypes.c_void_p), ("v2", ctypes.c_void_p), ("m_in", ctypes.c_void_p), ("m_h", ctypes.c_void_p),
+                ("I", ctypes.c_int), ("H", ctypes.c_int)]
+
+
+class MadeSampleArgs(ctypes.Structure):
+    """gm_made_sample_args (include/gm_hip.h): the one-launch ancestral sampler."""
+    _fields_ = [("W2", ctypes.c_void_p), ("b2", ctypes.c_void_p), ("W1T", ctypes.c_void_p), ("b1", ctypes.c_void_p),
+                ("m_h", ctypes.c_void_p), ("inv_order", ctypes.c_void_p), ("x", ctypes.c_void_p),
+                ("ldx", ctypes.c_int64), ("p", ctypes.c_void_p), ("ldp", ctypes.c_int64), ("given", ctypes.c_void_p),
+                ("ldg", ctypes.c_int64), ("seed", ctypes.c_uint64), ("n", ctypes.c_int64), ("I", ctypes.c_int),
+                ("H", ctypes.c_int), ("n_known", ctypes.c_int)]
+
+
+def _made_f32(t, shape, name):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise _lib.GMError("%s must be a contiguous float32 device tensor of shape %s" % (name, tuple(shape)))
+    return t
+
+
+def _made_i32(t, n, name):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n):
+        raise _lib.GMError("%s must be a contiguous int32 device tensor of %d elements" % (name, n))
+    return t
+
+
+def made_bce(logits, x, part, B, scale, dA=None, stream=None):
+    """part[b] = sum_d softplus(a) - x a of row b and, with dA, dA = (sigmoid(a) - x) scale (gm_made_bce)."""
+    I = logits.shape[1]
+    if _rows2d(logits, "logits").shape[0] < B or _rows2d(x, "x").shape[0] < B or x.shape[1] < I or part.numel() < B \
+            or not part.is_contiguous() or (dA is not None and (_rows2d(dA, "dA").shape[0] < B or dA.shape[1] != I)):
+        raise _lib.GMError("made_bce: the arrays do not fit B=%d, I=%d" % (B, I))
+    _lib.call("gm_made_bce", stream or stream_ptr(), logits.data_ptr(), _ld(logits), x.data_ptr(), _ld(x),
+              dA.data_ptr() if dA is not None else None, _ld(dA) if dA is not None else 0, part.data_ptr(), scale, B, I)
+
+
+def made_mask(W1, W2, m_in, m_h, moments1=None, moments2=None, stream=None):
+    """Zeroes the masked entries of linear.weight W1 [H, I] and out.weight W2 [I, H] and -- moments = (m, v) flat views
+    -- of their Adam moments (gm_made_mask); every other entry stays as it is."""
+    H, I = W1.shape
+    _made_f32(W1, (H, I), "W1"), _made_f32(W2, (I, H), "W2")
+    a = MadeMaskArgs()
+    a.W1, a.W2 = W1.data_ptr(), W2.data_ptr()
+    a.m_in, a.m_h = _made_i32(m_in, I, "m_in").data_ptr(), _made_i32(m_h, H, "m_h").data_ptr()
+    for mv, names in ((moments1, ("m1", "v1")), (moments2, ("m2", "v2"))):
+        if mv is not None:
+            for t, nm in zip(mv, names):
+                setattr(a, nm, _made_f32(t.view(-1), (I * H,), nm).data_ptr())
+    a.I, a.H = I, H
+    _lib.call("gm_made_mask", stream or stream_ptr(), ctypes.byref(a))
+
+
+def made_sample(W2, b2, W1T, b1, m_h, inv_order, n, seed, x=None, p=None, given=None, n_known=0, stream=None):
+    """x [n, I] in {0, 1} drawn pixel by pixel in order of degree in ONE launch (gm_made_sample); p (a [n, I] tensor)
+    receives the conditionals; the first n_known positions of the order are copied from given [n, I]."""
+    I, H = W2.shape
+    _made_f32(W2, (I, H), "W2"), _made_f32(W1T, (I, H), "W1T"), _made_f32(b2, (I,), "b2"), _made_f32(b1, (H,), "b1")
+    x = torch.empty(n, I, device=W2.device) if x is None else x
+    for t, nm in ((x, "x"), (p, "p"), (given, "given")):
+        if t is not None and (_rows2d(t, nm).shape[0] < n or t.shape[1] < I):
+            raise _lib.GMError("made_sample: %s %s does not fit %d rows of %d" % (nm, tuple(t.shape), n, I))
+    a = MadeSampleArgs()
+    a.W2, a.b2, a.W1T, a.b1 = W2.data_ptr(), b2.data_ptr(), W1T.data_ptr(), b1.data_ptr()
+    a.m_h, a.inv_order = _made_i32(m_h, H, "m_h").data_ptr(), _made_i32(inv_order, I, "inv_order").data_ptr()
+    a.x, a.ldx = x.data_ptr(), _ld(x)
+    if p is not None:
+        a.p, a.ldp = p.data_ptr(), _ld(p)
+    if given is not None:
+        a.given, a.ldg = given.data_ptr(), _ld(given)
+    a.seed, a.n, a.I, a.H, a.n_known = int(seed), int(n), I, H, int(n_known)
+    _lib.call("gm_made_sample", stream or stream_ptr(), ctypes.byref(a))
+    return x
+
+
+def made_uniform(n, I, seed, row0=0, device="cuda", stream=None):
+    """u [n, I]: the sampler's uniforms of sample rows row0 .. row0 + n - 1 (gm_made_uniform)."""
+    u = torch.empty(n, I, device=device)
+    _lib.call("gm_made_uniform", stream or stream_ptr(), u.data_ptr(), _ld(u), int(seed), int(row0), int(n), int(I))
+    return u

@@ -1085,6 +1085,55 @@ int gm_ddpm_reverse(void* stream, const gm_ddpm_reverse_args* a);
 int gm_ddpm_prior(void* stream, float* xin, int64_t ldin, const float* temb, uint64_t seed, int64_t step, int t,
                   float* traj, int rows, int I, int E, int T);
 
+/* ---- masked autoregressive model, MADE (Germain et al., arXiv 1502.03509; made.py holds the contract; csrc/gm_made.hip,
+ * the sampling rule in csrc/gm_made.h) ----------------------------------------------------------------------------------
+ * A 784 -> H -> 784 MLP whose weights are masked by the degrees m_in [I] (a permutation of 1 .. I) and m_h [H] (in
+ * [1, I - 1]), int32 device vectors: linear.weight [H, I] keeps (k, i) iff m_h[k] >= m_in[i], out.weight [I, H] keeps
+ * (d, k) iff m_in[d] > m_h[k].  No mask is ever stored as a matrix. */
+#define GM_MADE_TAG_S 0x4D414453u             /* "MADS": the sampler's fourth counter word */
+#define GM_MADE_MIN_I 2
+#define GM_MADE_MAX_I 8192
+#define GM_MADE_MAX_H 1024
+/* The Bernoulli-logit loss of one batch (made.py MADEEngine._issue, MADETrainer.log_likelihood): part[b] = sum_d
+ * softplus(a) - x a of row b, softplus(a) = max(a, 0) + log1p(exp(-|a|)) (fp32, fixed order; gm_sum_finalize* scales and
+ * adds them up) and, when dA is not NULL, dA = (sigmoid(a) - x) scale -- with scale = 1 / B the gradient of the batch's
+ * mean negative log-likelihood in nats per image. */
+int gm_made_bce(void* stream, const float* logits, int64_t lda, const float* x, int64_t ldx, float* dA, int64_t ldd,
+                float* part, float scale, int B, int I);
+/* Zeroes W and Adam's moments m, v (both NULL, or both given) at the masked entries of both layers in one launch
+ * (made.py MADEEngine._issue, behind the weight-gradient + Adam launch whose epilogue steps every entry).  Every other
+ * entry is left as it is; no weight is read. */
+typedef struct gm_made_mask_args {
+    float* W1; float* m1; float* v1;          /* linear.weight [H, I] and its moments */
+    float* W2; float* m2; float* v2;          /* out.weight [I, H] and its moments */
+    const int32_t* m_in; const int32_t* m_h;
+    int I, H;
+} gm_made_mask_args;
+int gm_made_mask(void* stream, const gm_made_mask_args* a);
+/* The ancestral sampler in one launch (made.py MADETrainer.sample / complete).  Pixels are drawn in order of degree,
+ * inv_order[t] the pixel of degree t + 1; for pixel d of row r:
+ *   a = b2[d] + sum_k [m_h[k] < m_in[d]] W2[d, k] relu(h_k)   (lane-local sums in ascending k, then the wave butterfly);
+ *   x = 1 iff u < 1 / (1 + expf(-a)) in fp32, u = ph_unit of word d & 3 of Philox4x32-10 at counter (d >> 2, 0, r,
+ *   GM_MADE_TAG_S) under key (seed mod 2^32, seed >> 32);   h_k += x W1T[d, k] for every k with m_h[k] >= m_in[d],
+ * h starting from b1.  W1T [I, H] is linear.weight transposed (rows H floats apart, like W2's).  The first n_known
+ * positions take x from `given` instead of drawing it.  p (may be NULL) receives the conditionals sigmoid(a).  A row's
+ * bits depend on (seed, r) and the weights alone, not on n or the grid. */
+typedef struct gm_made_sample_args {
+    const float* W2; const float* b2;         /* out.weight [I, H], out.bias [I] */
+    const float* W1T; const float* b1;        /* linear.weight^T [I, H], linear.bias [H] */
+    const int32_t* m_h; const int32_t* inv_order;
+    float* x; int64_t ldx;                    /* [n, >= I]: the samples, 0 or 1 (given's value at a known pixel) */
+    float* p; int64_t ldp;                    /* [n, >= I] or NULL */
+    const float* given; int64_t ldg;          /* [n, >= I]; may be NULL when n_known == 0 */
+    uint64_t seed;
+    int64_t n;
+    int I, H, n_known;                        /* 0 <= n_known <= I */
+} gm_made_sample_args;
+int gm_made_sample(void* stream, const gm_made_sample_args* a);
+/* u[b, d] = the sampler's uniform of pixel d of sample row row0 + b (made.py MADETrainer._sample_general: the sampler of
+ * an edited model runs I forward passes under the same rule). */
+int gm_made_uniform(void* stream, float* u, int64_t ldu, uint64_t seed, int64_t row0, int64_t rows, int I);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

@@ -83,8 +83,14 @@ def host_thread_plan():
 
 def __getattr__(name):
     """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine, SNGAN / SNGANTrainer / SNGANEngine,
-    DDPM / DDPMTrainer / DDPMEngine and MADE / MADETrainer / MADEEngine, imported on first use (importing the package
-    stays free of torch)."""
+    DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine and NFVAE / NFVAETrainer / NFVAEEngine, imported
+    on first use (importing the package stays free of torch)."""
+    if name in ("NFVAE", "NFVAETrainer"):
+        from . import nfvae
+        return getattr(nfvae, name)
+    if name == "NFVAEEngine":
+        from . import engine
+        return engine.NFVAEEngine
     if name in ("MADE", "MADETrainer", "MADEEngine"):
         from . import made
         return getattr(made, name)

@@ -124,8 +124,10 @@ class CorruptArgs(ctypes.Structure):
 
 IWAE_TAG_TRAIN, IWAE_TAG_EVAL = 0x49574145, 0x49574556      # GM_IWAE_TAG_TRAIN / GM_IWAE_TAG_EVAL
 IWAE_MAX_K, IWAE_MAX_Z = 64, 32                             # GM_IWAE_MAX_K / GM_IWAE_MAX_Z
-# (gm_iwae_noise, gm_acgan_heads_args and the gm_sn_*_args travel by pointer; their ctypes forms, IwaeNoise,
-# ACGANHeadsArgs and SNPowerArgs / SNHeadArgs / SNGradArgs, live in ops_fused beside their wrappers)
+FLOW_MAX_K, FLOW_PART_STRIDE = 32, 68                       # GM_FLOW_MAX_K / GM_FLOW_PART_STRIDE
+# (gm_iwae_noise, gm_flow_params, gm_flow_step_args, gm_acgan_heads_args and the gm_sn_*_args travel by pointer; their
+# ctypes forms, IwaeNoise, FlowParams, FlowStepArgs, ACGANHeadsArgs and SNPowerArgs / SNHeadArgs / SNGradArgs, live in
+# ops_fused beside their wrappers)
 
 DDPM_TAG_T, DDPM_TAG_E, DDPM_TAG_V, DDPM_TAG_VE, DDPM_TAG_S = 0x44445054, 0x4444504D, 0x44445056, 0x44445057, 0x44445053
 DDPM_MAX_I, DDPM_MIN_E, DDPM_MAX_E, DDPM_MAX_T = 8192, 4, 128, 4096      # GM_DDPM_* (include/gm_hip.h)
@@ -364,6 +366,9 @@ _SIGNATURES = {
     "gm_iwae_weights": (c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_int64, _P, c_int, c_int, c_int]),
     "gm_iwae_reduce": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, c_int,
                                c_int, c_int]),
+    "gm_flow_sample": (c_int, [_P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int]),
+    "gm_flow_reduce": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int]),
+    "gm_flow_step": (c_int, [_P, _P]),
     "gm_ddpm_qsample": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int]),
     "gm_gather_rows_qsample": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
     "gm_gather_rows_bits_qsample": (c_int, [_P, _P, _P, _P, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),

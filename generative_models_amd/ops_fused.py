@@ -812,6 +812,82 @@ def iwae_normals(n_images, k, Z, seed, step, tag, device="cuda"):
     return out.view(n_images * k, Z)
 
 
+# ---- Planar-flow posterior of the normalizing-flow VAE (csrc/gm_flow.hip; nfvae.py) --------------------------------
+class FlowParams(ctypes.Structure):
+    """gm_flow_params (include/gm_hip.h): the K planar layers' u [K, Z], w [K, Z], b [K]."""
+    _fields_ = [("u", ctypes.c_void_p), ("w", ctypes.c_void_p), ("b", ctypes.c_void_p), ("K", ctypes.c_int)]
+
+
+class FlowStepArgs(ctypes.Structure):
+    """gm_flow_step_args (include/gm_hip.h): gm_flow_step's arguments as one block."""
+    _fields_ = [("part", ctypes.c_void_p), ("nparts", ctypes.c_int), ("u", ctypes.c_void_p), ("w", ctypes.c_void_p),
+                ("b", ctypes.c_void_p), ("gu", ctypes.c_void_p), ("gw", ctypes.c_void_p), ("gb", ctypes.c_void_p),
+                ("mu", ctypes.c_void_p), ("vu", ctypes.c_void_p), ("mw", ctypes.c_void_p), ("vw", ctypes.c_void_p),
+                ("mb", ctypes.c_void_p), ("vb", ctypes.c_void_p), ("sched", ctypes.c_void_p), ("sched_slot", _lib.Slot),
+                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("K", ctypes.c_int), ("Z", ctypes.c_int)]
+
+
+def flow_params(u, w, b):
+    """A gm_flow_params block over u [K, Z], w [K, Z], b [K] (contiguous float32 device tensors that outlive every
+    launch and captured graph reading them)."""
+    K, Z = u.shape
+    for t, nm, shp in ((u, "u", (K, Z)), (w, "w", (K, Z)), (b, "b", (K,))):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shp):
+            raise _lib.GMError("flow_params: %s must be a contiguous float32 device tensor of shape %s, got %s"
+                               % (nm, shp, tuple(t.shape)))
+    return FlowParams(u.data_ptr(), w.data_ptr(), b.data_ptr(), K)
+
+
+def flow_parts(B, K, device="cuda"):
+    """The partial-gradient buffer flow_reduce fills and flow_step sums: ceil(B / 8) blocks of [K, 68] floats."""
+    return torch.zeros((B + 7) // 8, K, _lib.FLOW_PART_STRIDE, device=device)
+
+
+def flow_sample(ml, z, lp, noise, flow, B, k, Z, stream=None):
+    """z_K [B k, Z] and lp [B k] of the k samples of each of B images from ml [B, 2Z] through the planar chain
+    `flow` (a flow_params block) (gm_flow_sample)."""
+    if _rows2d(ml, "ml").shape[0] < B or ml.shape[1] < 2 * Z or _rows2d(z, "z").shape[0] < B * k or z.shape[1] < Z \
+            or lp.numel() < B * k or not lp.is_contiguous():
+        raise _lib.GMError("flow_sample: ml %s / z %s / lp %s do not fit B=%d, k=%d, Z=%d"
+                           % (tuple(ml.shape), tuple(z.shape), tuple(lp.shape), B, k, Z))
+    _lib.call("gm_flow_sample", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(flow), ml.data_ptr(), _ld(ml),
+              z.data_ptr(), _ld(z), lp.data_ptr(), B, k, Z)
+
+
+def flow_reduce(ml, wn, dzdec, dml, part, noise, flow, B, k, Z, stream=None):
+    """d loss / d [mu | lv] -> dml [B, 2Z] and the flow parameters' partial gradient blocks -> part (flow_parts) from
+    dzdec [B k, Z] = dHdec Wd1 and the weights wn [B k] (gm_flow_reduce)."""
+    if _rows2d(ml, "ml").shape[0] < B or ml.shape[1] < 2 * Z or _rows2d(dzdec, "dzdec").shape[0] < B * k \
+            or dzdec.shape[1] < Z or _rows2d(dml, "dml").shape[0] < B or dml.shape[1] < 2 * Z or wn.numel() < B * k \
+            or not part.is_contiguous() or part.numel() < (B + 7) // 8 * flow.K * _lib.FLOW_PART_STRIDE:
+        raise _lib.GMError("flow_reduce: the arrays do not fit B=%d, k=%d, Z=%d, K=%d" % (B, k, Z, flow.K))
+    _lib.call("gm_flow_reduce", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(flow), ml.data_ptr(), _ld(ml),
+              wn.data_ptr(), dzdec.data_ptr(), _ld(dzdec), dml.data_ptr(), _ld(dml), part.data_ptr(), B, k, Z)
+
+
+def flow_step(part, B, u, w, b, moments, sched, sched_slot=NO_SLOT, grads=None, betas=(0.9, 0.999), eps=1e-8,
+              weight_decay=0.0, stream=None):
+    """The flow's optimiser step (gm_flow_step): flow_reduce's blocks for a batch of B images summed, the gradients of
+    u, w, b formed (and written to grads = (gu, gw, gb) when given) and one Adam step taken at the schedule's slot;
+    moments = (mu, vu, mw, vw, mb, vb), laid out like their parameters."""
+    K, Z = u.shape
+    nparts = (B + 7) // 8
+    if len(moments) != 6 or part.numel() < nparts * K * _lib.FLOW_PART_STRIDE or not part.is_contiguous():
+        raise _lib.GMError("flow_step: six moment tensors and %d partial blocks are needed" % nparts)
+    n = [K * Z, K * Z, K]
+    ts = [u, w, b] + list(moments) + (list(grads) if grads is not None else [])
+    for t, cnt in zip(ts, n + [K * Z] * 4 + [K, K] + n):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == cnt):
+            raise _lib.GMError("flow_step: every tensor must be a contiguous float32 device tensor sized like its "
+                               "parameter (K=%d, Z=%d)" % (K, Z))
+    g = [t.data_ptr() for t in grads] if grads is not None else [None, None, None]
+    a = FlowStepArgs(part.data_ptr(), nparts, u.data_ptr(), w.data_ptr(), b.data_ptr(), g[0], g[1], g[2],
+                     *[t.data_ptr() for t in moments], sched.data_ptr(), sched_slot, betas[0], betas[1], eps,
+                     weight_decay, K, Z)
+    _lib.call("gm_flow_step", stream or stream_ptr(), ctypes.byref(a))
+
+
 # ---- Denoising diffusion (csrc/gm_ddpm.hip, gm_ddpm.h; ddpm.py) ----------------------------------------------------
 class DdpmNoise(ctypes.Structure):
     """gm_ddpm_noise (include/gm_hip.h): seed, the two tags, the step and the first row's batch position."""

@@ -19,7 +19,7 @@ class VAEEngine:
         enc, dec = model.encoder, model.decoder
         plist = [enc.linear.weight, enc.linear.bias,
                  (enc.mu.weight, enc.log_var.weight), (enc.mu.bias, enc.log_var.bias),
-                 dec.linear.weight, dec.linear.bias, dec.recon.weight, dec.recon.bias]
+                 dec.linear.weight, dec.linear.bias, dec.recon.weight, dec.recon.bias] + self._extra_params(model)
         self._dp_init(plist, world_size, rank, process_group, force_dp)
         self.fp = FlatParams(plist, device, grad_alloc=self._grad_alloc)
         fp = self.fp
@@ -42,6 +42,10 @@ class VAEEngine:
         self._common_init(device)
 
     has_eps = True              # the VAE draws eps per batch (vae.py:104); the plain AE does not
+
+    def _extra_params(self, model):
+        """Parameters a subclass packs behind the encoder's and the decoder's (NFVAEEngine: the flow's)."""
+        return []
 
     # ---- data parallel (SURVEY.md 8e): every batch's rows are split over the ranks; the losses are
     # SUMS (vae.py:203,212), so the gradient all-reduce is a plain sum with no 1/N and the per-rank
@@ -873,11 +877,21 @@ class IWAEEngine(VAEEngine):
             return of_.iwae_noise(self.trainer.seed, tag, self.k, step_ctr=self.ctr, step_base=base)
         return of_.iwae_noise(self.trainer.seed, tag, self.k, step=t, step_base=base)
 
+    def _sample(self, st, nz, b):
+        """Launch 3: z and lp of the batch's b k sample rows."""
+        from . import ops_fused as of_
+        of_.iwae_sample(self.ml, self.Zs, self.lp, nz, b, self.k, self.Z, stream=st)
+
+    def _reduce(self, st, nz, b, adam):
+        """Launch 10: d loss / d [mu | lv] from dzdec and the weights."""
+        from . import ops_fused as of_
+        of_.iwae_reduce(self.ml, self.wn, self.dzdec, self.dml, nz, b, self.k, self.Z, stream=st)
+
     def _issue(self, st, t, b, train, pos=0, of=1):
         """One batch of size b: forward on b k sample rows + -L_k, ess (+ backward + Adam when train)."""
         from . import ops_fused as of_
         of = max(1, of)
-        R, B, Z, k = self.R, self.B, self.Z, self.k
+        R, B, k = self.R, self.B, self.k
         E1, ML, D1, D2 = self.E1, self.ML, self.D1, self.D2
         idx_slot = self._slot(t, 1, 0, R, B)
         loss_slot = self._slot(t, 1, 0, 0, 1)
@@ -889,7 +903,7 @@ class IWAEEngine(VAEEngine):
         ops.linear_fwd(X, E1.W, E1.b, self.He, "relu", M=b, stream=st)
         self._fwd_with_prefetch(st, t, 0, b, self.He, ML, self.ml, "id", nxt, train=train)
         nz = self._noise(t, train)
-        of_.iwae_sample(self.ml, self.Zs, self.lp, nz, b, k, Z, stream=st)
+        self._sample(st, nz, b)
         ops.linear_fwd(self.Zs, D1.W, D1.b, self.Hdec, "relu", M=b * k, stream=st)
         ops.linear_fwd(self.Hdec, D2.W, D2.b, self.Xr, "sigmoid", M=b * k, stream=st)
         of_.iwae_weights(X, self.Xr, self.lp, self.negL, self.essb, self.wn, b, k, dA=self.dA if train else None,
@@ -905,13 +919,67 @@ class IWAEEngine(VAEEngine):
         ops.linear_bwd_dw_adam_pair(dict(dA=self.dA, X=self.Hdec, lin=D2, adam=adam, M=b * k),
                                     dict(dA=self.dHdec, X=self.Zs, lin=D1, adam=adam, M=b * k),
                                     weight_decay=self.wd, stream=st)
-        of_.iwae_reduce(self.ml, self.wn, self.dzdec, self.dml, nz, b, k, Z, stream=st)
+        self._reduce(st, nz, b, adam)
         ops.linear_bwd_dx(self.dml, ML.W, self.dHe, below=self.He, epi="relu", M=b, stream=st)
         ops.linear_bwd_dw_adam_pair_finalize(
             dict(dA=self.dHe, X=X, lin=E1, adam=adam, M=b), dict(dA=self.dml, X=self.He, lin=ML, adam=adam, M=b),
             dict(pa=self.negL, na=b, out_a=loss_out, slot_a=loss_slot, pb=self.essb, nb=b, scale_b=1.0 / b,
                  out_b=ess_out, slot_b=loss_slot, done=self.fin_done, tick=tick),
             weight_decay=self.wd, stream=st)
+
+
+class NFVAEEngine(IWAEEngine):
+    """The normalizing-flow VAE (nfvae.py holds the contract): IWAEEngine's batch with a chain of K planar layers between
+    z_0 and the decoder.  13 launches per training batch: the IWAE's 12 with launch 3 replaced by gm_flow_sample (z_K,
+    lp with the log-determinants) and launch 10 by gm_flow_reduce (dml and the flow's partial gradient blocks), and
+    gm_flow_step (the blocks' sum, the constraint's backward, Adam on u, w, b at the batch's schedule slot) behind
+    gm_flow_reduce, which is the last reader of the flow's parameters.  The flow's parameters, gradients and moments
+    are views of the engine's flat buffers like every other parameter.  One GPU only."""
+
+    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
+                 trainer=None):
+        if world_size > 1 or force_dp:
+            raise GMError("the NF-VAE engine runs on one GPU: data parallelism is not implemented for it")
+        from ._lib import FLOW_MAX_K
+        K = int(model.flow.u.shape[0])
+        if not 1 <= K <= FLOW_MAX_K:
+            raise GMError("NFVAEEngine: 1 <= num_flows <= %d (got %d); NFVAETrainer trains these on the general path"
+                          % (FLOW_MAX_K, K))
+        super().__init__(model, device, use_graph=use_graph, trainer=trainer)
+        self.K = K
+        self._extra_config = {"num_flows": K}
+        fp, fl = self.fp, model.flow
+        ix = [[i for i, p in enumerate(fp.params) if p is q][0] for q in (fl.u, fl.w, fl.b)]
+        seg = lambda buf, i: buf[fp.offsets[i]:fp.offsets[i] + fp.params[i].numel()]
+        self.FU, self.FW, self.Fb = (fp.views[i] for i in ix)
+        self.Fgrads = tuple(seg(fp.grad, i) for i in ix)
+        self.Fmoments = tuple(seg(buf, i) for i in ix for buf in (fp.m, fp.v))
+
+    def _extra_params(self, model):
+        fl = model.flow
+        return [fl.u, fl.w, fl.b]
+
+    def _alloc(self, B):
+        if self._bufB == B:
+            return
+        super()._alloc(B)
+        from . import ops_fused as of_
+        self.fpart = of_.flow_parts(B, self.K, device=self.device)
+
+    def _flow(self):
+        from . import ops_fused as of_
+        return of_.flow_params(self.FU, self.FW, self.Fb)
+
+    def _sample(self, st, nz, b):
+        from . import ops_fused as of_
+        of_.flow_sample(self.ml, self.Zs, self.lp, nz, self._flow(), b, self.k, self.Z, stream=st)
+
+    def _reduce(self, st, nz, b, adam):
+        from . import ops_fused as of_
+        of_.flow_reduce(self.ml, self.wn, self.dzdec, self.dml, self.fpart, nz, self._flow(), b, self.k, self.Z,
+                        stream=st)
+        of_.flow_step(self.fpart, b, self.FU, self.FW, self.Fb, self.Fmoments, adam["sched"], adam["sched_slot"],
+                      grads=self.Fgrads, weight_decay=self.wd, stream=st)
 
 
 def aae_fused_ok(model):

@@ -1007,6 +1007,46 @@ int gm_iwae_reduce(void* stream, const gm_iwae_noise* n, const float* ml, int64_
                    const float* dzdec, int64_t lddz, float* dml, int64_t lddml, float* dZ, int64_t lddZ, int B, int k,
                    int Z);
 
+/* ---- Planar-flow posterior of the normalizing-flow VAE (csrc/gm_flow.hip; nfvae.py holds the contract, DESIGN.md
+ * section 22).  gm_iwae_sample / gm_iwae_reduce with a chain of K planar layers between z_0 = mu + eps exp(lv / 2) and
+ * the decoder; rows, noise block and limits on k and Z are the IWAE's.  Per layer, from the parameters alone:
+ * s0 = w.u, u_hat = u + (m(s0) - s0) w / (|w|^2 + 1e-12) with m(x) = -1 + softplus(x), s = w.u_hat; per row:
+ * t = tanh(w.z + b), logdet = log(1 + (1 - t^2) s), z <- z + u_hat t.  1 <= K <= 32.  Fixed reduction orders, no
+ * atomics.  Out-of-range, NULL or aliased arguments return GM_EINVAL before any launch. */
+#define GM_FLOW_MAX_K 32
+#define GM_FLOW_PART_STRIDE 68                 /* floats per layer of a partial block */
+typedef struct gm_flow_params {
+    const float* u;                           /* [K, Z] contiguous */
+    const float* w;                           /* [K, Z] contiguous */
+    const float* b;                           /* [K] */
+    int K;
+} gm_flow_params;
+/* z [B*k, Z] = z_K and lp[b k + j] = 1/2 |eps|^2 + 1/2 sum_c lv_c + sum_k logdet_k - 1/2 |z_K|^2. */
+int gm_flow_sample(void* stream, const gm_iwae_noise* n, const gm_flow_params* f, const float* ml, int64_t ldml,
+                   float* z, int64_t ldz, float* lp, int B, int k, int Z);
+/* The backward of gm_flow_sample: eps and the chain rebuilt, then walked back from g_K = wn_j z_K + dzdec_j with
+ * d loss / d logdet = -wn_j.  dml [B, 2Z] = [sum_j g_0 | sum_j g_0 eps_j exp(lv / 2) / 2 - 1/2], j ascending.  part
+ * (16-byte aligned) takes ceil(B / 8) blocks of [K, GM_FLOW_PART_STRIDE] floats, one per workgroup of 8 images: per
+ * layer the sums over the block's sample rows of d loss / d u_hat at [0, Z), of d loss / d w through a = w.z + b at
+ * [32, 32 + Z), of d loss / d b at 64 and of d loss / d s at 65. */
+int gm_flow_reduce(void* stream, const gm_iwae_noise* n, const gm_flow_params* f, const float* ml, int64_t ldml,
+                   const float* wn, const float* dzdec, int64_t lddz, float* dml, int64_t lddml, float* part, int B,
+                   int k, int Z);
+typedef struct gm_flow_step_args {
+    const float* part;                        /* gm_flow_reduce's partial blocks */
+    int nparts;                               /* their number: ceil(B / 8) */
+    float* u; float* w; float* b;             /* the parameters, stepped in place */
+    float* gu; float* gw; float* gb;          /* the gradients, written when not NULL (all three or none) */
+    float* mu; float* vu; float* mw; float* vw; float* mb; float* vb;      /* Adam moments */
+    const float* sched;                       /* [steps, 2]: lr / (1 - b1^t), sqrt(1 - b2^t) (gm_adam's) */
+    gm_slot sched_slot;
+    double beta1, beta2, eps, weight_decay;
+    int K, Z;
+} gm_flow_step_args;
+/* One workgroup: the partial blocks summed in ascending order, d loss / d u_hat (d s folded in) mapped through the
+ * constraint onto u and w, then gm_adam's step on u, w and b at the schedule's slot. */
+int gm_flow_step(void* stream, const gm_flow_step_args* a);
+
 /* ---- Denoising diffusion (csrc/gm_ddpm.hip, gm_ddpm.h; ddpm.py holds the contract).  One
  * 256-thread workgroup per row, fixed reduction orders, no floating-point atomics.  Noise: Philox4x32-10 with key
  * (seed mod 2^32, seed >> 32); batch row `row` = row0 + the row's position in the call, step = (step_ctr ? *step_ctr :

@@ -83,8 +83,14 @@ def host_thread_plan():
 
 def __getattr__(name):
     """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine, SNGAN / SNGANTrainer / SNGANEngine,
-    DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine and NFVAE / NFVAETrainer / NFVAEEngine, imported
-    on first use (importing the package stays free of torch)."""
+    DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine, NFVAE / NFVAETrainer / NFVAEEngine and CatVAE /
+    CatVAETrainer / CatVAEEngine, imported on first use (importing the package stays free of torch)."""
+    if name in ("CatVAE", "CatVAETrainer"):
+        from . import catvae
+        return getattr(catvae, name)
+    if name == "CatVAEEngine":
+        from . import engine
+        return engine.CatVAEEngine
     if name in ("NFVAE", "NFVAETrainer"):
         from . import nfvae
         return getattr(nfvae, name)

@@ -125,6 +125,10 @@ class CorruptArgs(ctypes.Structure):
 IWAE_TAG_TRAIN, IWAE_TAG_EVAL = 0x49574145, 0x49574556      # GM_IWAE_TAG_TRAIN / GM_IWAE_TAG_EVAL
 IWAE_MAX_K, IWAE_MAX_Z = 64, 32                             # GM_IWAE_MAX_K / GM_IWAE_MAX_Z
 FLOW_MAX_K, FLOW_PART_STRIDE = 32, 68                       # GM_FLOW_MAX_K / GM_FLOW_PART_STRIDE
+CAT_TAG_TRAIN, CAT_TAG_EVAL = 0x43415454, 0x43415445        # GM_CAT_TAG_TRAIN / GM_CAT_TAG_EVAL
+CAT_MIN_C, CAT_MAX_C, CAT_MAX_NC = 2, 64, 1024              # GM_CAT_MIN_C / GM_CAT_MAX_C / GM_CAT_MAX_NC
+CAT_RELAXED, CAT_ST, CAT_DISCRETE, CAT_NOISE = 0, 1, 2, 3   # GM_CAT_RELAXED / _ST / _DISCRETE / _NOISE
+# (gm_cat_args travels by pointer too: CatArgs in ops_fused)
 # (gm_iwae_noise, gm_flow_params, gm_flow_step_args, gm_acgan_heads_args and the gm_sn_*_args travel by pointer; their
 # ctypes forms, IwaeNoise, FlowParams, FlowStepArgs, ACGANHeadsArgs and SNPowerArgs / SNHeadArgs / SNGradArgs, live in
 # ops_fused beside their wrappers)
@@ -369,6 +373,8 @@ _SIGNATURES = {
     "gm_flow_sample": (c_int, [_P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int]),
     "gm_flow_reduce": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int]),
     "gm_flow_step": (c_int, [_P, _P]),
+    "gm_cat_sample": (c_int, [_P, _P, _P]),
+    "gm_cat_reduce": (c_int, [_P, _P, _P]),
     "gm_ddpm_qsample": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int]),
     "gm_gather_rows_qsample": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
     "gm_gather_rows_bits_qsample": (c_int, [_P, _P, _P, _P, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),

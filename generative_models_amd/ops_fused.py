@@ -888,6 +888,97 @@ def flow_step(part, B, u, w, b, moments, sched, sched_slot=NO_SLOT, grads=None, 
     _lib.call("gm_flow_step", stream or stream_ptr(), ctypes.byref(a))
 
 
+# ---- Gumbel-Softmax posterior of the categorical VAE (csrc/gm_cat.hip; catvae.py) ----------------------------------
+class CatArgs(ctypes.Structure):
+    """gm_cat_args (include/gm_hip.h): gm_cat_sample's and gm_cat_reduce's arguments as one block."""
+    _fields_ = [("logits", ctypes.c_void_p), ("ldl", ctypes.c_int64), ("tau_tab", ctypes.c_void_p),
+                ("tau_slot", _lib.Slot), ("tau", ctypes.c_float), ("B", ctypes.c_int), ("k", ctypes.c_int),
+                ("N", ctypes.c_int), ("C", ctypes.c_int), ("mode", ctypes.c_int), ("y", ctypes.c_void_p),
+                ("ldy", ctypes.c_int64), ("lp", ctypes.c_void_p), ("kl", ctypes.c_void_p), ("codes", ctypes.c_void_p),
+                ("dzdec", ctypes.c_void_p), ("lddz", ctypes.c_int64), ("wn", ctypes.c_void_p),
+                ("dlogits", ctypes.c_void_p), ("lddl", ctypes.c_int64)]
+
+
+def _cat_f32(t, name):
+    if not (t.is_cuda and t.dtype == torch.float32):
+        raise _lib.GMError("%s must be a float32 device tensor (got %s on %s)" % (name, t.dtype, t.device))
+    return t
+
+
+def _cat_tau(a, tau, tau_tab, tau_slot):
+    if tau_tab is not None:
+        if not (tau_tab.is_cuda and tau_tab.dtype == torch.float32 and tau_tab.is_contiguous()):
+            raise _lib.GMError("the temperature table must be a contiguous float32 device tensor")
+        a.tau_tab, a.tau_slot = tau_tab.data_ptr(), tau_slot
+    elif tau is not None:
+        a.tau = float(tau)
+
+
+def cat_sample(logits, y, lp, noise, B, k, N, C, mode, tau=None, tau_tab=None, tau_slot=NO_SLOT, kl=None, codes=None,
+               stream=None):
+    """The decoder's input y [B k, N C], lp [B k] and (kl [B], codes [B k, N] int32) of the k samples of each of B
+    images from logits [B, N C] (gm_cat_sample).  mode: _lib.CAT_RELAXED (reads tau, a float, or tau_tab at tau_slot),
+    CAT_ST, CAT_DISCRETE (needs codes) or CAT_NOISE (y = the Gumbel noise; logits and lp may be None)."""
+    W = N * C
+    a = CatArgs()
+    if _rows2d(_cat_f32(y, "y"), "y").shape[0] < B * k or y.shape[1] < W:
+        raise _lib.GMError("cat_sample: y %s does not fit B=%d, k=%d, N=%d, C=%d" % (tuple(y.shape), B, k, N, C))
+    if mode != _lib.CAT_NOISE:
+        if logits is None or lp is None or _rows2d(_cat_f32(logits, "logits"), "logits").shape[0] < B \
+                or logits.shape[1] < W or _cat_f32(lp, "lp").numel() < B * k or not lp.is_contiguous():
+            raise _lib.GMError("cat_sample: logits / lp do not fit B=%d, k=%d, N=%d, C=%d" % (B, k, N, C))
+        a.logits, a.ldl, a.lp = logits.data_ptr(), _ld(logits), lp.data_ptr()
+        if kl is not None:
+            if _cat_f32(kl, "kl").numel() < B or not kl.is_contiguous():
+                raise _lib.GMError("cat_sample: kl holds one float per image")
+            a.kl = kl.data_ptr()
+    if codes is not None:
+        if not (codes.is_cuda and codes.dtype == torch.int32 and codes.is_contiguous() and codes.numel() >= B * k * N):
+            raise _lib.GMError("cat_sample: codes must be a contiguous int32 device tensor of B k N elements")
+        a.codes = codes.data_ptr()
+    a.y, a.ldy = y.data_ptr(), _ld(y)
+    a.B, a.k, a.N, a.C, a.mode = B, k, N, C, int(mode)
+    _cat_tau(a, tau, tau_tab, tau_slot)
+    _lib.call("gm_cat_sample", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(a))
+
+
+def cat_reduce(logits, dzdec, wn, dlogits, noise, B, N, C, tau=None, tau_tab=None, tau_slot=NO_SLOT, stream=None):
+    """d loss / d logits -> dlogits [B, N C] from dzdec [B, N C] = d loss / d (decoder input) and wn [B], the Gumbel
+    noise regenerated (gm_cat_reduce; the backward of CAT_RELAXED and of CAT_ST alike, k = 1)."""
+    W = N * C
+    for t, nm in ((logits, "logits"), (dzdec, "dzdec"), (dlogits, "dlogits")):
+        if _rows2d(_cat_f32(t, nm), nm).shape[0] < B or t.shape[1] < W:
+            raise _lib.GMError("cat_reduce: %s %s does not fit B=%d, N=%d, C=%d" % (nm, tuple(t.shape), B, N, C))
+    if _cat_f32(wn, "wn").numel() < B or not wn.is_contiguous():
+        raise _lib.GMError("cat_reduce: wn holds one float per image")
+    a = CatArgs()
+    a.logits, a.ldl = logits.data_ptr(), _ld(logits)
+    a.dzdec, a.lddz, a.wn = dzdec.data_ptr(), _ld(dzdec), wn.data_ptr()
+    a.dlogits, a.lddl = dlogits.data_ptr(), _ld(dlogits)
+    a.B, a.k, a.N, a.C, a.mode = B, 1, N, C, _lib.CAT_RELAXED
+    _cat_tau(a, tau, tau_tab, tau_slot)
+    _lib.call("gm_cat_reduce", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(a))
+
+
+def catvae_gumbels(n_images, k, N, C, seed, step, tag, device="cuda"):
+    """g [n_images k, N C]: the Gumbel noise gm_cat_sample draws for (seed, step, tag), through gm_cat_sample's NOISE
+    mode, bit for bit.  The noise of a row depends on the element's index alone, so any N, C and k go in pieces of 64
+    samples by 1024 elements (each piece a launch over 256 "variables" of 4 "classes").  What the tests and the general
+    path's compute_batch feed the relaxation."""
+    W, MK, MW = N * C, _lib.IWAE_MAX_K, _lib.CAT_MAX_NC
+    out = torch.empty(n_images, k, W, device=device)
+    for j0 in range(0, k, MK):
+        kc = min(MK, k - j0)
+        for e0 in range(0, W, MW):
+            nq = (min(MW, W - e0) + 3) // 4
+            g = torch.empty(n_images * kc, 4 * nq, device=device)
+            cat_sample(None, g, None, iwae_noise(seed, tag, k, j0=j0, step=step, q0=e0 // 4), n_images, kc, nq, 4,
+                       _lib.CAT_NOISE)
+            w = min(MW, W - e0)
+            out[:, j0:j0 + kc, e0:e0 + w] = g.view(n_images, kc, 4 * nq)[:, :, :w]
+    return out.view(n_images * k, W)
+
+
 # ---- Denoising diffusion (csrc/gm_ddpm.hip, gm_ddpm.h; ddpm.py) ----------------------------------------------------
 class DdpmNoise(ctypes.Structure):
     """gm_ddpm_noise (include/gm_hip.h): seed, the two tags, the step and the first row's batch position."""

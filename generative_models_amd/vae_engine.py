@@ -17,31 +17,37 @@ class VAEEngine:
                  force_dp=False):
         self.model, self.device, self.use_graph = model, device, use_graph
         enc, dec = model.encoder, model.decoder
-        plist = [enc.linear.weight, enc.linear.bias,
-                 (enc.mu.weight, enc.log_var.weight), (enc.mu.bias, enc.log_var.bias),
+        hw, hb, Z = self._head(enc)
+        plist = [enc.linear.weight, enc.linear.bias, hw, hb,
                  dec.linear.weight, dec.linear.bias, dec.recon.weight, dec.recon.bias] + self._extra_params(model)
         self._dp_init(plist, world_size, rank, process_group, force_dp)
         self.fp = FlatParams(plist, device, grad_alloc=self._grad_alloc)
         fp = self.fp
         self.E1, self.D1, self.D2 = _Linear(fp, enc.linear), _Linear(fp, dec.linear), \
             _Linear(fp, dec.recon)
-        Z, H = enc.mu.weight.shape
+        H = hw[0].shape[1]
+        Wh = sum(w.shape[0] for w in hw)             # the packed head's width (the VAE's: 2 Z)
         self.Z, self.H, self.I = Z, H, enc.linear.weight.shape[1]
-        i_w = [i for i, p in enumerate(fp.params) if p is enc.mu.weight][0]
-        i_b = [i for i, p in enumerate(fp.params) if p is enc.mu.bias][0]
+        i_w = [i for i, p in enumerate(fp.params) if p is hw[0]][0]
+        i_b = [i for i, p in enumerate(fp.params) if p is hb[0]][0]
         o_w, o_b = fp.offsets[i_w], fp.offsets[i_b]
 
         class _Packed:          # [mu ; log_var] as one 2Z x H layer
-            W = fp.flat[o_w:o_w + 2 * Z * H].view(2 * Z, H)
-            b = fp.flat[o_b:o_b + 2 * Z]
-            gW = fp.grad[o_w:o_w + 2 * Z * H].view(2 * Z, H)
-            gb = fp.grad[o_b:o_b + 2 * Z]
-            mW, vW = fp.m[o_w:o_w + 2 * Z * H], fp.v[o_w:o_w + 2 * Z * H]
-            mb, vb = fp.m[o_b:o_b + 2 * Z], fp.v[o_b:o_b + 2 * Z]
+            W = fp.flat[o_w:o_w + Wh * H].view(Wh, H)
+            b = fp.flat[o_b:o_b + Wh]
+            gW = fp.grad[o_w:o_w + Wh * H].view(Wh, H)
+            gb = fp.grad[o_b:o_b + Wh]
+            mW, vW = fp.m[o_w:o_w + Wh * H], fp.v[o_w:o_w + Wh * H]
+            mb, vb = fp.m[o_b:o_b + Wh], fp.v[o_b:o_b + Wh]
         self.ML = _Packed
         self._common_init(device)
 
     has_eps = True              # the VAE draws eps per batch (vae.py:104); the plain AE does not
+
+    def _head(self, enc):
+        """The encoder's head as the packed layer behind its first one: (weights, biases, latent width) -- the tensors
+        packed row block after row block, the width what the decoder reads.  (CatVAEEngine: the logits layer alone.)"""
+        return (enc.mu.weight, enc.log_var.weight), (enc.mu.bias, enc.log_var.bias), enc.mu.weight.shape[0]
 
     def _extra_params(self, model):
         """Parameters a subclass packs behind the encoder's and the decoder's (NFVAEEngine: the flow's)."""
@@ -824,36 +830,46 @@ class IWAEEngine(VAEEngine):
                  trainer=None):
         if world_size > 1 or force_dp:
             raise GMError("the IWAE engine runs on one GPU: data parallelism is not implemented for it")
-        from ._lib import IWAE_MAX_K, IWAE_MAX_Z
-        k, Z = int(trainer.k), model.encoder.mu.weight.shape[0]
-        if not (1 <= k <= IWAE_MAX_K and 1 <= Z <= IWAE_MAX_Z):
-            raise GMError("IWAEEngine: 1 <= k <= %d and 1 <= z_dim <= %d (got k=%d, z_dim=%d); IWAETrainer trains "
-                          "these on the general path" % (IWAE_MAX_K, IWAE_MAX_Z, k, Z))
+        k = int(trainer.k)
+        self._check_limits(model, k)
         super().__init__(model, device, use_graph=use_graph)
         self.trainer, self.k = trainer, k            # seed and noise_steps are read from the trainer
         self.nbase = torch.zeros(1, dtype=torch.int64, device=device)
+
+    def _check_limits(self, model, k):
+        """GMError unless k and the latent width fit the sampling kernels."""
+        from ._lib import IWAE_MAX_K, IWAE_MAX_Z
+        Z = model.encoder.mu.weight.shape[0]
+        if not (1 <= k <= IWAE_MAX_K and 1 <= Z <= IWAE_MAX_Z):
+            raise GMError("IWAEEngine: 1 <= k <= %d and 1 <= z_dim <= %d (got k=%d, z_dim=%d); IWAETrainer trains "
+                          "these on the general path" % (IWAE_MAX_K, IWAE_MAX_Z, k, Z))
 
     def _alloc(self, B):
         if self._bufB == B:
             return
         dev, I, H, Z, k = self.device, self.I, self.H, self.Z, self.k
-        Hd = self.D1.W.shape[0]
+        Hd, Wh = self.D1.W.shape[0], self.ML.W.shape[0]          # Wh: the head's width (2 Z; CatVAEEngine: Z)
         z = lambda *s: torch.zeros(*s, device=dev)
-        self.X, self.He, self.ml = z(B, I), z(B, H), z(B, 2 * Z)
+        self.X, self.He, self.ml = z(B, I), z(B, H), z(B, Wh)
         self.Xb = (self.X, z(B, I))
         self.Zs, self.lp, self.wn = z(B * k, Z), z(B * k), z(B * k)
         self.Hdec, self.Xr, self.dA = z(B * k, Hd), z(B * k, I), z(B * k, I)
         self.dHdec, self.dzdec = z(B * k, Hd), z(B * k, Z)
         self.negL, self.essb = z(B), z(B)
-        self.dml, self.dHe = z(B, 2 * Z), z(B, H)
+        self.dml, self.dHe = z(B, Wh), z(B, H)
         self._bufB = B
         self.graphs = {}
+
+    def _settings(self):
+        """The run's settings beside the VAE engine's: saved in checkpoints, compared on resume, and a change drops the
+        captured graphs."""
+        return {"k": self.k, "seed": int(self.trainer.seed)}
 
     def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
         tr = self.trainer
         if int(tr.k) != self.k:
             raise GMError("IWAETrainer.k changed after the engine was built (%d -> %d)" % (self.k, int(tr.k)))
-        now = {"k": self.k, "seed": int(tr.seed)}
+        now = self._settings()
         if resume is not None and resume.get("config") is not None and not resume.get("lenient", False):
             saved = resume["config"]
             diff = {n: (saved[n], now[n]) for n in now if n in saved and saved[n] != now[n]}
@@ -871,16 +887,26 @@ class IWAEEngine(VAEEngine):
         """The batch's noise stream: training batches read ctr + nbase (eager: t + nbase) under the training tag,
         validation batches their index in the pass under the evaluation tag."""
         from . import ops_fused as of_
-        from ._lib import IWAE_TAG_EVAL, IWAE_TAG_TRAIN
-        tag, base = (IWAE_TAG_TRAIN, self.nbase) if train else (IWAE_TAG_EVAL, None)
+        tags = self._tags()
+        tag, base = (tags[0], self.nbase) if train else (tags[1], None)
         if self.use_graph:
             return of_.iwae_noise(self.trainer.seed, tag, self.k, step_ctr=self.ctr, step_base=base)
         return of_.iwae_noise(self.trainer.seed, tag, self.k, step=t, step_base=base)
 
-    def _sample(self, st, nz, b):
-        """Launch 3: z and lp of the batch's b k sample rows."""
+    def _tags(self):
+        """The noise stream's (training, evaluation) tags."""
+        from ._lib import IWAE_TAG_EVAL, IWAE_TAG_TRAIN
+        return IWAE_TAG_TRAIN, IWAE_TAG_EVAL
+
+    def _sample(self, st, nz, b, t=0, train=True):
+        """Launch 3: z and lp of the batch's b k sample rows (t, train: the batch's ring step and kind, for a
+        subclass whose sampling depends on them)."""
         from . import ops_fused as of_
         of_.iwae_sample(self.ml, self.Zs, self.lp, nz, b, self.k, self.Z, stream=st)
+
+    def _second_sum(self, b):
+        """What the batch's second sum reads: (per-image buffer, scale) -- the mean effective sample size."""
+        return self.essb, 1.0 / b
 
     def _reduce(self, st, nz, b, adam):
         """Launch 10: d loss / d [mu | lv] from dzdec and the weights."""
@@ -903,13 +929,14 @@ class IWAEEngine(VAEEngine):
         ops.linear_fwd(X, E1.W, E1.b, self.He, "relu", M=b, stream=st)
         self._fwd_with_prefetch(st, t, 0, b, self.He, ML, self.ml, "id", nxt, train=train)
         nz = self._noise(t, train)
-        self._sample(st, nz, b)
+        self._sample(st, nz, b, t, train)
         ops.linear_fwd(self.Zs, D1.W, D1.b, self.Hdec, "relu", M=b * k, stream=st)
         ops.linear_fwd(self.Hdec, D2.W, D2.b, self.Xr, "sigmoid", M=b * k, stream=st)
         of_.iwae_weights(X, self.Xr, self.lp, self.negL, self.essb, self.wn, b, k, dA=self.dA if train else None,
                          stream=st)
+        sum_b, scale_b = self._second_sum(b)
         if not train:
-            of_.sum_finalize2(self.negL, b, loss_out, loss_slot, self.essb, b, ess_out, loss_slot, scale_b=1.0 / b,
+            of_.sum_finalize2(self.negL, b, loss_out, loss_slot, sum_b, b, ess_out, loss_slot, scale_b=scale_b,
                               tick=tick, stream=st)
             return
         adam = dict(sched=self.sched, sched_slot=self._slot(t, 1, 0, 0, 1))
@@ -923,7 +950,7 @@ class IWAEEngine(VAEEngine):
         ops.linear_bwd_dx(self.dml, ML.W, self.dHe, below=self.He, epi="relu", M=b, stream=st)
         ops.linear_bwd_dw_adam_pair_finalize(
             dict(dA=self.dHe, X=X, lin=E1, adam=adam, M=b), dict(dA=self.dml, X=self.He, lin=ML, adam=adam, M=b),
-            dict(pa=self.negL, na=b, out_a=loss_out, slot_a=loss_slot, pb=self.essb, nb=b, scale_b=1.0 / b,
+            dict(pa=self.negL, na=b, out_a=loss_out, slot_a=loss_slot, pb=sum_b, nb=b, scale_b=scale_b,
                  out_b=ess_out, slot_b=loss_slot, done=self.fin_done, tick=tick),
             weight_decay=self.wd, stream=st)
 
@@ -970,7 +997,7 @@ class NFVAEEngine(IWAEEngine):
         from . import ops_fused as of_
         return of_.flow_params(self.FU, self.FW, self.Fb)
 
-    def _sample(self, st, nz, b):
+    def _sample(self, st, nz, b, t=0, train=True):
         from . import ops_fused as of_
         of_.flow_sample(self.ml, self.Zs, self.lp, nz, self._flow(), b, self.k, self.Z, stream=st)
 
@@ -980,6 +1007,78 @@ class NFVAEEngine(IWAEEngine):
                         stream=st)
         of_.flow_step(self.fpart, b, self.FU, self.FW, self.Fb, self.Fmoments, adam["sched"], adam["sched_slot"],
                       grads=self.Fgrads, weight_decay=self.wd, stream=st)
+
+
+class CatVAEEngine(IWAEEngine):
+    """The categorical VAE (catvae.py holds the contract): IWAEEngine's 12-launch batch at k = 1 with the `logits` layer
+    (width N C) as the encoder's head instead of the packed [mu | log_var], launch 3 replaced by gm_cat_sample (the
+    relaxed sample, or the straight-through one-hot with hard=True and in every validation batch; lp = -KL and the
+    per-image KL) and launch 10 by gm_cat_reduce (d loss / d logits, the Gumbel noise regenerated).  The finalize block
+    sums -L (-> `recon`) and the per-image KL (-> `kl`), scale 1.  The temperature of training batch t is entry t of a
+    device table laid out and indexed like the Adam schedule (one float per batch of the train() call), so a replayed
+    graph needs no host update; validation reads none.  One GPU only."""
+
+    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
+                 trainer=None):
+        if world_size > 1 or force_dp:
+            raise GMError("the categorical VAE engine runs on one GPU: data parallelism is not implemented for it")
+        self.N, self.C = int(model.num_vars), int(model.num_classes)
+        super().__init__(model, device, use_graph=use_graph, trainer=trainer)
+
+    def _check_limits(self, model, k):
+        from ._lib import CAT_MAX_C, CAT_MAX_NC, CAT_MIN_C
+        if k != 1 or not (self.N >= 1 and CAT_MIN_C <= self.C <= CAT_MAX_C and self.N * self.C <= CAT_MAX_NC):
+            raise GMError("CatVAEEngine: k = 1, %d <= num_classes <= %d and num_vars * num_classes <= %d (got k=%d, "
+                          "num_vars=%d, num_classes=%d); CatVAETrainer trains these on the general path"
+                          % (CAT_MIN_C, CAT_MAX_C, CAT_MAX_NC, k, self.N, self.C))
+
+    def _head(self, enc):
+        return (enc.logits.weight,), (enc.logits.bias,), enc.logits.weight.shape[0]
+
+    def _tags(self):
+        from ._lib import CAT_TAG_EVAL, CAT_TAG_TRAIN
+        return CAT_TAG_TRAIN, CAT_TAG_EVAL
+
+    def _alloc(self, B):
+        if self._bufB == B:
+            return
+        super()._alloc(B)
+        self.klrow = torch.zeros(B, device=self.device)
+
+    def _settings(self):
+        tr = self.trainer
+        now = super()._settings()
+        now.update(num_vars=self.N, num_classes=self.C, hard=bool(tr.hard), tau0=float(tr.tau0),
+                   tau_min=float(tr.tau_min), anneal_rate=float(tr.anneal_rate))
+        return now
+
+    def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
+        from .catvae import temperature
+        super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
+        tr = self.trainer
+        t0 = int(tr.noise_steps)
+        taus = np.array([temperature(t0 + i, tr.tau0, tr.tau_min, tr.anneal_rate)
+                         for i in range(max(1, n_train_steps))], dtype=np.float32)
+        self._moved = False
+        self.tau_tab = GANEngine._pbuf(self, "tau", taus)
+        if self._moved:
+            self.graphs = {}
+
+    def _second_sum(self, b):
+        return self.klrow, 1.0
+
+    def _sample(self, st, nz, b, t=0, train=True):
+        from . import ops_fused as of_
+        from ._lib import CAT_RELAXED, CAT_ST
+        relaxed = train and not self.trainer.hard
+        of_.cat_sample(self.ml, self.Zs, self.lp, nz, b, 1, self.N, self.C, CAT_RELAXED if relaxed else CAT_ST,
+                       tau_tab=self.tau_tab if relaxed else None,
+                       tau_slot=self._slot(t, 1, 0, 0, 1) if relaxed else ops.slot(), kl=self.klrow, stream=st)
+
+    def _reduce(self, st, nz, b, adam):
+        from . import ops_fused as of_
+        of_.cat_reduce(self.ml, self.dzdec, self.wn, self.dml, nz, b, self.N, self.C, tau_tab=self.tau_tab,
+                       tau_slot=adam["sched_slot"], stream=st)
 
 
 def aae_fused_ok(model):

@@ -1047,6 +1047,45 @@ typedef struct gm_flow_step_args {
  * constraint onto u and w, then gm_adam's step on u, w and b at the schedule's slot. */
 int gm_flow_step(void* stream, const gm_flow_step_args* a);
 
+/* ---- Gumbel-Softmax posterior of the categorical VAE (csrc/gm_cat.hip; catvae.py holds the contract, DESIGN.md
+ * section 23).  N categorical variables of C classes per sample row, rows image-major, gm_iwae_noise's counter layout
+ * under the two tags below: element e = n C + c of noise row `row` is word e & 3 of Philox counter (q0 + (e >> 2), step,
+ * row, tag), mapped to u in (0, 1) as every uniform here, g = -log(-log(u)).  With l = logits [N, C] of the row's image:
+ *   a = (l + g) / tau, y = softmax_c(a), q = softmax_c(l), KL_n = sum_c q_nc (log q_nc + log C).
+ * Limits: 2 <= C <= 64, N C <= 1024, 1 <= k <= 64; outside them, or with a NULL or aliased array, both entry points
+ * return GM_EINVAL before any launch.  No atomics, fixed orders. */
+#define GM_CAT_TAG_TRAIN 0x43415454u           /* "CATT" */
+#define GM_CAT_TAG_EVAL 0x43415445u            /* "CATE" */
+#define GM_CAT_MIN_C 2
+#define GM_CAT_MAX_C 64
+#define GM_CAT_MAX_NC 1024
+#define GM_CAT_RELAXED 0                       /* y = the relaxed sample, lp = -sum_n KL_n */
+#define GM_CAT_ST 1                            /* y = onehot(argmax_c (l + g)), lowest index first; lp as RELAXED */
+#define GM_CAT_DISCRETE 2                      /* y as ST, lp = -N log C - sum_n log q_n,z_n, codes written */
+#define GM_CAT_NOISE 3                         /* y = g itself; logits, lp, kl unused */
+typedef struct gm_cat_args {
+    const float* logits; int64_t ldl;         /* [B, N C] */
+    const float* tau_tab;                     /* device table read at tau_slot's index (gm_adam's schedule scheme) ... */
+    gm_slot tau_slot;
+    float tau;                                /* ... or, with tau_tab NULL, the temperature itself (> 0) */
+    int B, k, N, C, mode;
+    /* gm_cat_sample */
+    float* y; int64_t ldy;                    /* [B k, N C]: the decoder's input */
+    float* lp;                                /* [B k] */
+    float* kl;                                /* [B] = sum_n KL_n per image, or NULL (not written in DISCRETE mode) */
+    int32_t* codes;                           /* [B k, N], DISCRETE mode only */
+    /* gm_cat_reduce (k = 1) */
+    const float* dzdec; int64_t lddz;         /* [B, N C]: d loss / d y */
+    const float* wn;                          /* [B]: -d loss / d lp */
+    float* dlogits; int64_t lddl;             /* [B, N C], every element written */
+} gm_cat_args;
+/* Tau is read in RELAXED mode only. */
+int gm_cat_sample(void* stream, const gm_iwae_noise* n, const gm_cat_args* a);
+/* The backward of RELAXED and of ST (the straight-through estimator uses the relaxed one), g regenerated:
+ * da_c = y_c (dy_c - sum_c' y_c' dy_c'), dl_c = da_c / tau + wn q_c (log q_c - sum_c' q_c' log q_c'); y has
+ * gm_cat_sample's bits. */
+int gm_cat_reduce(void* stream, const gm_iwae_noise* n, const gm_cat_args* a);
+
 /* ---- Denoising diffusion (csrc/gm_ddpm.hip, gm_ddpm.h; ddpm.py holds the contract).  One
  * 256-thread workgroup per row, fixed reduction orders, no floating-point atomics.  Noise: Philox4x32-10 with key
  * (seed mod 2^32, seed >> 32); batch row `row` = row0 + the row's position in the call, step = (step_ctr ? *step_ctr :

@@ -1,0 +1,350 @@
+"""The categorical VAE without a GPU: module surface, signatures, defaults and state_dict keys, vae.py's Decoder reused,
+the refusals (constructor, temperature, codes, data parallel, iwae.log_likelihood), temperature() and its floor, the fp64
+reference's closed-form backward against autograd of its own forward (ST mode included), sum_c y = 1 and KL >= 0 with
+KL = 0 at equal logits, logits of +-60, the C-ABI of the new kernels and its refusals, struct and limit mirrors, and
+fused / general path selection."""
+import ctypes
+import inspect
+import math
+import os
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "generative_models_amd", "src"))
+sys.path.insert(0, HERE)
+
+import cat_vae  # noqa: E402
+import catvae_reference as R  # noqa: E402
+import vae  # noqa: E402
+from generative_models_amd import _lib, metrics, ops_fused  # noqa: E402
+from generative_models_amd import catvae as gcat  # noqa: E402
+from generative_models_amd import iwae as giwae  # noqa: E402
+
+NEW = ("gm_cat_sample", "gm_cat_reduce")
+
+
+def _loaders(n=40, batch=8, side=4):
+    x = torch.bernoulli(torch.full((n, 1, side, side), 0.5))
+    ds = torch.utils.data.TensorDataset(x, torch.zeros(n, dtype=torch.int64))
+    dl = lambda: torch.utils.data.DataLoader(ds, batch_size=batch, shuffle=True)
+    return dl(), dl(), dl()
+
+
+def _trainer(model, cls=None):
+    tr = object.__new__(cls or cat_vae.CatVAETrainer)    # selection runs before anything touches a GPU
+    tr.model, tr.train_iter, tr.val_iter, tr.test_iter = model, *_loaders()
+    tr.k, tr.seed, tr.hard = 1, 0, False
+    tr.tau0, tr.tau_min, tr.anneal_rate, tr.noise_steps = 1.0, 0.5, 3e-5, 0
+    return tr
+
+
+def test_module_surface_and_state_dict_keys():
+    m = cat_vae.CatVAE(16, 12, 3, 5)
+    assert list(m.state_dict()) == list(R.KEYS)
+    assert tuple(m.encoder.logits.weight.shape) == (15, 12) and tuple(m.decoder.linear.weight.shape) == (12, 15)
+    assert (m.image_size, m.hidden_dim, m.num_vars, m.num_classes, m.z_dim, m.shape) == (16, 12, 3, 5, 15, 4)
+    assert type(m.decoder) is vae.Decoder and cat_vae.Decoder is vae.Decoder              # vae.py's Decoder reused
+    assert list(m.decoder.state_dict()) == list(vae.VAE(16, 12, 15).decoder.state_dict())
+    assert cat_vae.Encoder is gcat.Encoder and cat_vae.Encoder is not vae.Encoder
+    sig = inspect.signature(cat_vae.CatVAE.__init__).parameters
+    assert [(n, p.default) for n, p in list(sig.items())[1:]] == [("image_size", 784), ("hidden_dim", 400),
+                                                                  ("num_vars", 20), ("num_classes", 10)]
+    sig = inspect.signature(cat_vae.CatVAETrainer.__init__).parameters
+    assert (sig["seed"].default, sig["hard"].default, sig["viz"].default) == (0, False, False)
+    assert sig["seed"].kind is inspect.Parameter.KEYWORD_ONLY and sig["hard"].kind is inspect.Parameter.KEYWORD_ONLY
+    sig = inspect.signature(cat_vae.CatVAETrainer.train).parameters
+    assert [(n, p.default) for n, p in list(sig.items())[2:]] == [
+        ("lr", 1e-3), ("weight_decay", 1e-5), ("tau0", 1.0), ("tau_min", 0.5), ("anneal_rate", 3e-5), ("quiet", False)]
+    sig = inspect.signature(cat_vae.CatVAETrainer.log_likelihood).parameters
+    assert (sig["images"].default, sig["k"].default, sig["seed"].default) == (None, 500, 0)
+    sig = inspect.signature(cat_vae.CatVAETrainer.posterior_codes).parameters
+    assert [n for n in sig][1:] == ["images", "k", "seed"] and sig["seed"].default == 0
+    sig = inspect.signature(cat_vae.temperature).parameters
+    assert [n for n in sig] == ["t", "tau0", "tau_min", "anneal_rate"]
+    for name in ("sample", "parzen", "log_likelihood", "posterior_codes", "codes", "decode", "save_checkpoint",
+                 "load_checkpoint"):
+        assert callable(getattr(cat_vae.CatVAETrainer, name))
+    for name in ("Encoder", "Decoder", "CatVAE", "CatVAETrainer", "CatVAEError", "temperature", "get_data", "to_cuda"):
+        assert hasattr(cat_vae, name), name
+    assert issubclass(gcat.CatVAEError, _lib.GMError) and issubclass(gcat.CatVAEError, ValueError)
+    import generative_models_amd as pkg
+    from generative_models_amd.engine import CatVAEEngine, IWAEEngine
+    assert pkg.CatVAE is gcat.CatVAE and pkg.CatVAETrainer is gcat.CatVAETrainer and pkg.CatVAEEngine is CatVAEEngine
+    assert issubclass(CatVAEEngine, IWAEEngine) and issubclass(gcat.CatVAETrainer, giwae.IWAETrainer)
+    for f in ("_sample", "_reduce", "_alloc", "_head", "_second_sum", "_tags", "_settings", "_check_limits"):
+        assert f in CatVAEEngine.__dict__ and f in IWAEEngine.__dict__ or f == "_head", f
+    assert gcat.__doc__ and "RELAXED" in gcat.__doc__ and "DISCRETE" in gcat.__doc__
+    assert metrics.IWAEResult._fields == ("ll_mean", "ll_stderr", "k", "n")
+    assert len({gcat.TAG_TRAIN, gcat.TAG_EVAL, giwae.TAG_TRAIN, giwae.TAG_EVAL, _lib.MADE_TAG_S, _lib.DDPM_TAG_T,
+                _lib.DDPM_TAG_E, _lib.DDPM_TAG_V, _lib.DDPM_TAG_VE, _lib.DDPM_TAG_S}) == 10          # tags of its own
+
+
+@pytest.mark.parametrize("kw", [dict(num_vars=0), dict(num_vars=-1), dict(num_vars=2.0), dict(num_vars=True),
+                                dict(num_vars=None), dict(num_classes=1), dict(num_classes=0), dict(num_classes=2.5),
+                                dict(num_classes=False)])
+def test_constructor_refusals(kw):
+    with pytest.raises(gcat.CatVAEError):
+        cat_vae.CatVAE(16, 12, **kw)
+    with pytest.raises(ValueError):
+        cat_vae.CatVAE(16, 12, **kw)
+
+
+@pytest.mark.parametrize("kw", [dict(seed=-1), dict(seed=1 << 64), dict(seed=1.5)])
+def test_trainer_argument_refusals(kw):
+    with pytest.raises(giwae.IWAEError):
+        cat_vae.CatVAETrainer(cat_vae.CatVAE(16, 12, 3, 4), *_loaders(), **kw)
+    with pytest.raises(gcat.CatVAEError):
+        cat_vae.CatVAETrainer(cat_vae.CatVAE(16, 12, 3, 4), *_loaders(), hard=1)
+
+
+@pytest.mark.parametrize("kw", [dict(tau_min=0.0), dict(tau_min=-0.1), dict(tau0=0.4, tau_min=0.5),
+                                dict(anneal_rate=-1e-5), dict(tau0=float("nan")), dict(tau0=float("inf")),
+                                dict(tau_min="x")])
+def test_temperature_refusals(kw):
+    with pytest.raises(gcat.CatVAEError):
+        cat_vae.temperature(3, **kw)
+    tr = _trainer(cat_vae.CatVAE(16, 12, 3, 4))
+    with pytest.raises(gcat.CatVAEError):
+        tr.train(1, **kw)                                                 # before anything runs
+    for t in (-1, 1.5, True):
+        with pytest.raises(gcat.CatVAEError):
+            cat_vae.temperature(t)
+
+
+def test_temperature_values_and_floor():
+    assert cat_vae.temperature(0) == 1.0 and cat_vae.temperature(0, 2.0, 0.5, 0.1) == 2.0
+    for t in (1, 10, 1000, 20000):
+        want = float(np.float32(max(0.5, math.exp(-3e-5 * t))))
+        assert cat_vae.temperature(t) == want and cat_vae.temperature(t, 1.0, 0.5, 3e-5) == want
+    assert cat_vae.temperature(23104) > 0.5 and cat_vae.temperature(23105) == 0.5       # ln 2 / 3e-5 = 23104.9
+    assert cat_vae.temperature(10 ** 9) == 0.5 and cat_vae.temperature(5, 0.7, 0.7, 1.0) == float(np.float32(0.7))
+    assert cat_vae.temperature(7, 1.0, 0.1, 0.0) == 1.0
+    v = cat_vae.temperature(3, 1.0, 0.1, 0.25)
+    assert isinstance(v, float) and v == float(np.float32(v)) and abs(v - math.exp(-0.75)) <= 2.0 ** -25
+    ts = [cat_vae.temperature(t, 1.0, 0.5, 0.4) for t in range(6)]
+    assert ts == sorted(ts, reverse=True) and ts[0] == 1.0 and ts[1] < 1.0 and ts[2:] == [0.5] * 4
+
+
+def _rows(N, C, B, seed=0, scale=1.5):
+    gen = torch.Generator().manual_seed(seed)
+    l = torch.randn(B, N * C, generator=gen, dtype=torch.float64) * scale
+    g = R.gumbel(R.philox_words(B, N * C, 9, 4, gcat.TAG_TRAIN))
+    dy = torch.randn(B, N * C, generator=gen, dtype=torch.float64)
+    wn = torch.rand(B, generator=gen, dtype=torch.float64) + 0.5
+    return l.numpy(), g, dy.numpy(), wn.numpy()
+
+
+@pytest.mark.parametrize("N,C,B", [(1, 2, 5), (3, 5, 7), (20, 10, 9), (4, 64, 3)])
+def test_reference_closed_form_backward_is_autograds(N, C, B):
+    l, g, dy, wn = _rows(N, C, B)
+    for tau in (1.0, 0.5, 0.1):
+        closed = R.dlogits_closed(l, g, N, C, tau, dy, wn)
+        for hard in (False, True):                                        # ST: the same backward, with the relaxed y
+            auto = R.rows_reference(l, g, N, C, 1, tau, dy=dy, wn=wn, hard=hard)["dlogits"]
+            err = np.abs(auto - closed).max() / np.abs(closed).max()
+            assert err <= 1e-13, (tau, hard, err)
+    # the package's torch relaxation (the general path) is the same function
+    lt, gt = torch.tensor(l, requires_grad=True), torch.tensor(g)
+    for hard in (False, True):
+        z = gcat.gumbel_softmax(lt, gt, 0.5, N, C, hard=hard)
+        ref = R.rows_reference(l, g, N, C, 1, 0.5)
+        assert np.abs(z.detach().numpy() - ref["onehot" if hard else "y"]).max() <= 1e-14
+    assert np.abs(gcat.categorical_kl(lt, N, C).detach().numpy() - ref["kl"]).max() <= 1e-12
+
+
+def test_reference_noise_mapping():
+    words = np.array([[0, 511, 512, 0xFFFFFFFF, 0x80000000]], dtype=np.uint64)
+    u = R.unit(words)
+    assert u.min() == 2.0 ** -24 and u.max() == 1.0 - 2.0 ** -24 and u[0, 1] == u[0, 0] and u[0, 2] == 3 * 2.0 ** -24
+    g = R.gumbel(words)
+    assert np.isfinite(g).all() and g.min() > -2.82 and g.max() < 16.64           # finite for every word
+    w = R.philox_words(5, 30, 7, 3, gcat.TAG_EVAL)
+    assert w.shape == (5, 30) and not np.array_equal(w, R.philox_words(5, 30, 7, 3, gcat.TAG_TRAIN))
+    assert np.array_equal(w[:, :8], R.philox_words(5, 8, 7, 3, gcat.TAG_EVAL))    # element e is a function of e alone
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_simplex_kl_sign_and_extreme_logits(dtype):
+    N, C, B = 6, 5, 8
+    l, g, dy, _ = _rows(N, C, B)
+    r = R.rows_reference(l, g, N, C, 1, 0.5, dtype, dy=dy)
+    eps = 1e-12 if dtype == torch.float64 else 1e-5
+    assert np.abs(r["y"].reshape(B, N, C).sum(-1) - 1).max() <= eps and r["y"].min() >= 0
+    assert (r["kl"] >= -eps).all() and r["kl"].min() > 1e-3 and np.allclose(r["lp"], -r["kl"])
+    assert (r["lp_discrete"] + N * math.log(C) <= eps - r["log_q"]).all() and (r["log_q"] <= 0).all()
+    z = R.rows_reference(np.full((B, N * C), 3.25), g, N, C, 1, 0.5, dtype)
+    assert np.abs(z["kl"]).max() <= eps                                   # KL = 0 at equal logits
+    gen = torch.Generator().manual_seed(1)
+    ext = torch.where(torch.rand(B, N * C, generator=gen) < 0.5, -60.0, 60.0).numpy()
+    ext[0] = 60.0
+    for tau in (1.0, 0.1):
+        for hard in (False, True):
+            e = R.rows_reference(ext, g, N, C, 1, tau, dtype, dy=dy, hard=hard)
+            for n in ("y", "lp", "kl", "log_q", "lp_discrete", "dlogits"):
+                assert np.isfinite(e[n]).all(), (n, tau, hard)            # q = 0 contributes 0, never NaN
+            assert np.abs(e["y"].reshape(B, N, C).sum(-1) - 1).max() <= eps and (e["kl"] >= -eps).all()
+    P = {n: v.detach().double().numpy() for n, v in cat_vae.CatVAE(16, 12, N, C).state_dict().items()}
+    x = np.random.RandomState(0).rand(B, 16)
+    for mode in ("relaxed", "hard", "eval"):
+        out = R.model_reference(P, x, g, N, C, 0.7, mode, dtype)
+        assert math.isfinite(out["loss"]) and out["kl"] >= -eps and ("grads" in out) == (mode != "eval")
+
+
+def test_new_symbols_are_declared_and_bound():
+    lib = _lib.load()
+    declared = _lib.declared_symbols()
+    for name in NEW:
+        assert name in declared and name in _lib._SIGNATURES and hasattr(lib, name), name
+    assert (_lib.CAT_MIN_C, _lib.CAT_MAX_C, _lib.CAT_MAX_NC) == (2, 64, 1024)
+    assert (_lib.CAT_RELAXED, _lib.CAT_ST, _lib.CAT_DISCRETE, _lib.CAT_NOISE) == (0, 1, 2, 3)
+    hdr = open(os.path.join(os.path.dirname(HERE), "include", "gm_hip.h")).read()
+    for line in ("#define GM_CAT_MIN_C 2", "#define GM_CAT_MAX_C 64", "#define GM_CAT_MAX_NC 1024",
+                 "#define GM_CAT_RELAXED 0", "#define GM_CAT_ST 1", "#define GM_CAT_DISCRETE 2", "#define GM_CAT_NOISE 3",
+                 "#define GM_CAT_TAG_TRAIN 0x%08Xu" % _lib.CAT_TAG_TRAIN, "#define GM_CAT_TAG_EVAL 0x%08Xu" % _lib.CAT_TAG_EVAL):
+        assert line in hdr, line
+    from generative_models_amd import _build
+    assert "gm_cat.hip" in _build.SOURCES
+
+
+def test_kernels_reject_null_out_of_range_and_aliased_arguments():
+    """Host arrays stand in for device ones: every call below must return before it launches anything."""
+    lib = _lib.load()
+    a = [np.zeros(4096, dtype=np.float32) for _ in range(10)]
+    p = lambda i: a[i].ctypes.data
+    names = [n for n, _ in ops_fused.CatArgs._fields_]
+    B, k, N, C = 4, 2, 3, 5
+
+    def args(**kw):
+        v = dict(logits=p(0), ldl=N * C, tau_tab=None, tau_slot=_lib.NO_SLOT, tau=0.5, B=B, k=k, N=N, C=C,
+                 mode=_lib.CAT_RELAXED, y=p(1), ldy=N * C, lp=p(2), kl=p(3), codes=p(4), dzdec=p(5), lddz=N * C, wn=p(6),
+                 dlogits=p(7), lddl=N * C)
+        v.update(kw)
+        return ops_fused.CatArgs(*[v[n] for n in names])
+    noise = ops_fused.IwaeNoise(0, gcat.TAG_TRAIN, None, None, 0, 2, 0, 0)
+    nz = ctypes.byref(noise)
+    bad_noise = [ops_fused.IwaeNoise(0, 1, None, None, 0, 1, 0, 0),       # k_total < k
+                 ops_fused.IwaeNoise(0, 1, None, None, 0, 2, -1, 0), ops_fused.IwaeNoise(0, 1, None, None, 0, 2, 0, -1)]
+    shape = [dict(B=0), dict(k=0), dict(k=65), dict(N=0), dict(C=1), dict(C=65), dict(N=103, C=10), dict(N=17, C=64),
+             dict(mode=-1), dict(mode=4)]
+    sample = shape + [dict(y=None), dict(ldy=N * C - 1), dict(logits=None), dict(ldl=N * C - 1), dict(lp=None),
+                      dict(y=p(0)), dict(lp=p(0)), dict(lp=p(1)), dict(kl=p(2)), dict(kl=p(1)), dict(kl=p(0)),
+                      dict(tau=0.0), dict(tau=-1.0), dict(tau=float("inf")), dict(tau=float("nan")),
+                      dict(mode=_lib.CAT_DISCRETE, codes=None), dict(mode=_lib.CAT_NOISE, y=None)]
+    assert lib.gm_cat_sample(None, nz, None) == _lib.GM_EINVAL
+    assert lib.gm_cat_sample(None, None, ctypes.byref(args())) == _lib.GM_EINVAL
+    for kw in sample:
+        assert lib.gm_cat_sample(None, nz, ctypes.byref(args(**kw))) == _lib.GM_EINVAL, kw
+        assert b"bad argument" in lib.gm_last_error()
+    for n in bad_noise:
+        assert lib.gm_cat_sample(None, ctypes.byref(n), ctypes.byref(args())) == _lib.GM_EINVAL
+    red = dict(k=1)
+    reduce = [dict(k=2), dict(B=0), dict(N=0), dict(C=1), dict(C=65), dict(N=103, C=10), dict(mode=_lib.CAT_DISCRETE),
+              dict(mode=_lib.CAT_NOISE), dict(logits=None), dict(dzdec=None), dict(wn=None), dict(dlogits=None),
+              dict(ldl=N * C - 1), dict(lddz=N * C - 1), dict(lddl=N * C - 1), dict(dlogits=p(0)), dict(dlogits=p(5)),
+              dict(dlogits=p(6)), dict(tau=0.0), dict(tau=float("nan"))]
+    assert lib.gm_cat_reduce(None, nz, None) == _lib.GM_EINVAL
+    assert lib.gm_cat_reduce(None, None, ctypes.byref(args(**red))) == _lib.GM_EINVAL
+    for kw in reduce:
+        assert lib.gm_cat_reduce(None, nz, ctypes.byref(args(**dict(red, **kw)))) == _lib.GM_EINVAL, kw
+        assert b"bad argument" in lib.gm_last_error()
+    for t in a:
+        assert not t.any()                                               # nothing was written
+    with pytest.raises(_lib.GMError):
+        _lib.call("gm_cat_sample", None, None, None)
+
+
+def test_struct_layout_matches_the_c_header(tmp_path):
+    gcc = shutil.which("gcc") or shutil.which("cc")
+    if gcc is None:
+        pytest.skip("no host C compiler")
+    structs = {"gm_cat_args": ops_fused.CatArgs}
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "gm_hip.h"', 'int main(void) {']
+    for cname, ct in structs.items():
+        lines.append('printf("%s size %%zu\\n", sizeof(%s));' % (cname, cname))
+        for fname, _ in ct._fields_:
+            lines.append('printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, fname, cname, fname))
+    lines += ['return 0;', '}']
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "layout"
+    subprocess.run([gcc, "-I", os.path.join(os.path.dirname(HERE), "include"), str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    seen = 0
+    for line in out.splitlines():
+        cname, field, val = line.split()
+        ct = structs[cname]
+        if field == "size":
+            assert ctypes.sizeof(ct) == int(val), (cname, ctypes.sizeof(ct), val)
+        else:
+            assert getattr(ct, field).offset == int(val), (cname, field)
+        seen += 1
+    assert seen == sum(len(ct._fields_) + 1 for ct in structs.values())
+
+
+class _Mine(cat_vae.CatVAETrainer):
+    def compute_batch(self, batch):
+        return super().compute_batch(batch)
+
+
+def test_path_selection():
+    assert _trainer(cat_vae.CatVAE(16, 12, 3, 5))._stock()
+    assert _trainer(cat_vae.CatVAE(16, 12, 16, 64))._stock() and _trainer(cat_vae.CatVAE(16, 12, 512, 2))._stock()  # limits
+    assert _trainer(cat_vae.CatVAE(16, 12, 1, 2))._stock()
+    assert not _trainer(cat_vae.CatVAE(16, 12, 3, 65))._stock()                    # C above the limit
+    assert not _trainer(cat_vae.CatVAE(16, 12, 103, 10))._stock()                  # N C above the limit
+    assert not _trainer(cat_vae.CatVAE(16, 12, 3, 5), cls=_Mine)._stock()          # an overridden hook
+    m = cat_vae.CatVAE(16, 12, 3, 5)
+    m.encoder.extra = torch.nn.Linear(2, 2)
+    assert not _trainer(m)._stock()                                                # an edited encoder
+    m = cat_vae.CatVAE(16, 12, 3, 5)
+    m.encoder.logits = torch.nn.Linear(12, 16)
+    assert not _trainer(m)._stock()                                                # a head of another width
+    m = cat_vae.CatVAE(16, 12, 3, 5)
+    m.encoder = vae.Encoder(16, 12, 15)
+    assert not _trainer(m)._stock()                                                # another encoder
+
+    class Sub(cat_vae.CatVAE):
+        pass
+    assert not _trainer(Sub(16, 12, 3, 5))._stock()                                # a subclassed model
+    tr = _trainer(cat_vae.CatVAE(16, 12, 3, 5))
+    tr.k = 2
+    assert not tr._stock()                                                         # k > 1 training is out of scope
+
+
+def test_data_parallel_is_refused():
+    from generative_models_amd.engine import CatVAEEngine
+    m = cat_vae.CatVAE(16, 12, 3, 5)
+    for kw in (dict(world_size=2), dict(force_dp=True)):
+        with pytest.raises(_lib.GMError, match="one GPU"):
+            CatVAEEngine(m, "cpu", trainer=_trainer(m), **kw)
+    tr = _trainer(m)
+    tr.force_dp = True
+    with pytest.raises(_lib.GMError, match="one GPU"):
+        tr.train(1)
+    with pytest.raises(_lib.GMError, match="general path"):
+        CatVAEEngine(cat_vae.CatVAE(16, 12, 3, 65), "cpu", trainer=_trainer(m))    # outside the limits: refused, no launch
+
+
+def test_bad_codes_are_refused():
+    tr = _trainer(cat_vae.CatVAE(16, 12, 3, 5))
+    ok = torch.zeros(4, 3, dtype=torch.int64)
+    for bad in (ok[:, :2], ok.float(), ok - 1, ok + 5, ok == 0, ok[0]):
+        with pytest.raises(ValueError):
+            tr.decode(bad)
+
+
+def test_iwae_log_likelihood_refuses_the_model():
+    tr = _trainer(cat_vae.CatVAE(16, 12, 3, 5))
+    with pytest.raises(_lib.GMError, match="Encoder"):
+        giwae.log_likelihood(tr, torch.zeros(2, 16), 3, 0)
+    own = cat_vae.CatVAETrainer.__dict__["log_likelihood"]
+    src = inspect.getsource(own)
+    assert "cat_sample" in src and "CAT_DISCRETE" in src and "iwae_sample" not in src
+    assert "cat_sample" in inspect.getsource(cat_vae.CatVAETrainer.posterior_codes)

@@ -83,8 +83,12 @@ def host_thread_plan():
 
 def __getattr__(name):
     """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine, SNGAN / SNGANTrainer / SNGANEngine,
-    DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine, NFVAE / NFVAETrainer / NFVAEEngine and CatVAE /
-    CatVAETrainer / CatVAEEngine, imported on first use (importing the package stays free of torch)."""
+    DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine, NFVAE / NFVAETrainer / NFVAEEngine, CatVAE /
+    CatVAETrainer / CatVAEEngine and RealNVP / RealNVPTrainer / RealNVPEngine, imported on first use (importing the
+    package stays free of torch)."""
+    if name in ("RealNVP", "RealNVPTrainer", "RealNVPEngine"):
+        from . import realnvp
+        return getattr(realnvp, name)
     if name in ("CatVAE", "CatVAETrainer"):
         from . import catvae
         return getattr(catvae, name)

@@ -141,6 +141,13 @@ MADE_TAG_S = 0x4D414453                                     # GM_MADE_TAG_S ("MA
 MADE_MIN_I, MADE_MAX_I, MADE_MAX_H = 2, 8192, 1024          # GM_MADE_* (include/gm_hip.h)
 # (gm_made_mask_args / gm_made_sample_args travel by pointer; their ctypes forms live in ops_fused)
 
+NVP_TAG_TRAIN, NVP_TAG_EVAL, NVP_TAG_S = 0x4E565044, 0x4E565056, 0x4E565053     # GM_NVP_TAG_* ("NVPD", "NVPV", "NVPS")
+NVP_MIN_D, NVP_MAX_D, NVP_MAX_H, NVP_MAX_K = 2, 8192, 1024, 16              # GM_NVP_* (include/gm_hip.h)
+NVP_MAX_LEVELS, NVP_MAX_S_CAP = 65536, 8
+NVP_CHECKER, NVP_HALF = 0, 1                                # GM_NVP_CHECKER / GM_NVP_HALF
+NVP_PRE, NVP_NOISE, NVP_POST, NVP_PRIOR = 0, 1, 0, 1        # gm_nvp_pre's and gm_nvp_post's modes
+# (the gm_nvp_*_args travel by pointer; their ctypes forms live in ops_fused)
+
 NOISE = {"salt_pepper": 1, "gaussian": 2}       # GM_NOISE_SALT_PEPPER, GM_NOISE_GAUSSIAN (GM_NOISE_NONE = 0)
 
 
@@ -385,6 +392,11 @@ _SIGNATURES = {
     "gm_made_mask": (c_int, [_P, _P]),
     "gm_made_sample": (c_int, [_P, _P]),
     "gm_made_uniform": (c_int, [_P, _P, c_int64, ctypes.c_uint64, c_int64, c_int64, c_int]),
+    "gm_nvp_pre": (c_int, [_P, _P]),
+    "gm_nvp_couple": (c_int, [_P, _P]),
+    "gm_nvp_loss": (c_int, [_P, _P]),
+    "gm_nvp_couple_bwd": (c_int, [_P, _P]),
+    "gm_nvp_post": (c_int, [_P, _P]),
 }
 
 _lib = None

@@ -1215,3 +1215,168 @@ def made_uniform(n, I, seed, row0=0, device="cuda", stream=None):
     u = torch.empty(n, I, device=device)
     _lib.call("gm_made_uniform", stream or stream_ptr(), u.data_ptr(), _ld(u), int(seed), int(row0), int(n), int(I))
     return u
+
+
+# ---- RealNVP coupling flow (csrc/gm_nvp.hip, gm_nvp.h; realnvp.py) ---------------------------------------------------
+class NvpPreArgs(ctypes.Structure):
+    """gm_nvp_pre_args (include/gm_hip.h): dequantise + logit + split, or the noise alone."""
+    _fields_ = [("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("ya", ctypes.c_void_p), ("lda", ctypes.c_int64),
+                ("yb", ctypes.c_void_p), ("ldb", ctypes.c_int64), ("logdet", ctypes.c_void_p), ("u", ctypes.c_void_p),
+                ("ldu", ctypes.c_int64), ("seed", ctypes.c_uint64), ("step_ctr", ctypes.c_void_p),
+                ("step_base", ctypes.c_void_p), ("step_add", ctypes.c_int64), ("row0", ctypes.c_int64),
+                ("tag", ctypes.c_uint32), ("alpha", ctypes.c_float), ("levels", ctypes.c_int), ("mask", ctypes.c_int),
+                ("mode", ctypes.c_int), ("B", ctypes.c_int), ("D", ctypes.c_int)]
+
+
+class NvpCoupleArgs(ctypes.Structure):
+    """gm_nvp_couple_args (include/gm_hip.h): one affine coupling, forward or inverse."""
+    _fields_ = [("st", ctypes.c_void_p), ("ldst", ctypes.c_int64), ("inp", ctypes.c_void_p), ("ldin", ctypes.c_int64),
+                ("out", ctypes.c_void_p), ("ldout", ctypes.c_int64), ("logdet", ctypes.c_void_p),
+                ("s_cap", ctypes.c_float), ("inverse", ctypes.c_int), ("B", ctypes.c_int), ("Dt", ctypes.c_int)]
+
+
+class NvpLossArgs(ctypes.Structure):
+    """gm_nvp_loss_args (include/gm_hip.h): the rows' negative log-likelihood and dz."""
+    _fields_ = [("za", ctypes.c_void_p), ("ldza", ctypes.c_int64), ("zb", ctypes.c_void_p), ("ldzb", ctypes.c_int64),
+                ("logdet", ctypes.c_void_p), ("part", ctypes.c_void_p), ("dza", ctypes.c_void_p),
+                ("lddza", ctypes.c_int64), ("dzb", ctypes.c_void_p), ("lddzb", ctypes.c_int64), ("cst", ctypes.c_float),
+                ("scale", ctypes.c_float), ("B", ctypes.c_int), ("Da", ctypes.c_int), ("Db", ctypes.c_int)]
+
+
+class NvpCoupleBwdArgs(ctypes.Structure):
+    """gm_nvp_couple_bwd_args (include/gm_hip.h): the coupling's backward."""
+    _fields_ = [("st", ctypes.c_void_p), ("ldst", ctypes.c_int64), ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64),
+                ("g0", ctypes.c_void_p), ("ldg0", ctypes.c_int64), ("g1", ctypes.c_void_p), ("ldg1", ctypes.c_int64),
+                ("dst", ctypes.c_void_p), ("lddst", ctypes.c_int64), ("dx", ctypes.c_void_p), ("lddx", ctypes.c_int64),
+                ("c", ctypes.c_float), ("s_cap", ctypes.c_float), ("B", ctypes.c_int), ("Dt", ctypes.c_int)]
+
+
+class NvpPostArgs(ctypes.Structure):
+    """gm_nvp_post_args (include/gm_hip.h): halves -> image, or the sampler's normals -> halves."""
+    _fields_ = [("ya", ctypes.c_void_p), ("lda", ctypes.c_int64), ("yb", ctypes.c_void_p), ("ldb", ctypes.c_int64),
+                ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("seed", ctypes.c_uint64), ("row0", ctypes.c_int64),
+                ("alpha", ctypes.c_float), ("temperature", ctypes.c_float), ("mask", ctypes.c_int), ("mode", ctypes.c_int),
+                ("B", ctypes.c_int), ("D", ctypes.c_int)]
+
+
+NVP_MASKS = {"checker": _lib.NVP_CHECKER, "half": _lib.NVP_HALF}
+
+
+def _nvp_rows(t, B, W, name):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= B
+            and t.shape[1] >= W):
+        raise _lib.GMError("%s must be a float32 device tensor of at least [%d, %d] with contiguous rows" % (name, B, W))
+    return t
+
+
+def _nvp_vec(t, B, name):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= B):
+        raise _lib.GMError("%s must be a contiguous float32 device tensor of %d elements" % (name, B))
+    return t
+
+
+def _nvp_seed(seed):
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise _lib.GMError("the seed must lie in [0, 2^64)")
+    return seed
+
+
+def _nvp_mask(mask):
+    return NVP_MASKS[mask] if isinstance(mask, str) else int(mask)
+
+
+def _nvp_noise(a, seed, tag, step, step_ctr, step_base, row0):
+    for t, nm in ((step_ctr, "step_ctr"), (step_base, "step_base")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int64):
+            raise _lib.GMError("%s must be an int64 device tensor" % nm)
+    a.seed, a.tag, a.step_add, a.row0 = _nvp_seed(seed), int(tag), int(step), int(row0)
+    a.step_ctr = step_ctr.data_ptr() if step_ctr is not None else None
+    a.step_base = step_base.data_ptr() if step_base is not None else None
+
+
+def nvp_pre(x, ya, yb, logdet, B, seed, tag, alpha, levels, mask, step=0, step_ctr=None, step_base=None, row0=0,
+            stream=None):
+    """Dequantise + logit + split of rows x [B, D] into ya [B, Da], yb [B, Db] and the rows' preprocessing
+    log-determinant (gm_nvp_pre); the noise step is *step_ctr + *step_base + step."""
+    D = x.shape[1]
+    a = NvpPreArgs()
+    _nvp_rows(x, B, D, "x"), _nvp_rows(ya, B, (D + 1) // 2, "ya"), _nvp_rows(yb, B, D // 2, "yb")
+    a.x, a.ldx, a.ya, a.lda, a.yb, a.ldb = x.data_ptr(), _ld(x), ya.data_ptr(), _ld(ya), yb.data_ptr(), _ld(yb)
+    a.logdet = _nvp_vec(logdet, B, "logdet").data_ptr()
+    _nvp_noise(a, seed, tag, step, step_ctr, step_base, row0)
+    a.alpha, a.levels, a.mask, a.mode, a.B, a.D = float(alpha), int(levels), _nvp_mask(mask), _lib.NVP_PRE, B, D
+    _lib.call("gm_nvp_pre", stream or stream_ptr(), ctypes.byref(a))
+
+
+def nvp_uniforms(n, D, seed, tag, step=0, row0=0, device="cuda", stream=None):
+    """u [n, D]: the dequantisation noise gm_nvp_pre draws for (seed, tag, step) on rows row0 .., through its NOISE
+    mode, bit for bit: what the general path and the tests feed the preprocessing."""
+    u = torch.empty(n, D, device=device)
+    a = NvpPreArgs()
+    a.u, a.ldu, a.mode, a.B, a.D = u.data_ptr(), _ld(u), _lib.NVP_NOISE, n, D
+    _nvp_noise(a, seed, tag, step, None, None, row0)
+    _lib.call("gm_nvp_pre", stream or stream_ptr(), ctypes.byref(a))
+    return u
+
+
+def nvp_couple(st, inp, out, B, Dt, s_cap, logdet=None, inverse=False, stream=None):
+    """out = inp exp(s) + t and logdet += sum s, or (inverse) out = (inp - t) exp(-s), with s = s_cap tanh(st[:, :Dt]),
+    t = st[:, Dt:] (gm_nvp_couple)."""
+    a = NvpCoupleArgs()
+    _nvp_rows(st, B, 2 * Dt, "st"), _nvp_rows(inp, B, Dt, "inp"), _nvp_rows(out, B, Dt, "out")
+    a.st, a.ldst, a.inp, a.ldin, a.out, a.ldout = st.data_ptr(), _ld(st), inp.data_ptr(), _ld(inp), out.data_ptr(), _ld(out)
+    if not inverse:
+        a.logdet = _nvp_vec(logdet, B, "logdet").data_ptr()
+    a.s_cap, a.inverse, a.B, a.Dt = float(s_cap), 1 if inverse else 0, B, Dt
+    _lib.call("gm_nvp_couple", stream or stream_ptr(), ctypes.byref(a))
+
+
+def nvp_loss(za, zb, logdet, part, B, cst, scale=1.0, dza=None, dzb=None, stream=None):
+    """part[r] = 0.5 sum z^2 - logdet[r] + cst and, with dza / dzb, dz = z scale (gm_nvp_loss)."""
+    Da, Db = za.shape[1], zb.shape[1]
+    a = NvpLossArgs()
+    _nvp_rows(za, B, Da, "za"), _nvp_rows(zb, B, Db, "zb")
+    a.za, a.ldza, a.zb, a.ldzb = za.data_ptr(), _ld(za), zb.data_ptr(), _ld(zb)
+    a.logdet, a.part = _nvp_vec(logdet, B, "logdet").data_ptr(), _nvp_vec(part, B, "part").data_ptr()
+    if dza is not None or dzb is not None:
+        _nvp_rows(dza, B, Da, "dza"), _nvp_rows(dzb, B, Db, "dzb")
+        a.dza, a.lddza, a.dzb, a.lddzb = dza.data_ptr(), _ld(dza), dzb.data_ptr(), _ld(dzb)
+    a.cst, a.scale, a.B, a.Da, a.Db = float(cst), float(scale), B, Da, Db
+    _lib.call("gm_nvp_loss", stream or stream_ptr(), ctypes.byref(a))
+
+
+def nvp_couple_bwd(st, x, g0, dst, B, Dt, s_cap, c, g1=None, dx=None, stream=None):
+    """dst[:, :Dt] = (g x exp(s) + c) s_cap (1 - tanh^2), dst[:, Dt:] = g, dx = g exp(s), with g = g0 (+ g1)
+    (gm_nvp_couple_bwd)."""
+    a = NvpCoupleBwdArgs()
+    _nvp_rows(st, B, 2 * Dt, "st"), _nvp_rows(x, B, Dt, "x"), _nvp_rows(g0, B, Dt, "g0"), _nvp_rows(dst, B, 2 * Dt, "dst")
+    a.st, a.ldst, a.x, a.ldx, a.g0, a.ldg0 = st.data_ptr(), _ld(st), x.data_ptr(), _ld(x), g0.data_ptr(), _ld(g0)
+    a.dst, a.lddst = dst.data_ptr(), _ld(dst)
+    if g1 is not None:
+        a.g1, a.ldg1 = _nvp_rows(g1, B, Dt, "g1").data_ptr(), _ld(g1)
+    if dx is not None:
+        a.dx, a.lddx = _nvp_rows(dx, B, Dt, "dx").data_ptr(), _ld(dx)
+    a.c, a.s_cap, a.B, a.Dt = float(c), float(s_cap), B, Dt
+    _lib.call("gm_nvp_couple_bwd", stream or stream_ptr(), ctypes.byref(a))
+
+
+def nvp_post(ya, yb, x, B, alpha, mask, stream=None):
+    """x [B, D] = clamp((sigmoid(y) - alpha) / (1 - 2 alpha), 0, 1) from the halves (gm_nvp_post)."""
+    D = x.shape[1]
+    a = NvpPostArgs()
+    _nvp_rows(ya, B, (D + 1) // 2, "ya"), _nvp_rows(yb, B, D // 2, "yb"), _nvp_rows(x, B, D, "x")
+    a.ya, a.lda, a.yb, a.ldb, a.x, a.ldx = ya.data_ptr(), _ld(ya), yb.data_ptr(), _ld(yb), x.data_ptr(), _ld(x)
+    a.alpha, a.mask, a.mode, a.B, a.D = float(alpha), _nvp_mask(mask), _lib.NVP_POST, B, D
+    _lib.call("gm_nvp_post", stream or stream_ptr(), ctypes.byref(a))
+
+
+def nvp_prior(za, zb, B, D, seed, mask, temperature=1.0, row0=0, stream=None):
+    """The sampler's starting normals of rows row0 .. as halves za [B, Da], zb [B, Db], scaled by the temperature
+    (gm_nvp_post's PRIOR mode)."""
+    a = NvpPostArgs()
+    _nvp_rows(za, B, (D + 1) // 2, "za"), _nvp_rows(zb, B, D // 2, "zb")
+    a.ya, a.lda, a.yb, a.ldb = za.data_ptr(), _ld(za), zb.data_ptr(), _ld(zb)
+    a.seed, a.row0, a.temperature = _nvp_seed(seed), int(row0), float(temperature)
+    a.mask, a.mode, a.B, a.D = _nvp_mask(mask), _lib.NVP_PRIOR, B, D
+    _lib.call("gm_nvp_post", stream or stream_ptr(), ctypes.byref(a))

@@ -1,0 +1,693 @@
+"""RealNVP coupling flow (Dinh, Sohl-Dickstein & Bengio, "Density estimation using Real NVP", arXiv 1605.08803; its additive
+ancestor NICE, arXiv 1410.8516) with MLP conditioners: the collection's invertible model -- an exact density for
+grey-level data, sampling in one pass, and a latent code that is a bijection of the image.  Exported by src/real_nvp.py
+as RealNVP / RealNVPTrainer.
+
+The contract.
+
+Model.  RealNVP(image_size D = 784, hidden_dim H = 400, num_couplings K = 4, mask = "checker", alpha = 0.05, levels = 256,
+s_cap = 2.0).  Limits: 2 <= D <= 8192, 1 <= H <= 1024, 1 <= K <= 16, 0 <= alpha < 0.5, 2 <= levels <= 65536,
+0 < s_cap <= 8; anything else raises RealNVPError(GMError, ValueError) in the constructor.
+
+Split.  "checker": half A is the even-indexed pixels, half B the odd ones.  "half": half A is the first ceil(D / 2)
+pixels, half B the rest.  Da = ceil(D / 2), Db = floor(D / 2).  The halves live in two separate contiguous row-major
+buffers throughout, so every GEMM operand is dense.
+
+Couplings.  couplings = ModuleList of K Coupling modules, each linear = Linear(Dc, H) and out = Linear(H, 2 Dt).  Even k
+(0-based) transforms B conditioned on A, odd k transforms A conditioned on B.  st = out(relu(linear(x_c)));
+s = s_cap tanh(st[:, :Dt]), t = st[:, Dt:];  y_t = x_t exp(s) + t, y_c = x_c;  logdet += sum_j s_j.  out.weight and
+out.bias are zero at construction, so a fresh model is the identity flow.  state_dict keys:
+couplings.{k}.linear.{weight,bias} and couplings.{k}.out.{weight,bias}.
+
+Preprocessing.  For pixel e of row r with value x in [0, 1]:  q = floor(x (levels - 1) + 0.5);  v = (q + u) / levels;
+w = alpha + (1 - 2 alpha) v;  y = log(w) - log1p(-w);  the element's log-determinant is log(1 - 2 alpha) - log(w) -
+log1p(-w).  (In fp32, on the device and in `preprocess` below alike, 1 - w is alpha + (1 - 2 alpha) vc with vc =
+((levels - 1 - q) + (1 - u)) / levels: 1 - u is exact and nothing cancels, so both logarithms are finite for every word
+even at alpha = 0.)  u is ph_unit (csrc/gm_philox.h) of word e & 3 of Philox4x32-10 at counter (e >> 2, step, row, TAG)
+under key (seed mod 2^32, seed >> 32); e is the pixel's index in the unsplit image, row the row's position in the whole
+batch.  Training: TAG_TRAIN = "NVPD", step = the count of training batches taken.  Validation and log_likelihood:
+TAG_EVAL = "NVPV", step = the batch's index in that pass, so a validation number is reproducible.  u is never 0 or 1, so
+alpha = 0 is legal.
+
+Loss.  Per row  nll_r = 0.5 sum z^2 + 0.5 D log(2 pi) - logdet_pre_r - logdet_r + D log(levels)  in nats per image: the
+negative of the dequantisation bound on the discrete image's log-probability.  The batch loss is the mean over rows;
+gradients are of that mean: dz = z / b, and the log-determinant's cotangent is -1 / b.
+
+Sampling.  z of element e of sample row r is the Box-Muller normal (ph_box_muller, ph_normal4's word pairing) of Philox
+counter (e >> 2, 0, r, TAG_S = "NVPS"): indexed by row and element, so a row does not depend on n.  z *= temperature; the
+couplings are inverted last to first, x_t = (y_t - t) exp(-s);  x = clamp((sigmoid(y) - alpha) / (1 - 2 alpha), 0, 1).
+
+Fused path: RealNVPEngine below (csrc/gm_nvp.hip) -- per training batch the gather, gm_nvp_pre,
+K x (two forwards, gm_nvp_couple), gm_nvp_loss, K x (gm_nvp_couple_bwd, the two input gradients -- the first coupling
+needs only one -- and both weight gradients + Adam as a pair) and the loss sum with the counter tick: 7 K + 3 launches.
+A validation batch is the forward and the sum; sampling is gm_nvp_post's PRIOR mode, K x (two forwards, the inverse
+couple) and gm_nvp_post: 3 K + 2 launches.  An overridden compute_batch / evaluate or an edited model: the general loop --
+autograd over ops.fused_linear plus torch ops on the same u (gm_nvp_pre's NOISE mode)."""
+import math
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._lib import (NVP_MAX_D, NVP_MAX_H, NVP_MAX_K, NVP_MAX_LEVELS, NVP_MAX_S_CAP, NVP_MIN_D, NVP_TAG_EVAL, NVP_TAG_S,
+                   NVP_TAG_TRAIN, GMError)
+from .dvae import philox4x32_10
+from .trainers import FlatAdam, VAETrainer, _dataset_rows, _epoch_order, _stock_module, stock, stock_model, to_cuda
+from .engine import FlatParams, VAEEngine, _Linear
+
+TAG_TRAIN, TAG_EVAL, TAG_S = NVP_TAG_TRAIN, NVP_TAG_EVAL, NVP_TAG_S
+MASKS = ("checker", "half")
+_M32 = 0xFFFFFFFF
+
+
+class RealNVPError(GMError, ValueError):
+    """A bad image size, width, coupling count, mask, alpha, levels, s_cap, seed, n or temperature: a ValueError, and a
+    GMError like the package's other refusals."""
+
+
+def _int(v, name):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise RealNVPError("%s must be an integer, got %r" % (name, v))
+    return int(v)
+
+
+def _real(v, name):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise RealNVPError("%s must be a number, got %r" % (name, v))
+    v = float(v)
+    if not math.isfinite(v):
+        raise RealNVPError("%s must be finite, got %r" % (name, v))
+    return v
+
+
+def check_config(image_size, hidden_dim, num_couplings, mask, alpha, levels, s_cap):
+    """(D, H, K, mask, alpha, levels, s_cap) validated against the kernels' limits; else RealNVPError."""
+    D, H, K = _int(image_size, "image_size"), _int(hidden_dim, "hidden_dim"), _int(num_couplings, "num_couplings")
+    if not NVP_MIN_D <= D <= NVP_MAX_D:
+        raise RealNVPError("image_size must lie in [%d, %d], got %d" % (NVP_MIN_D, NVP_MAX_D, D))
+    if not 1 <= H <= NVP_MAX_H:
+        raise RealNVPError("hidden_dim must lie in [1, %d], got %d" % (NVP_MAX_H, H))
+    if not 1 <= K <= NVP_MAX_K:
+        raise RealNVPError("num_couplings must lie in [1, %d], got %d" % (NVP_MAX_K, K))
+    if not isinstance(mask, str) or mask not in MASKS:
+        raise RealNVPError("mask must be one of %s, got %r" % (MASKS, mask))
+    alpha, s_cap, levels = _real(alpha, "alpha"), _real(s_cap, "s_cap"), _int(levels, "levels")
+    if not (0.0 <= alpha < 0.5 and float(np.float32(alpha)) < 0.5):
+        raise RealNVPError("alpha must lie in [0, 0.5), got %r" % alpha)
+    if not 2 <= levels <= NVP_MAX_LEVELS:
+        raise RealNVPError("levels must lie in [2, %d], got %d" % (NVP_MAX_LEVELS, levels))
+    if not (0.0 < s_cap <= NVP_MAX_S_CAP and float(np.float32(s_cap)) > 0.0):
+        raise RealNVPError("s_cap must lie in (0, %d], got %r" % (NVP_MAX_S_CAP, s_cap))
+    return D, H, K, mask, alpha, levels, s_cap
+
+
+def check_seed(seed, name="seed"):
+    seed = _int(seed, name)
+    if not 0 <= seed < 1 << 64:
+        raise RealNVPError("%s must lie in [0, 2^64), got %d" % (name, seed))
+    return seed
+
+
+# ---- the split and the noise rules in numpy (the tests' reference reads the same contract) ----------------------------
+def split_indices(D, mask="checker"):
+    """(A, B): the pixel indices of the two halves, int64, each ascending; together they partition 0 .. D - 1."""
+    D = _int(D, "image_size")
+    if mask not in MASKS:
+        raise RealNVPError("mask must be one of %s, got %r" % (MASKS, mask))
+    e = np.arange(D, dtype=np.int64)
+    if mask == "checker":
+        return e[0::2].copy(), e[1::2].copy()
+    Da = (D + 1) // 2
+    return e[:Da].copy(), e[Da:].copy()
+
+
+def philox_words(n, D, seed, step, tag, row0=0):
+    """The uint32 word of pixel e of rows row0 ..: word e & 3 of counter (e >> 2, step, row, tag); [n, D]."""
+    nq = (D + 3) // 4
+    ctr = np.zeros((n, nq, 4), dtype=np.uint64)
+    ctr[..., 0] = np.arange(nq, dtype=np.uint64)[None, :]
+    ctr[..., 1] = np.uint64(int(step) & _M32)
+    ctr[..., 2] = ((np.arange(n, dtype=np.uint64) + np.uint64(row0)) & np.uint64(_M32))[:, None]
+    ctr[..., 3] = np.uint64(tag)
+    key = np.array([seed & _M32, (seed >> 32) & _M32], dtype=np.uint64)
+    return philox4x32_10(ctr, key).reshape(n, 4 * nq)[:, :D]
+
+
+def uniforms_reference(n, D, seed, step, tag=TAG_TRAIN, row0=0):
+    """u [n, D] float32: the dequantisation noise by the contract's rule, bit for bit."""
+    w = philox_words(n, D, seed, step, tag, row0).astype(np.uint64)
+    return ((2 * (w >> np.uint64(9)) + 1).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
+
+
+def normals_reference(n, D, seed, row0=0):
+    """z [n, D] float64: the sampler's starting normals by the contract's rule (the device rounds to fp32)."""
+    nq = (D + 3) // 4
+    w = philox_words(n, 4 * nq, seed, 0, TAG_S, row0).astype(np.uint64)
+    u = (2.0 * (w >> np.uint64(9)).astype(np.float64) + 1.0) * 2.0 ** -24
+    p = u.reshape(n, 2 * nq, 2)
+    r, phi = np.sqrt(-2.0 * np.log(p[..., 0])), 2.0 * np.pi * p[..., 1]
+    return np.stack([r * np.cos(phi), r * np.sin(phi)], axis=-1).reshape(n, 4 * nq)[:, :D]
+
+
+def nll_constant(D, levels):
+    """0.5 D log(2 pi) + D log(levels)."""
+    return 0.5 * D * math.log(2.0 * math.pi) + D * math.log(levels)
+
+
+def preprocess(x, u, alpha, levels):
+    """(y [n, D], logdet [n]) of pixel rows x in [0, 1] and noise u in (0, 1), by torch ops in x's dtype: the general
+    path's (and the fp32 statement of the kernel's) dequantise + logit."""
+    top = float(levels - 1)
+    q = torch.clamp(torch.floor(x * top + 0.5), 0.0, top)
+    v = (q + u) / levels
+    vc = ((top - q) + (1.0 - u)) / levels
+    w, wc = alpha + (1.0 - 2.0 * alpha) * v, alpha + (1.0 - 2.0 * alpha) * vc
+    lw, lwc = torch.log(w), torch.log(wc)
+    return lw - lwc, ((math.log(1.0 - 2.0 * alpha) - lw) - lwc).sum(1)
+
+
+def postprocess(y, alpha):
+    """x = clamp((sigmoid(y) - alpha) / (1 - 2 alpha), 0, 1)."""
+    return torch.clamp((torch.sigmoid(y) - alpha) / (1.0 - 2.0 * alpha), 0.0, 1.0)
+
+
+# ---- modules ---------------------------------------------------------------------------------------------------------
+@stock_model
+class Coupling(nn.Module):
+    """One conditioner: linear (Dc -> H, relu) and out (H -> 2 Dt), out starting at zero."""
+
+    def __init__(self, cond_dim, trans_dim, hidden_dim):
+        super().__init__()
+        self.linear = nn.Linear(cond_dim, hidden_dim)
+        self.out = nn.Linear(hidden_dim, 2 * trans_dim)
+        with torch.no_grad():
+            self.out.weight.zero_()
+            self.out.bias.zero_()
+
+    def forward(self, x_c):
+        """st [n, 2 Dt] of the conditioning half."""
+        if not x_c.is_cuda:
+            raise GMError("generative_models_amd computes on MI355X only: got a %s tensor and there is no CPU "
+                          "fallback (move the model and inputs with to_cuda)" % x_c.device)
+        h = ops.fused_linear(x_c.contiguous(), self.linear.weight, self.linear.bias, "relu")
+        return ops.fused_linear(h, self.out.weight, self.out.bias, "id")
+
+
+@stock_model
+class RealNVP(nn.Module):
+    """K affine couplings over the two halves of a logit-space image."""
+
+    def __init__(self, image_size=784, hidden_dim=400, num_couplings=4, mask="checker", alpha=0.05, levels=256,
+                 s_cap=2.0):
+        super().__init__()
+        (self.image_size, self.hidden_dim, self.num_couplings, self.mask, self.alpha, self.levels,
+         self.s_cap) = check_config(image_size, hidden_dim, num_couplings, mask, alpha, levels, s_cap)
+        D = self.image_size
+        self.Da, self.Db = (D + 1) // 2, D // 2
+        dims = [(self.Da, self.Db) if k % 2 == 0 else (self.Db, self.Da) for k in range(self.num_couplings)]
+        self.couplings = nn.ModuleList([Coupling(dc, dt, self.hidden_dim) for dc, dt in dims])
+        self.shape = int(D ** 0.5)
+
+    def split(self, y):
+        """(a [n, Da], b [n, Db]) of y [n, D]."""
+        ia, ib = split_indices(self.image_size, self.mask)
+        return (y[:, torch.from_numpy(ia).to(y.device)].contiguous(),
+                y[:, torch.from_numpy(ib).to(y.device)].contiguous())
+
+    def merge(self, a, b):
+        """y [n, D] of the halves."""
+        ia, ib = split_indices(self.image_size, self.mask)
+        y = torch.empty(a.shape[0], self.image_size, dtype=a.dtype, device=a.device)
+        y[:, torch.from_numpy(ia).to(a.device)] = a
+        y[:, torch.from_numpy(ib).to(a.device)] = b
+        return y
+
+    def _st(self, k, x_c):
+        st = self.couplings[k](x_c)
+        dt = st.shape[1] // 2
+        return self.s_cap * torch.tanh(st[:, :dt]), st[:, dt:]
+
+    def flow(self, y):
+        """(z [n, D], logdet [n]) of logit-space rows y, by autograd-able torch ops over the fused linear kernels."""
+        h = list(self.split(y))
+        logdet = torch.zeros(y.shape[0], dtype=y.dtype, device=y.device)
+        for k in range(len(self.couplings)):
+            t = 1 - (k & 1)                          # even k transforms B
+            s, sh = self._st(k, h[1 - t])
+            h[t] = h[t] * torch.exp(s) + sh
+            logdet = logdet + s.sum(1)
+        return self.merge(h[0], h[1]), logdet
+
+    def inverse(self, z):
+        """y [n, D] with flow(y)[0] == z: the couplings inverted last to first."""
+        h = list(self.split(z))
+        for k in reversed(range(len(self.couplings))):
+            t = 1 - (k & 1)
+            s, sh = self._st(k, h[1 - t])
+            h[t] = (h[t] - sh) * torch.exp(-s)
+        return self.merge(h[0], h[1])
+
+    def forward(self, y):
+        return self.flow(y)
+
+
+def realnvp_fused_ok(model):
+    """True iff the model is RealNVP itself with its couplings unchanged and consistent shapes and settings."""
+    if not type(model).__dict__.get("_gm_stock_model", False) or type(model) is not RealNVP:
+        return False
+    kids = list(model.children())
+    cs = getattr(model, "couplings", None)
+    if len(kids) != 1 or kids[0] is not cs or type(cs) is not nn.ModuleList:
+        return False
+    try:
+        D, H, K, mask, alpha, levels, s_cap = check_config(model.image_size, model.hidden_dim, model.num_couplings,
+                                                           model.mask, model.alpha, model.levels, model.s_cap)
+    except (RealNVPError, AttributeError):
+        return False
+    if len(cs) != K:
+        return False
+    Da, Db = (D + 1) // 2, D // 2
+    for k, c in enumerate(cs):
+        dc, dt = (Da, Db) if k % 2 == 0 else (Db, Da)
+        if not (type(c) is Coupling and _stock_module(c, 2) and type(getattr(c, "linear", None)) is nn.Linear
+                and type(getattr(c, "out", None)) is nn.Linear and c.linear.bias is not None and c.out.bias is not None
+                and tuple(c.linear.weight.shape) == (H, dc) and tuple(c.out.weight.shape) == (2 * dt, H)):
+            return False
+    return True
+
+
+def nll_rows(z, logdet_pre, logdet, D, levels):
+    """The rows' negative log-likelihood in nats per image, by torch ops."""
+    return 0.5 * (z * z).sum(1) + nll_constant(D, levels) - logdet_pre - logdet
+
+
+# ---- engine ----------------------------------------------------------------------------------------------------------
+class RealNVPEngine(VAEEngine):
+    """RealNVP on the VAE engine's epoch machinery (index ring, multi-batch hipGraphs over a device counter).  Per
+    training batch: 1. gm_gather_rows[_bits];  2. gm_nvp_pre;  3. K x (H1 = relu(linear(x_c)), ST = out(H1),
+    gm_nvp_couple);  4. gm_nvp_loss (dZ, row partials);  5. for k = K - 1 .. 0: gm_nvp_couple_bwd, dH = dST Wout [H1 > 0],
+    for k > 0 the conditioning half's cotangent dH Wlin + its direct cotangent in the GEMM's epilogue -- both input
+    gradients BEFORE the pair that steps the coupling's weights -- and the two weight gradients + Adam as a pair;
+    6. the loss sum with the counter tick.  Every coupling keeps its H1, ST and output half: nothing is recomputed.  A
+    validation batch is launches 1-4 (no dZ) and the sum.  The noise step of a training batch is ctr + nbase (DDPMEngine's
+    scheme), of a validation batch ctr (the batch's index in the pass).  No host noise ring, every batch its own gather.
+    One GPU only."""
+
+    has_eps = False
+
+    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
+                 trainer=None):
+        if world_size > 1 or force_dp:
+            raise GMError("the RealNVP engine runs on one GPU: data parallelism is not implemented for it")
+        if not realnvp_fused_ok(model):
+            raise GMError("RealNVPEngine: the model is not realnvp.RealNVP with its couplings unchanged; RealNVPTrainer "
+                          "trains such models on the general path")
+        self.model, self.device, self.use_graph = model, device, use_graph
+        plist = []
+        for c in model.couplings:
+            plist += [c.linear.weight, c.linear.bias, c.out.weight, c.out.bias]
+        self._dp_init(plist, 1, 0, None, False)
+        self.fp = FlatParams(plist, device)
+        self.C = [(_Linear(self.fp, c.linear), _Linear(self.fp, c.out)) for c in model.couplings]
+        self.D, self.H, self.K = model.image_size, model.hidden_dim, model.num_couplings
+        self.Da, self.Db = model.Da, model.Db
+        self.I = self.D
+        self.Z = 1                                   # width of VAEEngine.configure's (unused, dropped) eps ring
+        self.trainer = trainer                       # seed and noise_steps are read from it
+        self.nbase = torch.zeros(1, dtype=torch.int64, device=device)
+        self._common_init(device)
+
+    def _dt(self, k):
+        return self.Db if k % 2 == 0 else self.Da
+
+    def _alloc(self, B):
+        if self._bufB == B:
+            return
+        z = lambda *s: torch.zeros(*s, device=self.device)
+        D, H, K, Da, Db = self.D, self.H, self.K, self.Da, self.Db
+        self.X, self.Y0 = z(B, D), (z(B, Da), z(B, Db))
+        self.H1 = [z(B, H) for _ in range(K)]
+        self.ST = [z(B, 2 * self._dt(k)) for k in range(K)]
+        self.Y = [z(B, self._dt(k)) for k in range(K)]
+        self.logdet, self.part = z(B), z(B)
+        self.dZ = (z(B, Da), z(B, Db))
+        self.dST = (z(B, 2 * Da), z(B, 2 * Db))      # by the transformed half: A's, B's
+        self.dH = z(B, H)
+        self.dX = [z(B, self._dt(k)) if k >= 2 else None for k in range(K)]          # d loss / d (coupling k's input)
+        self.G = [z(B, self._dt(k - 1)) if k >= 1 else None for k in range(K)]       # cotangent of coupling k's x_c
+        self._bufB = B
+        self.graphs = {}
+
+    def _settings(self):
+        m = self.model
+        return {"mask": str(m.mask), "alpha": float(m.alpha), "levels": int(m.levels), "s_cap": float(m.s_cap),
+                "seed": int(self.trainer.seed)}
+
+    def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
+        self._extra_config = self._settings()
+        super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
+        self.eps_ring = None                         # the noise is drawn on the device: no host ring, no upload
+        for s in self.stage:
+            s.pop("eps", None)
+        key = tuple(sorted(self._extra_config.items()))
+        if getattr(self, "_noise_key", None) != key:
+            self.graphs = {}                         # the seed and the settings are launch arguments of the graphs
+        self._noise_key = key
+        self.nbase.fill_(int(self.trainer.noise_steps))
+
+    def _chain(self):
+        """Per coupling k: (index of the transformed half, its input x_t, the conditioning half x_c), and the final
+        halves (Za, Zb)."""
+        cur = [self.Y0[0], self.Y0[1]]
+        steps = []
+        for k in range(self.K):
+            t = 1 - (k & 1)
+            steps.append((t, cur[t], cur[1 - t]))
+            cur[t] = self.Y[k]
+        return steps, cur
+
+    def _issue(self, st, t, b, train, pos=0, of=1):
+        """One batch of size b: preprocessing, the K couplings, the loss (+ backward and Adam when train)."""
+        from . import ops_fused as of_
+        m, K = self.model, self.K
+        idx_slot = self._slot(t, 1, 0, self.R, self.B)
+        loss_slot = self._slot(t, 1, 0, 0, 1)
+        ops.gather_rows(self.data, self.idx_ring.view(-1), self.X, B=b, idx_slot=idx_slot, stream=st)
+        noise = dict(step_ctr=self.ctr, step=0) if self.use_graph else dict(step=t)
+        of_.nvp_pre(self.X, self.Y0[0], self.Y0[1], self.logdet, b, self.trainer.seed,
+                    TAG_TRAIN if train else TAG_EVAL, m.alpha, m.levels, m.mask,
+                    step_base=self.nbase if train else None, stream=st, **noise)
+        steps, (Za, Zb) = self._chain()
+        for k, (th, xt, xc) in enumerate(steps):
+            L1, L2 = self.C[k]
+            ops.linear_fwd(xc, L1.W, L1.b, self.H1[k], "relu", M=b, stream=st)
+            ops.linear_fwd(self.H1[k], L2.W, L2.b, self.ST[k], "id", M=b, stream=st)
+            of_.nvp_couple(self.ST[k], xt, self.Y[k], b, self._dt(k), m.s_cap, logdet=self.logdet, stream=st)
+        scale = float(np.float32(1.0 / b))
+        cst = float(np.float32(nll_constant(self.D, m.levels)))
+        of_.nvp_loss(Za, Zb, self.logdet, self.part, b, cst, scale=scale, dza=self.dZ[0] if train else None,
+                     dzb=self.dZ[1] if train else None, stream=st)
+        if train:
+            adam = dict(sched=self.sched, sched_slot=self._slot(t, 1, 0, 0, 1))
+            for k in range(K - 1, -1, -1):
+                th, xt, xc = steps[k]
+                L1, L2 = self.C[k]
+                dST = self.dST[th]
+                g = self.dZ[th] if k == K - 1 else self.G[k + 1]
+                of_.nvp_couple_bwd(self.ST[k], xt, g, dST, b, self._dt(k), m.s_cap, -scale, dx=self.dX[k], stream=st)
+                # both input gradients read the coupling's weights BEFORE the paired dW(+Adam) launch updates them
+                ops.linear_bwd_dx(dST, L2.W, self.dH, below=self.H1[k], epi="relu", M=b, stream=st)
+                if k > 0:
+                    direct = self.dZ[1 - th] if k == K - 1 else self.dX[k + 1]
+                    ops.linear_bwd_dx(self.dH, L1.W, self.G[k], M=b, add=direct, stream=st)
+                ops.linear_bwd_dw_adam_pair(dict(dA=dST, X=self.H1[k], lin=L2, adam=adam, M=b),
+                                            dict(dA=self.dH, X=xc, lin=L1, adam=adam, M=b),
+                                            weight_decay=self.wd, stream=st)
+        of_.sum_finalize(self.part, b, self.recon if train else self.vrecon, scale=scale, out_slot=loss_slot,
+                         tick=self.ctr if self.use_graph else None, stream=st)
+
+
+# ---- trainer ---------------------------------------------------------------------------------------------------------
+@stock
+class RealNVPTrainer(VAETrainer):
+    """Trains a RealNVP on its exact (dequantised) negative log-likelihood; samples, encodes and decodes.  Histories:
+    `losses` (the NLL in nats per image, one per training batch); the epoch line (mean training NLL, validation NLL);
+    best_val_loss / best_model as the other VAE-family trainers; checkpoints (+ mask, alpha, levels, s_cap, seed in the
+    optimizer state's config, checked under strict=True, and the number of training batches taken, so a resumed run
+    continues the noise stream bit for bit).  One GPU only."""
+    _hook_names = ("compute_batch", "evaluate")
+
+    def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, seed=0):
+        self.seed = check_seed(seed)                 # before anything runs
+        super().__init__(model, train_iter, val_iter, test_iter, viz=viz)
+        del self.kl_loss, self.recon_loss
+        self.losses = []
+        self.noise_steps = 0                         # training batches taken: the next one's noise step
+        self._eval_step = 0                          # batch index within an evaluate() call
+
+    def _stock(self):
+        return (self._hooks_stock() and realnvp_fused_ok(self.model) and self._loader_ok(self.train_iter)
+                and self._loader_ok(self.val_iter) and self.train_iter.batch_size == self.val_iter.batch_size)
+
+    def compute_batch(self, batch):
+        """The batch's NLL in nats per image (general path: autograd over the fused linear kernels; u from gm_nvp_pre's
+        NOISE mode on the contract's counter stream -- the training stream while the model trains, the validation one
+        otherwise)."""
+        from . import ops_fused as of_
+        images, _ = batch
+        x = to_cuda(images.view(images.shape[0], -1))
+        if not x.is_cuda:
+            raise GMError("generative_models_amd computes on MI355X only: no GPU is visible")
+        x = x.to(torch.float32).contiguous()
+        m = self.model
+        if m.training:
+            u = of_.nvp_uniforms(x.shape[0], x.shape[1], self.seed, TAG_TRAIN, step=self.noise_steps, device=x.device)
+            self.noise_steps += 1
+        else:
+            u = of_.nvp_uniforms(x.shape[0], x.shape[1], self.seed, TAG_EVAL, step=self._eval_step, device=x.device)
+            self._eval_step += 1
+        y, ld0 = preprocess(x, u, m.alpha, m.levels)
+        z, ld = m(y)
+        return nll_rows(z, ld0, ld, x.shape[1], m.levels).sum() / x.shape[0]
+
+    def evaluate(self, iterator):
+        """Mean over the batches of the NLL in nats per image on the validation stream (batch i at noise step i)."""
+        self._eval_step = 0
+        with torch.no_grad():
+            return np.mean([self.compute_batch(batch).item() for batch in iterator])
+
+    def _engine_class(self):
+        import functools
+        return functools.partial(RealNVPEngine, trainer=self)
+
+    def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
+        from copy import deepcopy
+        from . import dp
+        if dp.current()[0] > 1 or getattr(self, "force_dp", False):
+            raise GMError("RealNVPTrainer runs on one GPU: data parallelism is not implemented for it")
+        if self._stock():
+            if not torch.cuda.is_available():
+                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
+            dev = next(self.model.parameters()).device
+            if self._engine is None:
+                self._engine = self._engine_class()(self.model, dev, use_graph=self.use_graph)
+            eng = self._engine
+            eng.use_graph = self.use_graph
+            steps, nval = len(self.train_iter), len(self.val_iter)
+            eng.configure(self.train_iter.batch_size, num_epochs * steps, lr, weight_decay,
+                          resume=self.__dict__.pop("_resume_optim", None))
+            tdata, vdata = self._device_data(self.train_iter), self._device_data(self.val_iter)
+            eng.alloc_val(nval)
+            for epoch in range(1, num_epochs + 1):
+                self.model.train()
+                t0 = (epoch - 1) * steps
+                eng.run_pass(tdata, _epoch_order(self.train_iter), True, t0)
+                self.model.eval()
+                eng.run_pass(vdata, _epoch_order(self.val_iter), False, 0)
+                loss = [float(v) for v in eng.read_losses(eng.recon, t0, steps)]     # one sync
+                val_loss = np.mean([float(v) for v in eng.read_losses(eng.vrecon, 0, nval)])
+                self._end_epoch_nvp(epoch, num_epochs, loss, val_loss, deepcopy, quiet)
+            self.noise_steps += num_epochs * steps
+            return
+        # GENERAL path (compute_batch / evaluate overridden, an edited model)
+        opt = FlatAdam(self.model.parameters(), lr, weight_decay=weight_decay)
+        for epoch in range(1, num_epochs + 1):
+            self.model.train()
+            loss = []
+            for batch in self.train_iter:
+                opt.zero_grad()
+                l = self.compute_batch(batch)
+                l.backward()
+                opt.step()
+                loss.append(l.item())
+            self.model.eval()
+            val_loss = self.evaluate(self.val_iter)
+            self._end_epoch_nvp(epoch, num_epochs, loss, val_loss, deepcopy, quiet)
+        self._general_opt = opt                      # the moments, for inspection
+
+    def _end_epoch_nvp(self, epoch, num_epochs, loss, val_loss, deepcopy, quiet):
+        self.losses.extend(loss)
+        if val_loss < self.best_val_loss:
+            self.best_model = deepcopy(self.model)
+            self.best_val_loss = val_loss
+        if not quiet:
+            print("Epoch[%d/%d], NLL: %.6f, Val NLL: %.6f" % (epoch, num_epochs, np.mean(loss), val_loss))
+        self.num_epochs += 1
+        self._viz_epoch(epoch)
+
+    # ---- the flow on device rows, no autograd --------------------------------------------------------------------------
+    def _device(self):
+        if not torch.cuda.is_available():
+            raise GMError("sampling and scoring run on the MI355X only: no GPU is visible")
+        dev = next(self.model.parameters()).device
+        if dev.type != "cuda":
+            raise GMError("the model is not on the GPU")
+        return dev
+
+    def _rows(self, images):
+        x = images.reshape(images.shape[0], -1)
+        if x.shape[1] != self.model.image_size:
+            raise RealNVPError("images have %d pixels, the model %d" % (x.shape[1], self.model.image_size))
+        return x.to(self._device(), torch.float32).contiguous()
+
+    def _st(self, k, xc):
+        """ST of coupling k on device rows xc: the two GEMM launches."""
+        c = self.model.couplings[k]
+        h = torch.empty(xc.shape[0], c.linear.weight.shape[0], device=xc.device)
+        st = torch.empty(xc.shape[0], c.out.weight.shape[0], device=xc.device)
+        ops.linear_fwd(xc, c.linear.weight.detach(), c.linear.bias.detach(), h, "relu")
+        ops.linear_fwd(h, c.out.weight.detach(), c.out.bias.detach(), st, "id")
+        return st
+
+    def _forward_rows(self, x, seed, tag, step, row0=0):
+        """(za, zb, nll [n]) of device rows x under the noise of (seed, tag, step, row0 ..): the kernels for a stock model,
+        the model's own forward on the same u otherwise."""
+        from . import ops_fused as of_
+        m, n = self.model, x.shape[0]
+        with torch.no_grad():
+            if not realnvp_fused_ok(m):
+                u = of_.nvp_uniforms(n, m.image_size, seed, tag, step=step, row0=row0, device=x.device)
+                y, ld0 = preprocess(x, u, m.alpha, m.levels)
+                z, ld = m(y)
+                a, b = m.split(z)
+                return a, b, nll_rows(z, ld0, ld, m.image_size, m.levels)
+            h = [torch.empty(n, m.Da, device=x.device), torch.empty(n, m.Db, device=x.device)]
+            logdet, part = torch.empty(n, device=x.device), torch.empty(n, device=x.device)
+            of_.nvp_pre(x, h[0], h[1], logdet, n, seed, tag, m.alpha, m.levels, m.mask, step=step, row0=row0)
+            for k in range(m.num_couplings):
+                t = 1 - (k & 1)
+                out = torch.empty_like(h[t])
+                of_.nvp_couple(self._st(k, h[1 - t]), h[t], out, n, h[t].shape[1], m.s_cap, logdet=logdet)
+                h[t] = out
+            of_.nvp_loss(h[0], h[1], logdet, part, n, float(np.float32(nll_constant(m.image_size, m.levels))))
+            return h[0], h[1], part
+
+    def _inverse_rows(self, za, zb):
+        """x [n, D] in [0, 1] of latent halves: the couplings inverted last to first, then gm_nvp_post."""
+        from . import ops_fused as of_
+        m, n = self.model, za.shape[0]
+        with torch.no_grad():
+            if not realnvp_fused_ok(m):
+                return postprocess(m.inverse(m.merge(za, zb)), m.alpha).contiguous()
+            h = [za, zb]
+            for k in reversed(range(m.num_couplings)):
+                t = 1 - (k & 1)
+                out = torch.empty_like(h[t])
+                of_.nvp_couple(self._st(k, h[1 - t]), h[t], out, n, h[t].shape[1], m.s_cap, inverse=True)
+                h[t] = out
+            x = torch.empty(n, m.image_size, device=za.device)
+            of_.nvp_post(h[0], h[1], x, n, m.alpha, m.mask)
+            return x
+
+    # ---- sampling and scoring ------------------------------------------------------------------------------------------
+    def sample(self, n, seed=0, temperature=1.0):
+        """n samples [n, D] float32 in [0, 1]: the contract's normals (indexed by row and element: rows 0 .. 4 of
+        sample(300) are sample(5)) times the temperature through the inverse flow -- 3 K + 2 launches for a stock model.
+        Runs after a device synchronise; the global generator, the model's mode and the parameters are untouched."""
+        from . import ops_fused as of_
+        n, seed, temperature = _int(n, "n"), check_seed(seed), _real(temperature, "temperature")
+        if not 1 <= n < 1 << 31:
+            raise RealNVPError("n must lie in [1, 2^31), got %d" % n)
+        if temperature < 0.0:
+            raise RealNVPError("temperature must be >= 0, got %r" % temperature)
+        dev, m = self._device(), self.model
+        torch.cuda.synchronize()
+        za, zb = torch.empty(n, m.Da, device=dev), torch.empty(n, m.Db, device=dev)
+        of_.nvp_prior(za, zb, n, m.image_size, seed, m.mask, temperature=temperature)
+        x = self._inverse_rows(za, zb)
+        torch.cuda.synchronize()
+        return x
+
+    def encode(self, images, seed=0, batch=1024):
+        """(z [n, D], log_px [n]): the latent code of every image under the validation stream's noise of `seed` (step 0,
+        row = the image's position in `images`) and the dequantisation bound on its log-probability in nats."""
+        seed = check_seed(seed)
+        x = self._rows(images)
+        m = self.model
+        torch.cuda.synchronize()
+        zs, lls = [], []
+        for i in range(0, x.shape[0], batch):
+            a, b, nll = self._forward_rows(x[i:i + batch], seed, TAG_EVAL, 0, row0=i)
+            zs.append(m.merge(a, b))
+            lls.append(-nll)
+        torch.cuda.synchronize()
+        return torch.cat(zs), torch.cat(lls)
+
+    def decode(self, z, batch=1024):
+        """x [n, D] in [0, 1] of latent codes z [n, D]: encode's inverse (up to the dequantisation noise inside a
+        grey level)."""
+        z = z.reshape(z.shape[0], -1)
+        m = self.model
+        if z.shape[1] != m.image_size:
+            raise RealNVPError("codes have %d elements, the model %d" % (z.shape[1], m.image_size))
+        z = z.to(self._device(), torch.float32).contiguous()
+        torch.cuda.synchronize()
+        out = [self._inverse_rows(*m.split(z[i:i + batch])) for i in range(0, z.shape[0], batch)]
+        torch.cuda.synchronize()
+        return torch.cat(out)
+
+    def interpolate(self, a, b, steps=8, seed=0):
+        """[steps, D]: the decoded line from image a to image b in z."""
+        steps = _int(steps, "steps")
+        if steps < 2:
+            raise RealNVPError("steps must be >= 2, got %d" % steps)
+        z, _ = self.encode(torch.stack([a.reshape(-1), b.reshape(-1)]), seed=seed)
+        w = torch.linspace(0.0, 1.0, steps, device=z.device)[:, None]
+        return self.decode((1.0 - w) * z[0:1] + w * z[1:2])
+
+    def log_likelihood_rows(self, images=None, seed=1, batch=1024):
+        """The bound on log p(x) per image in nats, a float64 CPU tensor [n]: batch i of `batch` rows at step i of the
+        validation stream under `seed`."""
+        seed = check_seed(seed)
+        x = self._rows(_dataset_rows(self.test_iter) if images is None else images)
+        torch.cuda.synchronize()
+        out = [-self._forward_rows(x[i:i + batch], seed, TAG_EVAL, i // batch)[2] for i in range(0, x.shape[0], batch)]
+        torch.cuda.synchronize()
+        return torch.cat(out).double().cpu()
+
+    def log_likelihood(self, images=None, seed=1, batch=1024):
+        """The dequantisation bound on log p(x) of every image in nats (images=None: the whole test_iter) ->
+        metrics.NLLResult(ll_mean, ll_stderr, n)."""
+        from . import metrics
+        ll = self.log_likelihood_rows(images, seed, batch)
+        return metrics.NLLResult(float(ll.mean()), float(ll.std(unbiased=False)) / float(np.sqrt(ll.numel())),
+                                 int(ll.numel()))
+
+    def bits_per_dim(self, res):
+        """A log_likelihood result (or a mean log-likelihood in nats) in bits per pixel."""
+        ll = res.ll_mean if hasattr(res, "ll_mean") else float(res)
+        return -ll / (self.model.image_size * math.log(2.0))
+
+    # ---- visualisation, checkpoints -----------------------------------------------------------------------------------
+    def _viz_epoch(self, epoch):
+        if self.viz:
+            self.sample_images(epoch)
+
+    def sample_images(self, epoch=-100, num_images=36, save=True):
+        from . import viz
+        return viz.realnvp_sample_images(self, epoch, num_images, save, self.viz_dir)
+
+    def generate_images(self, epoch=-100, num_outputs=36, save=True):
+        return self.sample_images(epoch, num_outputs, save)
+
+    def reconstruct_images(self, images, epoch, save=True):
+        raise GMError("a flow reconstructs exactly: decode(encode(images)[0]) returns the dequantised images")
+
+    def viz_loss(self):
+        import matplotlib.pyplot as plt
+        plt.style.use("ggplot")
+        plt.plot(np.linspace(1, max(1, self.num_epochs), len(self.losses)), self.losses, "r")
+        plt.legend(["NLL (nats per image)"])
+        plt.title(self.name)
+        plt.show()
+
+    def save_checkpoint(self, savepath, collective=True):
+        """VAETrainer.save_checkpoint + noise_steps (mask, alpha, levels, s_cap and seed travel in the optimizer state's
+        config)."""
+        from .trainers import _save_checkpoint
+        _save_checkpoint(self, savepath, ("losses", "num_epochs", "best_val_loss", "noise_steps"), collective=collective)
+
+
+__all__ = ["Coupling", "RealNVP", "RealNVPTrainer", "RealNVPEngine", "RealNVPError", "split_indices", "philox_words",
+           "uniforms_reference", "normals_reference", "preprocess", "postprocess", "nll_constant", "realnvp_fused_ok"]

@@ -183,3 +183,14 @@ def made_sample_images(trainer, epoch=-100, num_images=36, save=True, outdir=Non
         write_png_gray(os.path.join(_outdir(trainer, outdir), "sample_%d.png" % epoch),
                        make_grid(images, int(num_images ** 0.5)))
     return images
+
+
+def realnvp_sample_images(trainer, epoch=-100, num_images=36, save=True, outdir=None):
+    """A grid of trainer.sample(num_images, seed=max(epoch, 0)) -- the flow's inverse pass on the sampler's own counter
+    stream, so the global CPU generator stays where it is -- written as ../viz/<name>/sample_<epoch>.png."""
+    sample = trainer.sample(num_images, seed=max(int(epoch), 0))
+    images = _to_host_images(sample, trainer.model.shape)
+    if save:
+        write_png_gray(os.path.join(_outdir(trainer, outdir), "sample_%d.png" % epoch),
+                       make_grid(images, int(num_images ** 0.5)))
+    return images

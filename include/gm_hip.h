@@ -1213,6 +1213,94 @@ int gm_made_sample(void* stream, const gm_made_sample_args* a);
  * an edited model runs I forward passes under the same rule). */
 int gm_made_uniform(void* stream, float* u, int64_t ldu, uint64_t seed, int64_t row0, int64_t rows, int I);
 
+/* ---- RealNVP coupling flow (Dinh, Sohl-Dickstein & Bengio, arXiv 1605.08803; realnvp.py holds the contract; DESIGN.md
+ * section 24; csrc/gm_nvp.hip, the shared arithmetic in csrc/gm_nvp.h) -----------------------------------------------
+ * An image of D pixels lives as two dense row-major halves A [rows, Da] and B [rows, Db], Da = ceil(D / 2), Db =
+ * floor(D / 2): GM_NVP_CHECKER A = the even-indexed pixels, B = the odd ones; GM_NVP_HALF A = the first Da pixels, B =
+ * the rest.  Every kernel runs one 256-thread workgroup per row with fixed reduction orders (no floating-point atomics),
+ * by 16-byte accesses where a row's width is a multiple of 4 and its base and leading dimension allow them, element by
+ * element otherwise.  Out-of-limit fields and NULL return GM_EINVAL before any launch. */
+#define GM_NVP_TAG_TRAIN 0x4E565044u           /* "NVPD": the training dequantisation noise */
+#define GM_NVP_TAG_EVAL 0x4E565056u            /* "NVPV": validation and log_likelihood */
+#define GM_NVP_TAG_S 0x4E565053u               /* "NVPS": the sampler's normals */
+#define GM_NVP_MIN_D 2
+#define GM_NVP_MAX_D 8192
+#define GM_NVP_MAX_H 1024
+#define GM_NVP_MAX_K 16
+#define GM_NVP_MAX_LEVELS 65536
+#define GM_NVP_MAX_S_CAP 8
+#define GM_NVP_CHECKER 0
+#define GM_NVP_HALF 1
+#define GM_NVP_PRE 0                           /* gm_nvp_pre: dequantise + logit + split */
+#define GM_NVP_NOISE 1                         /* gm_nvp_pre: u itself, as [B, D] */
+#define GM_NVP_POST 0                          /* gm_nvp_post: halves -> image */
+#define GM_NVP_PRIOR 1                         /* gm_nvp_post: the sampler's starting normals -> halves */
+/* Pixel e of row r with value x in [0, 1]:  q = floor(x (levels - 1) + 0.5) clamped to [0, levels - 1];  v = (q + u) /
+ * levels, vc = ((levels - 1 - q) + (1 - u)) / levels (= 1 - v, formed without cancellation; 1 - u is exact);  w = alpha +
+ * (1 - 2 alpha) v, wc = alpha + (1 - 2 alpha) vc;  y = log(w) - log(wc);  logdet[r] = sum_e log(1 - 2 alpha) - log(w) -
+ * log(wc).  u = ph_unit of word e & 3 of Philox4x32-10 at counter (e >> 2, step, row0 + r, tag) under key (seed mod 2^32,
+ * seed >> 32), step = (step_ctr ? *step_ctr : 0) + (step_base ? *step_base : 0) + step_add truncated to 32 bits
+ * (gm_corrupt_args' scheme).  GM_NVP_NOISE writes u [B, D] alone. */
+typedef struct gm_nvp_pre_args {
+    const float* x; int64_t ldx;              /* [B, >= D] */
+    float* ya; int64_t lda;                   /* [B, >= Da] */
+    float* yb; int64_t ldb;                   /* [B, >= Db] */
+    float* logdet;                            /* [B] */
+    float* u; int64_t ldu;                    /* GM_NVP_NOISE: [B, >= D] */
+    uint64_t seed;
+    const int64_t* step_ctr; const int64_t* step_base; int64_t step_add;
+    int64_t row0;                             /* batch position of the first row (>= 0) */
+    uint32_t tag;
+    float alpha;
+    int levels, mask, mode, B, D;
+} gm_nvp_pre_args;
+int gm_nvp_pre(void* stream, const gm_nvp_pre_args* a);
+/* One affine coupling on the transformed half (width Dt):  s = s_cap tanh(st[:, :Dt]), t = st[:, Dt:];
+ *   forward:  out = in exp(s) + t,  logdet[r] += sum_j s_j (a plain read-add-write by the row's owner);
+ *   inverse:  out = (in - t) exp(-s);  logdet is not touched (may be NULL). */
+typedef struct gm_nvp_couple_args {
+    const float* st; int64_t ldst;            /* [B, >= 2 Dt] */
+    const float* inp; int64_t ldin;           /* [B, >= Dt] */
+    float* out; int64_t ldout;                /* [B, >= Dt]; none of st, inp */
+    float* logdet;                            /* [B] (forward) */
+    float s_cap;
+    int inverse, B, Dt;
+} gm_nvp_couple_args;
+int gm_nvp_couple(void* stream, const gm_nvp_couple_args* a);
+/* part[r] = 0.5 sum z^2 - logdet[r] + cst over both halves of row r (cst = 0.5 D log(2 pi) + D log(levels), from the
+ * host) and, when dza is not NULL, dza = za scale, dzb = zb scale. */
+typedef struct gm_nvp_loss_args {
+    const float* za; int64_t ldza; const float* zb; int64_t ldzb;
+    const float* logdet; float* part;
+    float* dza; int64_t lddza; float* dzb; int64_t lddzb;       /* both NULL or both given */
+    float cst, scale;
+    int B, Da, Db;
+} gm_nvp_loss_args;
+int gm_nvp_loss(void* stream, const gm_nvp_loss_args* a);
+/* The coupling's backward.  g = g0 (+ g1 when not NULL) is the transformed half's cotangent, c the log-determinant's:
+ *   dst[:, :Dt] = (g x exp(s) + c) s_cap (1 - tanh^2(st_s)),  dst[:, Dt:] = g,  dx = g exp(s) (dx may be NULL). */
+typedef struct gm_nvp_couple_bwd_args {
+    const float* st; int64_t ldst;            /* [B, >= 2 Dt] */
+    const float* x; int64_t ldx;              /* [B, >= Dt]: the coupling's input */
+    const float* g0; int64_t ldg0; const float* g1; int64_t ldg1;
+    float* dst; int64_t lddst;                /* [B, >= 2 Dt] */
+    float* dx; int64_t lddx;                  /* [B, >= Dt] or NULL */
+    float c, s_cap;
+    int B, Dt;
+} gm_nvp_couple_bwd_args;
+int gm_nvp_couple_bwd(void* stream, const gm_nvp_couple_bwd_args* a);
+/* GM_NVP_POST:  x[r, e] = clamp((sigmoid(y) - alpha) / (1 - 2 alpha), 0, 1), y the half's entry of pixel e.
+ * GM_NVP_PRIOR: the halves' entry of pixel e of row r = temperature * the Box-Muller normal (ph_normal4's word pairing)
+ * of element e of Philox counter (e >> 2, 0, row0 + r, GM_NVP_TAG_S); x, alpha unused. */
+typedef struct gm_nvp_post_args {
+    float* ya; int64_t lda; float* yb; int64_t ldb;             /* read (POST) or written (PRIOR) */
+    float* x; int64_t ldx;                    /* POST: [B, >= D] */
+    uint64_t seed; int64_t row0;
+    float alpha, temperature;
+    int mask, mode, B, D;
+} gm_nvp_post_args;
+int gm_nvp_post(void* stream, const gm_nvp_post_args* a);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

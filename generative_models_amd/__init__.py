@@ -84,8 +84,11 @@ def host_thread_plan():
 def __getattr__(name):
     """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine, SNGAN / SNGANTrainer / SNGANEngine,
     DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine, NFVAE / NFVAETrainer / NFVAEEngine, CatVAE /
-    CatVAETrainer / CatVAEEngine and RealNVP / RealNVPTrainer / RealNVPEngine, imported on first use (importing the
-    package stays free of torch)."""
+    CatVAETrainer / CatVAEEngine, RealNVP / RealNVPTrainer / RealNVPEngine and RBM / RBMTrainer / RBMEngine, imported on
+    first use (importing the package stays free of torch)."""
+    if name in ("RBM", "RBMTrainer", "RBMEngine"):
+        from . import rbm
+        return getattr(rbm, name)
     if name in ("RealNVP", "RealNVPTrainer", "RealNVPEngine"):
         from . import realnvp
         return getattr(realnvp, name)

@@ -148,6 +148,10 @@ NVP_CHECKER, NVP_HALF = 0, 1                                # GM_NVP_CHECKER / G
 NVP_PRE, NVP_NOISE, NVP_POST, NVP_PRIOR = 0, 1, 0, 1        # gm_nvp_pre's and gm_nvp_post's modes
 # (the gm_nvp_*_args travel by pointer; their ctypes forms live in ops_fused)
 
+RBM_TAG_D, RBM_TAG_H, RBM_TAG_V = 0x52424D44, 0x52424D48, 0x52424D56      # GM_RBM_TAG_* ("RBMD", "RBMH", "RBMV")
+RBM_MAX_DIM, RBM_MAX_STEPS = 1024, 1 << 24                  # GM_RBM_MAX_DIM / GM_RBM_MAX_STEPS
+# (gm_rbm_chain_args / gm_rbm_vbias_args travel by pointer; their ctypes forms live in ops_fused)
+
 NOISE = {"salt_pepper": 1, "gaussian": 2}       # GM_NOISE_SALT_PEPPER, GM_NOISE_GAUSSIAN (GM_NOISE_NONE = 0)
 
 
@@ -397,6 +401,12 @@ _SIGNATURES = {
     "gm_nvp_loss": (c_int, [_P, _P]),
     "gm_nvp_couple_bwd": (c_int, [_P, _P]),
     "gm_nvp_post": (c_int, [_P, _P]),
+    "gm_rbm_chain": (c_int, [_P, _P]),
+    "gm_rbm_grad": (c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_float, c_int, c_int, c_int]),
+    "gm_rbm_vbias": (c_int, [_P, _P]),
+    "gm_rbm_transpose": (c_int, [_P, _P, c_int64, _P, c_int64, c_int, c_int]),
+    "gm_rbm_uniform": (c_int, [_P, _P, c_int64, ctypes.c_uint64, ctypes.c_uint32, _P, _P, c_int64, c_int64, c_int64,
+                               c_int]),
 }
 
 _lib = None

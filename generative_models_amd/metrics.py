@@ -24,6 +24,8 @@ ParzenResult = collections.namedtuple("ParzenResult", "sigma ll_mean ll_stderr v
 IWAEResult = collections.namedtuple("IWAEResult", "ll_mean ll_stderr k n")
 # the exact log-likelihood of a model with a tractable one (made.MADETrainer.log_likelihood), nats per image
 NLLResult = collections.namedtuple("NLLResult", "ll_mean ll_stderr n")
+# rbm.RBMTrainer.log_likelihood: log p(v) = -F(v) - log Z with log Z by annealed importance sampling (chains x n_betas)
+AISResult = collections.namedtuple("AISResult", "ll_mean ll_stderr log_z log_z_stderr chains n_betas n")
 
 
 def default_sigmas():

@@ -1217,6 +1217,106 @@ def made_uniform(n, I, seed, row0=0, device="cuda", stream=None):
     return u
 
 
+# ---- Restricted Boltzmann machine (csrc/gm_rbm.hip, gm_rbm.h; rbm.py) --------------------------------------------------
+class RbmChainArgs(ctypes.Structure):
+    """gm_rbm_chain_args (include/gm_hip.h): the one-launch Gibbs chain."""
+    _fields_ = [("W", ctypes.c_void_p), ("WT", ctypes.c_void_p), ("c", ctypes.c_void_p), ("b", ctypes.c_void_p),
+                ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("v0_out", ctypes.c_void_p), ("ldv0", ctypes.c_int64),
+                ("v_out", ctypes.c_void_p), ("ldv", ctypes.c_int64), ("p_out", ctypes.c_void_p), ("ldp", ctypes.c_int64),
+                ("a_out", ctypes.c_void_p), ("lda", ctypes.c_int64), ("seed", ctypes.c_uint64), ("row0", ctypes.c_int64),
+                ("step_ctr", ctypes.c_void_p), ("step_base", ctypes.c_void_p), ("d_add", ctypes.c_int64),
+                ("g_mul", ctypes.c_int64), ("g_add", ctypes.c_int64), ("betas", ctypes.c_void_p),
+                ("b_A", ctypes.c_void_p), ("logw", ctypes.c_void_p), ("n", ctypes.c_int64), ("I", ctypes.c_int),
+                ("H", ctypes.c_int), ("steps", ctypes.c_int)]
+
+
+class RbmVbiasArgs(ctypes.Structure):
+    """gm_rbm_vbias_args (include/gm_hip.h): the visible bias' gradient and its Adam step."""
+    _fields_ = [("V", ctypes.c_void_p), ("ldv", ctypes.c_int64), ("g", ctypes.c_void_p), ("pb", ctypes.c_void_p),
+                ("mb", ctypes.c_void_p), ("vb", ctypes.c_void_p), ("sched", ctypes.c_void_p), ("sched_slot", _lib.Slot),
+                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("inv_b", ctypes.c_float), ("B", ctypes.c_int), ("I", ctypes.c_int)]
+
+
+def rbm_chain(W, WT, c, b, x, steps, seed, n=None, v0_out=None, v_out=None, p_out=None, a_out=None, row0=0,
+              step_ctr=None, step_base=None, d_add=0, g_mul=1, g_add=0, betas=None, b_A=None, logw=None, stream=None):
+    """n Gibbs chains of `steps` steps from the binarisation of x [n, >= I], in ONE launch (gm_rbm_chain).  Outputs, each
+    optional: v0_out (the binarisation), v_out (the last visible state; may be x), p_out / a_out (the conditionals of
+    the last visible draw and their logits).  betas (float32 [steps + 1] on the device), b_A [I] and logw (float64 [n])
+    together run the tempered chain of annealed importance sampling."""
+    H, I = W.shape
+    _made_f32(W, (H, I), "W"), _made_f32(WT, (I, H), "WT"), _made_f32(c, (H,), "c"), _made_f32(b, (I,), "b")
+    n = x.shape[0] if n is None else int(n)
+    a = RbmChainArgs()
+    for t, nm in ((x, "x"), (v0_out, "v0_out"), (v_out, "v_out"), (p_out, "p_out"), (a_out, "a_out")):
+        if t is not None and (_rows2d(t, nm).shape[0] < n or t.shape[1] < I):
+            raise _lib.GMError("rbm_chain: %s %s does not fit %d rows of %d" % (nm, tuple(t.shape), n, I))
+    a.W, a.WT, a.c, a.b = W.data_ptr(), WT.data_ptr(), c.data_ptr(), b.data_ptr()
+    a.x, a.ldx = x.data_ptr(), _ld(x)
+    for t, nm, ld in ((v0_out, "v0_out", "ldv0"), (v_out, "v_out", "ldv"), (p_out, "p_out", "ldp"),
+                      (a_out, "a_out", "lda")):
+        if t is not None:
+            setattr(a, nm, t.data_ptr())
+            setattr(a, ld, _ld(t))
+    if betas is not None or b_A is not None or logw is not None:
+        if betas is None or b_A is None or logw is None:
+            raise _lib.GMError("rbm_chain: betas, b_A and logw come together")
+        _made_f32(betas, (int(steps) + 1,), "betas"), _made_f32(b_A, (I,), "b_A")
+        if not (logw.is_cuda and logw.dtype == torch.float64 and logw.is_contiguous() and logw.numel() >= n):
+            raise _lib.GMError("rbm_chain: logw must be a contiguous float64 device tensor of >= %d elements" % n)
+        a.betas, a.b_A, a.logw = betas.data_ptr(), b_A.data_ptr(), logw.data_ptr()
+    a.seed, a.row0, a.n, a.I, a.H, a.steps = int(seed), int(row0), n, I, H, int(steps)
+    a.step_ctr = step_ctr.data_ptr() if step_ctr is not None else None
+    a.step_base = step_base.data_ptr() if step_base is not None else None
+    a.d_add, a.g_mul, a.g_add = int(d_add), int(g_mul), int(g_add)
+    _lib.call("gm_rbm_chain", stream or stream_ptr(), ctypes.byref(a))
+
+
+def rbm_grad(pre, V, b, dA, part, B, inv_b, stream=None):
+    """From pre [2B, H] of the stacked V = [v0; vk]: dA = [-p0; +pk] inv_b and part [2B] = the signed free energies
+    (gm_rbm_grad)."""
+    H, I = pre.shape[1], b.numel()
+    if _rows2d(pre, "pre").shape[0] < 2 * B or _rows2d(V, "V").shape[0] < 2 * B or V.shape[1] < I or \
+            _rows2d(dA, "dA").shape[0] < 2 * B or dA.shape[1] != H or part.numel() < 2 * B or not part.is_contiguous():
+        raise _lib.GMError("rbm_grad: the arrays do not fit B=%d, I=%d, H=%d" % (B, I, H))
+    _lib.call("gm_rbm_grad", stream or stream_ptr(), pre.data_ptr(), _ld(pre), V.data_ptr(), _ld(V),
+              _made_f32(b, (I,), "b").data_ptr(), dA.data_ptr(), _ld(dA), part.data_ptr(), inv_b, B, I, H)
+
+
+def rbm_vbias(V, B, I, inv_b, g=None, adam=None, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, stream=None):
+    """g [I] = inv_b sum_r (V[B + r] - V[r]) and, with adam = dict(p, m, v, sched, sched_slot), the Adam step of the
+    visible bias in the same launch (gm_rbm_vbias)."""
+    if _rows2d(V, "V").shape[0] < 2 * B or V.shape[1] < I:
+        raise _lib.GMError("rbm_vbias: V %s does not fit 2 x %d rows of %d" % (tuple(V.shape), B, I))
+    a = RbmVbiasArgs()
+    a.V, a.ldv, a.inv_b, a.B, a.I = V.data_ptr(), _ld(V), inv_b, B, I
+    if g is not None:
+        a.g = _made_f32(g, (I,), "g").data_ptr()
+    if adam is not None:
+        a.pb, a.mb, a.vb = (_made_f32(adam[k], (I,), k).data_ptr() for k in ("p", "m", "v"))
+        a.sched, a.sched_slot = adam["sched"].data_ptr(), adam.get("sched_slot", NO_SLOT)
+    a.beta1, a.beta2, a.eps, a.weight_decay = betas[0], betas[1], eps, weight_decay
+    _lib.call("gm_rbm_vbias", stream or stream_ptr(), ctypes.byref(a))
+
+
+def rbm_transpose(W, WT, stream=None):
+    """WT [cols, rows] = W [rows, cols] transposed, bit for bit (gm_rbm_transpose); either may be a row-strided view."""
+    rows, cols = _rows2d(W, "W").shape
+    if tuple(_rows2d(WT, "WT").shape) != (cols, rows):
+        raise _lib.GMError("rbm_transpose: WT %s is not the transpose of W %s" % (tuple(WT.shape), tuple(W.shape)))
+    _lib.call("gm_rbm_transpose", stream or stream_ptr(), W.data_ptr(), _ld(W), WT.data_ptr(), _ld(WT), rows, cols)
+    return WT
+
+
+def rbm_uniform(n, width, seed, tag, step=0, row0=0, step_ctr=None, step_base=None, device="cuda", stream=None):
+    """u [n, width]: the RBM noise rule's uniforms of chain rows row0 .. under `tag` at step (gm_rbm_uniform)."""
+    u = torch.empty(n, width, device=device)
+    _lib.call("gm_rbm_uniform", stream or stream_ptr(), u.data_ptr(), _ld(u), int(seed), int(tag),
+              step_ctr.data_ptr() if step_ctr is not None else None,
+              step_base.data_ptr() if step_base is not None else None, int(step), int(row0), int(n), int(width))
+    return u
+
+
 # ---- RealNVP coupling flow (csrc/gm_nvp.hip, gm_nvp.h; realnvp.py) ---------------------------------------------------
 class NvpPreArgs(ctypes.Structure):
     """gm_nvp_pre_args (include/gm_hip.h): dequantise + logit + split, or the noise alone."""

@@ -1301,6 +1301,67 @@ typedef struct gm_nvp_post_args {
 } gm_nvp_post_args;
 int gm_nvp_post(void* stream, const gm_nvp_post_args* a);
 
+/* ---- binary restricted Boltzmann machine (Smolensky 1986; Hinton 2002; Tieleman 2008; rbm.py holds the contract;
+ * DESIGN.md section 25; csrc/gm_rbm.hip, the noise rule and the pinned arithmetic in csrc/gm_rbm.h) --------------------
+ * W [H, I] (linear.weight), c [H] (linear.bias), b [I] (vbias); WT [I, H] is W transposed (gm_rbm_transpose).
+ * The noise rule: the uniform of unit e of chain row r at step t under tag T is ph_unit of word e & 3 of Philox4x32-10
+ * at counter (e >> 2, t, r, T) under key (seed mod 2^32, seed >> 32); a unit is lit iff u < 1 / (1 + expf(-a)) in fp32.
+ * The sum rule: pre_h[j] = c[j], then += WT[i, j] for the lit pixels i in ascending order; pre_v[i] = b[i], then +=
+ * W[j, i] for the lit hidden units j in ascending order; one fp32 accumulator per unit. */
+#define GM_RBM_TAG_D 0x52424D44u              /* "RBMD": the binarisation of the input rows, t = the batch step */
+#define GM_RBM_TAG_H 0x52424D48u              /* "RBMH": hidden draws, t = the Gibbs step */
+#define GM_RBM_TAG_V 0x52424D56u              /* "RBMV": visible draws, t = the Gibbs step */
+#define GM_RBM_MAX_DIM 1024                   /* 1 <= I, H <= 1024 */
+#define GM_RBM_MAX_STEPS (1 << 24)
+/* A Gibbs chain per row in ONE launch.  With C = (step_ctr ? *step_ctr : 0) + (step_base ? *step_base : 0):
+ *   v = v0 = (u_D < x) at t = C + d_add (truncated to 32 bits);  then for s = 0 .. steps - 1, at t = C g_mul + g_add + s:
+ *   h ~ sigmoid(pre_h(v)),  v ~ sigmoid(pre_v(h)).   steps = 0 binarises only (p_out, a_out are then left untouched).
+ * v0_out, v_out: 0 / 1 floats (either may be x itself);  p_out, a_out: the conditionals of the LAST visible draw and
+ * their logits.  Every output is optional.  Chain row = row0 + the row's position: a row's bits do not depend on n.
+ * Tempering (all three of betas, b_A, logw, or none; steps >= 1): betas[steps + 1] a device table; step s forms pre_h,
+ * adds (betas[s+1] - betas[s]) (b - b_A).v + sum_j sp(betas[s+1] pre_h_j) - sp(betas[s] pre_h_j) to the row's log-weight
+ * (sp(a) = max(a, 0) + log1pf(expf(-|a|)); fp32 per lane, the wave butterfly, then fp64 across steps), draws h from
+ * sigmoid(betas[s+1] pre_h) and v from sigmoid(betas[s+1] pre_v + (1 - betas[s+1]) b_A).  logw[r] receives the sum. */
+typedef struct gm_rbm_chain_args {
+    const float* W; const float* WT; const float* c; const float* b;
+    const float* x; int64_t ldx;              /* [n, >= I] in [0, 1] */
+    float* v0_out; int64_t ldv0;              /* [n, >= I] or NULL */
+    float* v_out; int64_t ldv;                /* [n, >= I] or NULL */
+    float* p_out; int64_t ldp;                /* [n, >= I] or NULL */
+    float* a_out; int64_t lda;                /* [n, >= I] or NULL */
+    uint64_t seed;
+    int64_t row0;                             /* chain row of the first row (>= 0) */
+    const int64_t* step_ctr; const int64_t* step_base;          /* device words or NULL */
+    int64_t d_add, g_mul, g_add;              /* host parts of the binarisation step and of the first Gibbs step */
+    const float* betas; const float* b_A; double* logw;         /* the tempering block */
+    int64_t n;
+    int I, H, steps;
+} gm_rbm_chain_args;
+int gm_rbm_chain(void* stream, const gm_rbm_chain_args* a);
+/* From pre [2B, H] = linear(V) of the stacked V = [v0; vk] [2B, I]:  dA [2B, H] = [-sigmoid(pre0); +sigmoid(prek)] inv_b
+ * (dA may be pre itself) and part[r] = +F(v0_r) for r < B, -F(vk_r) otherwise, F(v) = -b.v - sum_j sp(pre_j): inv_b times
+ * their sum is the batch's free-energy gap (gm_sum_finalize*). */
+int gm_rbm_grad(void* stream, const float* pre, int64_t ldpre, const float* V, int64_t ldv, const float* b, float* dA,
+                int64_t ldd, float* part, float inv_b, int B, int I, int H);
+/* The visible bias: g[i] = inv_b sum_{r < B} (V[B + r, i] - V[r, i]), rows in ascending order; g (may be NULL) receives
+ * it; with pb (then mb, vb, sched too) Adam steps b in the same launch by gm_adam's arithmetic. */
+typedef struct gm_rbm_vbias_args {
+    const float* V; int64_t ldv;              /* [2B, >= I] */
+    float* g;                                 /* [I] or NULL */
+    float* pb; float* mb; float* vb;          /* [I] each, or all NULL */
+    const float* sched; gm_slot sched_slot;
+    double beta1, beta2, eps, weight_decay;
+    float inv_b;
+    int B, I;
+} gm_rbm_vbias_args;
+int gm_rbm_vbias(void* stream, const gm_rbm_vbias_args* a);
+/* WT [cols, rows] = W [rows, cols]^T, 32-bit words copied bit for bit (rows ldw / ldt floats apart). */
+int gm_rbm_transpose(void* stream, const float* W, int64_t ldw, float* WT, int64_t ldt, int rows, int cols);
+/* u[r, e] = the rule's uniform of unit e < width of chain row row0 + r under `tag`, at step (step_ctr ? *step_ctr : 0) +
+ * (step_base ? *step_base : 0) + step_add truncated to 32 bits. */
+int gm_rbm_uniform(void* stream, float* u, int64_t ldu, uint64_t seed, uint32_t tag, const int64_t* step_ctr,
+                   const int64_t* step_base, int64_t step_add, int64_t row0, int64_t rows, int width);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

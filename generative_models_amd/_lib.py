@@ -416,6 +416,23 @@ class GMError(RuntimeError):
     pass
 
 
+def check_int(v, name, error=GMError):
+    """int(v) of an integer (Python's or numpy's, no bool); else `error`: the models' argument validator, raised as
+    the calling module's own error class."""
+    import numpy as np
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise error("%s must be an integer, got %r" % (name, v))
+    return int(v)
+
+
+def check_seed(seed, name="seed", error=GMError):
+    """A counter-generator seed: an integer in [0, 2^64); else `error`."""
+    seed = check_int(seed, name, error)
+    if not 0 <= seed < 1 << 64:
+        raise error("%s must lie in [0, 2^64), got %d" % (name, seed))
+    return seed
+
+
 def load():
     """Load libgm_hip.so; raise loudly if it is not there (build with __graft_entry__.build())."""
     global _lib

@@ -15,9 +15,9 @@ import torch
 import torch.nn as nn
 
 from ._lib import GMError
-from .trainers import (EPS, FlatAdam, VAETrainer, _TwoLayer, _epoch_order, _lin, _stock_module, stock, stock_model,
-                       to_cuda)
+from .trainers import EPS, FlatAdam, VAETrainer, _TwoLayer, _lin, _stock_module, stock, stock_model, to_cuda
 
+# a checkpoint's history keys: AAETrainer._series' lists, num_epochs, best_val_loss (what save_checkpoint derives)
 HISTORY = ("recon_loss", "Dlosses", "Glosses", "num_epochs", "best_val_loss")
 # what optim_state() adds to a checkpoint besides the AE / D moments ("m", "v") and the run settings
 OPTIM_FIELDS = ("m", "v", "step", "config", "mG", "vG", "steps")
@@ -86,6 +86,10 @@ class AAETrainer(VAETrainer):
     randn(36, z_dim) per epoch (sample_images)."""
     _gm_stock_class = True
     _hook_names = ("compute_batch", "train_D", "train_G", "evaluate")
+    _series = (("recon_loss", "recon"), ("Dlosses", "dloss"), ("Glosses", "gloss"))
+    _batch = "loss"             # the validation loss is vrecon alone, the epoch line has no total
+    _hands_force_dp = False
+    _line = "Epoch[%d/%d], Reconst Loss: %.4f, D Loss: %.4f, G Loss: %.4f, Val Loss: %.4f"
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False):
         self.model = to_cuda(model)
@@ -147,36 +151,11 @@ class AAETrainer(VAETrainer):
     def train(self, num_epochs, lr=1e-3, D_lr=2e-4, G_lr=2e-4, weight_decay=1e-5, quiet=False):
         """num_epochs passes of the three-phase loop; lr / weight_decay: the autoencoder's Adam, D_lr / G_lr: the
         discriminator's and the generator's (no weight decay)."""
-        from copy import deepcopy
         from . import dp
-        if dp.current()[0] > 1:
+        if dp.current()[0] > 1:                      # (not _one_gpu: this refusal never looked at force_dp)
             raise GMError("AAETrainer runs on one GPU: data parallelism is not implemented for it")
         if self._stock():
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            if self._engine is None:
-                self._engine = self._engine_class()(self.model, next(self.model.parameters()).device,
-                                                    use_graph=self.use_graph)
-            eng = self._engine
-            eng.use_graph = self.use_graph
-            steps = len(self.train_iter)
-            eng.configure(self.train_iter.batch_size, num_epochs * steps, lr, weight_decay, D_lr=D_lr, G_lr=G_lr,
-                          resume=self.__dict__.pop("_resume_optim", None))
-            tdata, vdata = self._device_data(self.train_iter), self._device_data(self.val_iter)
-            nval = len(self.val_iter)
-            eng.alloc_val(nval)
-            for epoch in range(1, num_epochs + 1):
-                self.model.train()
-                t0 = (epoch - 1) * steps
-                eng.run_pass(tdata, _epoch_order(self.train_iter), True, t0)
-                self.model.eval()
-                eng.run_pass(vdata, _epoch_order(self.val_iter), False, 0)
-                recon = [float(x) for x in eng.read_losses(eng.recon, t0, steps)]     # one sync
-                d = [float(x) for x in eng.read_losses(eng.dloss, t0, steps)]
-                g = [float(x) for x in eng.read_losses(eng.gloss, t0, steps)]
-                val_loss = np.mean([float(x) for x in eng.read_losses(eng.vrecon, 0, nval)])
-                self._end_epoch_aae(epoch, num_epochs, recon, d, g, val_loss, deepcopy, quiet)
-            return
+            return self._train_fused(num_epochs, lr, weight_decay, quiet, D_lr=D_lr, G_lr=G_lr)
         # GENERAL path: the three phases over autograd, three optimizers
         m = self.model
         ae_opt = FlatAdam(list(m.encoder.parameters()) + list(m.decoder.parameters()), lr, weight_decay=weight_decay)
@@ -202,30 +181,11 @@ class AAETrainer(VAETrainer):
                 recon.append(r.item()); d.append(dl.item()); g.append(gl.item())
             self.model.eval()
             val_loss = self.evaluate(self.val_iter)
-            self._end_epoch_aae(epoch, num_epochs, recon, d, g, val_loss, deepcopy, quiet)
-
-    def _end_epoch_aae(self, epoch, num_epochs, recon, d, g, val_loss, deepcopy, quiet):
-        self.recon_loss.extend(recon)
-        self.Dlosses.extend(d)
-        self.Glosses.extend(g)
-        if val_loss < self.best_val_loss:
-            self.best_model = deepcopy(self.model)
-            self.best_val_loss = val_loss
-        if not quiet:
-            print("Epoch[%d/%d], Reconst Loss: %.4f, D Loss: %.4f, G Loss: %.4f, Val Loss: %.4f"
-                  % (epoch, num_epochs, np.mean(recon), np.mean(d), np.mean(g), val_loss))
-        self.num_epochs += 1
-        self._viz_epoch(epoch)
+            self._end_epoch(epoch, num_epochs, (recon, d, g), val_loss, quiet)
 
     def viz_loss(self):
         from . import viz
         viz.vae_viz_loss(self, "none")
-
-    def save_checkpoint(self, savepath, collective=True):
-        """Weights, the three optimizers' moments and step counts, the RNG cursor and the histories (a finished
-        train() call on the fused engine)."""
-        from .trainers import _save_checkpoint
-        _save_checkpoint(self, savepath, tuple(n for n in HISTORY if hasattr(self, n)), collective=collective)
 
 
 __all__ = ["Encoder", "Decoder", "Discriminator", "AAE", "AAETrainer", "FlatAdam"]

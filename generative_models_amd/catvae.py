@@ -167,6 +167,10 @@ class CatVAETrainer(IWAETrainer):
     the training batches taken), sample / parzen from uniform one-hot codes, log_likelihood / posterior_codes under the
     discrete posterior, codes and decode.  One GPU only."""
 
+    _series = (("losses", "recon"), ("kl_loss", "kl"))
+    _line = "Epoch[%d/%d], Loss: %.4f, KL Div: %.4f, Val Loss: %.4f"
+    _one_gpu = "CatVAETrainer"
+
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, seed=0, hard=False):
         if not isinstance(hard, (bool, np.bool_)):
             raise CatVAEError("hard must be a bool, got %r" % (hard,))
@@ -203,10 +207,7 @@ class CatVAETrainer(IWAETrainer):
     def train(self, num_epochs, lr=1e-3, weight_decay=1e-5, tau0=1.0, tau_min=0.5, anneal_rate=3e-5, quiet=False):
         """vae.py's train loop on the relaxed (hard=True: straight-through) bound; batch t of the trainer's life runs at
         temperature(t, tau0, tau_min, anneal_rate)."""
-        from . import dp
         self.tau0, self.tau_min, self.anneal_rate = check_temperature(tau0, tau_min, anneal_rate)
-        if dp.current()[0] > 1 or getattr(self, "force_dp", False):
-            raise GMError("CatVAETrainer runs on one GPU: data parallelism is not implemented for it")
         return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
 
     def compute_batch(self, batch):
@@ -234,18 +235,6 @@ class CatVAETrainer(IWAETrainer):
         loss = ((x - self.model.decoder(z)) ** 2).sum() + kl
         return loss, kl.detach()
 
-    def _end_epoch_iwae(self, epoch, num_epochs, loss, kl, val_loss, deepcopy, quiet):
-        self.losses.extend(loss)
-        self.kl_loss.extend(kl)
-        if val_loss < self.best_val_loss:
-            self.best_model = deepcopy(self.model)
-            self.best_val_loss = val_loss
-        if not quiet:
-            print("Epoch[%d/%d], Loss: %.4f, KL Div: %.4f, Val Loss: %.4f"
-                  % (epoch, num_epochs, np.mean(loss), np.mean(kl), val_loss))
-        self.num_epochs += 1
-        self._viz_epoch(epoch)
-
     def _viz_epoch(self, epoch):
         pass                                         # vae.py's sample plot draws z ~ N(0, I): not this model's prior
 
@@ -257,13 +246,6 @@ class CatVAETrainer(IWAETrainer):
         plt.legend(["-log w"])
         plt.title(self.name)
         plt.show()
-
-    def save_checkpoint(self, savepath, collective=True):
-        """VAETrainer.save_checkpoint + noise_steps (the sizes, seed, hard and the temperature settings travel in the
-        optimizer state's config)."""
-        from .trainers import _save_checkpoint
-        _save_checkpoint(self, savepath, ("losses", "kl_loss", "num_epochs", "best_val_loss", "noise_steps"),
-                         collective=collective)
 
     # ---- codes, samples ------------------------------------------------------------------------------------------------
     def decode(self, codes):

@@ -50,16 +50,13 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _lib, ops, philox
 from ._lib import (DDPM_MAX_E, DDPM_MAX_I, DDPM_MAX_T, DDPM_MIN_E, DDPM_TAG_E, DDPM_TAG_S, DDPM_TAG_T, DDPM_TAG_V,
                    DDPM_TAG_VE, GMError)
-from .dvae import box_muller_normals, philox4x32_10
-from .trainers import (FlatAdam, VAETrainer, _epoch_order, _lin, _stock_module, stock, stock_model,  # noqa: F401
-                       to_cuda)
-from .engine import FlatParams, VAEEngine, _align4, _Linear
+from .trainers import FlatAdam, VAETrainer, _lin, _stock_module, stock, stock_model, to_cuda  # noqa: F401
+from .engine import VAEEngine, _align4, _Linear
 
 TAG_T, TAG_E, TAG_V, TAG_VE, TAG_S = DDPM_TAG_T, DDPM_TAG_E, DDPM_TAG_V, DDPM_TAG_VE, DDPM_TAG_S
-_M32 = 0xFFFFFFFF
 BETA_MAX = 0.999                 # cap of the scaled linear schedule (reached below T = 21 only)
 GRAPH_STEPS = 32                 # sampler steps per captured graph, at most
 
@@ -70,9 +67,11 @@ class DDPMError(GMError, ValueError):
 
 
 def _int(v, name):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        raise DDPMError("%s must be an integer, got %r" % (name, v))
-    return int(v)
+    return _lib.check_int(v, name, DDPMError)
+
+
+def check_seed(seed):
+    return _lib.check_seed(seed, error=DDPMError)
 
 
 def check_shape(image_size, time_dim, T):
@@ -85,13 +84,6 @@ def check_shape(image_size, time_dim, T):
     if not 2 <= T <= DDPM_MAX_T:
         raise DDPMError("T must lie in [2, %d], got %d" % (DDPM_MAX_T, T))
     return I, E, T
-
-
-def check_seed(seed):
-    seed = _int(seed, "seed")
-    if not 0 <= seed < 1 << 64:
-        raise DDPMError("seed must lie in [0, 2^64), got %d" % seed)
-    return seed
 
 
 def check_sampler(T, steps, eta):
@@ -143,30 +135,15 @@ def reverse_table(T, steps=None, eta=1.0):
     return coef, tau
 
 
-def _counters(n_rows, nq, step, row0, tag):
-    ctr = np.zeros((n_rows, nq, 4), dtype=np.uint64)
-    ctr[..., 0] = np.arange(nq, dtype=np.uint64)[None, :]
-    ctr[..., 1] = np.uint64(int(step) & _M32)
-    ctr[..., 2] = ((np.arange(n_rows, dtype=np.uint64) + np.uint64(row0)) & np.uint64(_M32))[:, None]
-    ctr[..., 3] = np.uint64(int(tag) & _M32)
-    return ctr
-
-
-def _key(seed):
-    return np.array([seed & _M32, (seed >> 32) & _M32], dtype=np.uint64)
-
-
 def timesteps_reference(n_rows, T, seed, step, tag=TAG_T, row0=0):
     """t [n_rows] int64 of batch rows row0 .. at `step`: mulhi(word 0 of counter (0, step, row, tag), T)."""
-    w = philox4x32_10(_counters(n_rows, 1, step, row0, tag), _key(seed))[:, 0, 0].astype(np.uint64)
+    w = philox.words(n_rows, 1, seed, step, tag, row0)[:, 0].astype(np.uint64)
     return ((w * np.uint64(T)) >> np.uint64(32)).astype(np.int64)
 
 
 def noise_reference(n_rows, I, seed, step, tag=TAG_E, row0=0):
     """The normals [n_rows, I] float64 of rows row0 .. at `step` under `tag` (TAG_S: the sampler's z at step `step`)."""
-    nq = (I + 3) // 4
-    words = philox4x32_10(_counters(n_rows, nq, step, row0, tag), _key(seed)).reshape(n_rows, 4 * nq)
-    return box_muller_normals(words)[:, :I]
+    return philox.normals(n_rows, I, seed, step, tag, row0)
 
 
 def qsample_reference(x, T, E, seed, step, train=True, row0=0):
@@ -247,25 +224,20 @@ class DDPMEngine(VAEEngine):
     gather.  One GPU only."""
 
     has_eps = False
+    one_gpu = "the DDPM engine"
 
     def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
                  trainer=None):
-        if world_size > 1 or force_dp:
-            raise GMError("the DDPM engine runs on one GPU: data parallelism is not implemented for it")
+        self._refuse_dp(world_size, force_dp)
         if not ddpm_fused_ok(model):
             raise GMError("DDPMEngine: the model is not ddpm.DDPM with its Denoiser unchanged; DDPMTrainer trains "
                           "such models on the general path")
-        self.model, self.device, self.use_graph = model, device, use_graph
         d = model.denoiser
-        plist = [d.linear.weight, d.linear.bias, d.hidden.weight, d.hidden.bias, d.out.weight, d.out.bias]
-        self._dp_init(plist, 1, 0, None, False)
-        self.fp = FlatParams(plist, device)
+        self._init_flat(model, device, use_graph,
+                        [d.linear.weight, d.linear.bias, d.hidden.weight, d.hidden.bias, d.out.weight, d.out.bias])
+        self._bind_trainer(trainer)                  # seed and noise_steps are read from it
         self.L1, self.L2, self.L3 = _Linear(self.fp, d.linear), _Linear(self.fp, d.hidden), _Linear(self.fp, d.out)
         self.I, self.E, self.T, self.H = model.image_size, model.time_dim, model.T, d.linear.weight.shape[0]
-        self.Z = 1                                   # width of VAEEngine.configure's (unused, dropped) eps ring
-        self.trainer = trainer                       # seed and noise_steps are read from it
-        self.nbase = torch.zeros(1, dtype=torch.int64, device=device)
-        self._common_init(device)
 
     def _alloc(self, B):
         if self._bufB == B:
@@ -281,28 +253,19 @@ class DDPMEngine(VAEEngine):
         self._bufB = B
         self.graphs = {}
 
+    def _settings(self):
+        m = self.model
+        return {"T": int(m.T), "time_dim": int(m.time_dim), "seed": int(self.trainer.seed)}
+
+    def _graph_args(self):
+        m = self.model
+        return tuple(t.data_ptr() for t in (m.sa, m.s1, m.temb))     # the tables are launch arguments of the graphs
+
     def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
-        tr, m = self.trainer, self.model
-        now = {"T": int(m.T), "time_dim": int(m.time_dim), "seed": int(tr.seed)}
-        if resume is not None and resume.get("config") is not None and not resume.get("lenient", False):
-            saved = resume["config"]
-            diff = {n: (saved[n], now[n]) for n in now if n in saved and saved[n] != now[n]}
-            if diff:
-                raise GMError("checkpoint was written by a run with different settings (saved, now): %s; "
-                              "load_checkpoint(path, strict=False) overrides" % diff)
         super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
-        self.run_config.update(now)
-        self.eps_ring = None                         # the noise is drawn on the device: no host ring, no upload
-        for s in self.stage:
-            s.pop("eps", None)
         from . import ops_fused as of_
-        tabs = (m.sa, m.s1, m.temb)
-        key = (now["seed"],) + tuple(t.data_ptr() for t in tabs)
-        if getattr(self, "_noise_key", None) != key:
-            self.graphs = {}                         # the seed and the tables are launch arguments of the graphs
-        self._noise_key = key
-        self.tab = of_.ddpm_tables(*tabs)
-        self.nbase.fill_(int(tr.noise_steps))
+        m = self.model
+        self.tab = of_.ddpm_tables(m.sa, m.s1, m.temb)
 
     def _noise(self, t, train):
         from . import ops_fused as of_
@@ -345,6 +308,10 @@ class DDPMTrainer(VAETrainer):
     (+ T, time_dim, seed in the optimizer state's config, checked under strict=True, and the number of training batches
     taken, so a resumed run continues the noise stream bit for bit).  One GPU only."""
     _hook_names = ("compute_batch", "evaluate")
+    _series = (("losses", "recon"),)
+    _batch = "loss"
+    _line = "Epoch[%d/%d], Loss: %.6f, Val Loss: %.6f"
+    _one_gpu = "DDPMTrainer"
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, seed=0):
         self.seed = check_seed(seed)                 # before anything runs
@@ -395,58 +362,8 @@ class DDPMTrainer(VAETrainer):
         return functools.partial(DDPMEngine, trainer=self)
 
     def train(self, num_epochs, lr=2e-4, weight_decay=0.0, quiet=False):
-        from copy import deepcopy
-        from . import dp
-        if dp.current()[0] > 1 or getattr(self, "force_dp", False):
-            raise GMError("DDPMTrainer runs on one GPU: data parallelism is not implemented for it")
-        if self._stock():
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            dev = next(self.model.parameters()).device
-            if self._engine is None:
-                self._engine = self._engine_class()(self.model, dev, use_graph=self.use_graph)
-            eng = self._engine
-            eng.use_graph = self.use_graph
-            steps, nval = len(self.train_iter), len(self.val_iter)
-            eng.configure(self.train_iter.batch_size, num_epochs * steps, lr, weight_decay,
-                          resume=self.__dict__.pop("_resume_optim", None))
-            tdata, vdata = self._device_data(self.train_iter), self._device_data(self.val_iter)
-            eng.alloc_val(nval)
-            for epoch in range(1, num_epochs + 1):
-                self.model.train()
-                t0 = (epoch - 1) * steps
-                eng.run_pass(tdata, _epoch_order(self.train_iter), True, t0)
-                self.model.eval()
-                eng.run_pass(vdata, _epoch_order(self.val_iter), False, 0)
-                loss = [float(v) for v in eng.read_losses(eng.recon, t0, steps)]     # one sync
-                val_loss = np.mean([float(v) for v in eng.read_losses(eng.vrecon, 0, nval)])
-                self._end_epoch_ddpm(epoch, num_epochs, loss, val_loss, deepcopy, quiet)
-            self.noise_steps += num_epochs * steps
-            return
-        # GENERAL path (compute_batch / evaluate overridden, an edited model)
-        opt = FlatAdam(self.model.parameters(), lr, weight_decay=weight_decay)
-        for epoch in range(1, num_epochs + 1):
-            self.model.train()
-            loss = []
-            for batch in self.train_iter:
-                opt.zero_grad()
-                l = self.compute_batch(batch)
-                l.backward()
-                opt.step()
-                loss.append(l.item())
-            self.model.eval()
-            val_loss = self.evaluate(self.val_iter)
-            self._end_epoch_ddpm(epoch, num_epochs, loss, val_loss, deepcopy, quiet)
-
-    def _end_epoch_ddpm(self, epoch, num_epochs, loss, val_loss, deepcopy, quiet):
-        self.losses.extend(loss)
-        if val_loss < self.best_val_loss:
-            self.best_model = deepcopy(self.model)
-            self.best_val_loss = val_loss
-        if not quiet:
-            print("Epoch[%d/%d], Loss: %.6f, Val Loss: %.6f" % (epoch, num_epochs, np.mean(loss), val_loss))
-        self.num_epochs += 1
-        self._viz_epoch(epoch)
+        """VAETrainer.train with this model's defaults."""
+        return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
 
     # ---- sampling ---------------------------------------------------------------------------------------------------
     def sample(self, n, seed=0, steps=None, eta=1.0, clip=True, return_trajectory=False):
@@ -575,11 +492,6 @@ class DDPMTrainer(VAETrainer):
         plt.legend(["L_simple"])
         plt.title(self.name)
         plt.show()
-
-    def save_checkpoint(self, savepath, collective=True):
-        """VAETrainer.save_checkpoint + noise_steps (T, time_dim and seed travel in the optimizer state's config)."""
-        from .trainers import _save_checkpoint
-        _save_checkpoint(self, savepath, ("losses", "num_epochs", "best_val_loss", "noise_steps"), collective=collective)
 
 
 __all__ = ["Denoiser", "DDPM", "DDPMTrainer", "DDPMEngine", "DDPMError", "tables", "reverse_table",

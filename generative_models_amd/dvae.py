@@ -23,11 +23,12 @@ import math
 import numpy as np
 import torch
 
-from ._lib import NOISE, GMError
+from . import philox
+from ._lib import NOISE, GMError, check_seed
+from .philox import box_muller_normals, philox4x32_10  # noqa: F401  (imported from here by other modules and tests)
 from .trainers import VAE, Decoder, Encoder, FlatAdam, VAETrainer, stock, stock_model, to_cuda  # noqa: F401
 
 CTR_TAG = 0x44564145          # "DVAE": the fourth counter word
-_M32 = 0xFFFFFFFF
 _FLT_MAX = float(np.finfo(np.float32).max)
 
 
@@ -52,12 +53,7 @@ def check_noise(noise, level, seed):
         raise NoiseError("salt_pepper level (the replaced fraction) must lie in [0, 1], got %r" % level)
     if noise == "gaussian" and level < 0.0:
         raise NoiseError("gaussian level (the noise's standard deviation) must be >= 0, got %r" % level)
-    if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)):
-        raise NoiseError("seed must be an integer, got %r" % (seed,))
-    seed = int(seed)
-    if not 0 <= seed < 1 << 64:
-        raise NoiseError("seed must lie in [0, 2^64), got %d" % seed)
-    return noise, level, seed
+    return noise, level, check_seed(seed, error=NoiseError)
 
 
 def corrupt(images, noise="salt_pepper", level=0.25, seed=0, step=0, row0=0):
@@ -79,46 +75,14 @@ def corrupt(images, noise="salt_pepper", level=0.25, seed=0, step=0, row0=0):
 
 
 # ---- the rule in numpy (the tests' reference; also a CPU reading of what the device computes) ------------------------
-def philox4x32_10(ctr, key):
-    """Philox4x32-10 over arrays: ctr [..., 4] and key [..., 2] (broadcast) of uint32 -> [..., 4] uint32."""
-    c = [np.asarray(ctr[..., i], dtype=np.uint64) for i in range(4)]
-    k0 = np.asarray(key[..., 0], dtype=np.uint64)
-    k1 = np.asarray(key[..., 1], dtype=np.uint64)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c[0]
-        p1 = np.uint64(0xCD9E8D57) * c[2]
-        c = [((p1 >> np.uint64(32)) ^ c[1] ^ k0) & np.uint64(_M32), p1 & np.uint64(_M32),
-             ((p0 >> np.uint64(32)) ^ c[3] ^ k1) & np.uint64(_M32), p0 & np.uint64(_M32)]
-        k0 = (k0 + np.uint64(0x9E3779B9)) & np.uint64(_M32)
-        k1 = (k1 + np.uint64(0xBB67AE85)) & np.uint64(_M32)
-    return np.stack(c, axis=-1).astype(np.uint32)
-
-
 def corruption_words(n_rows, row_elems, seed, step, row0=0):
     """The uint32 word of every pixel: [n_rows, row_elems]."""
-    q = np.arange((row_elems + 3) // 4, dtype=np.uint64)
-    rows = (np.arange(n_rows, dtype=np.uint64) + np.uint64(row0)) & np.uint64(_M32)
-    ctr = np.zeros((n_rows, q.size, 4), dtype=np.uint64)
-    ctr[..., 0] = q[None, :]
-    ctr[..., 1] = np.uint64(int(step) & _M32)
-    ctr[..., 2] = rows[:, None]
-    ctr[..., 3] = CTR_TAG
-    key = np.array([seed & _M32, (seed >> 32) & _M32], dtype=np.uint64)
-    return philox4x32_10(ctr, key).reshape(n_rows, -1)[:, :row_elems]
+    return philox.words(n_rows, row_elems, seed, step, CTR_TAG, row0)
 
 
 def sp_threshold(p):
     """T = floor(p 2^31), in 64-bit on the host."""
     return int(math.floor(float(p) * 2.0 ** 31))
-
-
-def box_muller_normals(words):
-    """The normal of every word ([n, 4k] uint32: pairs (0, 1), (2, 3) of each group of four), float64."""
-    u = ((2.0 * (words >> np.uint32(9)).astype(np.float64) + 1.0) * 2.0 ** -24)
-    w = u.reshape(u.shape[0], -1, 2)
-    r = np.sqrt(-2.0 * np.log(w[..., 0]))
-    phi = 2.0 * np.pi * w[..., 1]
-    return np.stack([r * np.cos(phi), r * np.sin(phi)], axis=-1).reshape(u.shape)
 
 
 def corrupt_reference(x, noise, level, seed, step, row0=0):
@@ -155,6 +119,8 @@ class DVAETrainer(VAETrainer):
     kl_loss), epoch line, best_val_loss on clean validation images, checkpoints (+ the noise settings and the number of
     training batches taken, so a resumed run continues the noise stream).  One GPU only."""
 
+    _one_gpu = "DVAETrainer"
+
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, noise="salt_pepper", level=0.25, seed=0):
         self.noise, self.level, self.seed = check_noise(noise, level, seed)     # before anything runs
         super().__init__(model, train_iter, val_iter, test_iter, viz=viz)
@@ -177,17 +143,6 @@ class DVAETrainer(VAETrainer):
         from .engine import DVAEEngine
         return functools.partial(DVAEEngine, trainer=self)
 
-    def train(self, num_epochs, lr=1e-3, weight_decay=1e-5, quiet=False):
-        """vae.py:127-191 with corrupted encoder inputs."""
-        from . import dp
-        if dp.current()[0] > 1 or getattr(self, "force_dp", False):
-            raise GMError("DVAETrainer runs on one GPU: data parallelism is not implemented for it")
-        if self._stock():
-            super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
-            self.noise_steps += num_epochs * len(self.train_iter)
-            return
-        super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)     # compute_batch counts
-
     def denoise(self, images, batch=1024):
         """(noisy, recon): noisy = the corruption of `images` as training batch step 0 sees it (corrupt(images, ...,
         step=0)), recon = sigmoid(decoder(mu(encoder(noisy)))) -- the mean decoding, no sampling.  Device tensors
@@ -198,12 +153,6 @@ class DVAETrainer(VAETrainer):
             recon = torch.cat([self.model.decoder(self.model.encoder(noisy[i:i + batch])[0])
                                for i in range(0, noisy.shape[0], batch)])
         return noisy, recon
-
-    def save_checkpoint(self, savepath, collective=True):
-        """VAETrainer.save_checkpoint + noise_steps (the noise settings travel in the optimizer state's config)."""
-        from .trainers import _save_checkpoint
-        hist = ("recon_loss", "kl_loss", "num_epochs", "best_val_loss", "noise_steps")
-        _save_checkpoint(self, savepath, hist, collective=collective)
 
 
 __all__ = ["Encoder", "Decoder", "DVAE", "DVAETrainer", "NoiseError", "corrupt", "corrupt_reference", "FlatAdam"]

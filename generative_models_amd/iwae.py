@@ -36,14 +36,12 @@ import math
 import numpy as np
 import torch
 
+from . import _lib, philox
 from ._lib import IWAE_MAX_K, IWAE_MAX_Z, IWAE_TAG_EVAL, IWAE_TAG_TRAIN, GMError
-from .dvae import box_muller_normals, philox4x32_10
 from .metrics import IWAEResult
-from .trainers import (VAE, Decoder, Encoder, FlatAdam, VAETrainer, _epoch_order, _stock_module,  # noqa: F401
-                       stock, stock_model, to_cuda)
+from .trainers import VAE, Decoder, Encoder, FlatAdam, VAETrainer, _stock_module, stock, stock_model, to_cuda  # noqa: F401
 
 TAG_TRAIN, TAG_EVAL = IWAE_TAG_TRAIN, IWAE_TAG_EVAL
-_M32 = 0xFFFFFFFF
 LL_CHUNK = IWAE_MAX_K            # samples per launch group of log_likelihood
 LL_BATCH = 256                   # images per batch of log_likelihood (its noise step is the batch's index)
 
@@ -54,29 +52,16 @@ class IWAEError(GMError, ValueError):
 
 def check_k_seed(k, seed):
     """(k, seed) validated: an integer k >= 1 and an integer seed in [0, 2^64); else IWAEError."""
-    for v, nm in ((k, "k"), (seed, "seed")):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-            raise IWAEError("%s must be an integer, got %r" % (nm, v))
-    k, seed = int(k), int(seed)
+    k, seed = _lib.check_int(k, "k", IWAEError), _lib.check_int(seed, "seed", IWAEError)
     if k < 1:
         raise IWAEError("k (samples per image) must be >= 1, got %d" % k)
-    if not 0 <= seed < 1 << 64:
-        raise IWAEError("seed must lie in [0, 2^64), got %d" % seed)
-    return k, seed
+    return k, _lib.check_seed(seed, error=IWAEError)
 
 
 # ---- the rule in numpy and fp64 (the tests' reference; also a CPU reading of what the device computes) ---------------
 def iwae_noise_reference(n_rows, Z, seed, step, tag):
     """eps [n_rows, Z] float64: the normals of sample rows 0 .. n_rows - 1 at `step` under `tag`."""
-    nq = (Z + 3) // 4
-    ctr = np.zeros((n_rows, nq, 4), dtype=np.uint64)
-    ctr[..., 0] = np.arange(nq, dtype=np.uint64)[None, :]
-    ctr[..., 1] = np.uint64(int(step) & _M32)
-    ctr[..., 2] = (np.arange(n_rows, dtype=np.uint64) & np.uint64(_M32))[:, None]
-    ctr[..., 3] = np.uint64(int(tag) & _M32)
-    key = np.array([seed & _M32, (seed >> 32) & _M32], dtype=np.uint64)
-    words = philox4x32_10(ctr, key).reshape(n_rows, 4 * nq)
-    return box_muller_normals(words)[:, :Z]
+    return philox.normals(n_rows, Z, seed, step, tag)
 
 
 def iwae_reference(params, x, eps, k):
@@ -202,6 +187,10 @@ class IWAETrainer(VAETrainer):
     epoch line (mean loss, mean ess, validation loss), best_val_loss / best_model as VAETrainer, checkpoints (+ k, seed,
     the number of training batches taken, so a resumed run continues the noise stream).  One GPU only."""
     _hook_names = ("compute_batch", "evaluate")
+    _series = (("losses", "recon"), ("ess", "kl"))               # the engine's `kl` slots hold the mean ess
+    _batch = "loss+stat"
+    _line = "Epoch[%d/%d], Loss: %.4f, ESS: %.4f, Val Loss: %.4f"
+    _one_gpu = "IWAETrainer"
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, k=5, seed=0):
         self.k, self.seed = check_k_seed(k, seed)              # before anything runs
@@ -246,69 +235,14 @@ class IWAETrainer(VAETrainer):
         with torch.no_grad():
             return np.mean([self.compute_batch(batch)[0].item() for batch in iterator])
 
+    def _general_optimizer(self, lr, weight_decay):
+        # through this module's FlatAdam name: replacing iwae.FlatAdam is how this family's general optimiser is observed
+        return FlatAdam(self.model.parameters(), lr, weight_decay=weight_decay)
+
     def _engine_class(self):
         import functools
         from .engine import IWAEEngine
         return functools.partial(IWAEEngine, trainer=self)
-
-    def train(self, num_epochs, lr=1e-3, weight_decay=1e-5, quiet=False):
-        """vae.py's train loop on the k-sample bound."""
-        from copy import deepcopy
-        from . import dp
-        if dp.current()[0] > 1 or getattr(self, "force_dp", False):
-            raise GMError("IWAETrainer runs on one GPU: data parallelism is not implemented for it")
-        if self._stock():
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            dev = next(self.model.parameters()).device
-            if self._engine is None:
-                self._engine = self._engine_class()(self.model, dev, use_graph=self.use_graph)
-            eng = self._engine
-            eng.use_graph = self.use_graph
-            steps, nval = len(self.train_iter), len(self.val_iter)
-            eng.configure(self.train_iter.batch_size, num_epochs * steps, lr, weight_decay,
-                          resume=self.__dict__.pop("_resume_optim", None))
-            tdata, vdata = self._device_data(self.train_iter), self._device_data(self.val_iter)
-            eng.alloc_val(nval)
-            for epoch in range(1, num_epochs + 1):
-                self.model.train()
-                t0 = (epoch - 1) * steps
-                eng.run_pass(tdata, _epoch_order(self.train_iter), True, t0)
-                self.model.eval()
-                eng.run_pass(vdata, _epoch_order(self.val_iter), False, 0)
-                loss = [float(v) for v in eng.read_losses(eng.recon, t0, steps)]     # one sync
-                ess = [float(v) for v in eng.read_losses(eng.kl, t0, steps)]
-                val_loss = np.mean([float(v) for v in eng.read_losses(eng.vrecon, 0, nval)])
-                self._end_epoch_iwae(epoch, num_epochs, loss, ess, val_loss, deepcopy, quiet)
-            self.noise_steps += num_epochs * steps
-            return
-        # GENERAL path (compute_batch / evaluate overridden, an edited model, k or z_dim above the fused limits)
-        opt = FlatAdam(self.model.parameters(), lr, weight_decay=weight_decay)
-        for epoch in range(1, num_epochs + 1):
-            self.model.train()
-            loss, ess = [], []
-            for batch in self.train_iter:
-                opt.zero_grad()
-                l, e = self.compute_batch(batch)
-                l.backward()
-                opt.step()
-                loss.append(l.item())
-                ess.append(float(e))
-            self.model.eval()
-            val_loss = self.evaluate(self.val_iter)
-            self._end_epoch_iwae(epoch, num_epochs, loss, ess, val_loss, deepcopy, quiet)
-
-    def _end_epoch_iwae(self, epoch, num_epochs, loss, ess, val_loss, deepcopy, quiet):
-        self.losses.extend(loss)
-        self.ess.extend(ess)
-        if val_loss < self.best_val_loss:
-            self.best_model = deepcopy(self.model)
-            self.best_val_loss = val_loss
-        if not quiet:
-            print("Epoch[%d/%d], Loss: %.4f, ESS: %.4f, Val Loss: %.4f"
-                  % (epoch, num_epochs, np.mean(loss), np.mean(ess), val_loss))
-        self.num_epochs += 1
-        self._viz_epoch(epoch)
 
     def viz_loss(self):
         """The training loss (sum_b -L_k per batch) over the epochs."""
@@ -318,12 +252,6 @@ class IWAETrainer(VAETrainer):
         plt.legend(["-L_k"])
         plt.title(self.name)
         plt.show()
-
-    def save_checkpoint(self, savepath, collective=True):
-        """VAETrainer.save_checkpoint + noise_steps (k and seed travel in the optimizer state's config)."""
-        from .trainers import _save_checkpoint
-        hist = ("losses", "ess", "num_epochs", "best_val_loss", "noise_steps")
-        _save_checkpoint(self, savepath, hist, collective=collective)
 
 
 __all__ = ["Encoder", "Decoder", "IWAE", "IWAETrainer", "IWAEError", "iwae_noise_reference", "iwae_reference",

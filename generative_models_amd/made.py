@@ -37,15 +37,12 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _lib, ops, philox
 from ._lib import MADE_MAX_H, MADE_MAX_I, MADE_MIN_I, MADE_TAG_S, GMError
-from .dvae import philox4x32_10
-from .trainers import (FlatAdam, VAETrainer, _dataset_rows, _epoch_order, _stock_module, stock, stock_model,  # noqa: F401
-                       to_cuda)
-from .engine import FlatParams, VAEEngine, _Linear
+from .trainers import FlatAdam, VAETrainer, _dataset_rows, _stock_module, stock, stock_model, to_cuda  # noqa: F401
+from .engine import VAEEngine, _Linear
 
 TAG_MS = MADE_TAG_S
-_M32 = 0xFFFFFFFF
 ORDERS = ("natural", "random")
 
 
@@ -55,9 +52,11 @@ class MADEError(GMError, ValueError):
 
 
 def _int(v, name):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        raise MADEError("%s must be an integer, got %r" % (name, v))
-    return int(v)
+    return _lib.check_int(v, name, MADEError)
+
+
+def check_seed(seed, name="seed"):
+    return _lib.check_seed(seed, name, MADEError)
 
 
 def check_shape(image_size, hidden_dim):
@@ -68,13 +67,6 @@ def check_shape(image_size, hidden_dim):
     if not 1 <= H <= MADE_MAX_H:
         raise MADEError("hidden_dim must lie in [1, %d], got %d" % (MADE_MAX_H, H))
     return I, H
-
-
-def check_seed(seed, name="seed"):
-    seed = _int(seed, name)
-    if not 0 <= seed < 1 << 64:
-        raise MADEError("%s must lie in [0, 2^64), got %d" % (name, seed))
-    return seed
 
 
 def check_order(order, order_seed):
@@ -126,14 +118,7 @@ def inverse_order(m_in):
 
 def uniforms_reference(n, I, seed, row0=0):
     """u [n, I] float32: the sampler's uniforms of sample rows row0 .. by the contract's rule, bit for bit."""
-    nq = (I + 3) // 4
-    ctr = np.zeros((n, nq, 4), dtype=np.uint64)
-    ctr[..., 0] = np.arange(nq, dtype=np.uint64)[None, :]
-    ctr[..., 2] = ((np.arange(n, dtype=np.uint64) + np.uint64(row0)) & np.uint64(_M32))[:, None]
-    ctr[..., 3] = np.uint64(TAG_MS)
-    key = np.array([seed & _M32, (seed >> 32) & _M32], dtype=np.uint64)
-    w = philox4x32_10(ctr, key).reshape(n, 4 * nq)[:, :I].astype(np.uint64)
-    return ((2 * (w >> np.uint64(9)) + 1).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
+    return philox.unit_uniforms(philox.words(n, I, seed, 0, TAG_MS, row0))
 
 
 # ---- module ----------------------------------------------------------------------------------------------------------
@@ -208,21 +193,17 @@ class MADEEngine(VAEEngine):
     One GPU only."""
 
     has_eps = False
+    one_gpu = "the MADE engine"
 
     def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False):
-        if world_size > 1 or force_dp:
-            raise GMError("the MADE engine runs on one GPU: data parallelism is not implemented for it")
+        self._refuse_dp(world_size, force_dp)
         if not made_fused_ok(model):
             raise GMError("MADEEngine: the model is not made.MADE with its layers unchanged; MADETrainer trains such "
                           "models on the general path")
-        self.model, self.device, self.use_graph = model, device, use_graph
-        plist = [model.linear.weight, model.linear.bias, model.out.weight, model.out.bias]
-        self._dp_init(plist, 1, 0, None, False)
-        self.fp = FlatParams(plist, device)
+        self._init_flat(model, device, use_graph,
+                        [model.linear.weight, model.linear.bias, model.out.weight, model.out.bias])
         self.L1, self.L2 = _Linear(self.fp, model.linear), _Linear(self.fp, model.out)
         self.I, self.H = model.image_size, model.hidden_dim
-        self.Z = 1                                   # width of VAEEngine.configure's (unused, dropped) eps ring
-        self._common_init(device)
 
     def _alloc(self, B):
         if self._bufB == B:
@@ -233,17 +214,15 @@ class MADEEngine(VAEEngine):
         self._bufB = B
         self.graphs = {}
 
+    def _settings(self):
+        return {"order": str(self.model.order), "order_seed": int(self.model.order_seed)}
+
+    def _graph_args(self):
+        return self.model.m_in.data_ptr(), self.model.m_h.data_ptr()     # the degree vectors are launch arguments
+
     def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
         m = self.model
-        self._extra_config = {"order": str(m.order), "order_seed": int(m.order_seed)}
         super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
-        self.eps_ring = None                         # nothing is drawn: no host ring, no upload
-        for s in self.stage:
-            s.pop("eps", None)
-        key = (m.m_in.data_ptr(), m.m_h.data_ptr())
-        if getattr(self, "_degree_key", None) != key:
-            self.graphs = {}                         # the degree vectors are launch arguments of the graphs
-        self._degree_key = key
         from . import ops_fused as of_
         # whatever was loaded into the model, training starts from masked weights (resumed moments are masked already)
         of_.made_mask(self.L1.W, self.L2.W, m.m_in, m.m_h)
@@ -279,6 +258,10 @@ class MADETrainer(VAETrainer):
     the other VAE-family trainers; checkpoints (+ order, order_seed in the optimizer state's config, checked under
     strict=True; resuming is bit-identical).  One GPU only."""
     _hook_names = ("compute_batch", "evaluate")
+    _series = (("losses", "recon"),)
+    _batch = "loss"
+    _line = "Epoch[%d/%d], NLL: %.6f, Val NLL: %.6f"
+    _one_gpu = "MADETrainer"
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False):
         super().__init__(model, train_iter, val_iter, test_iter, viz=viz)
@@ -308,69 +291,11 @@ class MADETrainer(VAETrainer):
         return MADEEngine
 
     def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
-        from copy import deepcopy
-        from . import dp
-        if dp.current()[0] > 1 or getattr(self, "force_dp", False):
-            raise GMError("MADETrainer runs on one GPU: data parallelism is not implemented for it")
-        if self._stock():
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            dev = next(self.model.parameters()).device
-            if self._engine is None:
-                self._engine = self._engine_class()(self.model, dev, use_graph=self.use_graph)
-            eng = self._engine
-            eng.use_graph = self.use_graph
-            steps, nval = len(self.train_iter), len(self.val_iter)
-            eng.configure(self.train_iter.batch_size, num_epochs * steps, lr, weight_decay,
-                          resume=self.__dict__.pop("_resume_optim", None))
-            tdata, vdata = self._device_data(self.train_iter), self._device_data(self.val_iter)
-            eng.alloc_val(nval)
-            for epoch in range(1, num_epochs + 1):
-                self.model.train()
-                t0 = (epoch - 1) * steps
-                eng.run_pass(tdata, _epoch_order(self.train_iter), True, t0)
-                self.model.eval()
-                eng.run_pass(vdata, _epoch_order(self.val_iter), False, 0)
-                loss = [float(v) for v in eng.read_losses(eng.recon, t0, steps)]     # one sync
-                val_loss = np.mean([float(v) for v in eng.read_losses(eng.vrecon, 0, nval)])
-                self._end_epoch_made(epoch, num_epochs, loss, val_loss, deepcopy, quiet)
-            return
-        # GENERAL path (compute_batch / evaluate overridden, an edited model): weight * mask in the forward keeps every
-        # masked gradient, Adam moment and entry at zero
-        opt = FlatAdam(self.model.parameters(), lr, weight_decay=weight_decay)
-        for epoch in range(1, num_epochs + 1):
-            self.model.train()
-            loss = []
-            for batch in self.train_iter:
-                opt.zero_grad()
-                l = self.compute_batch(batch)
-                l.backward()
-                opt.step()
-                loss.append(l.item())
-            self.model.eval()
-            val_loss = self.evaluate(self.val_iter)
-            self._end_epoch_made(epoch, num_epochs, loss, val_loss, deepcopy, quiet)
-        self._general_opt = opt                      # the moments, for inspection
-
-    def _end_epoch_made(self, epoch, num_epochs, loss, val_loss, deepcopy, quiet):
-        self.losses.extend(loss)
-        if val_loss < self.best_val_loss:
-            self.best_model = deepcopy(self.model)
-            self.best_val_loss = val_loss
-        if not quiet:
-            print("Epoch[%d/%d], NLL: %.6f, Val NLL: %.6f" % (epoch, num_epochs, np.mean(loss), val_loss))
-        self.num_epochs += 1
-        self._viz_epoch(epoch)
+        """VAETrainer.train with this model's defaults (general path: weight * mask in the forward keeps every masked
+        gradient, Adam moment and entry at zero)."""
+        return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
 
     # ---- sampling and scoring ------------------------------------------------------------------------------------------
-    def _device(self):
-        if not torch.cuda.is_available():
-            raise GMError("sampling and scoring run on the MI355X only: no GPU is visible")
-        dev = next(self.model.parameters()).device
-        if dev.type != "cuda":
-            raise GMError("the model is not on the GPU")
-        return dev
-
     def _logits(self, x):
         """The model's logits of device rows x, no autograd: the two GEMM launches for a stock model, its own forward
         otherwise."""
@@ -490,12 +415,6 @@ class MADETrainer(VAETrainer):
         plt.legend(["NLL (nats per image)"])
         plt.title(self.name)
         plt.show()
-
-    def save_checkpoint(self, savepath, collective=True):
-        """VAETrainer.save_checkpoint with this trainer's history (order and order_seed travel in the optimizer state's
-        config, the degrees themselves in the model's state_dict)."""
-        from .trainers import _save_checkpoint
-        _save_checkpoint(self, savepath, ("losses", "num_epochs", "best_val_loss"), collective=collective)
 
 
 __all__ = ["MADE", "MADETrainer", "MADEEngine", "MADEError", "degrees", "masks", "inverse_order", "uniforms_reference",

@@ -123,6 +123,8 @@ class NFVAETrainer(IWAETrainer):
     checkpoints (+ k, seed, num_flows and the training batches taken), sample / parzen from the unchanged prior
     z ~ N(0, I), its own log_likelihood and posterior_samples.  One GPU only."""
 
+    _one_gpu = "NFVAETrainer"
+
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, k=1, seed=0):
         super().__init__(model, train_iter, val_iter, test_iter, viz=viz, k=k, seed=seed)
 
@@ -133,13 +135,6 @@ class NFVAETrainer(IWAETrainer):
         import functools
         from .engine import NFVAEEngine
         return functools.partial(NFVAEEngine, trainer=self)
-
-    def train(self, num_epochs, lr=1e-3, weight_decay=1e-5, quiet=False):
-        """vae.py's train loop on the k-sample bound with the flow posterior."""
-        from . import dp
-        if dp.current()[0] > 1 or getattr(self, "force_dp", False):
-            raise GMError("NFVAETrainer runs on one GPU: data parallelism is not implemented for it")
-        return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
 
     def compute_batch(self, batch):
         """(sum_b -L_k, mean ess) of a batch (general path: autograd over the fused linear kernels and the chain in

@@ -167,8 +167,9 @@ class PDWGANEngine(VAEEngine):
         self.graphs = {}
 
     def configure(self, B, n_train_steps, E_lr, G_lr=1e-4, D_lr=1e-4, lambda_z=LAMBDA_Z, lambda_gp=10.0, resume=None):
-        # (compared with a checkpoint's settings by VAEEngine.configure, like its own)
-        self._extra_config = {"G_lr": float(G_lr), "D_lr": float(D_lr), "lambda_z": float(lambda_z),
+        # (compared with a checkpoint's settings by VAEEngine.configure, like its own; as settings they are part of
+        # the graphs' key too, so a train() call with other learning rates captures its graphs anew)
+        self._run_settings = {"G_lr": float(G_lr), "D_lr": float(D_lr), "lambda_z": float(lambda_z),
                               "lambda_gp": float(lambda_gp)}
         from .engine import GANEngine
         super().configure(B, n_train_steps, E_lr, 0.0, resume=resume)
@@ -192,6 +193,9 @@ class PDWGANEngine(VAEEngine):
         if self._moved or getattr(self, "_lam_key", None) != lam:
             self.graphs = {}
         self._lam_key = lam
+
+    def _settings(self):
+        return self._run_settings
 
     def optim_state(self):
         st = super().optim_state()

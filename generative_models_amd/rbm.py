@@ -32,14 +32,11 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _lib, ops, philox
 from ._lib import RBM_MAX_DIM, RBM_MAX_STEPS, RBM_TAG_D, RBM_TAG_H, RBM_TAG_V, GMError
-from .dvae import philox4x32_10
-from .trainers import (FlatAdam, VAETrainer, _dataset_rows, _epoch_order, _stock_module, stock, stock_model,  # noqa: F401
-                       to_cuda)
-from .engine import FlatParams, VAEEngine, _Linear
+from .trainers import FlatAdam, VAETrainer, _dataset_rows, _stock_module, stock, stock_model, to_cuda  # noqa: F401
+from .engine import VAEEngine, _Linear
 
-_M32 = 0xFFFFFFFF
 _M64 = (1 << 64) - 1
 MODES = ("cd", "pcd")
 EVAL_KEY = 0x9E3779B97F4A7C15          # validation and log_likelihood binarise under seed + EVAL_KEY (mod 2^64)
@@ -52,9 +49,11 @@ class RBMError(GMError, ValueError):
 
 
 def _int(v, name):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        raise RBMError("%s must be an integer, got %r" % (name, v))
-    return int(v)
+    return _lib.check_int(v, name, RBMError)
+
+
+def check_seed(seed, name="seed"):
+    return _lib.check_seed(seed, name, RBMError)
 
 
 def check_shape(image_size, hidden_dim):
@@ -65,13 +64,6 @@ def check_shape(image_size, hidden_dim):
     if not 1 <= H <= RBM_MAX_DIM:
         raise RBMError("hidden_dim must lie in [1, %d], got %d" % (RBM_MAX_DIM, H))
     return I, H
-
-
-def check_seed(seed, name="seed"):
-    seed = _int(seed, name)
-    if not 0 <= seed < 1 << 64:
-        raise RBMError("%s must lie in [0, 2^64), got %d" % (name, seed))
-    return seed
 
 
 def check_steps(steps, lo=0, name="steps"):
@@ -114,15 +106,7 @@ def check_betas(betas):
 
 def uniforms_reference(n, width, seed, tag, t=0, row0=0):
     """u [n, width] float32: the rule's uniforms of chain rows row0 .. under `tag` at step t, bit for bit."""
-    nq = (width + 3) // 4
-    ctr = np.zeros((n, nq, 4), dtype=np.uint64)
-    ctr[..., 0] = np.arange(nq, dtype=np.uint64)[None, :]
-    ctr[..., 1] = np.uint64(int(t) & _M32)
-    ctr[..., 2] = ((np.arange(n, dtype=np.uint64) + np.uint64(row0)) & np.uint64(_M32))[:, None]
-    ctr[..., 3] = np.uint64(tag)
-    key = np.array([seed & _M32, (seed >> 32) & _M32], dtype=np.uint64)
-    w = philox4x32_10(ctr, key).reshape(n, 4 * nq)[:, :width].astype(np.uint64)
-    return ((2 * (w >> np.uint64(9)) + 1).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
+    return philox.unit_uniforms(philox.words(n, width, seed, t, tag, row0))
 
 
 def softplus(a):
@@ -194,27 +178,22 @@ class RBMEngine(VAEEngine):
     No eps ring.  One GPU only."""
 
     has_eps = False
+    one_gpu = "the RBM engine"
 
     def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
                  trainer=None):
-        if world_size > 1 or force_dp:
-            raise GMError("the RBM engine runs on one GPU: data parallelism is not implemented for it")
+        self._refuse_dp(world_size, force_dp)
         if not rbm_fused_ok(model):
             raise GMError("RBMEngine: the model is not rbm.RBM with its layer unchanged; RBMTrainer trains such models "
                           "on the general path")
-        self.model, self.device, self.use_graph, self.trainer = model, device, use_graph, trainer
-        plist = [model.linear.weight, model.linear.bias, model.vbias]
-        self._dp_init(plist, 1, 0, None, False)
-        self.fp = FlatParams(plist, device)
+        self._init_flat(model, device, use_graph, [model.linear.weight, model.linear.bias, model.vbias])
+        self._bind_trainer(trainer)                  # k, mode, seed and noise_steps are read from it
         self.L = _Linear(self.fp, model.linear)
         self.I, self.H = model.image_size, model.hidden_dim
         o = self.fp.offsets[2]
         self.vb, self.m_vb, self.v_vb = self.fp.views[2], self.fp.m[o:o + self.I], self.fp.v[o:o + self.I]
         self.WT = torch.zeros(self.I, self.H, device=device)
-        self.nbase = torch.zeros(1, dtype=torch.int64, device=device)
-        self.Z = 1                                   # width of VAEEngine.configure's (unused, dropped) eps ring
         self.pcd_ready = False
-        self._common_init(device)
 
     def _alloc(self, B):
         if self._bufB == B:
@@ -231,16 +210,7 @@ class RBMEngine(VAEEngine):
         from . import ops_fused as of_
         tr = self.trainer
         self.k, self.mode, self.seed = int(tr.k), str(tr.mode), int(tr.seed)
-        self._extra_config = {"k": self.k, "mode": self.mode, "seed": self.seed}
         super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
-        self.eps_ring = None                         # nothing is drawn on the host: no ring, no upload
-        for s in self.stage:
-            s.pop("eps", None)
-        key = (self.k, self.mode, self.seed)
-        if getattr(self, "_noise_key", None) != key:
-            self.graphs = {}                         # k, the mode and the seed are launch arguments of the graphs
-        self._noise_key = key
-        self.nbase.fill_(int(tr.noise_steps))
         if resume is not None and resume.get("pcd") is not None:
             if tuple(resume["pcd"].shape) != tuple(self.P.shape):
                 raise GMError("checkpoint's persistent chains %s do not match this run's %s"
@@ -250,6 +220,9 @@ class RBMEngine(VAEEngine):
         elif int(tr.noise_steps) == 0:
             self.pcd_ready = False                   # a fresh run: the first batch's v0 starts the chains
         of_.rbm_transpose(self.L.W, self.WT)
+
+    def _settings(self):
+        return {"k": self.k, "mode": self.mode, "seed": self.seed}
 
     def optim_state(self):
         st = super().optim_state()
@@ -318,6 +291,11 @@ class RBMTrainer(VAETrainer):
     epoch); best_val_loss / best_model on the latter; checkpoints carry the weights, Adam's state, the counters and the
     PCD chains, and resuming is bit-identical.  One GPU only."""
     _hook_names = ("compute_batch", "evaluate")
+    _series = (("losses", "recon"),)
+    _history = ("recon_loss",)
+    _batch = "loss"
+    _line = "Epoch[%d/%d], Free-energy gap: %.6f, Val recon CE: %.6f"
+    _one_gpu = "RBMTrainer"
 
     def __init__(self, model, train_iter, val_iter, test_iter, seed=0, k=1, mode="cd", viz=False):
         self.seed = check_seed(seed)
@@ -333,14 +311,6 @@ class RBMTrainer(VAETrainer):
                 and self._loader_ok(self.val_iter) and self.train_iter.batch_size == self.val_iter.batch_size)
 
     # ---- the chain on either path ---------------------------------------------------------------------------------------
-    def _device(self):
-        if not torch.cuda.is_available():
-            raise GMError("sampling and scoring run on the MI355X only: no GPU is visible")
-        dev = next(self.model.parameters()).device
-        if dev.type != "cuda":
-            raise GMError("the model is not on the GPU")
-        return dev
-
     def _weights(self):
         """(W, WT, c, b) of a stock model as contiguous device tensors; WT by gm_rbm_transpose."""
         from . import ops_fused as of_
@@ -432,65 +402,22 @@ class RBMTrainer(VAETrainer):
     def _engine_class(self):
         return RBMEngine
 
-    def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
-        from copy import deepcopy
-        from . import dp
-        if dp.current()[0] > 1 or getattr(self, "force_dp", False):
-            raise GMError("RBMTrainer runs on one GPU: data parallelism is not implemented for it")
-        steps = len(self.train_iter)
-        if self._stock():
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            dev = next(self.model.parameters()).device
-            if self._engine is None:
-                self._engine = RBMEngine(self.model, dev, use_graph=self.use_graph, trainer=self)
-            eng = self._engine
-            eng.use_graph = self.use_graph
-            nval = len(self.val_iter)
-            eng.configure(self.train_iter.batch_size, num_epochs * steps, lr, weight_decay,
-                          resume=self.__dict__.pop("_resume_optim", None))
-            tdata, vdata = self._device_data(self.train_iter), self._device_data(self.val_iter)
-            eng.alloc_val(nval)
-            for epoch in range(1, num_epochs + 1):
-                self.model.train()
-                t0 = (epoch - 1) * steps
-                eng.run_pass(tdata, _epoch_order(self.train_iter), True, t0)
-                self.model.eval()
-                eng.run_pass(vdata, _epoch_order(self.val_iter), False, 0)
-                loss = [float(v) for v in eng.read_losses(eng.recon, t0, steps)]     # one sync
-                val_loss = np.mean([float(v) for v in eng.read_losses(eng.vrecon, 0, nval)])
-                self._end_epoch_rbm(epoch, num_epochs, loss, val_loss, deepcopy, quiet)
-            self.noise_steps += num_epochs * steps
-            return
-        # GENERAL path (compute_batch / evaluate overridden, an edited model)
-        opt = FlatAdam(self.model.parameters(), lr, weight_decay=weight_decay)
-        self._general_t = 0
-        for epoch in range(1, num_epochs + 1):
-            self.model.train()
-            loss = []
-            self._general_t = (epoch - 1) * steps
-            for batch in self.train_iter:
-                opt.zero_grad()
-                l = self.compute_batch(batch)
-                l.backward()
-                opt.step()
-                loss.append(l.item())
-            self.model.eval()
-            val_loss = self.evaluate(self.val_iter)
-            self._end_epoch_rbm(epoch, num_epochs, loss, val_loss, deepcopy, quiet)
-        self.noise_steps += num_epochs * steps
-        self._general_opt = opt                      # the moments, for inspection
+    def _engine_kwargs(self):
+        return {"trainer": self}
 
-    def _end_epoch_rbm(self, epoch, num_epochs, loss, val_loss, deepcopy, quiet):
-        self.losses.extend(loss)
+    def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
+        """VAETrainer.train with this model's defaults."""
+        return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
+
+    def _begin_general_epoch(self, epoch):
+        self._general_t = (epoch - 1) * len(self.train_iter)     # the epoch's first batch step within this train() call
+
+    def _after_train(self, fused, steps):
+        self.noise_steps += steps                    # on both paths: the general compute_batch reads _general_t instead
+
+    def _end_epoch(self, epoch, num_epochs, series, val_loss, quiet):
         self.recon_loss.append(float(val_loss))
-        if val_loss < self.best_val_loss:
-            self.best_model = deepcopy(self.model)
-            self.best_val_loss = val_loss
-        if not quiet:
-            print("Epoch[%d/%d], Free-energy gap: %.6f, Val recon CE: %.6f" % (epoch, num_epochs, np.mean(loss), val_loss))
-        self.num_epochs += 1
-        self._viz_epoch(epoch)
+        super()._end_epoch(epoch, num_epochs, series, val_loss, quiet)
 
     # ---- sampling and scoring ------------------------------------------------------------------------------------------
     def sample(self, n, seed=0, steps=1000, return_probs=False):
@@ -625,13 +552,6 @@ class RBMTrainer(VAETrainer):
         plt.legend(["free-energy gap"])
         plt.title(self.name)
         plt.show()
-
-    def save_checkpoint(self, savepath, collective=True):
-        """VAETrainer.save_checkpoint with this trainer's histories and its batch step (k, mode and seed travel in the
-        optimizer state's config, checked under strict=True; the PCD chains beside Adam's moments)."""
-        from .trainers import _save_checkpoint
-        _save_checkpoint(self, savepath, ("losses", "recon_loss", "num_epochs", "best_val_loss", "noise_steps"),
-                         collective=collective)
 
 
 __all__ = ["RBM", "RBMTrainer", "RBMEngine", "RBMError", "rbm_fused_ok", "uniforms_reference", "default_betas",

@@ -49,16 +49,14 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _lib, ops, philox
 from ._lib import (NVP_MAX_D, NVP_MAX_H, NVP_MAX_K, NVP_MAX_LEVELS, NVP_MAX_S_CAP, NVP_MIN_D, NVP_TAG_EVAL, NVP_TAG_S,
                    NVP_TAG_TRAIN, GMError)
-from .dvae import philox4x32_10
-from .trainers import FlatAdam, VAETrainer, _dataset_rows, _epoch_order, _stock_module, stock, stock_model, to_cuda
-from .engine import FlatParams, VAEEngine, _Linear
+from .trainers import FlatAdam, VAETrainer, _dataset_rows, _stock_module, stock, stock_model, to_cuda  # noqa: F401
+from .engine import VAEEngine, _Linear
 
 TAG_TRAIN, TAG_EVAL, TAG_S = NVP_TAG_TRAIN, NVP_TAG_EVAL, NVP_TAG_S
 MASKS = ("checker", "half")
-_M32 = 0xFFFFFFFF
 
 
 class RealNVPError(GMError, ValueError):
@@ -67,9 +65,11 @@ class RealNVPError(GMError, ValueError):
 
 
 def _int(v, name):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        raise RealNVPError("%s must be an integer, got %r" % (name, v))
-    return int(v)
+    return _lib.check_int(v, name, RealNVPError)
+
+
+def check_seed(seed, name="seed"):
+    return _lib.check_seed(seed, name, RealNVPError)
 
 
 def _real(v, name):
@@ -102,13 +102,6 @@ def check_config(image_size, hidden_dim, num_couplings, mask, alpha, levels, s_c
     return D, H, K, mask, alpha, levels, s_cap
 
 
-def check_seed(seed, name="seed"):
-    seed = _int(seed, name)
-    if not 0 <= seed < 1 << 64:
-        raise RealNVPError("%s must lie in [0, 2^64), got %d" % (name, seed))
-    return seed
-
-
 # ---- the split and the noise rules in numpy (the tests' reference reads the same contract) ----------------------------
 def split_indices(D, mask="checker"):
     """(A, B): the pixel indices of the two halves, int64, each ascending; together they partition 0 .. D - 1."""
@@ -124,30 +117,17 @@ def split_indices(D, mask="checker"):
 
 def philox_words(n, D, seed, step, tag, row0=0):
     """The uint32 word of pixel e of rows row0 ..: word e & 3 of counter (e >> 2, step, row, tag); [n, D]."""
-    nq = (D + 3) // 4
-    ctr = np.zeros((n, nq, 4), dtype=np.uint64)
-    ctr[..., 0] = np.arange(nq, dtype=np.uint64)[None, :]
-    ctr[..., 1] = np.uint64(int(step) & _M32)
-    ctr[..., 2] = ((np.arange(n, dtype=np.uint64) + np.uint64(row0)) & np.uint64(_M32))[:, None]
-    ctr[..., 3] = np.uint64(tag)
-    key = np.array([seed & _M32, (seed >> 32) & _M32], dtype=np.uint64)
-    return philox4x32_10(ctr, key).reshape(n, 4 * nq)[:, :D]
+    return philox.words(n, D, seed, step, tag, row0)
 
 
 def uniforms_reference(n, D, seed, step, tag=TAG_TRAIN, row0=0):
     """u [n, D] float32: the dequantisation noise by the contract's rule, bit for bit."""
-    w = philox_words(n, D, seed, step, tag, row0).astype(np.uint64)
-    return ((2 * (w >> np.uint64(9)) + 1).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
+    return philox.unit_uniforms(philox.words(n, D, seed, step, tag, row0))
 
 
 def normals_reference(n, D, seed, row0=0):
     """z [n, D] float64: the sampler's starting normals by the contract's rule (the device rounds to fp32)."""
-    nq = (D + 3) // 4
-    w = philox_words(n, 4 * nq, seed, 0, TAG_S, row0).astype(np.uint64)
-    u = (2.0 * (w >> np.uint64(9)).astype(np.float64) + 1.0) * 2.0 ** -24
-    p = u.reshape(n, 2 * nq, 2)
-    r, phi = np.sqrt(-2.0 * np.log(p[..., 0])), 2.0 * np.pi * p[..., 1]
-    return np.stack([r * np.cos(phi), r * np.sin(phi)], axis=-1).reshape(n, 4 * nq)[:, :D]
+    return philox.normals(n, D, seed, 0, TAG_S, row0)
 
 
 def nll_constant(D, levels):
@@ -295,28 +275,23 @@ class RealNVPEngine(VAEEngine):
     One GPU only."""
 
     has_eps = False
+    one_gpu = "the RealNVP engine"
 
     def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
                  trainer=None):
-        if world_size > 1 or force_dp:
-            raise GMError("the RealNVP engine runs on one GPU: data parallelism is not implemented for it")
+        self._refuse_dp(world_size, force_dp)
         if not realnvp_fused_ok(model):
             raise GMError("RealNVPEngine: the model is not realnvp.RealNVP with its couplings unchanged; RealNVPTrainer "
                           "trains such models on the general path")
-        self.model, self.device, self.use_graph = model, device, use_graph
         plist = []
         for c in model.couplings:
             plist += [c.linear.weight, c.linear.bias, c.out.weight, c.out.bias]
-        self._dp_init(plist, 1, 0, None, False)
-        self.fp = FlatParams(plist, device)
+        self._init_flat(model, device, use_graph, plist)
+        self._bind_trainer(trainer)                  # seed and noise_steps are read from it
         self.C = [(_Linear(self.fp, c.linear), _Linear(self.fp, c.out)) for c in model.couplings]
         self.D, self.H, self.K = model.image_size, model.hidden_dim, model.num_couplings
         self.Da, self.Db = model.Da, model.Db
         self.I = self.D
-        self.Z = 1                                   # width of VAEEngine.configure's (unused, dropped) eps ring
-        self.trainer = trainer                       # seed and noise_steps are read from it
-        self.nbase = torch.zeros(1, dtype=torch.int64, device=device)
-        self._common_init(device)
 
     def _dt(self, k):
         return self.Db if k % 2 == 0 else self.Da
@@ -345,16 +320,9 @@ class RealNVPEngine(VAEEngine):
                 "seed": int(self.trainer.seed)}
 
     def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
-        self._extra_config = self._settings()
+        """VAEEngine.configure: the settings above are compared with a checkpoint's before anything is allocated or
+        reset, and are launch arguments of the graphs, with the seed."""
         super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
-        self.eps_ring = None                         # the noise is drawn on the device: no host ring, no upload
-        for s in self.stage:
-            s.pop("eps", None)
-        key = tuple(sorted(self._extra_config.items()))
-        if getattr(self, "_noise_key", None) != key:
-            self.graphs = {}                         # the seed and the settings are launch arguments of the graphs
-        self._noise_key = key
-        self.nbase.fill_(int(self.trainer.noise_steps))
 
     def _chain(self):
         """Per coupling k: (index of the transformed half, its input x_t, the conditioning half x_c), and the final
@@ -417,6 +385,10 @@ class RealNVPTrainer(VAETrainer):
     optimizer state's config, checked under strict=True, and the number of training batches taken, so a resumed run
     continues the noise stream bit for bit).  One GPU only."""
     _hook_names = ("compute_batch", "evaluate")
+    _series = (("losses", "recon"),)
+    _batch = "loss"
+    _line = "Epoch[%d/%d], NLL: %.6f, Val NLL: %.6f"
+    _one_gpu = "RealNVPTrainer"
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, seed=0):
         self.seed = check_seed(seed)                 # before anything runs
@@ -462,69 +434,10 @@ class RealNVPTrainer(VAETrainer):
         return functools.partial(RealNVPEngine, trainer=self)
 
     def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
-        from copy import deepcopy
-        from . import dp
-        if dp.current()[0] > 1 or getattr(self, "force_dp", False):
-            raise GMError("RealNVPTrainer runs on one GPU: data parallelism is not implemented for it")
-        if self._stock():
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            dev = next(self.model.parameters()).device
-            if self._engine is None:
-                self._engine = self._engine_class()(self.model, dev, use_graph=self.use_graph)
-            eng = self._engine
-            eng.use_graph = self.use_graph
-            steps, nval = len(self.train_iter), len(self.val_iter)
-            eng.configure(self.train_iter.batch_size, num_epochs * steps, lr, weight_decay,
-                          resume=self.__dict__.pop("_resume_optim", None))
-            tdata, vdata = self._device_data(self.train_iter), self._device_data(self.val_iter)
-            eng.alloc_val(nval)
-            for epoch in range(1, num_epochs + 1):
-                self.model.train()
-                t0 = (epoch - 1) * steps
-                eng.run_pass(tdata, _epoch_order(self.train_iter), True, t0)
-                self.model.eval()
-                eng.run_pass(vdata, _epoch_order(self.val_iter), False, 0)
-                loss = [float(v) for v in eng.read_losses(eng.recon, t0, steps)]     # one sync
-                val_loss = np.mean([float(v) for v in eng.read_losses(eng.vrecon, 0, nval)])
-                self._end_epoch_nvp(epoch, num_epochs, loss, val_loss, deepcopy, quiet)
-            self.noise_steps += num_epochs * steps
-            return
-        # GENERAL path (compute_batch / evaluate overridden, an edited model)
-        opt = FlatAdam(self.model.parameters(), lr, weight_decay=weight_decay)
-        for epoch in range(1, num_epochs + 1):
-            self.model.train()
-            loss = []
-            for batch in self.train_iter:
-                opt.zero_grad()
-                l = self.compute_batch(batch)
-                l.backward()
-                opt.step()
-                loss.append(l.item())
-            self.model.eval()
-            val_loss = self.evaluate(self.val_iter)
-            self._end_epoch_nvp(epoch, num_epochs, loss, val_loss, deepcopy, quiet)
-        self._general_opt = opt                      # the moments, for inspection
-
-    def _end_epoch_nvp(self, epoch, num_epochs, loss, val_loss, deepcopy, quiet):
-        self.losses.extend(loss)
-        if val_loss < self.best_val_loss:
-            self.best_model = deepcopy(self.model)
-            self.best_val_loss = val_loss
-        if not quiet:
-            print("Epoch[%d/%d], NLL: %.6f, Val NLL: %.6f" % (epoch, num_epochs, np.mean(loss), val_loss))
-        self.num_epochs += 1
-        self._viz_epoch(epoch)
+        """VAETrainer.train with this model's defaults."""
+        return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
 
     # ---- the flow on device rows, no autograd --------------------------------------------------------------------------
-    def _device(self):
-        if not torch.cuda.is_available():
-            raise GMError("sampling and scoring run on the MI355X only: no GPU is visible")
-        dev = next(self.model.parameters()).device
-        if dev.type != "cuda":
-            raise GMError("the model is not on the GPU")
-        return dev
-
     def _rows(self, images):
         x = images.reshape(images.shape[0], -1)
         if x.shape[1] != self.model.image_size:
@@ -681,12 +594,6 @@ class RealNVPTrainer(VAETrainer):
         plt.legend(["NLL (nats per image)"])
         plt.title(self.name)
         plt.show()
-
-    def save_checkpoint(self, savepath, collective=True):
-        """VAETrainer.save_checkpoint + noise_steps (mask, alpha, levels, s_cap and seed travel in the optimizer state's
-        config)."""
-        from .trainers import _save_checkpoint
-        _save_checkpoint(self, savepath, ("losses", "num_epochs", "best_val_loss", "noise_steps"), collective=collective)
 
 
 __all__ = ["Coupling", "RealNVP", "RealNVPTrainer", "RealNVPEngine", "RealNVPError", "split_indices", "philox_words",

@@ -776,6 +776,19 @@ class VAETrainer:
     """vae.py:109-223."""
     _gm_stock_class = True
     _hook_names = ("compute_batch", "kl_divergence", "evaluate")
+    # ---- what a trainer of this family declares; train() below is the family's only epoch loop ----
+    # (history attribute, engine loss buffer) per training series, in the epoch line's order; with num_epochs,
+    # best_val_loss, noise_steps and _history (those the trainer has) also what save_checkpoint writes
+    _series = (("recon_loss", "recon"), ("kl_loss", "kl"))
+    _history = ()
+    # what compute_batch returns: "terms" -- two loss terms, their sum back-propagated, both recorded, the epoch line
+    # led by their total and the validation loss vrecon + vkl; "loss" -- a scalar; "loss+stat" -- (loss, a statistic)
+    _batch = "terms"
+    _line = "Epoch[%d/%d], Total Loss: %.4f, Reconst Loss: %.4f, KL Div: %.7f, Val Loss: %.4f"
+    _one_gpu = None             # "<Name>Trainer" where data parallelism is not implemented: train() refuses it first
+    _hands_force_dp = True      # the engine is built with the trainer's force_dp (BIR-VAE, AAE: it never was)
+    _counts_epochs = True       # BIR-VAE: False
+    _checkpoint_numpy_rng = False   # BIR-VAE: numpy's global generator state travels in checkpoints
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False):
         self.model = to_cuda(model)
@@ -844,6 +857,15 @@ class VAETrainer:
         return (self._loader_ok(self.train_iter) and self._loader_ok(self.val_iter)
                 and self.train_iter.batch_size == self.val_iter.batch_size)
 
+    def _device(self):
+        """The model's device, for the launches of sampling and scoring; GMError when that is not a GPU."""
+        if not torch.cuda.is_available():
+            raise GMError("sampling and scoring run on the MI355X only: no GPU is visible")
+        dev = next(self.model.parameters()).device
+        if dev.type != "cuda":
+            raise GMError("the model is not on the GPU")
+        return dev
+
     def _device_data(self, loader):
         cache = self.__dict__.setdefault("_data_cache", {})
         key = id(loader.dataset)
@@ -860,69 +882,112 @@ class VAETrainer:
 
     def train(self, num_epochs, lr=1e-3, weight_decay=1e-5, quiet=False):
         """vae.py:127-191."""
-        from copy import deepcopy
-        if self._stock():
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            dev = next(self.model.parameters()).device
-            if self._engine is None:
-                from . import dp
-                world, rank, group = dp.current()
-                self._engine = self._engine_class()(self.model, dev, use_graph=self.use_graph, world_size=world,
-                                                    rank=rank, process_group=group,
-                                                    force_dp=getattr(self, "force_dp", False))
-            eng = self._engine
-            eng.use_graph = self.use_graph
-            B = self.train_iter.batch_size
-            steps = len(self.train_iter)
-            eng.configure(B, num_epochs * steps, lr, weight_decay,
-                          resume=self.__dict__.pop("_resume_optim", None))
-            tdata, vdata = self._device_data(self.train_iter), self._device_data(self.val_iter)
-            nval = len(self.val_iter)
-            eng.alloc_val(nval)
-            for epoch in range(1, num_epochs + 1):
-                self.model.train()
-                t0 = (epoch - 1) * steps
-                eng.run_pass(tdata, _epoch_order(self.train_iter), True, t0)
-                self.model.eval()
-                eng.run_pass(vdata, _epoch_order(self.val_iter), False, 0)
-                recon = [float(x) for x in eng.read_losses(eng.recon, t0, steps)]     # one sync
-                kl = [float(x) for x in eng.read_losses(eng.kl, t0, steps)]
-                vr, vk = eng.read_losses(eng.vrecon, 0, nval), eng.read_losses(eng.vkl, 0, nval)
-                val_loss = np.mean([float(a + b) for a, b in zip(vr, vk)])
-                self._end_epoch(epoch, num_epochs, recon, kl, val_loss, deepcopy, quiet)
-            return
-        # GENERAL path (compute_batch / evaluate overridden)
-        opt = FlatAdam(self.model.parameters(), lr, weight_decay=weight_decay)
+        if self._one_gpu:
+            from . import dp
+            if dp.current()[0] > 1 or getattr(self, "force_dp", False):
+                raise GMError("%s runs on one GPU: data parallelism is not implemented for it" % self._one_gpu)
+        fused = self._stock()
+        if fused:
+            self._train_fused(num_epochs, lr, weight_decay, quiet)
+        else:                                        # compute_batch / evaluate overridden, an edited model
+            self._general_opt = self._general_optimizer(lr, weight_decay)
+            self._train_general(num_epochs, self._general_opt, quiet)
+        self._after_train(fused, num_epochs * len(self.train_iter))
+
+    def _train_fused(self, num_epochs, lr, weight_decay, quiet, **settings):
+        """The epoch loop on the fused engine: per epoch one training and one validation pass, enqueued whole, then one
+        read-back of the epoch's loss slots.  settings: a subclass's further arguments of its engine's configure()."""
+        if not torch.cuda.is_available():
+            raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
+        if self._engine is None:
+            self._engine = self._new_engine(next(self.model.parameters()).device)
+        eng = self._engine
+        eng.use_graph = self.use_graph
+        steps, nval = len(self.train_iter), len(self.val_iter)
+        eng.configure(self.train_iter.batch_size, num_epochs * steps, lr, weight_decay,
+                      resume=self.__dict__.pop("_resume_optim", None), **settings)
+        tdata, vdata = self._device_data(self.train_iter), self._device_data(self.val_iter)
+        eng.alloc_val(nval)
         for epoch in range(1, num_epochs + 1):
             self.model.train()
-            recon, kl = [], []
+            t0 = (epoch - 1) * steps
+            eng.run_pass(tdata, _epoch_order(self.train_iter), True, t0)
+            self.model.eval()
+            eng.run_pass(vdata, _epoch_order(self.val_iter), False, 0)
+            series = [[float(x) for x in eng.read_losses(getattr(eng, buf), t0, steps)]     # one sync
+                      for _, buf in self._series]
+            val = eng.read_losses(eng.vrecon, 0, nval)
+            if self._batch == "terms":
+                val = val + eng.read_losses(eng.vkl, 0, nval)        # per batch, in fp32
+            self._end_epoch(epoch, num_epochs, series, np.mean([float(x) for x in val]), quiet)
+
+    def _train_general(self, num_epochs, opt, quiet):
+        """The epoch loop over autograd and the flat HIP Adam, through the trainer's own compute_batch / evaluate."""
+        for epoch in range(1, num_epochs + 1):
+            self._begin_general_epoch(epoch)
+            self.model.train()
+            series = [[] for _ in self._series]
             for batch in self.train_iter:
                 opt.zero_grad()
-                r, k = self.compute_batch(batch)
-                (r + k).backward()
+                out = self.compute_batch(batch)
+                if self._batch == "loss":
+                    out = (out,)
+                loss = out[0] + out[1] if self._batch == "terms" else out[0]
+                loss.backward()
                 opt.step()
-                recon.append(r.item())
-                kl.append(k.item())
+                for s, v in zip(series, out):
+                    s.append(v.item() if torch.is_tensor(v) else float(v))
             self.model.eval()
-            val_loss = self.evaluate(self.val_iter)
-            self._end_epoch(epoch, num_epochs, recon, kl, val_loss, deepcopy, quiet)
+            self._end_epoch(epoch, num_epochs, series, self.evaluate(self.val_iter), quiet)
+
+    def _general_optimizer(self, lr, weight_decay):
+        return FlatAdam(self.model.parameters(), lr, weight_decay=weight_decay)
+
+    def _begin_general_epoch(self, epoch):
+        pass
+
+    def _after_train(self, fused, steps):
+        """A device-noise trainer's count of training batches: the fused path adds a train() call's batches here, on
+        the general path compute_batch counts them one by one."""
+        if fused and hasattr(self, "noise_steps"):
+            self.noise_steps += steps
 
     def _engine_class(self):
         from .engine import VAEEngine
         return VAEEngine
 
-    def _end_epoch(self, epoch, num_epochs, recon, kl, val_loss, deepcopy, quiet):
-        self.kl_loss.extend(kl)
-        self.recon_loss.extend(recon)
+    def _engine_kwargs(self):
+        """Constructor arguments of the engine beside the model, the device, use_graph and the data-parallel group."""
+        return {}
+
+    def _new_engine(self, dev):
+        kw = self._engine_kwargs()
+        if not self._one_gpu:
+            from . import dp
+            world, rank, group = dp.current()
+            kw.update(world_size=world, rank=rank, process_group=group)
+            if self._hands_force_dp:
+                kw["force_dp"] = getattr(self, "force_dp", False)
+        return self._engine_class()(self.model, dev, use_graph=self.use_graph, **kw)
+
+    def _epoch_line(self, epoch, num_epochs, series, val_loss):
+        means = tuple(np.mean(s) for s in series)
+        if self._batch == "terms":
+            tot = [float(np.float32(a) + np.float32(b)) for a, b in zip(*series)]
+            means = (np.mean(tot),) + means
+        return self._line % ((epoch, num_epochs) + means + (val_loss,))
+
+    def _end_epoch(self, epoch, num_epochs, series, val_loss, quiet):
+        from copy import deepcopy
+        for (name, _), values in zip(self._series, series):
+            getattr(self, name).extend(values)
         if val_loss < self.best_val_loss:
             self.best_model = deepcopy(self.model)
             self.best_val_loss = val_loss
         if not quiet:
-            tot = [float(np.float32(a) + np.float32(b)) for a, b in zip(recon, kl)]
-            print("Epoch[%d/%d], Total Loss: %.4f, Reconst Loss: %.4f, KL Div: %.7f, Val Loss: %.4f"
-                  % (epoch, num_epochs, np.mean(tot), np.mean(recon), np.mean(kl), val_loss))
-        self.num_epochs += 1
+            print(self._epoch_line(epoch, num_epochs, series, val_loss))
+        if self._counts_epochs:
+            self.num_epochs += 1
         self._viz_epoch(epoch)
 
     # ---- visualisation hooks (vae.py:189-191, 225-362; SURVEY.md 8f item 4) ------------------
@@ -996,10 +1061,12 @@ class VAETrainer:
         self.model.load_state_dict(torch.load(loadpath))
 
     def save_checkpoint(self, savepath, collective=True):
-        """See GANTrainer.save_checkpoint; collective under data parallelism."""
-        hist = tuple(n for n in ("recon_loss", "kl_loss", "num_epochs", "best_val_loss")
-                     if hasattr(self, n))
-        _save_checkpoint(self, savepath, hist, collective=collective)
+        """See GANTrainer.save_checkpoint; collective under data parallelism.  The histories: the
+        training series' lists (recon_loss and kl_loss here, `losses` for most of the family), _history, num_epochs,
+        best_val_loss and, where the trainer counts its training batches, noise_steps."""
+        hist = tuple(n for n, _ in self._series) + self._history + ("num_epochs", "best_val_loss", "noise_steps")
+        _save_checkpoint(self, savepath, tuple(n for n in hist if hasattr(self, n)),
+                         numpy_rng=self._checkpoint_numpy_rng, collective=collective)
 
     def load_checkpoint(self, loadpath, strict=True):
         """strict: refuse a checkpoint whose run settings (batch size, D_steps, learning rates ...)
@@ -1067,6 +1134,11 @@ class BIRVAETrainer(VAETrainer):
     """bir_vae.py:99-232: the VAE loop with loss = sum (x - x_hat)^2 + 1000 * MMD(z)."""
     _gm_stock_class = True
     _hook_names = ("compute_batch", "evaluate", "maximum_mean_discrepancy", "compute_kernel")
+    _series = (("recon_loss", "recon"), ("mmd_loss", "kl"))      # the engine's `kl` / `vkl` hold the MMD terms
+    _line = "Epoch[%d/%d], Total Loss: %.4f, MSE Loss: %.4f, MMD Loss: %.4f, Val Loss: %.4f"
+    _counts_epochs = False      # bir_vae.py:119-178 never increments num_epochs; neither do we
+    _hands_force_dp = False
+    _checkpoint_numpy_rng = True    # the reparameterisation noise of bir_vae.py:92-94 comes from numpy's generator
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False):
         self.model = to_cuda(model)
@@ -1127,76 +1199,13 @@ class BIRVAETrainer(VAETrainer):
             loss.append((mse + mmd).item())
         return np.mean(loss)
 
-    def train(self, num_epochs, lr=1e-3, weight_decay=1e-5, quiet=False):
-        """bir_vae.py:119-178.  (The reference never increments num_epochs here; neither do we.)"""
-        from copy import deepcopy
-        if self._stock():
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            from .engine import BIRVAEEngine
-            dev = next(self.model.parameters()).device
-            if self._engine is None:
-                from . import dp
-                world, rank, group = dp.current()
-                self._engine = BIRVAEEngine(self.model, dev, use_graph=self.use_graph, world_size=world,
-                                            rank=rank, process_group=group)
-            eng = self._engine
-            eng.use_graph = self.use_graph
-            steps = len(self.train_iter)
-            eng.configure(self.train_iter.batch_size, num_epochs * steps, lr, weight_decay,
-                          resume=self.__dict__.pop("_resume_optim", None))
-            tdata, vdata = self._device_data(self.train_iter), self._device_data(self.val_iter)
-            nval = len(self.val_iter)
-            eng.alloc_val(nval)
-            for epoch in range(1, num_epochs + 1):
-                self.model.train()
-                t0 = (epoch - 1) * steps
-                eng.run_pass(tdata, _epoch_order(self.train_iter), True, t0)
-                self.model.eval()
-                eng.run_pass(vdata, _epoch_order(self.val_iter), False, 0)
-                recon = [float(x) for x in eng.read_losses(eng.recon, t0, steps)]     # one sync
-                mmd = [float(x) for x in eng.read_losses(eng.kl, t0, steps)]
-                vr, vm = eng.read_losses(eng.vrecon, 0, nval), eng.read_losses(eng.vkl, 0, nval)
-                val_loss = np.mean([float(a + b) for a, b in zip(vr, vm)])
-                self._end_epoch_bir(epoch, num_epochs, recon, mmd, val_loss, deepcopy, quiet)
-            return
-        opt = FlatAdam([p for p in self.model.parameters() if p.requires_grad], lr,
-                       weight_decay=weight_decay)
-        for epoch in range(1, num_epochs + 1):
-            self.model.train()
-            recon, mmd = [], []
-            for batch in self.train_iter:
-                opt.zero_grad()
-                a, b = self.compute_batch(batch)
-                (a + b).backward()
-                opt.step()
-                recon.append(a.item())
-                mmd.append(b.item())
-            self.model.eval()
-            val_loss = self.evaluate(self.val_iter)
-            self._end_epoch_bir(epoch, num_epochs, recon, mmd, val_loss, deepcopy, quiet)
-
-    def _end_epoch_bir(self, epoch, num_epochs, recon, mmd, val_loss, deepcopy, quiet):
-        self.mmd_loss.extend(mmd)
-        self.recon_loss.extend(recon)
-        if val_loss < self.best_val_loss:
-            self.best_model = deepcopy(self.model)
-            self.best_val_loss = val_loss
-        if not quiet:
-            tot = [float(np.float32(a) + np.float32(b)) for a, b in zip(recon, mmd)]
-            print("Epoch[%d/%d], Total Loss: %.4f, MSE Loss: %.4f, MMD Loss: %.4f, Val Loss: %.4f"
-                  % (epoch, num_epochs, np.mean(tot), np.mean(recon), np.mean(mmd), val_loss))
-        self._viz_epoch(epoch)                      # bir_vae.py:176-178
+    def _engine_class(self):
+        from .engine import BIRVAEEngine
+        return BIRVAEEngine
 
     def viz_loss(self):
         from . import viz
         viz.vae_viz_loss(self, "mmd_loss")
-
-    def save_checkpoint(self, savepath, collective=True):
-        """See GANTrainer.save_checkpoint; also carries numpy's global generator state (the
-        reparameterisation noise of bir_vae.py:92-94 comes from it)."""
-        hist = tuple(n for n in ("recon_loss", "mmd_loss", "num_epochs", "best_val_loss") if hasattr(self, n))
-        _save_checkpoint(self, savepath, hist, numpy_rng=True, collective=collective)
 
 
 # ============================================================================================
@@ -1245,6 +1254,9 @@ class AutoencoderTrainer(VAETrainer):
     """ae.py:69-205: same loop as the VAE trainer with one loss list (`recon_loss`)."""
     _gm_stock_class = True
     _hook_names = ("compute_batch", "evaluate")
+    _series = (("recon_loss", "recon"),)
+    _batch = "loss"
+    _line = "Epoch[%d/%d], Train Loss: %.4f, Val Loss: %.4f"
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False):
         self.model = to_cuda(model)
@@ -1274,64 +1286,9 @@ class AutoencoderTrainer(VAETrainer):
         """ae.py:162-164."""
         return np.mean([self.compute_batch(batch).item() for batch in iterator])
 
-    def train(self, num_epochs, lr=1e-3, weight_decay=1e-5, quiet=False):
-        """ae.py:87-145."""
-        from copy import deepcopy
-        if self._stock():
-            if not torch.cuda.is_available():
-                raise GMError("no MI355X visible: the fused step engine has no CPU fallback")
-            from .engine import AEEngine
-            dev = next(self.model.parameters()).device
-            if self._engine is None:
-                from . import dp
-                world, rank, group = dp.current()
-                self._engine = AEEngine(self.model, dev, use_graph=self.use_graph, world_size=world,
-                                        rank=rank, process_group=group,
-                                        force_dp=getattr(self, "force_dp", False))
-            eng = self._engine
-            eng.use_graph = self.use_graph
-            steps = len(self.train_iter)
-            eng.configure(self.train_iter.batch_size, num_epochs * steps, lr, weight_decay,
-                          resume=self.__dict__.pop("_resume_optim", None))
-            tdata, vdata = self._device_data(self.train_iter), self._device_data(self.val_iter)
-            nval = len(self.val_iter)
-            eng.alloc_val(nval)
-            for epoch in range(1, num_epochs + 1):
-                self.model.train()
-                t0 = (epoch - 1) * steps
-                eng.run_pass(tdata, _epoch_order(self.train_iter), True, t0)
-                self.model.eval()
-                eng.run_pass(vdata, _epoch_order(self.val_iter), False, 0)
-                recon = [float(x) for x in eng.read_losses(eng.recon, t0, steps)]     # one sync
-                val_loss = np.mean([float(x) for x in eng.read_losses(eng.vrecon, 0, nval)])
-                self._end_epoch_ae(epoch, num_epochs, recon, val_loss, deepcopy, quiet)
-            return
-        # GENERAL path (compute_batch / evaluate overridden)
-        opt = FlatAdam([p for p in self.model.parameters() if p.requires_grad], lr,
-                       weight_decay=weight_decay)
-        for epoch in range(1, num_epochs + 1):
-            self.model.train()
-            recon = []
-            for batch in self.train_iter:
-                opt.zero_grad()
-                loss = self.compute_batch(batch)
-                loss.backward()
-                opt.step()
-                recon.append(loss.item())
-            self.model.eval()
-            val_loss = self.evaluate(self.val_iter)
-            self._end_epoch_ae(epoch, num_epochs, recon, val_loss, deepcopy, quiet)
-
-    def _end_epoch_ae(self, epoch, num_epochs, recon, val_loss, deepcopy, quiet):
-        self.recon_loss.extend(recon)
-        if val_loss < self.best_val_loss:
-            self.best_model = deepcopy(self.model)
-            self.best_val_loss = val_loss
-        if not quiet:
-            print("Epoch[%d/%d], Train Loss: %.4f, Val Loss: %.4f"
-                  % (epoch, num_epochs, np.mean(recon), val_loss))
-        self.num_epochs += 1
-        self._viz_epoch(epoch)
+    def _engine_class(self):
+        from .engine import AEEngine
+        return AEEngine
 
     def _viz_epoch(self, epoch):
         if self.viz:

@@ -103,6 +103,36 @@ class VAEEngine:
             dp.allreduce_sum_(t, self.pg)
         return t.cpu().numpy()
 
+    one_gpu = None              # an engine without data parallelism names itself here ("the MADE engine")
+
+    def _refuse_dp(self, world_size, force_dp):
+        if world_size > 1 or force_dp:
+            raise GMError("%s runs on one GPU: data parallelism is not implemented for it" % self.one_gpu)
+
+    def _init_flat(self, model, device, use_graph, plist):
+        """What a one-GPU engine over a parameter list of its own starts with (after _refuse_dp and its model check): the
+        flat parameter / gradient / moment buffers over `plist` and the epoch machinery's state."""
+        self.model, self.device, self.use_graph = model, device, use_graph
+        self._dp_init(plist, 1, 0, None, False)
+        self.fp = FlatParams(plist, device)
+        self._common_init(device)
+
+    def _bind_trainer(self, trainer):
+        """The trainer a device-noise engine reads its seed and noise_steps from, and the device word configure() writes
+        the latter to: a training batch's noise step is ctr + nbase, so it is never baked into a graph."""
+        self.trainer = trainer
+        self.nbase = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def _settings(self):
+        """The run's settings beside B, lr and weight_decay: saved in checkpoints, compared on resume, and launch
+        arguments of the captured graphs (a change drops them)."""
+        return {}
+
+    def _graph_args(self):
+        """Device addresses the captured graphs hold beside the engine's own buffers and the dataset (MADEEngine: the
+        degree vectors; DDPMEngine: the tables): a change drops the graphs."""
+        return ()
+
     def _common_init(self, device):
         from . import _respect_cpu_quota
         _respect_cpu_quota(force=False)             # once per process, when the first engine is built
@@ -121,6 +151,7 @@ class VAEEngine:
         self.fuse_bwd_mid = True
         self.fin_in_dw = True
         self.fin_done = torch.zeros(1, dtype=torch.int32, device=device)
+        self.trainer = None                          # _bind_trainer sets it
 
     def _alloc(self, B):
         if self._bufB == B:
@@ -284,24 +315,26 @@ class VAEEngine:
 
     def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
         dev = self.device
+        settings = self._settings()
+        config = {"B": int(B), "lr": float(lr), "weight_decay": float(weight_decay)}
+        config.update(settings)
+        if resume is not None:                       # see GANEngine.configure; refused BEFORE anything is touched
+            saved = resume.get("config")
+            if saved is not None and not resume.get("lenient", False):
+                diff = {k: (saved[k], config[k]) for k in config if k in saved and saved[k] != config[k]}
+                if diff:
+                    raise GMError("checkpoint was written by a run with different settings (saved, now): "
+                                  "%s; load_checkpoint(path, strict=False) overrides" % diff)
+            if resume["m"].numel() != self.fp.m.numel():
+                raise GMError("checkpoint optimizer state does not match this model")
         self._alloc(B)
         self.B, self.wd = B, float(weight_decay)
         self.fp.rebind()
         self.fp.reset_state()
         self.fp.grad.zero_()
         self.step0 = 0
-        self.run_config = {"B": int(B), "lr": float(lr), "weight_decay": float(weight_decay)}
-        self.run_config.update(getattr(self, "_extra_config", {}))    # a subclass's own settings, compared below too
-        if resume is not None:                       # see GANEngine.configure
-            saved = resume.get("config")
-            if saved is not None and not resume.get("lenient", False):
-                diff = {k: (saved[k], self.run_config[k]) for k in self.run_config
-                        if k in saved and saved[k] != self.run_config[k]}
-                if diff:
-                    raise GMError("checkpoint was written by a run with different settings (saved, now): "
-                                  "%s; load_checkpoint(path, strict=False) overrides" % diff)
-            if resume["m"].numel() != self.fp.m.numel():
-                raise GMError("checkpoint optimizer state does not match this model")
+        self.run_config = config
+        if resume is not None:
             self.fp.m.copy_(resume["m"]); self.fp.v.copy_(resume["v"])
             self.step0 = int(resume["step"])
         self.steps_planned = n_train_steps
@@ -315,17 +348,23 @@ class VAEEngine:
         self.R = CHUNK
         if getattr(self, "_ring_B", None) != B:
             self.idx_ring = torch.zeros(self.R, B, dtype=torch.int64, device=dev)
-            self.eps_ring = torch.zeros(self.R, B, self.Z, device=dev)
-            self.stage = [dict(idx=torch.zeros(self.R, B, dtype=torch.int64).pin_memory(),
-                               eps=torch.zeros(self.R, B, self.Z).pin_memory(), event=None)
+            self.stage = [dict(idx=torch.zeros(self.R, B, dtype=torch.int64).pin_memory(), event=None)
                           for _ in range(2)]
+            if self.has_eps:                         # the host-drawn eps: a device ring and its two pinned halves
+                self.eps_ring = torch.zeros(self.R, B, self.Z, device=dev)
+                for st in self.stage:
+                    st["eps"] = torch.zeros(self.R, B, self.Z).pin_memory()
             self._ring_B = B
             self._moved = True
-        vkey = (B, self.wd, self.use_graph, self.fuse_adam, self.pair_dw, self.prefetch_gather)
+        # the settings' values and the subclass's extra addresses are launch arguments of the graphs
+        vkey = (B, self.wd, self.use_graph, self.fuse_adam, self.pair_dw, self.prefetch_gather,
+                tuple(settings.values()), self._graph_args())
         if self._moved or getattr(self, "_vkey", None) != vkey:
             self.graphs = {}
         self._vkey = vkey
         self.t_train = 0
+        if self.trainer is not None:
+            self.nbase.fill_(int(self.trainer.noise_steps))
 
     def optim_state(self):
         torch.cuda.synchronize()
@@ -363,7 +402,7 @@ class VAEEngine:
         one ragged.  Global eps draws (vae.py:104) happen here, batch by batch, in order.
         t0: first loss/schedule slot.  Returns number of batches."""
         self.data = data
-        B, R, Z = self.B, self.R, self.Z
+        B, R = self.B, self.R
         n = perm.numel()
         nb = (n + B - 1) // B
         self.ctr.fill_(t0)
@@ -453,7 +492,6 @@ class AEEngine(VAEEngine):
         self.fp = FlatParams(plist, device, grad_alloc=self._grad_alloc)
         self.E1, self.D2 = _Linear(self.fp, enc.linear), _Linear(self.fp, dec.linear)
         self.H, self.I = enc.linear.weight.shape
-        self.Z = 1                                   # dummy width of the (unused) eps ring
         self._common_init(device)
 
     def _alloc(self, B):
@@ -753,13 +791,13 @@ class DVAEEngine(VAEEngine):
     trainer's count of training batches, so a graph captured in one train() call serves the next.  Validation batches
     are the VAE's, clean.  One GPU only."""
 
+    one_gpu = "the DVAE engine"
+
     def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
                  trainer=None):
-        if world_size > 1 or force_dp:
-            raise GMError("the DVAE engine runs on one GPU: data parallelism is not implemented for it")
+        self._refuse_dp(world_size, force_dp)
         super().__init__(model, device, use_graph=use_graph)
-        self.trainer = trainer                       # noise, level, seed and noise_steps are read from it
-        self.nbase = torch.zeros(1, dtype=torch.int64, device=device)
+        self._bind_trainer(trainer)                  # noise, level, seed and noise_steps are read from it
 
     def _alloc(self, B):
         if self._bufB == B:
@@ -767,21 +805,9 @@ class DVAEEngine(VAEEngine):
         super()._alloc(B)
         self.Xcb = (torch.zeros(B, self.I, device=self.device), torch.zeros(B, self.I, device=self.device))
 
-    def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
+    def _settings(self):
         tr = self.trainer
-        now = {"noise": tr.noise, "level": float(tr.level), "seed": int(tr.seed)}
-        if resume is not None and resume.get("config") is not None and not resume.get("lenient", False):
-            saved = resume["config"]
-            diff = {k: (saved[k], now[k]) for k in now if k in saved and saved[k] != now[k]}
-            if diff:
-                raise GMError("checkpoint was written by a run with different settings (saved, now): %s; "
-                              "load_checkpoint(path, strict=False) overrides" % diff)
-        super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
-        self.run_config.update(now)
-        if getattr(self, "_noise_key", None) != tuple(now.values()):
-            self.graphs = {}                         # the rule and the seed are launch arguments of the graphs
-        self._noise_key = tuple(now.values())
-        self.nbase.fill_(int(tr.noise_steps))
+        return {"noise": tr.noise, "level": float(tr.level), "seed": int(tr.seed)}
 
     def _xc(self, X):
         return self.Xcb[0] if X is self.Xb[0] else self.Xcb[1]
@@ -824,17 +850,17 @@ class IWAEEngine(VAEEngine):
     A validation batch is launches 1-6 in evaluation mode and the two sums.  The noise step of a training batch is
     ctr + nbase (DVAEEngine's scheme), of a validation batch ctr (the batch's index in the pass).  One GPU only."""
 
-    has_eps = False              # the noise is drawn on the device: no host eps ring traffic
+    has_eps = False              # the noise is drawn on the device: no host eps ring
+    one_gpu = "the IWAE engine"
 
     def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
                  trainer=None):
-        if world_size > 1 or force_dp:
-            raise GMError("the IWAE engine runs on one GPU: data parallelism is not implemented for it")
+        self._refuse_dp(world_size, force_dp)
         k = int(trainer.k)
         self._check_limits(model, k)
         super().__init__(model, device, use_graph=use_graph)
-        self.trainer, self.k = trainer, k            # seed and noise_steps are read from the trainer
-        self.nbase = torch.zeros(1, dtype=torch.int64, device=device)
+        self._bind_trainer(trainer)                  # seed and noise_steps are read from it
+        self.k = k
 
     def _check_limits(self, model, k):
         """GMError unless k and the latent width fit the sampling kernels."""
@@ -861,27 +887,13 @@ class IWAEEngine(VAEEngine):
         self.graphs = {}
 
     def _settings(self):
-        """The run's settings beside the VAE engine's: saved in checkpoints, compared on resume, and a change drops the
-        captured graphs."""
         return {"k": self.k, "seed": int(self.trainer.seed)}
 
     def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
-        tr = self.trainer
-        if int(tr.k) != self.k:
-            raise GMError("IWAETrainer.k changed after the engine was built (%d -> %d)" % (self.k, int(tr.k)))
-        now = self._settings()
-        if resume is not None and resume.get("config") is not None and not resume.get("lenient", False):
-            saved = resume["config"]
-            diff = {n: (saved[n], now[n]) for n in now if n in saved and saved[n] != now[n]}
-            if diff:
-                raise GMError("checkpoint was written by a run with different settings (saved, now): %s; "
-                              "load_checkpoint(path, strict=False) overrides" % diff)
+        k = int(self.trainer.k)
+        if k != self.k:
+            raise GMError("IWAETrainer.k changed after the engine was built (%d -> %d)" % (self.k, k))
         super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
-        self.run_config.update(now)
-        if getattr(self, "_noise_key", None) != tuple(now.values()):
-            self.graphs = {}                         # the seed is a launch argument of the graphs
-        self._noise_key = tuple(now.values())
-        self.nbase.fill_(int(tr.noise_steps))
 
     def _noise(self, t, train):
         """The batch's noise stream: training batches read ctr + nbase (eager: t + nbase) under the training tag,
@@ -963,10 +975,11 @@ class NFVAEEngine(IWAEEngine):
     gm_flow_reduce, which is the last reader of the flow's parameters.  The flow's parameters, gradients and moments
     are views of the engine's flat buffers like every other parameter.  One GPU only."""
 
+    one_gpu = "the NF-VAE engine"
+
     def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
                  trainer=None):
-        if world_size > 1 or force_dp:
-            raise GMError("the NF-VAE engine runs on one GPU: data parallelism is not implemented for it")
+        self._refuse_dp(world_size, force_dp)
         from ._lib import FLOW_MAX_K
         K = int(model.flow.u.shape[0])
         if not 1 <= K <= FLOW_MAX_K:
@@ -974,7 +987,6 @@ class NFVAEEngine(IWAEEngine):
                           % (FLOW_MAX_K, K))
         super().__init__(model, device, use_graph=use_graph, trainer=trainer)
         self.K = K
-        self._extra_config = {"num_flows": K}
         fp, fl = self.fp, model.flow
         ix = [[i for i, p in enumerate(fp.params) if p is q][0] for q in (fl.u, fl.w, fl.b)]
         seg = lambda buf, i: buf[fp.offsets[i]:fp.offsets[i] + fp.params[i].numel()]
@@ -985,6 +997,9 @@ class NFVAEEngine(IWAEEngine):
     def _extra_params(self, model):
         fl = model.flow
         return [fl.u, fl.w, fl.b]
+
+    def _settings(self):
+        return dict(num_flows=self.K, **super()._settings())
 
     def _alloc(self, B):
         if self._bufB == B:
@@ -1018,10 +1033,11 @@ class CatVAEEngine(IWAEEngine):
     device table laid out and indexed like the Adam schedule (one float per batch of the train() call), so a replayed
     graph needs no host update; validation reads none.  One GPU only."""
 
+    one_gpu = "the categorical VAE engine"
+
     def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
                  trainer=None):
-        if world_size > 1 or force_dp:
-            raise GMError("the categorical VAE engine runs on one GPU: data parallelism is not implemented for it")
+        self._refuse_dp(world_size, force_dp)
         self.N, self.C = int(model.num_vars), int(model.num_classes)
         super().__init__(model, device, use_graph=use_graph, trainer=trainer)
 

@@ -426,6 +426,28 @@ def test_bitwise_reproducibility_graph_eager_and_resume(tmp_path):
     quiet(t3.train, 1)
 
 
+def test_a_refused_resume_leaves_the_engine_as_it_was(tmp_path):
+    """A trainer that has trained loads a checkpoint written under another seed: train() refuses it ("different
+    settings") before anything is touched -- the engine's parameters and both Adam moments are bit for bit what they
+    were before the call."""
+    cfg = dict(k=2, n_train=2 * 16, I=49, H=32, Z=8, batch=16)          # two training batches
+    torch.manual_seed(99)
+    tr, _, its = _trained_small(seed=0, **cfg)
+    path = str(tmp_path / "ck.pt")
+    tr.save_checkpoint(path)
+    t2, _, _ = _trained_small(seed=1, its=its, **cfg)
+    t2.load_checkpoint(path)
+    fp = t2._engine.fp
+    torch.cuda.synchronize()
+    before = [t.cpu().clone() for t in (fp.flat, fp.m, fp.v)]
+    assert float(before[1].abs().sum()) > 0 and float(before[2].sum()) > 0
+    with pytest.raises(GMError, match="different settings"):
+        t2.train(1)
+    torch.cuda.synchronize()
+    for b, t in zip(before, (fp.flat, fp.m, fp.v)):
+        assert torch.equal(b, t.cpu())
+
+
 # ---- paths ------------------------------------------------------------------------------------------------------------------
 class Mine(iwae.IWAETrainer):
     def compute_batch(self, batch):

@@ -320,6 +320,29 @@ def test_bitwise_reproducibility_and_resume(tmp_path):
     assert torch.equal(t3.model.m_in.cpu(), m.m_in.cpu()) and masked_zero(t3.model)
 
 
+def test_a_refused_resume_leaves_the_engine_as_it_was(tmp_path):
+    """A trainer that has trained loads a checkpoint written under another order: train() refuses it ("different
+    settings") before anything is touched -- the engine's parameters and both Adam moments are bit for bit what they
+    were before the call."""
+    cfg = dict(SMALL, n_train=2 * 16, n_val=16)             # two training batches
+    torch.manual_seed(99)
+    its = mk_loaders(cfg)
+    tr, _ = product(cfg, its, 1)
+    path = str(tmp_path / "ck.pt")
+    tr.save_checkpoint(path)
+    t2, _ = product(dict(cfg, order="random"), its, 1)
+    t2.load_checkpoint(path)
+    fp = t2._engine.fp
+    torch.cuda.synchronize()
+    before = [t.cpu().clone() for t in (fp.flat, fp.m, fp.v)]
+    assert float(before[1].abs().sum()) > 0 and float(before[2].sum()) > 0
+    with pytest.raises(GMError, match="different settings"):
+        t2.train(1)
+    torch.cuda.synchronize()
+    for b, t in zip(before, (fp.flat, fp.m, fp.v)):
+        assert torch.equal(b, t.cpu())
+
+
 def test_general_path_agrees_with_the_fused_run():
     class Mine(made.MADETrainer):
         def compute_batch(self, batch):

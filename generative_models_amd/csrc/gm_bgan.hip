@@ -21,10 +21,6 @@
 
 namespace {
 
-__device__ __forceinline__ float f4_lane(const float4& v, int i) {
-    return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
-}
-
 __global__ __launch_bounds__(256) void philox_raw_kernel(const uint32_t* __restrict__ ctr,
                                                          const uint32_t* __restrict__ key, uint32_t* __restrict__ out,
                                                          int64_t n) {
@@ -57,7 +53,7 @@ __global__ __launch_bounds__(256) void philox_normal_kernel(NormalP p) {
     if (e0 + 4 <= p.n && (((uintptr_t)(o + e0)) & 15) == 0) {
         *reinterpret_cast<float4*>(o + e0) = v;
     } else {
-        for (int i = 0; i < 4 && e0 + i < p.n; ++i) o[e0 + i] = f4_lane(v, i);
+        for (int i = 0; i < 4 && e0 + i < p.n; ++i) o[e0 + i] = ph_lane(v, i);
     }
 }
 
@@ -109,7 +105,7 @@ __global__ __launch_bounds__(256) void sghmc_kernel(SghmcP p) {
     } else {
         for (int i = 0; i < 4 && e0 + i < n; ++i) {
             float th = p.theta[base + i], v = p.mom[base + i];
-            sghmc_elem(th, p.grad[base + i], v, f4_lane(xi, i), keep, lr, p.prior, sd);
+            sghmc_elem(th, p.grad[base + i], v, ph_lane(xi, i), keep, lr, p.prior, sd);
             p.theta[base + i] = th;
             p.mom[base + i] = v;
         }

@@ -1,6 +1,6 @@
 // Gumbel-Softmax posterior of the categorical VAE (catvae.py holds the contract; gm_hip.h).  N
 // categorical variables of C classes per sample row; rows are image-major (sample j of image b is row b k + j); the noise
-// block and the counter layout are gm_iwae.hip's, under tags of their own.
+// block and the counter layout are gm_philox.h's PhNoise, under tags of their own.
 //
 // Noise: element e = n C + c of a row is word e & 3 of the row's Philox block e >> 2, through ph_unit to u in (0, 1), and
 //   g = -log(-log(u)) (finite for every word: 2^-24 <= u <= 1 - 2^-24).  Never stored: the backward regenerates it.
@@ -16,33 +16,21 @@
 
 namespace {
 
-struct CatNoise {                                                // gm_iwae.hip's NoiseP
-    uint64_t seed; uint32_t tag;
-    const int64_t* ctr; const int64_t* base; int64_t add;
-    int64_t kt, j0;
-    uint32_t q0;
-};
-
-__device__ __forceinline__ uint32_t cat_step(const CatNoise& n) {
-    return (uint32_t)((n.ctr ? *n.ctr : 0) + (n.base ? *n.base : 0) + n.add);
-}
-
 // The Gumbel values of one noise row, element by element: the row's Philox block is recomputed when the walk leaves it.
 struct CatG {
-    uint32_t k0, k1, q0, step, row, tag, cur;
+    uint64_t seed;
+    uint32_t q0, step, row, tag, cur;
     uint4 w;
-    __device__ __forceinline__ CatG(const CatNoise& n, uint32_t step_, uint32_t row_)
-        : k0((uint32_t)n.seed), k1((uint32_t)(n.seed >> 32)), q0(n.q0), step(step_), row(row_), tag(n.tag),
-          cur(0xFFFFFFFFu), w(make_uint4(0u, 0u, 0u, 0u)) {}
+    __device__ __forceinline__ CatG(const PhNoise& n, uint32_t step_, uint32_t row_)
+        : seed(n.seed), q0(n.q0), step(step_), row(row_), tag(n.tag), cur(0xFFFFFFFFu), w(make_uint4(0u, 0u, 0u, 0u)) {}
     __device__ __forceinline__ float at(uint32_t e) {
         const uint32_t blk = e >> 2;
         if (blk != cur) {
-            w = philox10(make_uint4(q0 + blk, step, row, tag), k0, k1);
+            w = PH_BLOCK(seed, q0 + blk, step, row, tag);
             cur = blk;
         }
         const uint32_t j = e & 3u;
-        const float u = ph_unit(j == 0u ? w.x : j == 1u ? w.y : j == 2u ? w.z : w.w);
-        return -logf(-logf(u));
+        return -logf(-logf(ph_unit(PH_WORD(w, j))));
     }
 };
 
@@ -110,7 +98,7 @@ __device__ __forceinline__ float cat_tau(const CatP& p) {
     return p.tau_tab ? p.tau_tab[gm_slot_index(p.tau_slot)] : p.tau;
 }
 
-__global__ __launch_bounds__(256) void cat_sample_kernel(CatP p, CatNoise n) {
+__global__ __launch_bounds__(256) void cat_sample_kernel(CatP p, PhNoise n) {
     const int64_t gi = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t r = gi >> p.gshift, rr = min(r, p.rows - 1);   // rows past the end redo the last one and store nothing
     const int G = 1 << p.gshift, q = (int)(gi & (G - 1));
@@ -118,7 +106,7 @@ __global__ __launch_bounds__(256) void cat_sample_kernel(CatP p, CatNoise n) {
     const int64_t b = rr / p.k;
     const int j = (int)(rr - b * p.k);
     const int C = p.C, mode = p.mode;
-    CatG gen(n, cat_step(n), (uint32_t)(b * n.kt + n.j0 + j));
+    CatG gen(n, ph_step(n.clk), (uint32_t)(b * n.kt + n.j0 + j));
     const float tau = mode == GM_CAT_RELAXED ? cat_tau(p) : 1.f;
     const float logC = logf((float)C);
     float acc = 0.f;
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(256) void cat_sample_kernel(CatP p, CatNoise n) {
     }
 }
 
-__global__ __launch_bounds__(256) void cat_reduce_kernel(CatP p, CatNoise n) {
+__global__ __launch_bounds__(256) void cat_reduce_kernel(CatP p, PhNoise n) {
 #pragma clang fp contract(off)
     const int64_t gi = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (gi >= p.rows * p.N) return;
@@ -169,7 +157,7 @@ __global__ __launch_bounds__(256) void cat_reduce_kernel(CatP p, CatNoise n) {
     const float* l = p.l + b * p.ldl + e0;
     const float* dy = p.dy + b * p.lddy + e0;
     float* dl = p.dl + b * p.lddl + e0;
-    CatG gen(n, cat_step(n), (uint32_t)(b * n.kt + n.j0));
+    CatG gen(n, ph_step(n.clk), (uint32_t)(b * n.kt + n.j0));
     const CatSoft s = cat_soft(l, gen, e0, C, tau, true);
     const CatQ qs = cat_q(l, C);
     float ydy = 0.f;                                             // sum_c y_c dy_c
@@ -181,16 +169,6 @@ __global__ __launch_bounds__(256) void cat_reduce_kernel(CatP p, CatNoise n) {
         const float d = l[c] - qs.lmax, qc = expf(d) / qs.lS;
         dl[c] = da / tau + wn * (qc * ((d - qs.logS) - qs.qlq));
     }
-}
-
-inline int cat_noise_fill(const gm_iwae_noise* a, int B, int k, CatNoise* n) {   // gm_iwae.hip's iw_noise_fill
-    GM_CHECK_ARG(a != nullptr);
-    GM_CHECK_ARG(a->j0 >= 0 && a->k_total >= a->j0 + k && a->q0 >= 0 && a->q0 < (1ll << 31));
-    GM_CHECK_ARG(a->k_total < (1ll << 32) / B);
-    n->seed = a->seed; n->tag = a->tag;
-    n->ctr = a->step_ctr; n->base = a->step_base; n->add = a->step_add;
-    n->kt = a->k_total; n->j0 = a->j0; n->q0 = (uint32_t)a->q0;
-    return 0;
 }
 
 inline int cat_shape_ok(const gm_cat_args* a) {
@@ -220,8 +198,8 @@ extern "C" int gm_cat_sample(void* stream, const gm_iwae_noise* na, const gm_cat
     }
     GM_CHECK_ARG(a->mode != GM_CAT_DISCRETE || a->codes != nullptr);
     if (a->mode == GM_CAT_RELAXED && (rc = cat_tau_ok(a))) return rc;
-    CatNoise n{};
-    if ((rc = cat_noise_fill(na, a->B, a->k, &n))) return rc;
+    PhNoise n{};
+    if ((rc = ph_noise_fill(na, a->B, a->k, &n))) return rc;
     int gshift = 0;
     while ((1 << gshift) < a->N && gshift < 6) ++gshift;
     CatP p{};
@@ -246,8 +224,8 @@ extern "C" int gm_cat_reduce(void* stream, const gm_iwae_noise* na, const gm_cat
     GM_CHECK_ARG((const float*)a->dlogits != a->logits && (const float*)a->dlogits != a->dzdec &&
                  (const float*)a->dlogits != a->wn);
     if ((rc = cat_tau_ok(a))) return rc;
-    CatNoise n{};
-    if ((rc = cat_noise_fill(na, a->B, 1, &n))) return rc;
+    PhNoise n{};
+    if ((rc = ph_noise_fill(na, a->B, 1, &n))) return rc;
     CatP p{};
     p.l = a->logits; p.ldl = a->ldl;
     p.tau_tab = a->tau_tab; p.tau_slot = a->tau_slot; p.tau = a->tau;

@@ -3,7 +3,7 @@
 //
 // The rule.  Philox4x32-10 with key (seed mod 2^32, seed >> 32):
 //   timestep of batch row `row` at batch `step`: word 0 of counter (0, step, row, tag_t), t = mulhi(word, T);
-//   noise of pixels 4q .. 4q + 3 of that row: counter (q, step, row, tag_e), ph_box_muller on words (0, 1) and (2, 3);
+//   noise of pixels 4q .. 4q + 3 of that row: ph_normals at counter (q, step, row, tag_e);
 //   x0 = fmaf(2, x, -1);   x_t = fmaf(s1[t], n, sa[t] * x0)   (the product rounded, then one fused multiply-add);
 //   sampler: z of pixels 4q .. 4q + 3 of sample row `row` at sampler step s: counter (q, s, row, GM_DDPM_TAG_S).
 // One 256-thread workgroup per row, thread i the quads i, i + 256, ...: a 784-pixel row is one quad per thread on 196
@@ -14,28 +14,14 @@
 
 struct DdpmNoiseP {
     uint64_t seed; uint32_t tag_t, tag_e;
-    const int64_t* ctr; const int64_t* base; int64_t add;    // step = (ctr ? *ctr : 0) + (base ? *base : 0) + add
+    PhClock clk;
     int64_t row0;                                            // batch position of the first row
 };
 struct DdpmTabP { const float* sa; const float* s1; const float* temb; int T, E; };
 struct DdpmOutP { float* xin; int64_t ldin; float* eps; int64_t lde; int32_t* t; int vec_tail; };
 
-static __device__ __forceinline__ uint32_t ddpm_step(const DdpmNoiseP& n) {
-    return (uint32_t)((n.ctr ? *n.ctr : 0) + (n.base ? *n.base : 0) + n.add);
-}
-
 static __device__ __forceinline__ uint32_t ddpm_timestep(const DdpmNoiseP& n, uint32_t step, uint32_t row, uint32_t T) {
-    const uint4 u = philox10(make_uint4(0u, step, row, n.tag_t), (uint32_t)n.seed, (uint32_t)(n.seed >> 32));
-    return __umulhi(u.x, T);
-}
-
-static __device__ __forceinline__ float4 ddpm_normal4(uint64_t seed, uint32_t q, uint32_t step, uint32_t row,
-                                                      uint32_t tag) {
-    const uint4 u = philox10(make_uint4(q, step, row, tag), (uint32_t)seed, (uint32_t)(seed >> 32));
-    float4 n;
-    ph_box_muller(u.x, u.y, n.x, n.y);
-    ph_box_muller(u.z, u.w, n.z, n.w);
-    return n;
+    return __umulhi(PH_BLOCK(n.seed, 0u, step, row, n.tag_t).x, T);
 }
 
 // x_t of one pixel: the image pixel x in [0, 1], its normal n.
@@ -58,22 +44,14 @@ static __device__ __forceinline__ float ddpm_reverse1(float xt, float e, float z
     return __builtin_fmaf(sig, z, m);
 }
 
-static __device__ __forceinline__ float ddpm_f4(const float4& v, int i) {
-    return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
-}
-
 // Where a row's clean pixels come from: fp32 (src) or one bit per pixel (w).
 struct DdpmRow {
     const float* src; const uint32_t* w;
     __device__ __forceinline__ float4 quad(int q) const {
-        if (w) {
-            const uint32_t m = w[q >> 3] >> (4 * (q & 7));
-            return make_float4((float)(m & 1u), (float)((m >> 1) & 1u), (float)((m >> 2) & 1u), (float)((m >> 3) & 1u));
-        }
-        return reinterpret_cast<const float4*>(src)[q];
+        return w ? gather_bits4(w, q) : reinterpret_cast<const float4*>(src)[q];
     }
     __device__ __forceinline__ float elem(int i) const {
-        return w ? (float)((w[i >> 5] >> (i & 31)) & 1u) : src[i];
+        return w ? gather_bit(w, i) : src[i];
     }
 };
 
@@ -90,7 +68,7 @@ static __device__ __forceinline__ void ddpm_tail(float* tail, const float* te, i
 // Batch row b (this workgroup's): t, [x_t | temb[t]] -> o.xin, the noise -> o.eps, the clean pixels -> clean (or null).
 static __device__ __forceinline__ void ddpm_qsample_row(const DdpmNoiseP& n, const DdpmTabP& s, const DdpmOutP& o,
                                                         int64_t b, int I, int vec, float* clean, const DdpmRow& rs) {
-    const uint32_t step = ddpm_step(n), row = (uint32_t)(n.row0 + b);
+    const uint32_t step = ph_step(n.clk), row = (uint32_t)(n.row0 + b);
     uint32_t t = 0;
     if ((threadIdx.x & 63) == 0) t = ddpm_timestep(n, step, row, (uint32_t)s.T);
     t = (uint32_t)__shfl((int)t, 0, 64);
@@ -100,7 +78,7 @@ static __device__ __forceinline__ void ddpm_qsample_row(const DdpmNoiseP& n, con
     if (vec) {                             // I % 4 == 0, every row 16-byte aligned
         for (int q = threadIdx.x; q < (I >> 2); q += blockDim.x) {
             const float4 v = rs.quad(q);
-            const float4 z = ddpm_normal4(n.seed, (uint32_t)q, step, row, n.tag_e);
+            const float4 z = ph_normals(n.seed, (uint32_t)q, step, row, n.tag_e);
             if (clean) reinterpret_cast<float4*>(clean)[q] = v;
             reinterpret_cast<float4*>(xin)[q] = make_float4(ddpm_noised(sa, s1, v.x, z.x), ddpm_noised(sa, s1, v.y, z.y),
                                                             ddpm_noised(sa, s1, v.z, z.z), ddpm_noised(sa, s1, v.w, z.w));
@@ -108,11 +86,11 @@ static __device__ __forceinline__ void ddpm_qsample_row(const DdpmNoiseP& n, con
         }
     } else {
         for (int q = threadIdx.x; 4 * q < I; q += blockDim.x) {
-            const float4 z = ddpm_normal4(n.seed, (uint32_t)q, step, row, n.tag_e);
+            const float4 z = ph_normals(n.seed, (uint32_t)q, step, row, n.tag_e);
             const int cnt = min(4, I - 4 * q);
             for (int j = 0; j < cnt; ++j) {
                 const int i = 4 * q + j;
-                const float x = rs.elem(i), zj = ddpm_f4(z, j);
+                const float x = rs.elem(i), zj = ph_lane(z, j);
                 if (clean) clean[i] = x;
                 xin[i] = ddpm_noised(sa, s1, x, zj);
                 ep[i] = zj;

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void ddpm_reverse_kernel(RevP p) {
     if (p.vec) {
         for (int q = threadIdx.x; q < (p.I >> 2); q += 256) {
             const float4 xt = reinterpret_cast<const float4*>(x)[q], ev = reinterpret_cast<const float4*>(e)[q];
-            const float4 z = noisy ? ddpm_normal4(p.seed, (uint32_t)q, (uint32_t)s, (uint32_t)b, GM_DDPM_TAG_S)
+            const float4 z = noisy ? ph_normals(p.seed, (uint32_t)q, (uint32_t)s, (uint32_t)b, GM_DDPM_TAG_S)
                                    : make_float4(0.f, 0.f, 0.f, 0.f);
             const float4 y = make_float4(ddpm_reverse1(xt.x, ev.x, z.x, s1, sa, sap, dir, sig, p.clip),
                                          ddpm_reverse1(xt.y, ev.y, z.y, s1, sa, sap, dir, sig, p.clip),
@@ -96,12 +96,12 @@ __global__ __launch_bounds__(256) void ddpm_reverse_kernel(RevP p) {
         }
     } else {
         for (int q = threadIdx.x; 4 * q < p.I; q += 256) {
-            const float4 z = noisy ? ddpm_normal4(p.seed, (uint32_t)q, (uint32_t)s, (uint32_t)b, GM_DDPM_TAG_S)
+            const float4 z = noisy ? ph_normals(p.seed, (uint32_t)q, (uint32_t)s, (uint32_t)b, GM_DDPM_TAG_S)
                                    : make_float4(0.f, 0.f, 0.f, 0.f);
             const int cnt = min(4, p.I - 4 * q);
             for (int j = 0; j < cnt; ++j) {
                 const int i = 4 * q + j;
-                const float y = ddpm_reverse1(x[i], e[i], ddpm_f4(z, j), s1, sa, sap, dir, sig, p.clip);
+                const float y = ddpm_reverse1(x[i], e[i], ph_lane(z, j), s1, sa, sap, dir, sig, p.clip);
                 x[i] = y;
                 if (tr) tr[i] = y;
             }
@@ -128,15 +128,15 @@ __global__ __launch_bounds__(256) void ddpm_prior_kernel(PriorP p) {
     float* x = p.xin + b * p.ldin;
     float* tr = p.traj ? p.traj + b * (int64_t)p.I : nullptr;
     for (int q = threadIdx.x; 4 * q < p.I; q += 256) {
-        const float4 z = ddpm_normal4(p.seed, (uint32_t)q, p.step, (uint32_t)b, GM_DDPM_TAG_S);
+        const float4 z = ph_normals(p.seed, (uint32_t)q, p.step, (uint32_t)b, GM_DDPM_TAG_S);
         if (p.vec) {
             reinterpret_cast<float4*>(x)[q] = z;
             if (tr) reinterpret_cast<float4*>(tr)[q] = z;
         } else {
             const int cnt = min(4, p.I - 4 * q);
             for (int j = 0; j < cnt; ++j) {
-                x[4 * q + j] = ddpm_f4(z, j);
-                if (tr) tr[4 * q + j] = ddpm_f4(z, j);
+                x[4 * q + j] = ph_lane(z, j);
+                if (tr) tr[4 * q + j] = ph_lane(z, j);
             }
         }
     }
@@ -158,7 +158,7 @@ inline int qs_fill(const gm_ddpm_noise* a, const gm_ddpm_tables* s, const gm_ddp
     GM_CHECK_ARG(s->sa && s->s1 && s->temb && shape_ok(I, s->E, s->T));
     GM_CHECK_ARG(o->xin && o->eps && o->ldin >= (int64_t)I + s->E && o->lde >= I && (const float*)o->xin != o->eps);
     GM_CHECK_ARG(a->row0 >= 0 && B >= 1 && B < (1ll << 31) && a->row0 + B <= (1ll << 32));
-    *n = DdpmNoiseP{a->seed, a->tag_t, a->tag_e, a->step_ctr, a->step_base, a->step_add, a->row0};
+    *n = DdpmNoiseP{a->seed, a->tag_t, a->tag_e, PhClock{a->step_ctr, a->step_base, a->step_add}, a->row0};
     *t = DdpmTabP{s->sa, s->s1, s->temb, s->T, s->E};
     const bool rows4 = I % 4 == 0 && o->ldin % 4 == 0 && al16(o->xin);
     *out = DdpmOutP{o->xin, o->ldin, o->eps, o->lde, o->t, (rows4 && al16(s->temb)) ? 1 : 0};

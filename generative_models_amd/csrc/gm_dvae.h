@@ -5,7 +5,7 @@
 // The rule.  Philox4x32-10 with key (seed mod 2^32, seed >> 32) and counter (e >> 2, step, row, 0x44564145) gives word
 // e & 3 of the call to pixel e of row `row` (the row's position in the whole batch) at training batch `step`:
 //   salt-and-pepper, T = floor(p 2^31) (host, 64-bit): u < T -> 0; else u - T < T -> 1; else x;
-//   gaussian, sigma: fmaf(sigma, n, x) with n the Box-Muller normal of that word (ph_normal4's mapping);
+//   gaussian, sigma: fmaf(sigma, n, x) with n the Box-Muller normal of that word (ph_normals_of);
 //   none (level 0): x, bit for bit.
 #pragma once
 #include "gm_gather.h"
@@ -15,15 +15,11 @@
 
 struct CorruptP {
     uint64_t seed;
-    const int64_t* ctr; const int64_t* base; int64_t add;    // step = (ctr ? *ctr : 0) + (base ? *base : 0) + add
+    PhClock clk;
     int kind; uint32_t thresh; float sigma;
     int64_t row0;                                            // batch position of the first row
     float* out_c; int64_t ld_c;                              // the corrupted rows (the gathers)
 };
-
-static __device__ __forceinline__ uint32_t corrupt_step(const CorruptP& c) {
-    return (uint32_t)((c.ctr ? *c.ctr : 0) + (c.base ? *c.base : 0) + c.add);
-}
 
 static __device__ __forceinline__ float sp_pixel(uint32_t u, uint32_t T, float x) {
     return u < T ? 0.f : (u - T < T ? 1.f : x);
@@ -32,19 +28,13 @@ static __device__ __forceinline__ float sp_pixel(uint32_t u, uint32_t T, float x
 // Pixels 4q .. 4q + 3 of row `row` (x: their clean values).
 static __device__ __forceinline__ float4 corrupt4(const CorruptP& c, uint32_t step, uint32_t row, uint32_t q, float4 x) {
     if (c.kind == GM_NOISE_NONE) return x;
-    const uint4 u = philox10(make_uint4(q, step, row, GM_DVAE_CTR_TAG), (uint32_t)c.seed, (uint32_t)(c.seed >> 32));
+    const uint4 u = PH_BLOCK(c.seed, q, step, row, GM_DVAE_CTR_TAG);
     if (c.kind == GM_NOISE_SALT_PEPPER)
         return make_float4(sp_pixel(u.x, c.thresh, x.x), sp_pixel(u.y, c.thresh, x.y), sp_pixel(u.z, c.thresh, x.z),
                            sp_pixel(u.w, c.thresh, x.w));
-    float4 n;
-    ph_box_muller(u.x, u.y, n.x, n.y);
-    ph_box_muller(u.z, u.w, n.z, n.w);
+    const float4 n = ph_normals_of(u);
     return make_float4(fmaf(c.sigma, n.x, x.x), fmaf(c.sigma, n.y, x.y), fmaf(c.sigma, n.z, x.z),
                        fmaf(c.sigma, n.w, x.w));
-}
-
-static __device__ __forceinline__ float f4_get(const float4& v, int i) {
-    return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
 }
 
 // gather_body (gm_gather.h) that also writes the corrupted copy of every row to c.out_c: one row per wave, lane l takes
@@ -59,18 +49,12 @@ static __device__ __forceinline__ void gather_corrupt_body(const GatherP& p, con
     if (r < 0 || r >= p.n_rows) r = 0;     // never fault on a corrupt index; parity tests catch it
     float* dst = p.out + (int64_t)b * p.ld_out;
     float* dsc = c.out_c + (int64_t)b * c.ld_c;
-    const uint32_t step = corrupt_step(c), row = (uint32_t)(c.row0 + b);
+    const uint32_t step = ph_step(c.clk), row = (uint32_t)(c.row0 + b);
     const uint32_t* w = p.bits ? p.bits + r * (int64_t)p.wpr : nullptr;
     const float* src = p.bits ? nullptr : p.data + r * (int64_t)p.row_elems;
     if (p.vec) {                           // row_elems % 4 == 0, 16-byte aligned rows (X and Xc)
         for (int q = lane; q < (p.row_elems >> 2); q += 64) {
-            float4 v;
-            if (w) {
-                const uint32_t m = w[q >> 3] >> (4 * (q & 7));
-                v = make_float4((float)(m & 1u), (float)((m >> 1) & 1u), (float)((m >> 2) & 1u), (float)((m >> 3) & 1u));
-            } else {
-                v = reinterpret_cast<const float4*>(src)[q];
-            }
+            const float4 v = w ? gather_bits4(w, q) : reinterpret_cast<const float4*>(src)[q];
             reinterpret_cast<float4*>(dst)[q] = v;
             reinterpret_cast<float4*>(dsc)[q] = corrupt4(c, step, row, (uint32_t)q, v);
         }
@@ -81,13 +65,13 @@ static __device__ __forceinline__ void gather_corrupt_body(const GatherP& p, con
         const int n = min(4, p.row_elems - 4 * q);
         for (int j = 0; j < n; ++j) {
             const int i = 4 * q + j;
-            const float x = w ? (float)((w[i >> 5] >> (i & 31)) & 1u) : src[i];
+            const float x = w ? gather_bit(w, i) : src[i];
             if (j == 0) v.x = x; else if (j == 1) v.y = x; else if (j == 2) v.z = x; else v.w = x;
         }
         const float4 o = corrupt4(c, step, row, (uint32_t)q, v);
         for (int j = 0; j < n; ++j) {
-            dst[4 * q + j] = f4_get(v, j);
-            dsc[4 * q + j] = f4_get(o, j);
+            dst[4 * q + j] = ph_lane(v, j);
+            dsc[4 * q + j] = ph_lane(o, j);
         }
     }
 }
@@ -104,7 +88,7 @@ static inline int gm_corrupt_fill(const gm_corrupt_args* a, CorruptP* c) {
     GM_CHECK_ARG(a->kind != GM_NOISE_SALT_PEPPER || a->level <= 1.0);
     GM_CHECK_ARG(a->row0 >= 0);
     c->seed = a->seed;
-    c->ctr = a->step_ctr; c->base = a->step_base; c->add = a->step_add;
+    c->clk = PhClock{a->step_ctr, a->step_base, a->step_add};
     c->kind = a->level == 0.0 ? GM_NOISE_NONE : a->kind;
     const int64_t T = (int64_t)(a->level * 2147483648.0);                                 // floor(p 2^31), p in [0, 1]
     c->thresh = a->kind == GM_NOISE_SALT_PEPPER ? (uint32_t)T : 0u;

@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void dvae_corrupt_kernel(CorruptRowsP p, Corru
     if (gi >= p.rows * p.nq) return;
     const int64_t r = gi / p.nq;
     const int q = (int)(gi - r * p.nq);
-    const uint32_t step = corrupt_step(c), row = (uint32_t)(c.row0 + r);
+    const uint32_t step = ph_step(c.clk), row = (uint32_t)(c.row0 + r);
     const float* xs = p.x + r * p.ldx;
     float* o = p.out + r * p.ldo;
     if (p.vec) {
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void dvae_corrupt_kernel(CorruptRowsP p, Corru
     if (n > 2) v.z = xs[4 * q + 2];
     if (n > 3) v.w = xs[4 * q + 3];
     const float4 y = corrupt4(c, step, row, (uint32_t)q, v);
-    for (int j = 0; j < n; ++j) o[4 * q + j] = f4_get(y, j);
+    for (int j = 0; j < n; ++j) o[4 * q + j] = ph_lane(y, j);
 }
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

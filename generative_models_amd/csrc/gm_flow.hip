@@ -1,6 +1,6 @@
 // Planar-flow posterior of the normalizing-flow VAE (nfvae.py holds the contract; gm_hip.h).  The
 // IWAE's two row kernels with a chain of K planar layers between z_0 and the decoder, and the flow's own optimiser step.
-// Rows are image-major (sample j of image b is row b k + j); the noise block and the counter layout are gm_iwae.hip's.
+// Rows are image-major (sample j of image b is row b k + j); the noise block and the counter layout are gm_philox.h's PhNoise.
 //
 // Layer constants (every kernel, once per workgroup, into LDS): 8 lanes per layer, lane q the latents 4q .. 4q + 3;
 //   s0 = w.u, u_hat = u + (m(s0) - s0) w / (|w|^2 + 1e-12) with m(x) = -1 + softplus(x), s = w.u_hat.
@@ -20,23 +20,6 @@ namespace {
 
 constexpr int FL_K = GM_FLOW_MAX_K, FL_Z = GM_IWAE_MAX_Z, FL_FS = GM_FLOW_PART_STRIDE;
 static_assert(FL_K == 32 && FL_Z == 32 && FL_FS >= 2 * FL_Z + 2 && FL_FS % 4 == 0, "the lane mappings assume 32 x 32");
-
-struct FlNoise {                                                 // gm_iwae.hip's NoiseP
-    uint64_t seed; uint32_t tag;
-    const int64_t* ctr; const int64_t* base; int64_t add;
-    int64_t kt, j0;
-    uint32_t q0;
-};
-
-__device__ __forceinline__ uint32_t fl_step(const FlNoise& n) {
-    return (uint32_t)((n.ctr ? *n.ctr : 0) + (n.base ? *n.base : 0) + n.add);
-}
-
-__device__ __forceinline__ void fl_eps4(const FlNoise& n, uint32_t step, uint32_t row, uint32_t q, float (&e)[4]) {
-    const uint4 u = philox10(make_uint4(n.q0 + q, step, row, n.tag), (uint32_t)n.seed, (uint32_t)(n.seed >> 32));
-    ph_box_muller(u.x, u.y, e[0], e[1]);
-    ph_box_muller(u.z, u.w, e[2], e[3]);
-}
 
 struct FlowW { const float* u; const float* w; const float* b; int K; };
 
@@ -125,7 +108,7 @@ struct SampleP {
     int64_t rows; int k, Z;
 };
 
-__global__ __launch_bounds__(256) void flow_sample_kernel(SampleP p, FlowW f, FlNoise n) {
+__global__ __launch_bounds__(256) void flow_sample_kernel(SampleP p, FlowW f, PhNoise n) {
     __shared__ FlowLds L;
     fl_constants(f, p.Z, L);
     __syncthreads();
@@ -135,7 +118,7 @@ __global__ __launch_bounds__(256) void flow_sample_kernel(SampleP p, FlowW f, Fl
     const int64_t b = rr / p.k;
     const int j = (int)(rr - b * p.k);
     float e[4], z[4];
-    fl_eps4(n, fl_step(n), (uint32_t)(b * n.kt + n.j0 + j), (uint32_t)q, e);
+    ph_noise_eps4(n, ph_step(n.clk), (uint32_t)(b * n.kt + n.j0 + j), (uint32_t)q, e);
     const float* ml = p.ml + b * p.ldml;
     float acc = 0.f;
 #pragma unroll
@@ -177,7 +160,7 @@ __device__ __forceinline__ float fl_sum_groups(float v) {
     return v;
 }
 
-__global__ __launch_bounds__(64) void flow_reduce_kernel(ReduceP p, FlowW f, FlNoise n) {
+__global__ __launch_bounds__(64) void flow_reduce_kernel(ReduceP p, FlowW f, PhNoise n) {
     __shared__ FlowLds L;
     __shared__ float tl[FL_K][64];                               // t_k of the lane's current sample (its own column)
     __shared__ float acc[FL_K][FL_FS];                           // the workgroup's partial block
@@ -197,11 +180,11 @@ __global__ __launch_bounds__(64) void flow_reduce_kernel(ReduceP p, FlowW f, FlN
         sd[i] = expf(lv[i] / 2.f);
         amu[i] = alv[i] = 0.f;
     }
-    const uint32_t step = fl_step(n);
+    const uint32_t step = ph_step(n.clk);
     for (int j = 0; j < p.k; ++j) {
         const int64_t r = bb * p.k + j;
         float e[4], z[4], g[4];
-        fl_eps4(n, step, (uint32_t)(bb * n.kt + n.j0 + j), (uint32_t)q, e);
+        ph_noise_eps4(n, step, (uint32_t)(bb * n.kt + n.j0 + j), (uint32_t)q, e);
 #pragma unroll
         for (int i = 0; i < 4; ++i) z[i] = 4 * q + i < Z ? gm_reparam_z(mu[i], e[i], lv[i]) : 0.f;
         for (int k = 0; k < f.K; ++k) {
@@ -331,16 +314,6 @@ __global__ __launch_bounds__(256) void flow_step_kernel(StepP p) {
     }
 }
 
-inline int fl_noise_fill(const gm_iwae_noise* a, int B, int k, FlNoise* n) {     // gm_iwae.hip's iw_noise_fill
-    GM_CHECK_ARG(a != nullptr);
-    GM_CHECK_ARG(a->j0 >= 0 && a->k_total >= a->j0 + k && a->q0 >= 0 && a->q0 < (1ll << 31));
-    GM_CHECK_ARG(a->k_total < (1ll << 32) / B);
-    n->seed = a->seed; n->tag = a->tag;
-    n->ctr = a->step_ctr; n->base = a->step_base; n->add = a->step_add;
-    n->kt = a->k_total; n->j0 = a->j0; n->q0 = (uint32_t)a->q0;
-    return 0;
-}
-
 inline int fl_params_fill(const gm_flow_params* a, FlowW* f) {
     GM_CHECK_ARG(a != nullptr);
     GM_CHECK_ARG(a->u && a->w && a->b && a->K >= 1 && a->K <= GM_FLOW_MAX_K);
@@ -359,9 +332,9 @@ extern "C" int gm_flow_sample(void* stream, const gm_iwae_noise* a, const gm_flo
     FL_CHECK_SHAPE(B, k, Z);
     GM_CHECK_ARG(ml && z && lp && ldml >= 2 * Z && ldz >= Z);
     GM_CHECK_ARG((const float*)z != ml && (const float*)lp != ml && lp != z);
-    FlNoise n{};
+    PhNoise n{};
     FlowW f{};
-    int rc = fl_noise_fill(a, B, k, &n);
+    int rc = ph_noise_fill(a, B, k, &n);
     if (rc) return rc;
     rc = fl_params_fill(fp, &f);
     if (rc) return rc;
@@ -381,9 +354,9 @@ extern "C" int gm_flow_reduce(void* stream, const gm_iwae_noise* a, const gm_flo
     GM_CHECK_ARG((const float*)dml != ml && (const float*)dml != dzdec && (const float*)dml != wn);
     GM_CHECK_ARG((const float*)part != ml && (const float*)part != dzdec && (const float*)part != wn && part != dml);
     GM_CHECK_ARG((reinterpret_cast<uintptr_t>(part) & 15) == 0);
-    FlNoise n{};
+    PhNoise n{};
     FlowW f{};
-    int rc = fl_noise_fill(a, B, k, &n);
+    int rc = ph_noise_fill(a, B, k, &n);
     if (rc) return rc;
     rc = fl_params_fill(fp, &f);
     if (rc) return rc;

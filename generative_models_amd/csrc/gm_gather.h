@@ -21,6 +21,15 @@ struct GatherP {
     uint32_t* out_bits;
 };
 
+// Bit-packed rows (GatherP::bits): pixels 4q .. 4q + 3 of the row at words w, and the one-pixel form.
+static __device__ __forceinline__ float4 gather_bits4(const uint32_t* w, int q) {
+    const uint32_t v = w[q >> 3] >> (4 * (q & 7));
+    return make_float4((float)(v & 1u), (float)((v >> 1) & 1u), (float)((v >> 2) & 1u), (float)((v >> 3) & 1u));
+}
+static __device__ __forceinline__ float gather_bit(const uint32_t* w, int i) {
+    return (float)((w[i >> 5] >> (i & 31)) & 1u);
+}
+
 // bid: index among the gather workgroups; every workgroup has blockDim.x / 64 waves = rows.
 static __device__ __forceinline__ void gather_body(const GatherP& p, int bid) {
     const int64_t* ix = p.idx + gm_slot_offset(p.idx_slot);
@@ -39,13 +48,9 @@ static __device__ __forceinline__ void gather_body(const GatherP& p, int bid) {
         }
         if (p.vec) {                        // 4 pixels = 4 bits of one word (row_elems % 4 == 0)
             float4* d4 = reinterpret_cast<float4*>(dst);
-            for (int q = lane; q < (p.row_elems >> 2); q += 64) {
-                const uint32_t v = w[q >> 3] >> (4 * (q & 7));
-                d4[q] = make_float4((float)(v & 1u), (float)((v >> 1) & 1u), (float)((v >> 2) & 1u),
-                                    (float)((v >> 3) & 1u));
-            }
+            for (int q = lane; q < (p.row_elems >> 2); q += 64) d4[q] = gather_bits4(w, q);
         } else {
-            for (int i = lane; i < p.row_elems; i += 64) dst[i] = (float)((w[i >> 5] >> (i & 31)) & 1u);
+            for (int i = lane; i < p.row_elems; i += 64) dst[i] = gather_bit(w, i);
         }
         return;
     }

@@ -17,24 +17,6 @@
 
 namespace {
 
-struct NoiseP {
-    uint64_t seed; uint32_t tag;
-    const int64_t* ctr; const int64_t* base; int64_t add;    // step = (ctr ? *ctr : 0) + (base ? *base : 0) + add
-    int64_t kt, j0;                                          // noise row = b kt + j0 + j
-    uint32_t q0;                                             // counter word 0 = q0 + the call's latent quad
-};
-
-__device__ __forceinline__ uint32_t iw_step(const NoiseP& n) {
-    return (uint32_t)((n.ctr ? *n.ctr : 0) + (n.base ? *n.base : 0) + n.add);
-}
-
-// The normals of latents 4q .. 4q + 3 of noise row `row`.
-__device__ __forceinline__ void iw_eps4(const NoiseP& n, uint32_t step, uint32_t row, uint32_t q, float (&e)[4]) {
-    const uint4 u = philox10(make_uint4(n.q0 + q, step, row, n.tag), (uint32_t)n.seed, (uint32_t)(n.seed >> 32));
-    ph_box_muller(u.x, u.y, e[0], e[1]);
-    ph_box_muller(u.z, u.w, e[2], e[3]);
-}
-
 struct SampleP {
     const float* ml; int64_t ldml;
     float* z; int64_t ldz;
@@ -42,7 +24,7 @@ struct SampleP {
     int64_t rows; int k, Z, nq;
 };
 
-__global__ __launch_bounds__(256) void iwae_sample_kernel(SampleP p, NoiseP n) {
+__global__ __launch_bounds__(256) void iwae_sample_kernel(SampleP p, PhNoise n) {
     const int64_t gi = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t r = gi >> 3;
     const int q = (int)(gi & 7);
@@ -51,7 +33,7 @@ __global__ __launch_bounds__(256) void iwae_sample_kernel(SampleP p, NoiseP n) {
         const int64_t b = r / p.k;
         const int j = (int)(r - b * p.k);
         float e[4];
-        iw_eps4(n, iw_step(n), (uint32_t)(b * n.kt + n.j0 + j), (uint32_t)q, e);
+        ph_noise_eps4(n, ph_step(n.clk), (uint32_t)(b * n.kt + n.j0 + j), (uint32_t)q, e);
         const float* ml = p.ml + b * p.ldml;
         float* zo = p.z + r * p.ldz;
 #pragma unroll
@@ -179,7 +161,7 @@ struct ReduceP {
     int64_t B; int k, Z, nq;
 };
 
-__global__ __launch_bounds__(256) void iwae_reduce_kernel(ReduceP p, NoiseP n) {
+__global__ __launch_bounds__(256) void iwae_reduce_kernel(ReduceP p, PhNoise n) {
     const int64_t gi = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (gi >= p.B * p.nq) return;
     const int64_t b = gi / p.nq;
@@ -195,11 +177,11 @@ __global__ __launch_bounds__(256) void iwae_reduce_kernel(ReduceP p, NoiseP n) {
         sd[i] = expf(lv[i] / 2.f);
         amu[i] = alv[i] = 0.f;
     }
-    const uint32_t step = iw_step(n);
+    const uint32_t step = ph_step(n.clk);
     for (int j = 0; j < p.k; ++j) {
         const int64_t r = b * p.k + j;
         float e[4];
-        iw_eps4(n, step, (uint32_t)(b * n.kt + n.j0 + j), (uint32_t)q, e);
+        ph_noise_eps4(n, step, (uint32_t)(b * n.kt + n.j0 + j), (uint32_t)q, e);
         const float w = p.wn[r];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -225,17 +207,6 @@ __global__ __launch_bounds__(256) void iwae_reduce_kernel(ReduceP p, NoiseP n) {
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// Host: the device form of a gm_iwae_noise for B images of k samples, or GM_EINVAL.
-inline int iw_noise_fill(const gm_iwae_noise* a, int B, int k, NoiseP* n) {
-    GM_CHECK_ARG(a != nullptr);
-    GM_CHECK_ARG(a->j0 >= 0 && a->k_total >= a->j0 + k && a->q0 >= 0 && a->q0 < (1ll << 31));
-    GM_CHECK_ARG(a->k_total < (1ll << 32) / B);              // the noise row is a 32-bit counter word
-    n->seed = a->seed; n->tag = a->tag;
-    n->ctr = a->step_ctr; n->base = a->step_base; n->add = a->step_add;
-    n->kt = a->k_total; n->j0 = a->j0; n->q0 = (uint32_t)a->q0;
-    return 0;
-}
-
 }  // namespace
 
 #define IW_CHECK_SHAPE(B, k, Z) \
@@ -245,8 +216,8 @@ extern "C" int gm_iwae_sample(void* stream, const gm_iwae_noise* a, const float*
                               int64_t ldz, float* lp, int B, int k, int Z) {
     IW_CHECK_SHAPE(B, k, Z);
     GM_CHECK_ARG(ml && z && lp && ldml >= 2 * Z && ldz >= Z);
-    NoiseP n{};
-    const int rc = iw_noise_fill(a, B, k, &n);
+    PhNoise n{};
+    const int rc = ph_noise_fill(a, B, k, &n);
     if (rc) return rc;
     SampleP p{ml, ldml, z, ldz, lp, (int64_t)B * k, k, Z, (Z + 3) / 4};
     const int64_t blocks = (p.rows * 8 + 255) / 256;
@@ -278,8 +249,8 @@ extern "C" int gm_iwae_reduce(void* stream, const gm_iwae_noise* a, const float*
     IW_CHECK_SHAPE(B, k, Z);
     GM_CHECK_ARG(ml && wn && dzdec && dml && ldml >= 2 * Z && lddz >= Z && lddml >= 2 * Z);
     GM_CHECK_ARG(!dZ || (lddZ >= Z && (const float*)dZ != dzdec));
-    NoiseP n{};
-    const int rc = iw_noise_fill(a, B, k, &n);
+    PhNoise n{};
+    const int rc = ph_noise_fill(a, B, k, &n);
     if (rc) return rc;
     ReduceP p{ml, ldml, wn, dzdec, lddz, dml, lddml, dZ, lddZ, (int64_t)B, k, Z, (Z + 3) / 4};
     const int64_t blocks = (p.B * p.nq + 255) / 256;

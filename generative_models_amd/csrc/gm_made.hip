@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void made_sample_kernel(SampP q) {
         float ul = 0.f, bl = 0.f, gl = 0.f;
         if (tl < q.I) {
             dl = min(max(q.inv_order[tl], 0), q.I - 1);   // never read outside a row, whatever the table holds
-            ul = made_unit(q.seed, (uint32_t)dl, (uint32_t)r);
+            ul = ph_uniform(q.seed, (uint32_t)dl, 0u, (uint32_t)r, GM_MADE_TAG_S);
             bl = q.b2[dl];
             if (tl < q.n_known) gl = q.given[r * q.ldg + dl];
         }
@@ -161,7 +161,7 @@ struct UniP { float* u; int64_t ldu; uint64_t seed; int64_t row0; int I; };
 __global__ __launch_bounds__(256) void made_uniform_kernel(UniP p) {
     const int64_t b = blockIdx.x;
     for (int d = threadIdx.x; d < p.I; d += 256)
-        p.u[b * p.ldu + d] = made_unit(p.seed, (uint32_t)d, (uint32_t)(p.row0 + b));
+        p.u[b * p.ldu + d] = ph_uniform(p.seed, (uint32_t)d, 0u, (uint32_t)(p.row0 + b), GM_MADE_TAG_S);
 }
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

@@ -3,7 +3,7 @@
 //
 // Split: pixel e of an image of D pixels is an entry of half A or of half B (Da = ceil(D / 2)): GM_NVP_CHECKER A = the
 // even pixels, GM_NVP_HALF A = the first Da.  Noise: the uniform of pixel e is ph_unit of word e & 3 of the row's Philox
-// block e >> 2; the sampler's normal of pixel e is the Box-Muller value of that word under ph_normal4's pairing.  Both are
+// block e >> 2; the sampler's normal of pixel e is the Box-Muller value of that word under ph_normals' pairing.  Both are
 // indexed by (row, pixel) alone: no work mapping can change a bit.
 #pragma once
 #include "gm_philox.h"

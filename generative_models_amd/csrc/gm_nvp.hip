@@ -18,24 +18,19 @@ namespace {
 
 struct PreP {
     const float* x; int64_t ldx; float* ya; int64_t lda; float* yb; int64_t ldb; float* logdet; float* u; int64_t ldu;
-    uint64_t seed; const int64_t* ctr; const int64_t* base; int64_t add; int64_t row0; uint32_t tag;
+    uint64_t seed; PhClock clk; int64_t row0; uint32_t tag;
     NvpPre c; int mask, mode, D, Da, vec_x, vec_h;
 };
-
-__device__ __forceinline__ float4 nvp_units(const uint4& w) {
-    return make_float4(ph_unit(w.x), ph_unit(w.y), ph_unit(w.z), ph_unit(w.w));
-}
 
 __global__ __launch_bounds__(256) void nvp_pre_kernel(PreP p) {
     __shared__ float sh[4];
     const int64_t r = blockIdx.x;
-    const uint32_t step = (uint32_t)((p.ctr ? *p.ctr : 0) + (p.base ? *p.base : 0) + p.add);
-    const uint32_t row = (uint32_t)(p.row0 + r), k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
+    const uint32_t step = ph_step(p.clk), row = (uint32_t)(p.row0 + r);
     const int nq = (p.D + 3) >> 2;
     if (p.mode == GM_NVP_NOISE) {
         float* u = p.u + r * p.ldu;
         for (int q = threadIdx.x; q < nq; q += 256)
-            nvp_store4(u, q, p.D, p.vec_x, nvp_units(philox10(make_uint4((uint32_t)q, step, row, p.tag), k0, k1)));
+            nvp_store4(u, q, p.D, p.vec_x, ph_units_of(PH_BLOCK(p.seed, (uint32_t)q, step, row, p.tag)));
         return;
     }
     const float* x = p.x + r * p.ldx;
@@ -44,7 +39,7 @@ __global__ __launch_bounds__(256) void nvp_pre_kernel(PreP p) {
     float acc = 0.f;
     for (int q = threadIdx.x; q < nq; q += 256) {
         const float4 xv = nvp_load4(x, q, p.D, p.vec_x);
-        const float4 uv = nvp_units(philox10(make_uint4((uint32_t)q, step, row, p.tag), k0, k1));
+        const float4 uv = ph_units_of(PH_BLOCK(p.seed, (uint32_t)q, step, row, p.tag));
         float4 y;
         const float l0 = nvp_pre_elem(xv.x, uv.x, p.c, y.x), l1 = nvp_pre_elem(xv.y, uv.y, p.c, y.y);
         const float l2 = nvp_pre_elem(xv.z, uv.z, p.c, y.z), l3 = nvp_pre_elem(xv.w, uv.w, p.c, y.w);
@@ -175,12 +170,10 @@ __global__ __launch_bounds__(256) void nvp_post_kernel(PostP p) {
     float* yb = p.yb + r * p.ldb;
     const int nq = (p.D + 3) >> 2;
     if (p.mode == GM_NVP_PRIOR) {
+        // PH_BLOCK with the key split once, ahead of the loop
         const uint32_t row = (uint32_t)(p.row0 + r), k0 = (uint32_t)p.seed, k1 = (uint32_t)(p.seed >> 32);
         for (int q = threadIdx.x; q < nq; q += 256) {
-            const uint4 w = philox10(make_uint4((uint32_t)q, 0u, row, GM_NVP_TAG_S), k0, k1);
-            float4 z;
-            ph_box_muller(w.x, w.y, z.x, z.y);
-            ph_box_muller(w.z, w.w, z.z, z.w);
+            float4 z = ph_normals_of(philox10(make_uint4((uint32_t)q, 0u, row, GM_NVP_TAG_S), k0, k1));
             z = make_float4(z.x * p.temp, z.y * p.temp, z.z * p.temp, z.w * p.temp);
             nvp_split_store(ya, yb, q, p.D, p.Da, p.mask, p.vec_h, z);
         }
@@ -222,7 +215,7 @@ extern "C" int gm_nvp_pre(void* stream, const gm_nvp_pre_args* a) {
     GM_CHECK_ARG(a->row0 >= 0 && a->row0 + (int64_t)a->B <= (1ll << 32));
     const int Da = (a->D + 1) / 2, Db = a->D / 2;
     PreP p{};
-    p.seed = a->seed; p.ctr = a->step_ctr; p.base = a->step_base; p.add = a->step_add; p.row0 = a->row0; p.tag = a->tag;
+    p.seed = a->seed; p.clk = PhClock{a->step_ctr, a->step_base, a->step_add}; p.row0 = a->row0; p.tag = a->tag;
     p.mode = a->mode; p.D = a->D; p.Da = Da;
     if (a->mode == GM_NVP_NOISE) {
         GM_CHECK_ARG(a->u && a->ldu >= a->D);

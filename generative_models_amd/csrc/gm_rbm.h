@@ -1,19 +1,13 @@
 // The restricted Boltzmann machine's noise rule and pinned arithmetic (rbm.py; gm_hip.h), shared by every kernel of
 // gm_rbm.hip.
 //
-// The uniform of unit e of chain row r at step t under tag T: ph_unit of word e & 3 of Philox4x32-10 at counter
-// (e >> 2, t, r, T) under key (seed mod 2^32, seed >> 32).  T = GM_RBM_TAG_D: the binarisation of the input rows (t = the
+// The uniform of unit e of chain row r at step t under tag T: ph_uniform(seed, e, t, r, T) (gm_philox.h), word e & 3 of
+// the block at counter (e >> 2, t, r, T).  T = GM_RBM_TAG_D: the binarisation of the input rows (t = the
 // batch step);  GM_RBM_TAG_H / GM_RBM_TAG_V: the hidden / visible draws (t = the Gibbs step).  A unit is lit iff
 // u < made_prob(a), compared in fp32 (gm_made.h's pinned sigmoid).  Indexed by (seed, t, r, e) alone: no work mapping can
 // change a bit.
 #pragma once
 #include "gm_made.h"
-
-static __device__ __forceinline__ float rbm_unit(uint64_t seed, uint32_t e, uint32_t t, uint32_t r, uint32_t tag) {
-    const uint4 w = philox10(make_uint4(e >> 2, t, r, tag), (uint32_t)seed, (uint32_t)(seed >> 32));
-    const uint32_t j = e & 3u;
-    return ph_unit(j == 0u ? w.x : j == 1u ? w.y : j == 2u ? w.z : w.w);
-}
 
 // softplus, pinned: max(a, 0) + log1pf(expf(-|a|)).
 static __device__ __forceinline__ float rbm_sp(float a) {

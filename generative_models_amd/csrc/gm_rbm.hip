@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void rbm_chain_kernel(ChainP q) {
         const int i = w * 64 + lane;
         bool lit = false;
         if (i < I) {
-            lit = rbm_unit(q.seed, (uint32_t)i, dstep, row, GM_RBM_TAG_D) < q.x[r * q.ldx + i];
+            lit = ph_uniform(q.seed, (uint32_t)i, dstep, row, GM_RBM_TAG_D) < q.x[r * q.ldx + i];
             if (q.v0) q.v0[r * q.ldv0 + i] = lit ? 1.f : 0.f;
         }
         vb[w] = __ballot(lit);
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void rbm_chain_kernel(ChainP q) {
             bool lit = false;
             if (k < H) {
                 const float a = q.betas ? bc * pre[j] : pre[j];
-                lit = rbm_unit(q.seed, (uint32_t)k, t, row, GM_RBM_TAG_H) < made_prob(a);
+                lit = ph_uniform(q.seed, (uint32_t)k, t, row, GM_RBM_TAG_H) < made_prob(a);
             }
             hb[j] = __ballot(lit);
         }
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void rbm_chain_kernel(ChainP q) {
             if (i < I) {
                 const float a = q.betas ? rbm_temper_v(bc, pre[w], q.bA[i]) : pre[w];
                 const float pv = made_prob(a);
-                lit = rbm_unit(q.seed, (uint32_t)i, t, row, GM_RBM_TAG_V) < pv;
+                lit = ph_uniform(q.seed, (uint32_t)i, t, row, GM_RBM_TAG_V) < pv;
                 if (last) {
                     if (q.p) q.p[r * q.ldp + i] = pv;
                     if (q.a) q.a[r * q.lda + i] = a;
@@ -276,15 +276,15 @@ __global__ __launch_bounds__(256) void rbm_transpose_kernel(TransP p) {
 }
 
 struct UniP {
-    float* u; int64_t ldu; uint64_t seed; const int64_t* ctr; const int64_t* base; int64_t add; int64_t row0;
+    float* u; int64_t ldu; uint64_t seed; PhClock clk; int64_t row0;
     uint32_t tag; int width;
 };
 
 __global__ __launch_bounds__(256) void rbm_uniform_kernel(UniP p) {
     const int64_t b = blockIdx.x;
-    const uint32_t t = (uint32_t)((p.ctr ? *p.ctr : 0) + (p.base ? *p.base : 0) + p.add);
+    const uint32_t t = ph_step(p.clk);
     for (int e = threadIdx.x; e < p.width; e += 256)
-        p.u[b * p.ldu + e] = rbm_unit(p.seed, (uint32_t)e, t, (uint32_t)(p.row0 + b), p.tag);
+        p.u[b * p.ldu + e] = ph_uniform(p.seed, (uint32_t)e, t, (uint32_t)(p.row0 + b), p.tag);
 }
 
 inline bool dim_ok(int d) { return d >= 1 && d <= GM_RBM_MAX_DIM; }
@@ -365,7 +365,7 @@ extern "C" int gm_rbm_uniform(void* stream, float* u, int64_t ldu, uint64_t seed
     GM_CHECK_ARG(u && dim_ok(width) && ldu >= width && rows >= 1 && rows < (1ll << 31) && row0 >= 0 &&
                  row0 + rows <= (1ll << 32));
     GM_CHECK_ARG(tag == GM_RBM_TAG_D || tag == GM_RBM_TAG_H || tag == GM_RBM_TAG_V);
-    UniP p{u, ldu, seed, step_ctr, step_base, step_add, row0, tag, width};
+    UniP p{u, ldu, seed, PhClock{step_ctr, step_base, step_add}, row0, tag, width};
     hipLaunchKernelGGL(rbm_uniform_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, p);
     GM_LAUNCH_RET();
 }

@@ -269,10 +269,7 @@ class DDPMEngine(VAEEngine):
 
     def _noise(self, t, train):
         from . import ops_fused as of_
-        base = self.nbase if train else None
-        if self.use_graph:
-            return of_.ddpm_noise(self.trainer.seed, train, step_ctr=self.ctr, step_base=base)
-        return of_.ddpm_noise(self.trainer.seed, train, step=t, step_base=base)
+        return of_.ddpm_noise(self.trainer.seed, train, **self._clock(t, train))
 
     def _issue(self, st, t, b, train, pos=0, of=1):
         """One batch of size b: q-sample, forward, L_simple (+ backward + Adam when train)."""

@@ -622,20 +622,33 @@ def bgan_head(h, w2, b2, mode, B, Jg, Jd, ws, gw2=None, gb2=None, loss_out=None,
     _lib.call("gm_bgan_head", stream or stream_ptr(), ctypes.byref(a))
 
 
+# ---- The device noise clock and seed (csrc/gm_philox.h) --------------------------------------
+def _clock(who, step, step_ctr, step_base):
+    """(step_ctr's pointer, step_base's pointer, int(step)) of a noise block whose step is *step_ctr + *step_base +
+    step: each tensor an int64 device tensor, or None for 0.  Checked before anything is launched: a tensor of another
+    dtype or on the host would be read as raw memory."""
+    for t, nm in ((step_ctr, "step_ctr"), (step_base, "step_base")):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64):
+            raise _lib.GMError("%s: %s must be an int64 device tensor or None" % (who, nm))
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    return ptr(step_ctr), ptr(step_base), int(step)
+
+
+def _seed64(who, seed):
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise _lib.GMError("%s: seed must lie in [0, 2^64)" % who)
+    return seed
+
+
 # ---- Denoising VAE (csrc/gm_dvae.hip, gm_dvae.h; dvae.py) ---------------------------------------------------------
 def corrupt_args(noise, level, seed, step=0, step_ctr=None, step_base=None, row0=0):
     """A gm_corrupt_args block: noise "salt_pepper" / "gaussian" (or a GM_NOISE_* int), its level, the seed
     (0 <= seed < 2^64) and the training-batch step = *step_ctr + *step_base + step (int64 device tensors, or None for
     0).  The tensors must outlive every launch (and every captured graph) that reads them."""
     kind = _lib.NOISE[noise] if isinstance(noise, str) else int(noise)
-    for t, nm in ((step_ctr, "step_ctr"), (step_base, "step_base")):
-        if t is not None and not (t.is_cuda and t.dtype == torch.int64):
-            raise _lib.GMError("corrupt_args: %s must be an int64 device tensor" % nm)
-    seed = int(seed)
-    if not 0 <= seed < 1 << 64:
-        raise _lib.GMError("corrupt_args: seed must lie in [0, 2^64)")
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    return _lib.CorruptArgs(kind, float(level), seed, ptr(step_ctr), ptr(step_base), int(step), int(row0))
+    return _lib.CorruptArgs(kind, float(level), _seed64("corrupt_args", seed),
+                            *_clock("corrupt_args", step, step_ctr, step_base), int(row0))
 
 
 def _rows2d(x, name):
@@ -745,14 +758,8 @@ def iwae_noise(seed, tag, k_total, j0=0, step=0, step_ctr=None, step_base=None, 
     """A gm_iwae_noise block: the stream (seed, tag) at step = *step_ctr + *step_base + step (int64 device tensors, or
     None for 0); the call's sample j of image b draws noise row b * k_total + j0 + j.  The tensors must outlive every
     launch (and every captured graph) that reads them."""
-    for t, nm in ((step_ctr, "step_ctr"), (step_base, "step_base")):
-        if t is not None and not (t.is_cuda and t.dtype == torch.int64):
-            raise _lib.GMError("iwae_noise: %s must be an int64 device tensor" % nm)
-    seed = int(seed)
-    if not 0 <= seed < 1 << 64:
-        raise _lib.GMError("iwae_noise: seed must lie in [0, 2^64)")
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    return IwaeNoise(seed, int(tag) & 0xFFFFFFFF, ptr(step_ctr), ptr(step_base), int(step), int(k_total), int(j0), int(q0))
+    return IwaeNoise(_seed64("iwae_noise", seed), int(tag) & 0xFFFFFFFF,
+                     *_clock("iwae_noise", step, step_ctr, step_base), int(k_total), int(j0), int(q0))
 
 
 def iwae_sample(ml, z, lp, noise, B, k, Z, stream=None):
@@ -1012,15 +1019,9 @@ def ddpm_noise(seed, train=True, step=0, step_ctr=None, step_base=None, row0=0):
     """A gm_ddpm_noise block: the training stream (tags DDPT / DDPM) or the validation one (DDPV / DDPW) at step =
     *step_ctr + *step_base + step (int64 device tensors, or None for 0).  The tensors must outlive every launch (and
     every captured graph) that reads them."""
-    for t, nm in ((step_ctr, "step_ctr"), (step_base, "step_base")):
-        if t is not None and not (t.is_cuda and t.dtype == torch.int64):
-            raise _lib.GMError("ddpm_noise: %s must be an int64 device tensor" % nm)
-    seed = int(seed)
-    if not 0 <= seed < 1 << 64:
-        raise _lib.GMError("ddpm_noise: seed must lie in [0, 2^64)")
     tags = (_lib.DDPM_TAG_T, _lib.DDPM_TAG_E) if train else (_lib.DDPM_TAG_V, _lib.DDPM_TAG_VE)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    return DdpmNoise(seed, tags[0], tags[1], ptr(step_ctr), ptr(step_base), int(step), int(row0))
+    return DdpmNoise(_seed64("ddpm_noise", seed), tags[0], tags[1], *_clock("ddpm_noise", step, step_ctr, step_base),
+                     int(row0))
 
 
 def ddpm_tables(sa, s1, temb):
@@ -1245,9 +1246,10 @@ def rbm_chain(W, WT, c, b, x, steps, seed, n=None, v0_out=None, v_out=None, p_ou
     the last visible draw and their logits).  betas (float32 [steps + 1] on the device), b_A [I] and logw (float64 [n])
     together run the tempered chain of annealed importance sampling."""
     H, I = W.shape
+    a = RbmChainArgs()
+    a.step_ctr, a.step_base, _ = _clock("rbm_chain", 0, step_ctr, step_base)
     _made_f32(W, (H, I), "W"), _made_f32(WT, (I, H), "WT"), _made_f32(c, (H,), "c"), _made_f32(b, (I,), "b")
     n = x.shape[0] if n is None else int(n)
-    a = RbmChainArgs()
     for t, nm in ((x, "x"), (v0_out, "v0_out"), (v_out, "v_out"), (p_out, "p_out"), (a_out, "a_out")):
         if t is not None and (_rows2d(t, nm).shape[0] < n or t.shape[1] < I):
             raise _lib.GMError("rbm_chain: %s %s does not fit %d rows of %d" % (nm, tuple(t.shape), n, I))
@@ -1266,8 +1268,6 @@ def rbm_chain(W, WT, c, b, x, steps, seed, n=None, v0_out=None, v_out=None, p_ou
             raise _lib.GMError("rbm_chain: logw must be a contiguous float64 device tensor of >= %d elements" % n)
         a.betas, a.b_A, a.logw = betas.data_ptr(), b_A.data_ptr(), logw.data_ptr()
     a.seed, a.row0, a.n, a.I, a.H, a.steps = int(seed), int(row0), n, I, H, int(steps)
-    a.step_ctr = step_ctr.data_ptr() if step_ctr is not None else None
-    a.step_base = step_base.data_ptr() if step_base is not None else None
     a.d_add, a.g_mul, a.g_add = int(d_add), int(g_mul), int(g_add)
     _lib.call("gm_rbm_chain", stream or stream_ptr(), ctypes.byref(a))
 
@@ -1310,10 +1310,10 @@ def rbm_transpose(W, WT, stream=None):
 
 def rbm_uniform(n, width, seed, tag, step=0, row0=0, step_ctr=None, step_base=None, device="cuda", stream=None):
     """u [n, width]: the RBM noise rule's uniforms of chain rows row0 .. under `tag` at step (gm_rbm_uniform)."""
+    clock = _clock("rbm_uniform", step, step_ctr, step_base)
     u = torch.empty(n, width, device=device)
-    _lib.call("gm_rbm_uniform", stream or stream_ptr(), u.data_ptr(), _ld(u), int(seed), int(tag),
-              step_ctr.data_ptr() if step_ctr is not None else None,
-              step_base.data_ptr() if step_base is not None else None, int(step), int(row0), int(n), int(width))
+    _lib.call("gm_rbm_uniform", stream or stream_ptr(), u.data_ptr(), _ld(u), int(seed), int(tag), *clock, int(row0),
+              int(n), int(width))
     return u
 
 
@@ -1375,24 +1375,13 @@ def _nvp_vec(t, B, name):
     return t
 
 
-def _nvp_seed(seed):
-    seed = int(seed)
-    if not 0 <= seed < 1 << 64:
-        raise _lib.GMError("the seed must lie in [0, 2^64)")
-    return seed
-
-
 def _nvp_mask(mask):
     return NVP_MASKS[mask] if isinstance(mask, str) else int(mask)
 
 
 def _nvp_noise(a, seed, tag, step, step_ctr, step_base, row0):
-    for t, nm in ((step_ctr, "step_ctr"), (step_base, "step_base")):
-        if t is not None and not (t.is_cuda and t.dtype == torch.int64):
-            raise _lib.GMError("%s must be an int64 device tensor" % nm)
-    a.seed, a.tag, a.step_add, a.row0 = _nvp_seed(seed), int(tag), int(step), int(row0)
-    a.step_ctr = step_ctr.data_ptr() if step_ctr is not None else None
-    a.step_base = step_base.data_ptr() if step_base is not None else None
+    a.seed, a.tag, a.row0 = _seed64("nvp_pre", seed), int(tag), int(row0)
+    a.step_ctr, a.step_base, a.step_add = _clock("nvp_pre", step, step_ctr, step_base)
 
 
 def nvp_pre(x, ya, yb, logdet, B, seed, tag, alpha, levels, mask, step=0, step_ctr=None, step_base=None, row0=0,
@@ -1412,10 +1401,10 @@ def nvp_pre(x, ya, yb, logdet, B, seed, tag, alpha, levels, mask, step=0, step_c
 def nvp_uniforms(n, D, seed, tag, step=0, row0=0, device="cuda", stream=None):
     """u [n, D]: the dequantisation noise gm_nvp_pre draws for (seed, tag, step) on rows row0 .., through its NOISE
     mode, bit for bit: what the general path and the tests feed the preprocessing."""
-    u = torch.empty(n, D, device=device)
     a = NvpPreArgs()
-    a.u, a.ldu, a.mode, a.B, a.D = u.data_ptr(), _ld(u), _lib.NVP_NOISE, n, D
     _nvp_noise(a, seed, tag, step, None, None, row0)
+    u = torch.empty(n, D, device=device)
+    a.u, a.ldu, a.mode, a.B, a.D = u.data_ptr(), _ld(u), _lib.NVP_NOISE, n, D
     _lib.call("gm_nvp_pre", stream or stream_ptr(), ctypes.byref(a))
     return u
 
@@ -1477,6 +1466,6 @@ def nvp_prior(za, zb, B, D, seed, mask, temperature=1.0, row0=0, stream=None):
     a = NvpPostArgs()
     _nvp_rows(za, B, (D + 1) // 2, "za"), _nvp_rows(zb, B, D // 2, "zb")
     a.ya, a.lda, a.yb, a.ldb = za.data_ptr(), _ld(za), zb.data_ptr(), _ld(zb)
-    a.seed, a.row0, a.temperature = _nvp_seed(seed), int(row0), float(temperature)
+    a.seed, a.row0, a.temperature = _seed64("nvp_prior", seed), int(row0), float(temperature)
     a.mask, a.mode, a.B, a.D = _nvp_mask(mask), _lib.NVP_PRIOR, B, D
     _lib.call("gm_nvp_post", stream or stream_ptr(), ctypes.byref(a))

@@ -342,10 +342,8 @@ class RealNVPEngine(VAEEngine):
         idx_slot = self._slot(t, 1, 0, self.R, self.B)
         loss_slot = self._slot(t, 1, 0, 0, 1)
         ops.gather_rows(self.data, self.idx_ring.view(-1), self.X, B=b, idx_slot=idx_slot, stream=st)
-        noise = dict(step_ctr=self.ctr, step=0) if self.use_graph else dict(step=t)
         of_.nvp_pre(self.X, self.Y0[0], self.Y0[1], self.logdet, b, self.trainer.seed,
-                    TAG_TRAIN if train else TAG_EVAL, m.alpha, m.levels, m.mask,
-                    step_base=self.nbase if train else None, stream=st, **noise)
+                    TAG_TRAIN if train else TAG_EVAL, m.alpha, m.levels, m.mask, stream=st, **self._clock(t, train))
         steps, (Za, Zb) = self._chain()
         for k, (th, xt, xc) in enumerate(steps):
             L1, L2 = self.C[k]

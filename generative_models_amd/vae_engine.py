@@ -123,6 +123,15 @@ class VAEEngine:
         self.trainer = trainer
         self.nbase = torch.zeros(1, dtype=torch.int64, device=self.device)
 
+    def _clock(self, t, train, add=0):
+        """The noise-clock keywords of the batch at ring step t (+ add), for the ops_fused noise builders: a graph reads
+        the device counter ctr, an eager launch passes t; a training batch adds nbase on the device, a validation batch
+        (whose step is its index in the pass) has no base."""
+        base = self.nbase if train else None
+        if self.use_graph:
+            return dict(step=add, step_ctr=self.ctr, step_base=base)
+        return dict(step=t + add, step_ctr=None, step_base=base)
+
     def _settings(self):
         """The run's settings beside B, lr and weight_decay: saved in checkpoints, compared on resume, and launch
         arguments of the captured graphs (a change drops them)."""
@@ -813,12 +822,10 @@ class DVAEEngine(VAEEngine):
         return self.Xcb[0] if X is self.Xb[0] else self.Xcb[1]
 
     def _cargs(self, t, add):
-        """The corruption of the batch at ring step t (+ add): graphs read ctr + nbase, eager launches t + nbase."""
+        """The corruption of the training batch at ring step t (+ add)."""
         from . import ops_fused as of_
         tr = self.trainer
-        if self.use_graph:
-            return of_.corrupt_args(tr.noise, tr.level, tr.seed, step=add, step_ctr=self.ctr, step_base=self.nbase)
-        return of_.corrupt_args(tr.noise, tr.level, tr.seed, step=t + add, step_base=self.nbase)
+        return of_.corrupt_args(tr.noise, tr.level, tr.seed, **self._clock(t, True, add))
 
     def _encoder_rows(self, X, train):
         return self._xc(X) if train else X
@@ -896,14 +903,10 @@ class IWAEEngine(VAEEngine):
         super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
 
     def _noise(self, t, train):
-        """The batch's noise stream: training batches read ctr + nbase (eager: t + nbase) under the training tag,
-        validation batches their index in the pass under the evaluation tag."""
+        """The batch's noise stream: the training tag at the training clock, or the evaluation tag at the batch's index
+        in the pass (_clock)."""
         from . import ops_fused as of_
-        tags = self._tags()
-        tag, base = (tags[0], self.nbase) if train else (tags[1], None)
-        if self.use_graph:
-            return of_.iwae_noise(self.trainer.seed, tag, self.k, step_ctr=self.ctr, step_base=base)
-        return of_.iwae_noise(self.trainer.seed, tag, self.k, step=t, step_base=base)
+        return of_.iwae_noise(self.trainer.seed, self._tags()[0 if train else 1], self.k, **self._clock(t, train))
 
     def _tags(self):
         """The noise stream's (training, evaluation) tags."""

@@ -84,8 +84,14 @@ def host_thread_plan():
 def __getattr__(name):
     """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine, SNGAN / SNGANTrainer / SNGANEngine,
     DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine, NFVAE / NFVAETrainer / NFVAEEngine, CatVAE /
-    CatVAETrainer / CatVAEEngine, RealNVP / RealNVPTrainer / RealNVPEngine and RBM / RBMTrainer / RBMEngine, imported on
-    first use (importing the package stays free of torch)."""
+    CatVAETrainer / CatVAEEngine, RealNVP / RealNVPTrainer / RealNVPEngine, RBM / RBMTrainer / RBMEngine and VQVAE /
+    VQVAETrainer / VQVAEEngine, imported on first use (importing the package stays free of torch)."""
+    if name in ("VQVAE", "VQVAETrainer"):
+        from . import vqvae
+        return getattr(vqvae, name)
+    if name == "VQVAEEngine":
+        from . import engine
+        return engine.VQVAEEngine
     if name in ("RBM", "RBMTrainer", "RBMEngine"):
         from . import rbm
         return getattr(rbm, name)

@@ -152,6 +152,10 @@ RBM_TAG_D, RBM_TAG_H, RBM_TAG_V = 0x52424D44, 0x52424D48, 0x52424D56      # GM_R
 RBM_MAX_DIM, RBM_MAX_STEPS = 1024, 1 << 24                  # GM_RBM_MAX_DIM / GM_RBM_MAX_STEPS
 # (gm_rbm_chain_args / gm_rbm_vbias_args travel by pointer; their ctypes forms live in ops_fused)
 
+VQ_MIN_D, VQ_MAX_D, VQ_MAX_ND = 4, 64, 1024                 # GM_VQ_MIN_D / GM_VQ_MAX_D / GM_VQ_MAX_ND
+VQ_MIN_K, VQ_MAX_K, VQ_MAX_KD = 2, 1024, 16384              # GM_VQ_MIN_K / GM_VQ_MAX_K / GM_VQ_MAX_KD
+# (gm_vq_args / gm_vq_step_args travel by pointer; their ctypes forms live in ops_fused)
+
 NOISE = {"salt_pepper": 1, "gaussian": 2}       # GM_NOISE_SALT_PEPPER, GM_NOISE_GAUSSIAN (GM_NOISE_NONE = 0)
 
 
@@ -386,6 +390,9 @@ _SIGNATURES = {
     "gm_flow_step": (c_int, [_P, _P]),
     "gm_cat_sample": (c_int, [_P, _P, _P]),
     "gm_cat_reduce": (c_int, [_P, _P, _P]),
+    "gm_vq_quantise": (c_int, [_P, _P]),
+    "gm_vq_reduce": (c_int, [_P, _P]),
+    "gm_vq_step": (c_int, [_P, _P]),
     "gm_ddpm_qsample": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int]),
     "gm_gather_rows_qsample": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
     "gm_gather_rows_bits_qsample": (c_int, [_P, _P, _P, _P, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),

@@ -26,6 +26,9 @@ IWAEResult = collections.namedtuple("IWAEResult", "ll_mean ll_stderr k n")
 NLLResult = collections.namedtuple("NLLResult", "ll_mean ll_stderr n")
 # rbm.RBMTrainer.log_likelihood: log p(v) = -F(v) - log Z with log Z by annealed importance sampling (chains x n_betas)
 AISResult = collections.namedtuple("AISResult", "ll_mean ll_stderr log_z log_z_stderr chains n_betas n")
+# vqvae.VQVAETrainer.log_likelihood: the lower bound log p(x | z) + log p(z) at z = the image's codes, the prior a MADE over
+# the codes' bits; ll_mean = recon_mean + prior_mean
+VQResult = collections.namedtuple("VQResult", "ll_mean ll_stderr recon_mean prior_mean n")
 
 
 def default_sigmas():

@@ -986,6 +986,102 @@ def catvae_gumbels(n_images, k, N, C, seed, step, tag, device="cuda"):
     return out.view(n_images * k, W)
 
 
+# ---- Vector quantisation of the VQ-VAE (csrc/gm_vq.hip; vqvae.py) --------------------------------------------------
+class VqArgs(ctypes.Structure):
+    """gm_vq_args (include/gm_hip.h): gm_vq_quantise's and gm_vq_reduce's arguments as one block."""
+    _fields_ = [("ze", ctypes.c_void_p), ("ldz", ctypes.c_int64), ("E", ctypes.c_void_p), ("lde", ctypes.c_int64),
+                ("codes", ctypes.c_void_p), ("ldc", ctypes.c_int64), ("beta", ctypes.c_float), ("B", ctypes.c_int),
+                ("N", ctypes.c_int), ("D", ctypes.c_int), ("K", ctypes.c_int), ("zq", ctypes.c_void_p),
+                ("ldq", ctypes.c_int64), ("qerr", ctypes.c_void_p), ("lp", ctypes.c_void_p), ("dzdec", ctypes.c_void_p),
+                ("lddz", ctypes.c_int64), ("wn", ctypes.c_void_p), ("dml", ctypes.c_void_p), ("lddml", ctypes.c_int64)]
+
+
+class VqStepArgs(ctypes.Structure):
+    """gm_vq_step_args (include/gm_hip.h): gm_vq_step's arguments as one block."""
+    _fields_ = [("ze", ctypes.c_void_p), ("ldz", ctypes.c_int64), ("codes", ctypes.c_void_p), ("ldc", ctypes.c_int64),
+                ("E", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("grad", ctypes.c_void_p),
+                ("nk", ctypes.c_void_p), ("usage", ctypes.c_void_p), ("sched", ctypes.c_void_p),
+                ("sched_slot", _lib.Slot), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("B", ctypes.c_int), ("N", ctypes.c_int),
+                ("D", ctypes.c_int), ("K", ctypes.c_int)]
+
+
+def vq_fused_sizes(N, D, K):
+    """True iff (num_vars, code_dim, num_codes) fit the quantisation kernels (the GM_VQ_* limits)."""
+    return (N >= 1 and _lib.VQ_MIN_D <= D <= _lib.VQ_MAX_D and D % 4 == 0 and N * D <= _lib.VQ_MAX_ND
+            and _lib.VQ_MIN_K <= K <= _lib.VQ_MAX_K and K * D <= _lib.VQ_MAX_KD)
+
+
+def _vq_rows(t, name, rows, width, dtype=torch.float32):
+    if not (t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= rows
+            and t.shape[1] >= width):
+        raise _lib.GMError("%s must be a %s device tensor of at least [%d, %d] with unit column stride (got %s %s on %s)"
+                           % (name, dtype, rows, width, t.dtype, tuple(t.shape), t.device))
+    return t
+
+
+def _vq_vec(t, name, n, dtype=torch.float32):
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() >= n):
+        raise _lib.GMError("%s must be a contiguous %s device tensor of at least %d elements" % (name, dtype, n))
+    return t
+
+
+def _vq_common(ze, E, codes, beta, B, N, D):
+    K = E.shape[0]
+    a = VqArgs()
+    _vq_rows(ze, "ze", B, N * D), _vq_rows(E, "E", K, D), _vq_rows(codes, "codes", B, N, torch.int32)
+    a.ze, a.ldz, a.E, a.lde, a.codes, a.ldc = ze.data_ptr(), _ld(ze), E.data_ptr(), _ld(E), codes.data_ptr(), _ld(codes)
+    a.beta, a.B, a.N, a.D, a.K = float(beta), B, N, D, K
+    return a
+
+
+def vq_quantise(ze, E, zq, codes, qerr, lp, beta, B, N, D, stream=None):
+    """z_q [B, N D] = E[codes], codes [B, N] int32 (the nearest code of each variable, the lowest index on a tie), qerr
+    [B] and lp [B] = -(1 + beta) qerr from ze [B, N D] and the codebook E [K, D] (gm_vq_quantise)."""
+    a = _vq_common(ze, E, codes, beta, B, N, D)
+    _vq_rows(zq, "zq", B, N * D), _vq_vec(qerr, "qerr", B), _vq_vec(lp, "lp", B)
+    a.zq, a.ldq, a.qerr, a.lp = zq.data_ptr(), _ld(zq), qerr.data_ptr(), lp.data_ptr()
+    _lib.call("gm_vq_quantise", stream or stream_ptr(), ctypes.byref(a))
+
+
+def vq_reduce(ze, E, codes, dzdec, wn, dml, beta, B, N, D, stream=None):
+    """dml [B, N D] = dzdec + 2 beta wn (ze - E[codes]) (gm_vq_reduce): the decoder's input gradient straight through
+    plus the commitment term."""
+    a = _vq_common(ze, E, codes, beta, B, N, D)
+    _vq_rows(dzdec, "dzdec", B, N * D), _vq_rows(dml, "dml", B, N * D), _vq_vec(wn, "wn", B)
+    a.dzdec, a.lddz, a.wn, a.dml, a.lddml = dzdec.data_ptr(), _ld(dzdec), wn.data_ptr(), dml.data_ptr(), _ld(dml)
+    _lib.call("gm_vq_reduce", stream or stream_ptr(), ctypes.byref(a))
+
+
+def vq_step(ze, codes, E, B, N, D, moments=None, sched=None, sched_slot=NO_SLOT, grad=None, nk=None, usage=None,
+            betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, stream=None):
+    """The codebook's step (gm_vq_step): n_k and s_k of the batch's codes [B, N] and ze [B, N D] in a fixed order, the
+    gradient 2 (n_k E_k - s_k) (-> grad [K, D] when given), n_k (-> nk [K] int32; added to usage [K] int32) and, with
+    sched and moments = (m, v), one Adam step on E [K, D] at the schedule's slot.  E, the moments and grad are
+    contiguous."""
+    K = E.shape[0]
+    _vq_rows(ze, "ze", B, N * D), _vq_rows(codes, "codes", B, N, torch.int32)
+    a = VqStepArgs()
+    a.ze, a.ldz, a.codes, a.ldc = ze.data_ptr(), _ld(ze), codes.data_ptr(), _ld(codes)
+    if tuple(E.shape) != (K, D):
+        raise _lib.GMError("vq_step: E must be [K, %d], got %s" % (D, tuple(E.shape)))
+    a.E = _vq_vec(E, "E", K * D).data_ptr()
+    if sched is not None:
+        if moments is None or len(moments) != 2:
+            raise _lib.GMError("vq_step: an Adam step needs moments = (m, v)")
+        a.m, a.v = (_vq_vec(t, "moment", K * D).data_ptr() for t in moments)
+        a.sched, a.sched_slot = _vq_vec(sched, "sched", 2).data_ptr(), sched_slot
+    if grad is not None:
+        a.grad = _vq_vec(grad, "grad", K * D).data_ptr()
+    if nk is not None:
+        a.nk = _vq_vec(nk, "nk", K, torch.int32).data_ptr()
+    if usage is not None:
+        a.usage = _vq_vec(usage, "usage", K, torch.int32).data_ptr()
+    a.beta1, a.beta2, a.eps, a.weight_decay = betas[0], betas[1], eps, weight_decay
+    a.B, a.N, a.D, a.K = B, N, D, K
+    _lib.call("gm_vq_step", stream or stream_ptr(), ctypes.byref(a))
+
+
 # ---- Denoising diffusion (csrc/gm_ddpm.hip, gm_ddpm.h; ddpm.py) ----------------------------------------------------
 class DdpmNoise(ctypes.Structure):
     """gm_ddpm_noise (include/gm_hip.h): seed, the two tags, the step and the first row's batch position."""

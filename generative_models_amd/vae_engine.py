@@ -1100,6 +1100,80 @@ class CatVAEEngine(IWAEEngine):
                        tau_slot=adam["sched_slot"], stream=st)
 
 
+class VQVAEEngine(IWAEEngine):
+    """The vector-quantised VAE (vqvae.py holds the contract): IWAEEngine's 12-launch batch at k = 1 with the `embed`
+    layer (width N D) as the encoder's head, launch 3 replaced by gm_vq_quantise (z_q = the nearest codebook rows, the
+    codes, qerr and lp = -(1 + beta) qerr; nothing is drawn) and launch 10 by gm_vq_reduce (d loss / d z_e: the decoder's
+    input gradient straight through plus the commitment term), and gm_vq_step (n_k, s_k, the codebook's gradient and
+    Adam at the batch's schedule slot) behind gm_vq_reduce, which is the last reader of the codebook: 13 launches.  The
+    finalize block sums -log w (-> `recon`) and qerr (-> `kl`), scale 1.  The codebook, its gradient and its moments are
+    views of the engine's flat buffers like every other parameter.  Training and validation write separate `codes`
+    buffers; `usage` [K] counts the epoch's assignments (run_pass zeroes it before a training pass, gm_vq_step adds to
+    it, so a replayed graph needs no host update).  One GPU only."""
+
+    one_gpu = "the VQ-VAE engine"
+
+    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
+                 trainer=None):
+        self._refuse_dp(world_size, force_dp)
+        self.N, self.D, self.K = int(model.num_vars), int(model.code_dim), int(model.num_codes)
+        super().__init__(model, device, use_graph=use_graph, trainer=trainer)
+        fp, cb = self.fp, model.codebook.weight
+        i = [j for j, p in enumerate(fp.params) if p is cb][0]
+        seg = lambda buf: buf[fp.offsets[i]:fp.offsets[i] + cb.numel()]
+        self.CB, self.CBgrad, self.CBmoments = fp.views[i], seg(fp.grad), (seg(fp.m), seg(fp.v))
+        self.nk = torch.zeros(self.K, dtype=torch.int32, device=device)
+        self.usage = torch.zeros(self.K, dtype=torch.int32, device=device)
+
+    def _check_limits(self, model, k):
+        from . import ops_fused as of_
+        if k != 1 or not of_.vq_fused_sizes(self.N, self.D, self.K):
+            raise GMError("VQVAEEngine: k = 1 and (num_vars, code_dim, num_codes) inside the quantisation kernels' limits "
+                          "(got k=%d, %d, %d, %d); VQVAETrainer trains these on the general path"
+                          % (k, self.N, self.D, self.K))
+
+    def _head(self, enc):
+        return (enc.embed.weight,), (enc.embed.bias,), enc.embed.weight.shape[0]
+
+    def _extra_params(self, model):
+        return [model.codebook.weight]
+
+    def _alloc(self, B):
+        if self._bufB == B:
+            return
+        super()._alloc(B)
+        self.qerr = torch.zeros(B, device=self.device)
+        self.codes_train = torch.zeros(B, self.N, dtype=torch.int32, device=self.device)
+        self.codes_val = torch.zeros(B, self.N, dtype=torch.int32, device=self.device)
+
+    def _settings(self):
+        return dict(num_vars=self.N, code_dim=self.D, num_codes=self.K, beta=float(self.trainer.beta))
+
+    def _noise(self, t, train):
+        return None                                  # nothing is drawn
+
+    def run_pass(self, data, perm, train, t0):
+        if train:
+            self.usage.zero_()
+        return super().run_pass(data, perm, train, t0)
+
+    def _second_sum(self, b):
+        return self.qerr, 1.0
+
+    def _sample(self, st, nz, b, t=0, train=True):
+        from . import ops_fused as of_
+        of_.vq_quantise(self.ml, self.CB, self.Zs, self.codes_train if train else self.codes_val, self.qerr, self.lp,
+                        self.trainer.beta, b, self.N, self.D, stream=st)
+
+    def _reduce(self, st, nz, b, adam):
+        from . import ops_fused as of_
+        of_.vq_reduce(self.ml, self.CB, self.codes_train, self.dzdec, self.wn, self.dml, self.trainer.beta, b, self.N,
+                      self.D, stream=st)
+        of_.vq_step(self.ml, self.codes_train, self.CB, b, self.N, self.D, moments=self.CBmoments, sched=adam["sched"],
+                    sched_slot=adam["sched_slot"], grad=self.CBgrad, nk=self.nk, usage=self.usage,
+                    weight_decay=self.wd, stream=st)
+
+
 def aae_fused_ok(model):
     """True iff an AAE's shapes fit the fused kernels (gm_aae.hip): 1 <= Z <= 32 with Z % 4 == 0, hidden width <= 512,
     the decoder's and the discriminator's hidden widths equal to the encoder's, one discriminator output."""

@@ -1362,6 +1362,57 @@ int gm_rbm_transpose(void* stream, const float* W, int64_t ldw, float* WT, int64
 int gm_rbm_uniform(void* stream, float* u, int64_t ldu, uint64_t seed, uint32_t tag, const int64_t* step_ctr,
                    const int64_t* step_base, int64_t step_add, int64_t row0, int64_t rows, int width);
 
+/* ---- Vector quantisation of the VQ-VAE (csrc/gm_vq.hip; vqvae.py holds the contract).  N
+ * variables of D floats per row, a codebook E [K, D].  Per row and variable n: c_n = argmin_k sum_d (z_e,n,d - E_k,d)^2,
+ * the lowest index winning a tie, 0 when no distance compares less (NaN); z_q = E[c]; qerr = sum_n ||z_e,n - E_c_n||^2
+ * from the direct differences; lp = -(1 + beta) qerr.
+ * Limits: 4 <= D <= 64 with D % 4 == 0, N D <= 1024, 2 <= K <= 1024, K D <= 16384 (the codebook in 64 KB of LDS);
+ * outside them, or with a NULL or aliased array, the entry points return GM_EINVAL before any launch.  No floating-point
+ * atomics, fixed orders: the same bits on every run, and a row's outputs do not depend on where the row lands. */
+#define GM_VQ_MIN_D 4
+#define GM_VQ_MAX_D 64
+#define GM_VQ_MAX_ND 1024
+#define GM_VQ_MIN_K 2
+#define GM_VQ_MAX_K 1024
+#define GM_VQ_MAX_KD 16384
+typedef struct gm_vq_args {
+    const float* ze; int64_t ldz;             /* [B, N D]: the encoder's output */
+    const float* E; int64_t lde;              /* [K, D]: the codebook */
+    int32_t* codes; int64_t ldc;              /* [B, N]: written by gm_vq_quantise, read by gm_vq_reduce */
+    float beta;                               /* the commitment cost: finite, >= 0 */
+    int B, N, D, K;
+    /* gm_vq_quantise */
+    float* zq; int64_t ldq;                   /* [B, N D] = E[codes]: the decoder's input */
+    float* qerr;                              /* [B] */
+    float* lp;                                /* [B] = -(1 + beta) qerr */
+    /* gm_vq_reduce */
+    const float* dzdec; int64_t lddz;         /* [B, N D]: d loss / d z_q */
+    const float* wn;                          /* [B]: -d loss / d lp (1 at k = 1) */
+    float* dml; int64_t lddml;                /* [B, N D], every element written */
+} gm_vq_args;
+/* One wave per row, the codebook in LDS: lanes are (variable slot, share of the K codes); the search compares the direct
+ * squared distances, each summed over d ascending. */
+int gm_vq_quantise(void* stream, const gm_vq_args* a);
+/* dml = dzdec + 2 beta wn (z_e - E[codes]): the decoder's input gradient passed straight through, plus the commitment
+ * term.  A code outside [0, K) is clamped into it before E is read. */
+int gm_vq_reduce(void* stream, const gm_vq_args* a);
+typedef struct gm_vq_step_args {
+    const float* ze; int64_t ldz;             /* [B, N D] */
+    const int32_t* codes; int64_t ldc;        /* [B, N] */
+    float* E; float* m; float* v;             /* [K, D] contiguous: the codebook, stepped in place, and its Adam moments */
+    float* grad;                              /* [K, D] or NULL: d loss / d E = 2 (n_k E_k - s_k), before weight decay */
+    int32_t* nk;                              /* [K] or NULL: n_k, the (row, variable) pairs assigned to code k */
+    int32_t* usage;                           /* [K] or NULL: n_k is added to it (one plain integer add per code) */
+    const float* sched;                       /* [steps, 2] (gm_adam's), or NULL: gradient and counts only, E untouched */
+    gm_slot sched_slot;
+    double beta1, beta2, eps, weight_decay;
+    int B, N, D, K;
+} gm_vq_step_args;
+/* One 256-thread workgroup per code: wave w scans quarter w of the B N codes (pair b N + n ascending) and adds the
+ * matching rows of z_e in that order; the four partial sums are combined ((0 + 1) + 2) + 3.  The order depends on (B, N)
+ * alone.  Then gm_adam's step on E_k at the schedule's slot.  Launch it behind the last reader of E. */
+int gm_vq_step(void* stream, const gm_vq_step_args* a);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

@@ -216,6 +216,13 @@ class StageSeg(ctypes.Structure):
                 ("src_block_stride", c_int64), ("dst_block_stride", c_int64)]
 
 
+# gm_linear_plan (include/gm_hip.h): modes, kernel families, and the plan's fields in GM_PLAN_F_* order
+PLAN_MODE = {"fwd": 0, "dx": 1, "dw": 2}
+PLAN_FAMILY = {1: "lds", 2: "k32", 3: "split", 4: "riding"}
+PLAN_FIELDS = ("family", "mode", "mi", "ni", "lds_cfg", "lds_stages", "vec", "xv", "vec_epi", "dma", "slots", "launches",
+               "grid_x", "grid_y", "block")
+PLAN_INTS = 16                                              # GM_PLAN_FIELDS
+
 DRAW_SAMPLER, DRAW_NORMAL, DRAW_UNIFORM, DRAW_INFO = 0, 1, 2, 3
 GM_EUNSUPPORTED = -10002
 
@@ -237,6 +244,7 @@ _SIGNATURES = {
     "gm_linear_fwd_ex": (c_int, [_P, POINTER(FwdArgs)]),
     "gm_linear_bwd_dx_ex": (c_int, [_P, POINTER(DxArgs)]),
     "gm_linear_bwd_dw_ex": (c_int, [_P, POINTER(DwAdamArgs), POINTER(DwAdamArgs), POINTER(DwTail)]),
+    "gm_linear_plan": (c_int, [c_int, _P, POINTER(c_int32)]),
     "gm_gan_loss": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, POINTER(c_float), c_int,
                             c_float, _P, Slot, _P, _P, _P, _P]),
     "gm_gan_loss_phase": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, POINTER(c_float), c_int,

@@ -782,6 +782,42 @@ inline int lds_pick_cfg(int M, int N) {
     return pick;
 }
 
+// ---- launch-plan query (gm_linear_plan, gm_hip.h).  While plan_rec points at a plan on this thread, every launch site
+// of this file's host side RECORDS what it would launch -- from the template arguments it names -- instead of launching,
+// and GM_GEMM_RET returns without asking the runtime: the query is the dispatch itself, run dry.  The launch path pays
+// one test of a thread-local pointer per launch.
+thread_local int32_t* plan_rec = nullptr;
+
+inline void plan_launch(dim3 grid, dim3 block) {
+    plan_rec[GM_PLAN_F_LAUNCHES] += 1;
+    plan_rec[GM_PLAN_F_GRID_X] = (int32_t)grid.x; plan_rec[GM_PLAN_F_GRID_Y] = (int32_t)grid.y;
+    plan_rec[GM_PLAN_F_BLOCK] = (int32_t)block.x;
+    if (!plan_rec[GM_PLAN_F_FAMILY]) plan_rec[GM_PLAN_F_FAMILY] = GM_PLAN_RIDING;   // (a plain site names its family first)
+}
+inline void plan_kernel(int family, int mode, int mi, int ni, int lds_cfg, int lds_stages, bool vec, bool xv, int vec_epi,
+                        bool dma, bool slots) {
+    int32_t* r = plan_rec;
+    r[GM_PLAN_F_FAMILY] = family; r[GM_PLAN_F_MODE] = mode; r[GM_PLAN_F_MI] = mi; r[GM_PLAN_F_NI] = ni;
+    r[GM_PLAN_F_LDS_CFG] = lds_cfg; r[GM_PLAN_F_LDS_STAGES] = lds_stages; r[GM_PLAN_F_VEC] = vec; r[GM_PLAN_F_XV] = xv;
+    r[GM_PLAN_F_VEC_EPI] = vec_epi; r[GM_PLAN_F_DMA] = dma; r[GM_PLAN_F_SLOTS] = slots;
+}
+// hipLaunchKernelGGL, or its record; GM_LAUNCH_AS: a plain launch site, NOTE = the plan_kernel call that describes KERNEL
+#define GM_LAUNCH(KERNEL, GRID, BLOCK, ...)                                         \
+    do {                                                                            \
+        if (plan_rec) plan_launch(GRID, BLOCK);                                     \
+        else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, __VA_ARGS__);                  \
+    } while (0)
+#define GM_LAUNCH_AS(NOTE, KERNEL, GRID, BLOCK, ...)                                \
+    do {                                                                            \
+        if (plan_rec) { NOTE; plan_launch(GRID, BLOCK); }                           \
+        else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, __VA_ARGS__);                  \
+    } while (0)
+#define GM_GEMM_RET()                                                               \
+    do {                                                                            \
+        if (plan_rec) return 0;                                                     \
+        GM_LAUNCH_RET();                                                            \
+    } while (0)
+
 template <int MODE, int BM, int BN, int WTM, int WTN, int WK, int KU, int PD>
 int launch_lds_cfg(hipStream_t s, GemmP p) {
     using C = LdsCfg<MODE, BM, BN, WTM, WTN, WK, KU>;
@@ -792,10 +828,14 @@ int launch_lds_cfg(hipStream_t s, GemmP p) {
     // hidden widths); anything else takes the runtime loop
     constexpr int NS784 = (784 + C::BK - 1) / C::BK, NS400 = (400 + C::BK - 1) / C::BK;
     const int S = (p.K + C::BK - 1) / C::BK;
-    if (S == NS784) hipLaunchKernelGGL((gemm_lds_kernel<MODE, BM, BN, WTM, WTN, WK, KU, PD, NS784>), grid, block, 0, s, p);
-    else if (S == NS400) hipLaunchKernelGGL((gemm_lds_kernel<MODE, BM, BN, WTM, WTN, WK, KU, PD, NS400>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm_lds_kernel<MODE, BM, BN, WTM, WTN, WK, KU, PD, 0>), grid, block, 0, s, p);
-    GM_LAUNCH_RET();
+#define GM_LLDS(NS_)                                                                                                  \
+    GM_LAUNCH_AS(plan_kernel(GM_PLAN_LDS, MODE, 0, 0, BM == 64 ? 1 : 2, NS_, true, MODE == MODE_DX, p.vec_epi, false, false), \
+                 (gemm_lds_kernel<MODE, BM, BN, WTM, WTN, WK, KU, PD, NS_>), grid, block, 0, s, p)
+    if (S == NS784) GM_LLDS(NS784);
+    else if (S == NS400) GM_LLDS(NS400);
+    else GM_LLDS(0);
+#undef GM_LLDS
+    GM_GEMM_RET();
 }
 
 // Tile configuration of the LDS kernel for this forward / input-gradient launch, or 0 when the launch is not for it
@@ -2002,9 +2042,9 @@ struct Rider {
 inline void launch_gather_alone(hipStream_t s, const Rider& r) {
     const GatherP& gp = *r.gather;
     if (r.corrupt)
-        hipLaunchKernelGGL(gather_rows_corrupt_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp, *r.corrupt);
+        GM_LAUNCH(gather_rows_corrupt_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp, *r.corrupt);
     else
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp);
+        GM_LAUNCH(gather_rows_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp);
 }
 
 // Tile shapes of the 16-wave kernels, as sub-tiles (16 x 16) per wave: MI x NI
@@ -2090,8 +2130,8 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
                 return GM_EINVAL;
             }
             const dim3 bgrid((p.N + 31) / 32, (p.M + 31) / 32);
-            hipLaunchKernelGGL(gemm16_fwd_bits_kernel, bgrid, dim3(1024), 0, s, p);
-            GM_LAUNCH_RET();
+            GM_LAUNCH(gemm16_fwd_bits_kernel, bgrid, dim3(1024), 0, s, p);
+            GM_GEMM_RET();
         } else if constexpr (MODE == MODE_DW) {
             if (!head || !folded || head->fold.enabled != 1 || !xv || p.ones_from > 0 || rider.pair) {
                 gm_set_error("bit-packed rows: the weight gradient needs the folded head of a separable loss and "
@@ -2102,9 +2142,9 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
             const dim3 bgrid((p.N + 47) / 48, (p.M + 31) / 32);
             const int hblocks = gm_head_bwd_blocks(*head);
             const int hrows = (hblocks + (int)bgrid.x - 1) / (int)bgrid.x;
-            hipLaunchKernelGGL(gemm16_dw_head_bits_kernel, dim3(bgrid.x, bgrid.y + hrows), dim3(1024), 0, s, p, *head,
+            GM_LAUNCH(gemm16_dw_head_bits_kernel, dim3(bgrid.x, bgrid.y + hrows), dim3(1024), 0, s, p, *head,
                                hrows, hblocks);
-            GM_LAUNCH_RET();
+            GM_GEMM_RET();
         } else {
             gm_set_error("bit-packed rows: forward and weight gradient only");
             return GM_EINVAL;
@@ -2116,7 +2156,7 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
         if (!rider.pair && !folded && !p.hd_part && !p.sq_part && !slots) {
             const int cfg = lds_cfg_for<MODE>(p, vec, xv);
             if (cfg) {
-                if (head) hipLaunchKernelGGL(head_bwd_kernel, dim3(gm_head_bwd_blocks(*head)), dim3(1024), 0, s, *head);
+                if (head) GM_LAUNCH(head_bwd_kernel, dim3(gm_head_bwd_blocks(*head)), dim3(1024), 0, s, *head);
                 if (rider.gather) launch_gather_alone(s, rider);
                 return launch_lds<MODE>(s, p, cfg);
             }
@@ -2128,20 +2168,24 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
             const dim3 kgrid((p.N + 63) / 64, (p.M + 31) / 32);
             if (rider.gather && rider.corrupt) {                 // the corrupting gather is not compiled into this kernel
                 launch_gather_alone(s, rider);
-                if (slots) hipLaunchKernelGGL((gemm16_k32_fwd_kernel<true, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0);
-                else hipLaunchKernelGGL((gemm16_k32_fwd_kernel<false, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0);
+                if (slots) GM_LAUNCH((gemm16_k32_fwd_kernel<true, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0);
+                else GM_LAUNCH((gemm16_k32_fwd_kernel<false, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0);
             } else if (rider.gather) {
                 const GatherP& gp = *rider.gather;
                 const int gblocks = gm_gather_blocks(gp, 4);
                 const int grows = (gblocks + (int)kgrid.x - 1) / (int)kgrid.x;
                 const dim3 ggrid(kgrid.x, kgrid.y + grows);
-                if (slots) hipLaunchKernelGGL((gemm16_k32_fwd_kernel<true, true>), ggrid, dim3(256), 0, s, p, gp, grows, gblocks);
-                else hipLaunchKernelGGL((gemm16_k32_fwd_kernel<false, true>), ggrid, dim3(256), 0, s, p, gp, grows, gblocks);
+                if (slots) GM_LAUNCH((gemm16_k32_fwd_kernel<true, true>), ggrid, dim3(256), 0, s, p, gp, grows, gblocks);
+                else GM_LAUNCH((gemm16_k32_fwd_kernel<false, true>), ggrid, dim3(256), 0, s, p, gp, grows, gblocks);
             } else {
-                if (slots) hipLaunchKernelGGL((gemm16_k32_fwd_kernel<true, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0);
-                else hipLaunchKernelGGL((gemm16_k32_fwd_kernel<false, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0);
+#define GM_LK32(SL_)                                                                                             \
+    GM_LAUNCH_AS(plan_kernel(GM_PLAN_K32, MODE, 0, 0, 0, 0, true, false, p.vec_epi, false, SL_),                \
+                 (gemm16_k32_fwd_kernel<SL_, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0)
+                if (slots) GM_LK32(true);
+                else GM_LK32(false);
+#undef GM_LK32
             }
-            GM_LAUNCH_RET();
+            GM_GEMM_RET();
         }
     }
     const int tile = pick_tile<MODE>(p);
@@ -2159,7 +2203,7 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
             // template arguments: VEC (a k-contiguous notion: false), G, XV, MI, NI, OF (ones column with a row offset:
             // WGAN-GP's stacked gradient), FOLDED, DMA
 #define GM_LH(X, OFV, FD) GM_TILE_SWITCH(tile, p.dma && (X), GM_LH1_##X##_##OFV##_##FD)
-#define GM_LHK(X, OFV, FD, MI_, NI_, D_) hipLaunchKernelGGL((gemm16_dw_head_kernel<false, 1, X, MI_, NI_, OFV, FD, ((X) && (D_))>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks)
+#define GM_LHK(X, OFV, FD, MI_, NI_, D_) GM_LAUNCH((gemm16_dw_head_kernel<false, 1, X, MI_, NI_, OFV, FD, ((X) && (D_))>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks)
 #define GM_LH1_true_false_true(MI_, NI_, D_) GM_LHK(true, false, true, MI_, NI_, D_)
 #define GM_LH1_true_true_false(MI_, NI_, D_) GM_LHK(true, true, false, MI_, NI_, D_)
 #define GM_LH1_true_false_false(MI_, NI_, D_) GM_LHK(true, false, false, MI_, NI_, D_)
@@ -2169,7 +2213,7 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
                 // RaGAN / Fisher: operands through registers (the two-phase prologue's scratch and the DMA form's
                 // chunk buffers would share LDS)
                 p.dma = false;
-#define GM_LHTP(MI_, NI_, D_) hipLaunchKernelGGL((gemm16_dw_head_tp_kernel<MI_, NI_>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks)
+#define GM_LHTP(MI_, NI_, D_) GM_LAUNCH((gemm16_dw_head_tp_kernel<MI_, NI_>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks)
                 GM_TILE_SWITCH(tile, false, GM_LHTP);
 #undef GM_LHTP
             } else if (folded) GM_LH(true, false, true);
@@ -2182,7 +2226,7 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
 #undef GM_LH1_true_false_true
 #undef GM_LHK
 #undef GM_LH
-            GM_LAUNCH_RET();
+            GM_GEMM_RET();
         }
     }
     if constexpr (MODE == MODE_DX) {
@@ -2191,13 +2235,13 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
             const int hrows = (hblocks + (int)grid.x - 1) / (int)grid.x;
             const dim3 hgrid(grid.x, grid.y + hrows);
             if (tile == T12) {
-                if (folded) hipLaunchKernelGGL((gemm16_dx_head_kernel<1, 1, 2, true>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
-                else hipLaunchKernelGGL((gemm16_dx_head_kernel<1, 1, 2, false>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
+                if (folded) GM_LAUNCH((gemm16_dx_head_kernel<1, 1, 2, true>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
+                else GM_LAUNCH((gemm16_dx_head_kernel<1, 1, 2, false>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
             } else {
-                if (folded) hipLaunchKernelGGL((gemm16_dx_head_kernel<1, 2, 2, true>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
-                else hipLaunchKernelGGL((gemm16_dx_head_kernel<1, 2, 2, false>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
+                if (folded) GM_LAUNCH((gemm16_dx_head_kernel<1, 2, 2, true>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
+                else GM_LAUNCH((gemm16_dx_head_kernel<1, 2, 2, false>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
             }
-            GM_LAUNCH_RET();
+            GM_GEMM_RET();
         }
     }
     if (folded) {
@@ -2206,7 +2250,7 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
         return GM_EINVAL;
     }
     if (head)        // this configuration cannot carry the head workgroups: separate launch
-        hipLaunchKernelGGL(head_bwd_kernel, dim3(gm_head_bwd_blocks(*head)), dim3(1024), 0, s, *head);
+        GM_LAUNCH(head_bwd_kernel, dim3(gm_head_bwd_blocks(*head)), dim3(1024), 0, s, *head);
     if constexpr (MODE == MODE_DX) {
         if (rider.gather) {
             const GatherP& gp = *rider.gather;
@@ -2214,11 +2258,11 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
                 const int gblocks = gm_gather_blocks(gp, 16);
                 const int grows = (gblocks + (int)grid.x - 1) / (int)grid.x;
                 const dim3 ggrid(grid.x, grid.y + grows);
-                if (tile == T12) hipLaunchKernelGGL((gemm16_dx_gather_kernel<true, true, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
-                else hipLaunchKernelGGL((gemm16_dx_gather_kernel<true, true, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
-                GM_LAUNCH_RET();
+                if (tile == T12) GM_LAUNCH((gemm16_dx_gather_kernel<true, true, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
+                else GM_LAUNCH((gemm16_dx_gather_kernel<true, true, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
+                GM_GEMM_RET();
             }
-            hipLaunchKernelGGL(gather_rows_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp);
+            GM_LAUNCH(gather_rows_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp);
         }
     }
     if constexpr (MODE == MODE_FWD) {
@@ -2230,13 +2274,13 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
                 const dim3 ggrid(grid.x, grid.y + grows);
                 if (rider.corrupt) {
                     const CorruptP& cp = *rider.corrupt;
-                    if (tile == T12) hipLaunchKernelGGL((gemm16_fwd_gather_corrupt_kernel<true, 1, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, cp, grows, gblocks);
-                    else hipLaunchKernelGGL((gemm16_fwd_gather_corrupt_kernel<true, 1, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, cp, grows, gblocks);
-                    GM_LAUNCH_RET();
+                    if (tile == T12) GM_LAUNCH((gemm16_fwd_gather_corrupt_kernel<true, 1, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, cp, grows, gblocks);
+                    else GM_LAUNCH((gemm16_fwd_gather_corrupt_kernel<true, 1, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, cp, grows, gblocks);
+                    GM_GEMM_RET();
                 }
-                if (tile == T12) hipLaunchKernelGGL((gemm16_fwd_gather_kernel<true, 1, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
-                else hipLaunchKernelGGL((gemm16_fwd_gather_kernel<true, 1, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
-                GM_LAUNCH_RET();
+                if (tile == T12) GM_LAUNCH((gemm16_fwd_gather_kernel<true, 1, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
+                else GM_LAUNCH((gemm16_fwd_gather_kernel<true, 1, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
+                GM_GEMM_RET();
             }
             launch_gather_alone(s, rider);
         }
@@ -2274,19 +2318,19 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
                 const int tna = (int)grid.x, na = (int)(grid.x * grid.y);
                 if (l1_rides) {
                     const dim3 lgrid(na + (pb.M + 15) / 16);
-#define GM_LL1(MI_, NI_, D_) hipLaunchKernelGGL((gemm16_dw_pair_l1_kernel<MI_, NI_>), lgrid, dim3(1024), 0, s, p, pb, na, tna, *rider.l1)
+#define GM_LL1(MI_, NI_, D_) GM_LAUNCH((gemm16_dw_pair_l1_kernel<MI_, NI_>), lgrid, dim3(1024), 0, s, p, pb, na, tna, *rider.l1)
                     GM_TILE_SWITCH(tile, false, GM_LL1);
 #undef GM_LL1
-                    GM_LAUNCH_RET();
+                    GM_GEMM_RET();
                 }
                 const int tnb = (pb.N + 16 * ni - 1) / (16 * ni), tmb = (pb.M + 16 * mi - 1) / (16 * mi);
                 const dim3 pgrid(na + tnb * tmb);
                 const bool sl_b = has_slot(pb.a_slot) || has_slot(pb.b_slot);
 #define GM_LP2(K_, GRID_, MI_, NI_, D_, ...)                                                                              \
     do {                                                                                                                  \
-        if (slots) hipLaunchKernelGGL((K_<1, true, MI_, NI_, D_, true, true>), GRID_, dim3(1024), 0, s, __VA_ARGS__);     \
-        else if (sl_b) hipLaunchKernelGGL((K_<1, true, MI_, NI_, D_, false, true>), GRID_, dim3(1024), 0, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL((K_<1, true, MI_, NI_, D_, false, false>), GRID_, dim3(1024), 0, s, __VA_ARGS__);         \
+        if (slots) GM_LAUNCH((K_<1, true, MI_, NI_, D_, true, true>), GRID_, dim3(1024), 0, s, __VA_ARGS__);     \
+        else if (sl_b) GM_LAUNCH((K_<1, true, MI_, NI_, D_, false, true>), GRID_, dim3(1024), 0, s, __VA_ARGS__); \
+        else GM_LAUNCH((K_<1, true, MI_, NI_, D_, false, false>), GRID_, dim3(1024), 0, s, __VA_ARGS__);         \
     } while (0)
 #define GM_LP(MI_, NI_, D_) GM_LP2(gemm16_dw_pair_kernel, pgrid, MI_, NI_, D_, p, pb, na, tna, tnb)
 #define GM_LPF(MI_, NI_, D_) GM_LP2(gemm16_dw_pair_fin_kernel, dim3(pgrid.x + 1), MI_, NI_, D_, p, pb, na, tna, tnb, *rider.fin)
@@ -2295,7 +2339,7 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
 #undef GM_LP2
 #undef GM_LPF
 #undef GM_LP
-                GM_LAUNCH_RET();
+                GM_GEMM_RET();
             }
             // not pairable in this configuration: the second GEMM gets its own launch afterwards (and the sums theirs)
             Rider none;
@@ -2304,18 +2348,20 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
             rc = launch<MODE_DW>(s, pb, false, rider.pair_xvec, none);
             if (rc || !rider.fin) return rc;
             const gm_fin2& f = *rider.fin;
+            if (plan_rec) { gm_set_error("launch-plan query: the pair's loss sums are not reported"); return GM_EUNSUPPORTED; }
             return gm_sum_finalize2_tick(s, f.pa, f.na, f.sa, f.oa, f.slot_a, f.pb, f.nb, f.sb, f.ob, f.slot_b, f.tick);
         }
     }
     // template arguments: MODE, VEC, waves, G, XV, MI, NI, DMA
     // (ring slots exist on the batch-row operand of forward and weight-gradient launches only: gm_hip.h)
     if (MODE == MODE_DX && slots) { gm_set_error("ring slots: forward and weight-gradient operands only"); return GM_EINVAL; }
+#define GM_L16K1(V, X, MI_, NI_, DMA_, SL_)                                                                                  \
+    GM_LAUNCH_AS(plan_kernel(GM_PLAN_SPLIT, MODE, MI_, NI_, 0, 0, V, X, p.vec_epi, DMA_, SL_),                               \
+                 (gemm16_kernel<MODE, V, 16, 1, X, MI_, NI_, DMA_, SL_>), grid, dim3(1024), 0, s, p)
 #define GM_L16K(V, X, MI_, NI_, D_)                                                                                          \
     do {                                                                                                                     \
-        if (MODE != MODE_DX && slots)                                                                                        \
-            hipLaunchKernelGGL((gemm16_kernel<MODE, V, 16, 1, X, MI_, NI_, (MODE == MODE_DW && (X) && (D_)), MODE != MODE_DX>), grid, dim3(1024), 0, s, p); \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((gemm16_kernel<MODE, V, 16, 1, X, MI_, NI_, (MODE == MODE_DW && (X) && (D_)), false>), grid, dim3(1024), 0, s, p); \
+        if (MODE != MODE_DX && slots) GM_L16K1(V, X, MI_, NI_, (MODE == MODE_DW && (X) && (D_)), (MODE != MODE_DX));          \
+        else GM_L16K1(V, X, MI_, NI_, (MODE == MODE_DW && (X) && (D_)), false);                                              \
     } while (0)
 #define GM_L16_tt(MI_, NI_, D_) GM_L16K(true, true, MI_, NI_, D_)
 #define GM_L16_tf(MI_, NI_, D_) GM_L16K(true, false, MI_, NI_, D_)
@@ -2328,7 +2374,8 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
 #undef GM_L16_tf
 #undef GM_L16_tt
 #undef GM_L16K
-    GM_LAUNCH_RET();
+#undef GM_L16K1
+    GM_GEMM_RET();
 }
 
 inline gm_slot no_slot() { gm_slot z; z.ctr = nullptr; z.mul = 0; z.add = 0; z.ring = 0; z.stride = 0; return z; }
@@ -2442,12 +2489,12 @@ static int fwd_label_launch(hipStream_t s, const GemmP& p, bool vec) {
     const dim3 grid((p.N + 16 * tile_ni(tile) - 1) / (16 * tile_ni(tile)), (p.M + 16 * tile_mi(tile) - 1) / (16 * tile_mi(tile)));
 #define GM_LBL(MI_, NI_, D_)                                                                                \
     do {                                                                                                    \
-        if (vec) hipLaunchKernelGGL((gemm16_fwd_label_kernel<true, MI_, NI_>), grid, dim3(1024), 0, s, p);  \
-        else hipLaunchKernelGGL((gemm16_fwd_label_kernel<false, MI_, NI_>), grid, dim3(1024), 0, s, p);     \
+        if (vec) GM_LAUNCH((gemm16_fwd_label_kernel<true, MI_, NI_>), grid, dim3(1024), 0, s, p);  \
+        else GM_LAUNCH((gemm16_fwd_label_kernel<false, MI_, NI_>), grid, dim3(1024), 0, s, p);     \
     } while (0)
     GM_TILE_SWITCH(tile, false, GM_LBL);
 #undef GM_LBL
-    GM_LAUNCH_RET();
+    GM_GEMM_RET();
 }
 
 extern "C" int gm_linear_fwd(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
@@ -2656,4 +2703,41 @@ extern "C" int gm_linear_bwd_dw(void* stream, const float* dA, int64_t lda, cons
 extern "C" int gm_linear_bwd_dw_ex(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second,
                                    const gm_dw_tail* tail) {
     return dw_impl(stream, first, second, tail);
+}
+
+// The launch-plan query (gm_hip.h): the entry point's own checks and dispatch with this thread's launch sites recording.
+extern "C" int gm_linear_plan(int mode, const void* args, int32_t* plan) {
+    GM_CHECK_ARG(args && plan && mode >= GM_PLAN_MODE_FWD && mode <= GM_PLAN_MODE_DW);
+    bool riding = false;
+    if (mode == GM_PLAN_MODE_FWD) {
+        const gm_fwd_args& a = *static_cast<const gm_fwd_args*>(args);
+        riding = a.ip_eps || a.ip_x || a.ip_out || a.hd_w2 || a.hd_b2 || a.hd_part || a.hd_snap || a.xbits ||
+                 a.sq_target || a.sq_dA || a.sq_part || a.lb_E || a.lb.labels || a.gather;
+    } else if (mode == GM_PLAN_MODE_DX) {
+        const gm_dx_args& a = *static_cast<const gm_dx_args*>(args);
+        riding = a.head || a.fold || a.rp_ml || a.rp_eps || a.rp_dml || a.gather;
+    } else {
+        const gm_dw_adam_args& a = *static_cast<const gm_dw_adam_args*>(args);
+        riding = a.head || a.fold || a.xbits || a.ones_from != 0;
+    }
+    if (riding) {
+        gm_set_error("launch-plan query: plain launches only (this descriptor carries a riding block)");
+        return GM_EUNSUPPORTED;
+    }
+    int32_t rec[GM_PLAN_FIELDS] = {0};
+    rec[GM_PLAN_F_MODE] = mode;
+    struct Recording {          // the launch sites record while this lives, whichever way the dispatch returns
+        explicit Recording(int32_t* r) { plan_rec = r; }
+        ~Recording() { plan_rec = nullptr; }
+    };
+    int rc;
+    {
+        Recording on(rec);
+        if (mode == GM_PLAN_MODE_FWD) rc = fwd_impl(nullptr, static_cast<const gm_fwd_args*>(args));
+        else if (mode == GM_PLAN_MODE_DX) rc = dx_impl(nullptr, static_cast<const gm_dx_args*>(args));
+        else rc = dw_impl(nullptr, static_cast<const gm_dw_adam_args*>(args), nullptr, nullptr);
+    }
+    if (rc) return rc;
+    for (int i = 0; i < GM_PLAN_FIELDS; ++i) plan[i] = rec[i];
+    return 0;
 }

@@ -343,6 +343,20 @@ def linear_bwd_dx_reparam(dA, W, dZ, ml, eps, dml, M=None, eps_slot=NO_SLOT, str
     return dZ
 
 
+def linear_plan(mode, args):
+    """What gm_linear_fwd_ex / gm_linear_bwd_dx_ex / gm_linear_bwd_dw_ex would launch for the descriptor `args`
+    (_lib.FwdArgs / DxArgs / DwAdamArgs; mode "fwd" / "dx" / "dw"), from the library's own dispatch run dry
+    (gm_linear_plan, include/gm_hip.h): nothing is launched and no GPU is needed -- the pointers only have to carry the
+    alignment of the real ones.  A dict over _lib.PLAN_FIELDS, `family` as its name in _lib.PLAN_FAMILY.  Plain launches
+    only: a descriptor with a riding block raises GMError (GM_EUNSUPPORTED)."""
+    out = (ctypes.c_int32 * _lib.PLAN_INTS)()
+    _lib.call("gm_linear_plan", _lib.PLAN_MODE[mode], ctypes.cast(ctypes.pointer(args), ctypes.c_void_p), out)
+    plan = dict(zip(_lib.PLAN_FIELDS, out))
+    plan["family"] = _lib.PLAN_FAMILY[plan["family"]]
+    plan["mode"] = mode
+    return plan
+
+
 def lds_min_m():
     """Rows from which forward / dX launches take the LDS macro-tile kernel (csrc/gm_gemm.hip)."""
     import os

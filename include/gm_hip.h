@@ -949,6 +949,43 @@ typedef struct gm_dw_tail {
 int gm_linear_bwd_dw_ex(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second,
                         const gm_dw_tail* tail);
 
+/* ---- launch-plan query: what gm_linear_fwd_ex / gm_linear_bwd_dx_ex / gm_linear_bwd_dw_ex WOULD launch for a
+ * descriptor, without launching and without a call into the HIP runtime (works on a host without a GPU; the pointers
+ * are only looked at for their alignment).  The query runs the entry point's own argument checks and dispatch with the
+ * launch sites switched to recording, so it cannot disagree with the launch.
+ *   mode: GM_PLAN_MODE_FWD / _DX / _DW; args: a gm_fwd_args / gm_dx_args / gm_dw_adam_args (single gradient);
+ *   plan: GM_PLAN_FIELDS ints, written on success (indices below).
+ * Plain launches only (for the input gradient with or without `add`, for the weight gradient with or without Adam):
+ * a descriptor with a riding block (interp, head part, sqerr, label, gather, head, fold, reparam, xbits, ones_from)
+ * returns GM_EUNSUPPORTED; a descriptor the entry point refuses returns what the entry point returns. */
+#define GM_EUNSUPPORTED (-10002)
+#define GM_PLAN_MODE_FWD 0
+#define GM_PLAN_MODE_DX 1
+#define GM_PLAN_MODE_DW 2
+/* kernel families */
+#define GM_PLAN_LDS 1                     /* LDS macro-tile kernel (forward / input gradient over >= 1024 rows) */
+#define GM_PLAN_K32 2                     /* forward over a reduction of at most 32 */
+#define GM_PLAN_SPLIT 3                   /* 16-wave split reduction */
+#define GM_PLAN_RIDING 4                  /* a kernel that carries riding work (not reported in detail) */
+/* fields of the plan */
+#define GM_PLAN_F_FAMILY 0
+#define GM_PLAN_F_MODE 1
+#define GM_PLAN_F_MI 2                    /* split reduction: tile = 16 MI x 16 NI (0 otherwise) */
+#define GM_PLAN_F_NI 3
+#define GM_PLAN_F_LDS_CFG 4               /* LDS: 1 = 64x64 tile, 2 = 32x64 tile (0 otherwise) */
+#define GM_PLAN_F_LDS_STAGES 5            /* LDS: stages of the fully unrolled instantiation (13, 25), 0 = runtime loop */
+#define GM_PLAN_F_VEC 6                   /* 16-byte loads of the k-contiguous operands */
+#define GM_PLAN_F_XV 7                    /* 16-byte loads of the x-contiguous operands */
+#define GM_PLAN_F_VEC_EPI 8               /* float4 epilogue */
+#define GM_PLAN_F_DMA 9                   /* weight gradient: operand chunks by LDS-DMA */
+#define GM_PLAN_F_SLOTS 10                /* the slot-resolving instantiation */
+#define GM_PLAN_F_LAUNCHES 11             /* separate kernel launches */
+#define GM_PLAN_F_GRID_X 12               /* of the last launch */
+#define GM_PLAN_F_GRID_Y 13
+#define GM_PLAN_F_BLOCK 14
+#define GM_PLAN_FIELDS 16
+int gm_linear_plan(int mode, const void* args, int32_t* plan);
+
 /* ---- Primal-Dual Wasserstein GAN (csrc/gm_pdw.hip; pdwgan.py).  One wave per row, fixed
  * reduction order, no atomics.
  * The primal coupling (pdwgan.PDWGANEngine phase 1, after the decoder's output layer): per row of x [B, I] and its

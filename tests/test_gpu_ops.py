@@ -8,31 +8,19 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import os  # noqa: E402
+import sys  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
 from generative_models_amd import ops  # noqa: E402
 from oracle import port  # noqa: E402
 
 DEV = "cuda:0"
 
 
-def close(got, ref, tol=1e-5, what="", atol=0.0):
-    got = got.detach().cpu().double()
-    ref = ref.detach().cpu().double()
-    scale = max(ref.abs().max().item(), 1e-30)
-    err = max((got - ref).abs().max().item() - atol, 0.0) / scale
-    assert err <= tol, "%s: max err %.3e (scaled) > %.1e; ref scale %.3e" % (what, err, tol, scale)
-
-
-def close64(got, ref64, ref32, what=""):
-    """The HIP result against an fp64 evaluation of the same expression, bounded by TWICE the error the fp32 CPU
-    result (MKL / ATen, its own summation order) has against that fp64 value, plus one fp32 ulp of the output's scale
-    (exact cases: M = 1, identity operands).  An MKL-vs-HIP comparison with a sqrt(K) allowance cannot tell which of
-    the two is off; this can."""
-    got, ref32, ref64 = got.detach().cpu().double(), ref32.detach().cpu().double(), ref64.detach().cpu().double()
-    scale = max(ref64.abs().max().item(), 1e-30)
-    e_hip = (got - ref64).abs().max().item() / scale
-    e_cpu = (ref32 - ref64).abs().max().item() / scale
-    bound = 2.0 * e_cpu + 2.0 ** -23
-    assert e_hip <= bound, "%s: HIP err %.3e (scaled) > 2 x CPU fp32 err %.3e + 1 ulp; scale %.3e" % (what, e_hip, e_cpu, scale)
+# (the two criteria live beside the linear layers' case table, which tests/test_gpu_linear_paths.py shares)
+from linear_path_cases import close, close64  # noqa: E402,F401
 
 
 def act_cpu(y, act):

@@ -84,8 +84,12 @@ def host_thread_plan():
 def __getattr__(name):
     """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine, SNGAN / SNGANTrainer / SNGANEngine,
     DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine, NFVAE / NFVAETrainer / NFVAEEngine, CatVAE /
-    CatVAETrainer / CatVAEEngine, RealNVP / RealNVPTrainer / RealNVPEngine, RBM / RBMTrainer / RBMEngine and VQVAE /
-    VQVAETrainer / VQVAEEngine, imported on first use (importing the package stays free of torch)."""
+    CatVAETrainer / CatVAEEngine, RealNVP / RealNVPTrainer / RealNVPEngine, RBM / RBMTrainer / RBMEngine, VQVAE /
+    VQVAETrainer / VQVAEEngine and MAF / MAFTrainer / MAFEngine, imported on first use (importing the package stays free
+    of torch)."""
+    if name in ("MAF", "MAFTrainer", "MAFEngine"):
+        from . import maf
+        return getattr(maf, name)
     if name in ("VQVAE", "VQVAETrainer"):
         from . import vqvae
         return getattr(vqvae, name)

@@ -148,6 +148,10 @@ NVP_CHECKER, NVP_HALF = 0, 1                                # GM_NVP_CHECKER / G
 NVP_PRE, NVP_NOISE, NVP_POST, NVP_PRIOR = 0, 1, 0, 1        # gm_nvp_pre's and gm_nvp_post's modes
 # (the gm_nvp_*_args travel by pointer; their ctypes forms live in ops_fused)
 
+MAF_TAG_TRAIN, MAF_TAG_EVAL = 0x4D414644, 0x4D414656          # GM_MAF_TAG_TRAIN / GM_MAF_TAG_EVAL ("MAFD", "MAFV")
+MAF_MIN_D, MAF_MAX_D, MAF_MAX_H, MAF_MAX_K = 2, 8192, 1024, 16              # GM_MAF_* (include/gm_hip.h)
+# (the gm_maf_*_args travel by pointer; their ctypes forms live in ops_fused)
+
 RBM_TAG_D, RBM_TAG_H, RBM_TAG_V = 0x52424D44, 0x52424D48, 0x52424D56      # GM_RBM_TAG_* ("RBMD", "RBMH", "RBMV")
 RBM_MAX_DIM, RBM_MAX_STEPS = 1024, 1 << 24                  # GM_RBM_MAX_DIM / GM_RBM_MAX_STEPS
 # (gm_rbm_chain_args / gm_rbm_vbias_args travel by pointer; their ctypes forms live in ops_fused)
@@ -416,6 +420,10 @@ _SIGNATURES = {
     "gm_nvp_loss": (c_int, [_P, _P]),
     "gm_nvp_couple_bwd": (c_int, [_P, _P]),
     "gm_nvp_post": (c_int, [_P, _P]),
+    "gm_maf_couple": (c_int, [_P, _P]),
+    "gm_maf_couple_bwd": (c_int, [_P, _P]),
+    "gm_maf_mask": (c_int, [_P, _P]),
+    "gm_maf_invert": (c_int, [_P, _P]),
     "gm_rbm_chain": (c_int, [_P, _P]),
     "gm_rbm_grad": (c_int, [_P, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_float, c_int, c_int, c_int]),
     "gm_rbm_vbias": (c_int, [_P, _P]),

@@ -1565,3 +1565,102 @@ def nvp_prior(za, zb, B, D, seed, mask, temperature=1.0, row0=0, stream=None):
     a.seed, a.row0, a.temperature = _seed64("nvp_prior", seed), int(row0), float(temperature)
     a.mask, a.mode, a.B, a.D = _nvp_mask(mask), _lib.NVP_PRIOR, B, D
     _lib.call("gm_nvp_post", stream or stream_ptr(), ctypes.byref(a))
+
+
+# ---- Masked autoregressive flow (csrc/gm_maf.hip, gm_maf.h; maf.py) --------------------------------------------------
+class MafCoupleArgs(ctypes.Structure):
+    """gm_maf_couple_args (include/gm_hip.h): one layer, data -> noise."""
+    _fields_ = [("y", ctypes.c_void_p), ("ldy", ctypes.c_int64), ("ma", ctypes.c_void_p), ("ldma", ctypes.c_int64),
+                ("u", ctypes.c_void_p), ("ldu", ctypes.c_int64), ("logdet", ctypes.c_void_p), ("s_cap", ctypes.c_float),
+                ("B", ctypes.c_int), ("D", ctypes.c_int)]
+
+
+class MafCoupleBwdArgs(ctypes.Structure):
+    """gm_maf_couple_bwd_args (include/gm_hip.h): the layer's backward."""
+    _fields_ = [("ma", ctypes.c_void_p), ("ldma", ctypes.c_int64), ("u", ctypes.c_void_p), ("ldu", ctypes.c_int64),
+                ("g", ctypes.c_void_p), ("ldg", ctypes.c_int64), ("dout", ctypes.c_void_p), ("lddout", ctypes.c_int64),
+                ("dy", ctypes.c_void_p), ("lddy", ctypes.c_int64), ("c", ctypes.c_float), ("s_cap", ctypes.c_float),
+                ("B", ctypes.c_int), ("D", ctypes.c_int)]
+
+
+class MafMaskArgs(ctypes.Structure):
+    """gm_maf_mask_args (include/gm_hip.h): one layer's masked weights, their moments and the degree vectors."""
+    _fields_ = [("W1", ctypes.c_void_p), ("m1", ctypes.c_void_p), ("v1", ctypes.c_void_p), ("W2", ctypes.c_void_p),
+                ("m2", ctypes.c_void_p), ("v2", ctypes.c_void_p), ("m_in", ctypes.c_void_p), ("m_h", ctypes.c_void_p),
+                ("D", ctypes.c_int), ("H", ctypes.c_int)]
+
+
+class MafInvertArgs(ctypes.Structure):
+    """gm_maf_invert_args (include/gm_hip.h): one layer's inverse in one launch."""
+    _fields_ = [("u", ctypes.c_void_p), ("ldu", ctypes.c_int64), ("y", ctypes.c_void_p), ("ldy", ctypes.c_int64),
+                ("s", ctypes.c_void_p), ("lds", ctypes.c_int64), ("W2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("W1T", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("m_h", ctypes.c_void_p),
+                ("inv_order", ctypes.c_void_p), ("s_cap", ctypes.c_float), ("n", ctypes.c_int64), ("D", ctypes.c_int),
+                ("H", ctypes.c_int)]
+
+
+def maf_halves(t, D):
+    """The GM_NVP_HALF view of rows t [B, >= D]: (the first ceil(D / 2) columns, the rest), both inside t -- what
+    gm_nvp_pre / gm_nvp_loss / gm_nvp_post take for an unsplit MAF row array."""
+    Da = (D + 1) // 2
+    return t[:, :Da], t[:, Da:D]
+
+
+def maf_couple(y, ma, u, logdet, B, D, s_cap, stream=None):
+    """u = (y - m) exp(-s) and logdet -= sum s, with [m | a] = ma and s = s_cap tanh(a) (gm_maf_couple)."""
+    a = MafCoupleArgs()
+    _nvp_rows(y, B, D, "y"), _nvp_rows(ma, B, 2 * D, "ma"), _nvp_rows(u, B, D, "u")
+    a.y, a.ldy, a.ma, a.ldma, a.u, a.ldu = y.data_ptr(), _ld(y), ma.data_ptr(), _ld(ma), u.data_ptr(), _ld(u)
+    a.logdet = _nvp_vec(logdet, B, "logdet").data_ptr()
+    a.s_cap, a.B, a.D = float(s_cap), B, D
+    _lib.call("gm_maf_couple", stream or stream_ptr(), ctypes.byref(a))
+
+
+def maf_couple_bwd(ma, u, g, dout, B, D, s_cap, c, dy=None, stream=None):
+    """dout[:, :D] = -g exp(-s), dout[:, D:] = (-(g u) - c) s_cap (1 - tanh^2(a)) and, with dy, dy = g exp(-s)
+    (gm_maf_couple_bwd)."""
+    a = MafCoupleBwdArgs()
+    _nvp_rows(ma, B, 2 * D, "ma"), _nvp_rows(u, B, D, "u"), _nvp_rows(g, B, D, "g"), _nvp_rows(dout, B, 2 * D, "dout")
+    a.ma, a.ldma, a.u, a.ldu, a.g, a.ldg = ma.data_ptr(), _ld(ma), u.data_ptr(), _ld(u), g.data_ptr(), _ld(g)
+    a.dout, a.lddout = dout.data_ptr(), _ld(dout)
+    if dy is not None:
+        a.dy, a.lddy = _nvp_rows(dy, B, D, "dy").data_ptr(), _ld(dy)
+    a.c, a.s_cap, a.B, a.D = float(c), float(s_cap), B, D
+    _lib.call("gm_maf_couple_bwd", stream or stream_ptr(), ctypes.byref(a))
+
+
+def maf_mask(W1, W2, m_in, m_h, moments1=None, moments2=None, stream=None):
+    """Zeroes the masked entries of one layer's linear.weight W1 [H, D] and out.weight W2 [2 D, H] and -- moments =
+    (m, v) flat views -- of their Adam moments (gm_maf_mask); every other entry stays as it is."""
+    H, D = W1.shape
+    _made_f32(W1, (H, D), "W1"), _made_f32(W2, (2 * D, H), "W2")
+    a = MafMaskArgs()
+    a.W1, a.W2 = W1.data_ptr(), W2.data_ptr()
+    a.m_in, a.m_h = _made_i32(m_in, D, "m_in").data_ptr(), _made_i32(m_h, H, "m_h").data_ptr()
+    for mv, names, n in ((moments1, ("m1", "v1"), D * H), (moments2, ("m2", "v2"), 2 * D * H)):
+        if mv is not None:
+            for t, nm in zip(mv, names):
+                setattr(a, nm, _made_f32(t.view(-1), (n,), nm).data_ptr())
+    a.D, a.H = D, H
+    _lib.call("gm_maf_mask", stream or stream_ptr(), ctypes.byref(a))
+
+
+def maf_invert(u, W2, b2, W1T, b1, m_h, inv_order, s_cap, n=None, y=None, s=None, stream=None):
+    """y [n, D] with layer(y) = u, solved pixel by pixel in order of degree in ONE launch (gm_maf_invert); s (a [n, D]
+    tensor) receives the log-scales."""
+    D, H = W1T.shape
+    _made_f32(W2, (2 * D, H), "W2"), _made_f32(W1T, (D, H), "W1T"), _made_f32(b2, (2 * D,), "b2"), _made_f32(b1, (H,), "b1")
+    n = u.shape[0] if n is None else int(n)
+    y = torch.empty(n, D, device=u.device) if y is None else y
+    for t, nm in ((u, "u"), (y, "y"), (s, "s")):
+        if t is not None:
+            _nvp_rows(t, n, D, nm)
+    a = MafInvertArgs()
+    a.u, a.ldu, a.y, a.ldy = u.data_ptr(), _ld(u), y.data_ptr(), _ld(y)
+    if s is not None:
+        a.s, a.lds = s.data_ptr(), _ld(s)
+    a.W2, a.b2, a.W1T, a.b1 = W2.data_ptr(), b2.data_ptr(), W1T.data_ptr(), b1.data_ptr()
+    a.m_h, a.inv_order = _made_i32(m_h, H, "m_h").data_ptr(), _made_i32(inv_order, D, "inv_order").data_ptr()
+    a.s_cap, a.n, a.D, a.H = float(s_cap), n, D, H
+    _lib.call("gm_maf_invert", stream or stream_ptr(), ctypes.byref(a))
+    return y

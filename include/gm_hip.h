@@ -1338,6 +1338,77 @@ typedef struct gm_nvp_post_args {
 } gm_nvp_post_args;
 int gm_nvp_post(void* stream, const gm_nvp_post_args* a);
 
+/* ---- masked autoregressive flow, MAF (Papamakarios, Pavlakou & Murray, arXiv 1705.07057; maf.py holds the contract;
+ * DESIGN.md section 30; csrc/gm_maf.hip, the shared arithmetic in csrc/gm_maf.h) ------------------------------------------
+ * K layers, each a D -> H -> 2 D MLP masked by the degrees m_in [D] (a permutation of 1 .. D) and m_h [H] (in [1, D - 1]),
+ * int32 device vectors: linear.weight [H, D] keeps (j, i) iff m_h[j] >= m_in[i]; both halves of out.weight [2 D, H] (rows
+ * 0 .. D - 1 the shift m, rows D .. 2 D - 1 the log-scale pre-activation a) keep (d, j) iff m_in[d] > m_h[j].  A layer
+ * maps y to u = (y - m) exp(-s), s = s_cap tanh(a), and subtracts sum_d s_d from the log-determinant.  The preprocessing,
+ * the loss and the post-processing are gm_nvp_pre / gm_nvp_loss / gm_nvp_post on the GM_NVP_HALF split with both halves
+ * inside one [B, D] array (yb = ya + ceil(D / 2), lda = ldb = D), under the tags below.  Out-of-limit fields, NULL and
+ * aliased outputs return GM_EINVAL before any launch. */
+#define GM_MAF_TAG_TRAIN 0x4D414644u           /* "MAFD": the training dequantisation noise */
+#define GM_MAF_TAG_EVAL 0x4D414656u            /* "MAFV": validation, encode and log_likelihood */
+#define GM_MAF_MIN_D 2
+#define GM_MAF_MAX_D 8192
+#define GM_MAF_MAX_H 1024
+#define GM_MAF_MAX_K 16
+/* One layer, data -> noise (maf.py MAFEngine._issue, MAFTrainer._forward_rows):  s = s_cap tanh(ma[:, D:]) (nvp_s),
+ *   u = (y - ma[:, :D]) exp(-s),  logdet[r] -= sum_d s_d (a plain read-add-write by the row's owner).  One 256-thread
+ * workgroup per row, fixed reduction order; 16-byte accesses where D % 4 == 0 and every base and leading dimension allow
+ * them, element by element otherwise, with the same bits. */
+typedef struct gm_maf_couple_args {
+    const float* y; int64_t ldy;              /* [B, >= D]: the layer's input */
+    const float* ma; int64_t ldma;            /* [B, >= 2 D]: [m | a], the masked MLP's output */
+    float* u; int64_t ldu;                    /* [B, >= D]; none of y, ma */
+    float* logdet;                            /* [B] */
+    float s_cap;                              /* in (0, GM_NVP_MAX_S_CAP] */
+    int B, D;
+} gm_maf_couple_args;
+int gm_maf_couple(void* stream, const gm_maf_couple_args* a);
+/* The layer's backward (maf.py MAFEngine._issue).  g = dL/du, c the log-determinant's cotangent (-1 / B in training):
+ *   dout[:, :D] = -g exp(-s),  dout[:, D:] = (-(g u) - c) s_cap (1 - tanh^2(a)) with 1 - tanh^2 as 4 e / (1 + e)^2,
+ *   e = exp(-2 |a|),  dy = g exp(-s) (the direct cotangent of the layer's input; dy may be NULL). */
+typedef struct gm_maf_couple_bwd_args {
+    const float* ma; int64_t ldma;            /* [B, >= 2 D] */
+    const float* u; int64_t ldu;              /* [B, >= D]: the layer's output */
+    const float* g; int64_t ldg;              /* [B, >= D] */
+    float* dout; int64_t lddout;              /* [B, >= 2 D]; none of the inputs */
+    float* dy; int64_t lddy;                  /* [B, >= D] or NULL; none of the inputs, not dout */
+    float c, s_cap;
+    int B, D;
+} gm_maf_couple_bwd_args;
+int gm_maf_couple_bwd(void* stream, const gm_maf_couple_bwd_args* a);
+/* Zeroes W and Adam's moments m, v (both NULL, or both given) at the masked entries of one layer's linear.weight and of
+ * both halves of its out.weight in one launch (maf.py MAFEngine._issue, behind the weight-gradient + Adam launch whose
+ * epilogue steps every entry; MAFEngine.configure).  Every other entry is left as it is; no weight is read. */
+typedef struct gm_maf_mask_args {
+    float* W1; float* m1; float* v1;          /* linear.weight [H, D] and its moments */
+    float* W2; float* m2; float* v2;          /* out.weight [2 D, H] and its moments */
+    const int32_t* m_in; const int32_t* m_h;
+    int D, H;
+} gm_maf_mask_args;
+int gm_maf_mask(void* stream, const gm_maf_mask_args* a);
+/* One layer's inverse, noise -> data, in one launch (maf.py MAFTrainer.sample / decode).  Pixels are solved in order of
+ * degree, inv_order[t] (clamped into [0, D - 1]) the pixel of degree t + 1; for pixel d of row r at position t:
+ *   m = b2[d] + sum_j [m_h[j] <= t] W2[d, j] relu(h_j),  a = b2[D + d] + sum_j [m_h[j] <= t] W2[D + d, j] relu(h_j)
+ *   (lane-local sums in ascending j, then the wave butterfly);   s = s_cap tanh(a);   y = u exp(s) + m, the product
+ *   rounded before the add;   h_j += y W1T[d, j] for every j with m_h[j] > t,
+ * h starting from b1.  W1T [D, H] is linear.weight transposed (rows H floats apart, like W2's).  s (may be NULL) receives
+ * the log-scales.  One wave per row: a row's bits depend on its u and the weights alone, not on n or the grid. */
+typedef struct gm_maf_invert_args {
+    const float* u; int64_t ldu;              /* [n, >= D] */
+    float* y; int64_t ldy;                    /* [n, >= D]; not u */
+    float* s; int64_t lds;                    /* [n, >= D] or NULL; neither u nor y */
+    const float* W2; const float* b2;         /* out.weight [2 D, H], out.bias [2 D] */
+    const float* W1T; const float* b1;        /* linear.weight^T [D, H], linear.bias [H] */
+    const int32_t* m_h; const int32_t* inv_order;
+    float s_cap;
+    int64_t n;                                /* 1 <= n <= 2^32 */
+    int D, H;
+} gm_maf_invert_args;
+int gm_maf_invert(void* stream, const gm_maf_invert_args* a);
+
 /* ---- binary restricted Boltzmann machine (Smolensky 1986; Hinton 2002; Tieleman 2008; rbm.py holds the contract;
  * DESIGN.md section 25; csrc/gm_rbm.hip, the noise rule and the pinned arithmetic in csrc/gm_rbm.h) --------------------
  * W [H, I] (linear.weight), c [H] (linear.bias), b [I] (vbias); WT [I, H] is W transposed (gm_rbm_transpose).

@@ -1,0 +1,417 @@
+"""The masked autoregressive flow without a GPU: module surface and state_dict keys, the constructor's refusals at every
+limit, the degree rule (consecutive layers reversed), masked entries, the fp64 reference's Jacobian (triangular in the
+order, diagonal exp(-s): this pins logdet) and its own invertibility, the C-ABI of the new kernels and its refusals, struct
+mirrors, fused / general path selection, the data-parallel refusal, the checkpoint config's strict check, and the
+reference's own training on the learning test's data."""
+import ctypes
+import inspect
+import math
+import os
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "generative_models_amd", "src"))
+sys.path.insert(0, HERE)
+
+import maf  # noqa: E402
+import maf_reference as R  # noqa: E402
+from generative_models_amd import _lib, metrics, ops_fused  # noqa: E402
+from generative_models_amd import maf as gmaf  # noqa: E402
+from generative_models_amd import made as gmade  # noqa: E402
+from generative_models_amd import realnvp as gnvp  # noqa: E402
+
+NEW = ("gm_maf_couple", "gm_maf_couple_bwd", "gm_maf_mask", "gm_maf_invert")
+STRUCTS = {"gm_maf_couple_args": ops_fused.MafCoupleArgs, "gm_maf_couple_bwd_args": ops_fused.MafCoupleBwdArgs,
+           "gm_maf_mask_args": ops_fused.MafMaskArgs, "gm_maf_invert_args": ops_fused.MafInvertArgs}
+
+
+def _loaders(n=40, batch=8, side=4):
+    x = torch.rand(n, 1, side, side)
+    ds = torch.utils.data.TensorDataset(x, torch.zeros(n, dtype=torch.int64))
+    dl = lambda: torch.utils.data.DataLoader(ds, batch_size=batch, shuffle=True)
+    return dl(), dl(), dl()
+
+
+def _trainer(model, cls=None, **kw):
+    tr = object.__new__(cls or maf.MAFTrainer)       # selection runs before anything touches a GPU
+    tr.model, tr.train_iter, tr.val_iter, tr.test_iter = model, *_loaders()
+    tr.seed, tr.noise_steps, tr._engine = 0, 0, None
+    tr.alpha, tr.levels, tr.s_cap = kw.get("alpha", 0.05), kw.get("levels", 256), kw.get("s_cap", 2.0)
+    return tr
+
+
+def test_module_surface_and_state_dict_keys():
+    m = maf.MAF(7, 5, 3)
+    assert list(m.state_dict()) == R.keys(3, buffers=True)
+    shapes = [tuple(v.shape) for v in m.state_dict().values()]
+    assert shapes == [(7,), (5,), (5, 7), (5,), (14, 5), (14,)] * 3
+    assert all(m.state_dict()["layers.%d.%s" % (k, n)].dtype == torch.int32 for k in range(3) for n in ("m_in", "m_h"))
+    assert (m.image_size, m.hidden_dim, m.num_layers, m.order, m.order_seed) == (7, 5, 3, "natural", 0)
+    assert type(m.layers) is torch.nn.ModuleList and all(type(c) is maf.MAFLayer for c in m.layers)
+    sig = inspect.signature(maf.MAF.__init__).parameters
+    assert [(n, p.default) for n, p in list(sig.items())[1:]] == [
+        ("image_size", 784), ("hidden_dim", 400), ("num_layers", 5), ("order", "natural"), ("order_seed", 0)]
+    T = maf.MAFTrainer
+    sig = inspect.signature(T.__init__).parameters
+    assert [(n, p.default) for n, p in list(sig.items())[5:9]] == [("seed", 0), ("alpha", 0.05), ("levels", 256),
+                                                                   ("s_cap", 2.0)]
+    sig = inspect.signature(T.train).parameters
+    assert [(n, p.default) for n, p in list(sig.items())[2:4]] == [("lr", 1e-3), ("weight_decay", 0.0)]
+    assert T._hook_names == ("compute_batch", "evaluate") and T._series == (("losses", "recon"),)
+    sig = inspect.signature(T.sample).parameters
+    assert [(n, p.default) for n, p in list(sig.items())[1:]] == [("n", inspect.Parameter.empty), ("seed", 0),
+                                                                  ("temperature", 1.0)]
+    for name in ("sample", "encode", "decode", "parzen", "log_likelihood", "bits_per_dim", "sample_images",
+                 "generate_images", "save_checkpoint", "load_checkpoint"):
+        assert callable(getattr(T, name)), name
+    assert issubclass(gmaf.MAFError, _lib.GMError) and issubclass(gmaf.MAFError, ValueError)
+    import generative_models_amd as pkg
+    from generative_models_amd.engine import VAEEngine
+    from generative_models_amd.trainers import VAETrainer
+    assert pkg.MAF is gmaf.MAF and pkg.MAFTrainer is T and pkg.MAFEngine is gmaf.MAFEngine
+    assert issubclass(T, VAETrainer) and "train" in T.__dict__ and "_train_fused" not in T.__dict__   # the shared loop
+    assert issubclass(gmaf.MAFEngine, VAEEngine) and gmaf.MAFEngine.has_eps is False
+    for f in ("_alloc", "_issue", "configure"):
+        assert f in gmaf.MAFEngine.__dict__, f
+    assert gmaf.__doc__ and "The contract" in gmaf.__doc__ and "MAFD" in gmaf.__doc__
+    tr = _trainer(m)
+    assert abs(tr.bits_per_dim(metrics.NLLResult(-7 * math.log(2.0) * 3.5, 0.0, 1)) - 3.5) < 1e-12
+    tags = {gmaf.TAG_TRAIN, gmaf.TAG_EVAL, gnvp.TAG_TRAIN, gnvp.TAG_EVAL, gnvp.TAG_S, _lib.MADE_TAG_S, _lib.CAT_TAG_TRAIN,
+            _lib.CAT_TAG_EVAL, _lib.IWAE_TAG_TRAIN, _lib.IWAE_TAG_EVAL, _lib.DDPM_TAG_T, _lib.DDPM_TAG_E, _lib.DDPM_TAG_V,
+            _lib.DDPM_TAG_VE, _lib.DDPM_TAG_S, _lib.RBM_TAG_D, _lib.RBM_TAG_H, _lib.RBM_TAG_V}
+    assert len(tags) == 18                                                # tags of its own
+    assert (gmaf.TAG_TRAIN, gmaf.TAG_EVAL) == tuple(int.from_bytes(t, "big") for t in (b"MAFD", b"MAFV"))
+    assert (R.TAG_TRAIN, R.TAG_EVAL, R.TAG_S) == (gmaf.TAG_TRAIN, gmaf.TAG_EVAL, gmaf.TAG_S) and gmaf.TAG_S == gnvp.TAG_S
+
+
+@pytest.mark.parametrize("kw", [
+    dict(image_size=1), dict(image_size=8193), dict(image_size=16.0), dict(image_size=True),
+    dict(hidden_dim=0), dict(hidden_dim=1025), dict(hidden_dim=None),
+    dict(num_layers=0), dict(num_layers=17), dict(num_layers=2.0),
+    dict(order="stripes"), dict(order=0), dict(order_seed=-1), dict(order_seed=1 << 32), dict(order_seed=1.0)])
+def test_constructor_refusals(kw):
+    args = dict(image_size=16, hidden_dim=8, num_layers=2)
+    args.update(kw)
+    with pytest.raises(gmaf.MAFError):
+        maf.MAF(**args)
+    with pytest.raises(ValueError):
+        maf.MAF(**args)
+
+
+@pytest.mark.parametrize("kw", [
+    dict(alpha=-1e-3), dict(alpha=0.5), dict(alpha=float("nan")), dict(alpha="x"), dict(levels=1), dict(levels=65537),
+    dict(levels=256.0), dict(s_cap=0.0), dict(s_cap=8.5), dict(s_cap=-1.0), dict(s_cap=float("inf")), dict(seed=-1),
+    dict(seed=1 << 64), dict(seed=1.5)])
+def test_trainer_settings_refusals(kw):
+    """The trainer's settings are validated before anything runs (no loader is touched)."""
+    with pytest.raises(gmaf.MAFError):
+        maf.MAFTrainer(maf.MAF(16, 8, 2), None, None, None, **kw)
+    assert gmaf.check_settings(0.0, 2, 8) == (0.0, 2, 8.0) and gmaf.check_settings(0.4999, 65536, 1e-3)[1] == 65536
+
+
+def test_constructor_accepts_every_limit():
+    for kw in (dict(image_size=2, hidden_dim=1, num_layers=1), dict(image_size=16, hidden_dim=4, num_layers=16),
+               dict(image_size=16, hidden_dim=4, order="random", order_seed=(1 << 32) - 1)):
+        maf.MAF(**kw)
+    m = maf.MAF(8192, 1, 1)
+    assert tuple(m.layers[0].out.weight.shape) == (2 * 8192, 1)
+
+
+@pytest.mark.parametrize("order", ["natural", "random"])
+@pytest.mark.parametrize("D,H,K", [(2, 1, 2), (10, 7, 3), (49, 32, 4), (784, 400, 2)])
+def test_degrees_of_consecutive_layers_are_reverses(D, H, K, order):
+    ins, m_h = gmaf.degrees(D, H, K, order, 3)
+    rins, rm_h = R.degrees(D, H, K, order, 3)
+    gin, gm_h = gmade.degrees(D, H, order, 3)
+    assert np.array_equal(ins[0], gin) and np.array_equal(m_h, gm_h)       # layer 0 is MADE's order, m_h MADE's rule
+    assert np.array_equal(m_h, rm_h) and m_h.dtype == np.int32
+    assert np.array_equal(m_h, [1 + (j * (D - 1)) // H for j in range(H)]) and m_h.min() >= 1 and m_h.max() <= D - 1
+    for k in range(K):
+        assert ins[k].dtype == np.int32 and np.array_equal(ins[k], rins[k])
+        assert np.array_equal(np.sort(ins[k]), np.arange(1, D + 1))         # a permutation of 1 .. D
+        if k:
+            assert np.array_equal(ins[k], D + 1 - ins[k - 1])
+            assert np.array_equal(gmaf.inverse_order(ins[k]), gmaf.inverse_order(ins[k - 1])[::-1])
+    if order == "natural":
+        assert np.array_equal(ins[0], np.arange(1, D + 1))
+    m = maf.MAF(D, H, K, order, 3)
+    for k, c in enumerate(m.layers):
+        assert np.array_equal(c.m_in.numpy(), ins[k]) and np.array_equal(c.m_h.numpy(), m_h)
+    with pytest.raises(gmaf.MAFError):
+        gmaf.inverse_order(np.array([1, 1, 3]))
+
+
+@pytest.mark.parametrize("order", ["natural", "random"])
+def test_masked_entries_are_zero_after_construction(order):
+    D, H, K = 10, 7, 3
+    m = maf.MAF(D, H, K, order, 5)
+    for k, c in enumerate(m.layers):
+        M1, M2 = R.masks(c.m_in.numpy(), c.m_h.numpy())
+        g1, g2 = c.masks()
+        assert torch.equal(g1.double(), M1) and torch.equal(g2.double(), M2) and tuple(g2.shape) == (2 * D, H)
+        assert torch.equal(M2[:D], M2[D:])                                 # both halves of out.weight share the mask
+        assert c.linear.weight.abs().max() > 0
+        assert not c.linear.weight[M1 == 0].any() and (c.linear.weight[M1 == 1] != 0).all()
+        assert not c.out.weight.any() and not c.out.bias.any()             # out starts at zero: the identity flow
+        with torch.no_grad():
+            c.linear.weight.fill_(1.0)
+            c.out.weight.fill_(1.0)
+        c.apply_masks()
+        assert torch.equal(c.linear.weight.double(), M1) and torch.equal(c.out.weight.double(), M2)
+        # the pixel of degree 1 sees nothing; the pixel of degree D feeds nothing
+        first, last = int(np.argmin(c.m_in.numpy())), int(np.argmax(c.m_in.numpy()))
+        assert not M2[first].any() and not M2[D + first].any() and not M1[:, last].any()
+    P = R.f64(maf.MAF(D, H, K, order, 5).state_dict())
+    y = torch.randn(5, D, dtype=torch.float64)
+    z, ld = R.forward(P, y, K, 2.0)
+    assert torch.equal(z, y) and not ld.any()                              # a fresh model is the identity flow
+
+
+@pytest.mark.parametrize("order", ["natural", "random"])
+@pytest.mark.parametrize("D,H", [(2, 1), (10, 7), (49, 32)])
+def test_reference_jacobian_is_triangular_with_diagonal_exp_minus_s(D, H, order):
+    """du/dy of one fp64 layer, by autograd: zero wherever the input's degree is above the output's, exp(-s) on the
+    diagonal -- so log |det| = -sum s, the log-determinant the reference (and the contract) accumulates.  The layer with
+    reversed degrees too."""
+    cap = 2.0
+    P = R.f64(R.random_weights(D, H, 2, order, 7, seed=D, out_scale=2.0))
+    g = torch.Generator().manual_seed(D)
+    for k in (0, 1):
+        y = torch.randn(D, dtype=torch.float64, generator=g) * 2
+        J = torch.autograd.functional.jacobian(lambda v: R.couple(R.ma_of(P, k, v[None]), v[None], cap)[0][0], y)
+        m_in = P["layers.%d.m_in" % k].numpy()
+        above = torch.from_numpy(m_in[None, :] > m_in[:, None])            # [out d, in i]: degree of i above degree of d
+        assert J[above].abs().max().item() == 0.0 if above.any() else True
+        ma = R.ma_of(P, k, y[None])
+        s = cap * torch.tanh(ma[0, D:])
+        assert (torch.diagonal(J) - torch.exp(-s)).abs().max().item() <= 1e-14
+        if D > 2:
+            assert J[~above & ~torch.eye(D, dtype=torch.bool)].abs().max().item() > 0       # and it is not diagonal
+        sign, logabs = torch.linalg.slogdet(J)
+        _, ld = R.forward({n.replace("layers.%d." % k, "layers.0."): v for n, v in P.items() if n.startswith("layers.%d." % k)},
+                          y[None], 1, cap)
+        assert sign.item() > 0 and abs(logabs.item() - ld.item()) <= 1e-10 and abs(ld.item() + s.sum().item()) <= 1e-12
+
+
+@pytest.mark.parametrize("order", ["natural", "random"])
+@pytest.mark.parametrize("D,H,K", [(2, 1, 1), (10, 7, 3), (49, 32, 2)])
+def test_reference_inverse_of_forward(D, H, K, order):
+    P = R.f64(R.random_weights(D, H, K, order, 2, seed=D, out_scale=1.0))
+    y = torch.randn(6, D, dtype=torch.float64, generator=torch.Generator().manual_seed(1)) * 2
+    z, _ = R.forward(P, y, K, 2.0)
+    assert (z - y).abs().max() > 0.05
+    assert (R.inverse(P, z, K, 2.0) - y).abs().max().item() <= 1e-12
+    assert (R.forward(P, R.inverse(P, y, K, 2.0), K, 2.0)[0] - y).abs().max().item() <= 1e-12
+    # the closed-form backward is autograd's
+    ma = (torch.randn(6, 2 * D, dtype=torch.float64) * 0.8).requires_grad_(True)
+    g = torch.randn(6, D, dtype=torch.float64)
+    u, s = R.couple(ma, y, 2.0)
+    yy = y.clone().requires_grad_(True)
+    u2, s2 = R.couple(ma, yy, 2.0)
+    c = -0.25
+    ((u2 * g).sum() + c * (-s2).sum()).backward()
+    dout, dy = R.couple_bwd(ma.detach(), u.detach(), g, c, 2.0)
+    assert (dout - ma.grad).abs().max().item() <= 1e-12 and (dy - yy.grad).abs().max().item() <= 1e-12
+
+
+def test_new_symbols_are_declared_and_bound():
+    lib = _lib.load()
+    declared = _lib.declared_symbols()
+    for name in NEW:
+        assert name in declared and name in _lib._SIGNATURES and hasattr(lib, name), name
+    hdr = open(os.path.join(os.path.dirname(HERE), "include", "gm_hip.h")).read()
+    for line in ("#define GM_MAF_MIN_D %d" % _lib.MAF_MIN_D, "#define GM_MAF_MAX_D %d" % _lib.MAF_MAX_D,
+                 "#define GM_MAF_MAX_H %d" % _lib.MAF_MAX_H, "#define GM_MAF_MAX_K %d" % _lib.MAF_MAX_K,
+                 "#define GM_MAF_TAG_TRAIN 0x%08Xu" % _lib.MAF_TAG_TRAIN, "#define GM_MAF_TAG_EVAL 0x%08Xu" % _lib.MAF_TAG_EVAL):
+        assert line in hdr, line
+    assert (_lib.MAF_MIN_D, _lib.MAF_MAX_D, _lib.MAF_MAX_H, _lib.MAF_MAX_K) == (2, 8192, 1024, 16)
+    from generative_models_amd import _build
+    assert "gm_maf.hip" in _build.SOURCES and "gm_gemm.hip" == _build.SOURCES[0]
+    assert os.path.isfile(os.path.join(_build.CSRC, "gm_maf.h"))
+    src = open(os.path.join(_build.CSRC, "gm_maf.h")).read() + open(os.path.join(_build.CSRC, "gm_maf.hip")).read()
+    assert '#include "gm_nvp.h"' in src and "nvp_s(" in src and "tanhf" not in src     # s is formed in one place
+
+
+def _mk(ct, base, **kw):
+    v = dict(base)
+    v.update(kw)
+    return ct(*[v[n] for n, _ in ct._fields_])
+
+
+def test_kernels_reject_null_out_of_limit_and_aliased_arguments():
+    """Host arrays stand in for device ones: every call below must return before it launches anything."""
+    lib = _lib.load()
+    a = [np.zeros(1 << 15, dtype=np.float32) for _ in range(10)]
+    iv = [np.zeros(64, dtype=np.int32) for _ in range(2)]
+    p = lambda i: a[i].ctypes.data
+    B, D, H = 4, 10, 7
+    for name in NEW:
+        assert getattr(lib, name)(None, None) == _lib.GM_EINVAL, name
+        assert b"bad argument" in lib.gm_last_error()
+
+    def refused(name, ct, base, cases):
+        for kw in cases:
+            assert getattr(lib, name)(None, ctypes.byref(_mk(ct, base, **kw))) == _lib.GM_EINVAL, (name, kw)
+            assert b"bad argument" in lib.gm_last_error()
+
+    cpl = dict(y=p(0), ldy=D, ma=p(1), ldma=2 * D, u=p(2), ldu=D, logdet=p(3), s_cap=2.0, B=B, D=D)
+    refused("gm_maf_couple", ops_fused.MafCoupleArgs, cpl, [
+        dict(B=0), dict(D=1), dict(D=8193), dict(s_cap=0.0), dict(s_cap=8.5), dict(s_cap=float("nan")), dict(y=None),
+        dict(ma=None), dict(u=None), dict(logdet=None), dict(ldy=D - 1), dict(ldma=2 * D - 1), dict(ldu=D - 1),
+        dict(u=p(0)), dict(u=p(1)), dict(logdet=p(2)), dict(logdet=p(0)), dict(logdet=p(1))])
+    bwd = dict(ma=p(0), ldma=2 * D, u=p(1), ldu=D, g=p(2), ldg=D, dout=p(3), lddout=2 * D, dy=p(4), lddy=D, c=-0.25,
+               s_cap=2.0, B=B, D=D)
+    refused("gm_maf_couple_bwd", ops_fused.MafCoupleBwdArgs, bwd, [
+        dict(B=0), dict(D=1), dict(D=8193), dict(s_cap=0.0), dict(s_cap=9.0), dict(c=float("nan")), dict(c=float("inf")),
+        dict(ma=None), dict(u=None), dict(g=None), dict(dout=None), dict(ldma=2 * D - 1), dict(ldu=D - 1),
+        dict(ldg=D - 1), dict(lddout=2 * D - 1), dict(lddy=D - 1), dict(dy=p(3)), dict(dout=p(0)), dict(dout=p(1)),
+        dict(dout=p(2)), dict(dy=p(0)), dict(dy=p(1)), dict(dy=p(2))])
+    msk = dict(W1=p(0), m1=p(1), v1=p(2), W2=p(3), m2=p(4), v2=p(5), m_in=iv[0].ctypes.data, m_h=iv[1].ctypes.data, D=D,
+               H=H)
+    refused("gm_maf_mask", ops_fused.MafMaskArgs, msk, [
+        dict(D=1), dict(D=8193), dict(H=0), dict(H=1025), dict(W1=None), dict(W2=None), dict(m_in=None), dict(m_h=None),
+        dict(W2=p(0)), dict(m1=None), dict(v1=None), dict(m2=None), dict(v2=None)])
+    inv = dict(u=p(0), ldu=D, y=p(1), ldy=D, s=p(2), lds=D, W2=p(3), b2=p(4), W1T=p(5), b1=p(6), m_h=iv[1].ctypes.data,
+               inv_order=iv[0].ctypes.data, s_cap=2.0, n=B, D=D, H=H)
+    refused("gm_maf_invert", ops_fused.MafInvertArgs, inv, [
+        dict(n=0), dict(n=-1), dict(n=(1 << 32) + 1), dict(D=1), dict(D=8193), dict(H=0), dict(H=1025), dict(s_cap=0.0),
+        dict(s_cap=8.5), dict(s_cap=float("nan")), dict(u=None), dict(y=None), dict(W2=None), dict(b2=None),
+        dict(W1T=None), dict(b1=None), dict(m_h=None), dict(inv_order=None), dict(ldu=D - 1), dict(ldy=D - 1),
+        dict(lds=D - 1), dict(y=p(0)), dict(s=p(0)), dict(s=p(1))])
+    for t in a:
+        assert not t.any()                                                # nothing was written
+    with pytest.raises(_lib.GMError):
+        _lib.call("gm_maf_invert", None, None)
+
+
+def test_struct_layout_matches_the_c_header(tmp_path):
+    gcc = shutil.which("gcc") or shutil.which("cc")
+    if gcc is None:
+        pytest.skip("no host C compiler")
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "gm_hip.h"', 'int main(void) {']
+    for cname, ct in STRUCTS.items():
+        lines.append('printf("%s size %%zu\\n", sizeof(%s));' % (cname, cname))
+        for fname, _ in ct._fields_:
+            lines.append('printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, fname, cname, fname))
+    lines += ['return 0;', '}']
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "layout"
+    subprocess.run([gcc, "-I", os.path.join(os.path.dirname(HERE), "include"), str(src), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    seen = 0
+    for line in out.splitlines():
+        cname, field, val = line.split()
+        ct = STRUCTS[cname]
+        if field == "size":
+            assert ctypes.sizeof(ct) == int(val), (cname, ctypes.sizeof(ct), val)
+        else:
+            assert getattr(ct, field).offset == int(val), (cname, field)
+        seen += 1
+    assert seen == sum(len(ct._fields_) + 1 for ct in STRUCTS.values())
+
+
+class _Mine(maf.MAFTrainer):
+    def compute_batch(self, batch):
+        return super().compute_batch(batch)
+
+
+def test_path_selection():
+    assert _trainer(maf.MAF(16, 8, 3))._stock()
+    assert _trainer(maf.MAF(7, 1, 1, "random", 4), alpha=0.0, levels=2, s_cap=8)._stock()
+    assert _trainer(maf.MAF(16, 8, 16))._stock()
+    assert not _trainer(maf.MAF(16, 8, 3), cls=_Mine)._stock()                     # an overridden hook
+    m = maf.MAF(16, 8, 3)
+    m.layers[1].extra = torch.nn.Linear(2, 2)
+    assert not _trainer(m)._stock()                                                # an edited layer
+    m = maf.MAF(16, 8, 3)
+    m.layers[2].out = torch.nn.Linear(8, 16)
+    assert not _trainer(m)._stock()                                                # an out layer of another width
+    m = maf.MAF(16, 8, 3)
+    ins, m_h = gmaf.degrees(16, 8, 1)
+    m.layers.append(maf.MAFLayer(ins[0], m_h))
+    assert not _trainer(m)._stock()                                                # a layer more than num_layers
+    m = maf.MAF(16, 8, 3)
+    m.norm = torch.nn.BatchNorm1d(16)
+    assert not _trainer(m)._stock()                                                # another layer
+    m = maf.MAF(16, 8, 3)
+    m.layers[0].m_h = m.layers[0].m_h.long()
+    assert not _trainer(m)._stock()                                                # a degree buffer of another type
+    assert not _trainer(maf.MAF(16, 8, 3), s_cap=9.0)._stock()                     # a setting outside the kernels' limits
+
+    class Sub(maf.MAF):
+        pass
+    assert not _trainer(Sub(16, 8, 3))._stock()                                    # a subclassed model
+
+
+def test_data_parallel_is_refused():
+    m = maf.MAF(16, 8, 3)
+    for kw in (dict(world_size=2), dict(force_dp=True)):
+        with pytest.raises(_lib.GMError, match="one GPU"):
+            gmaf.MAFEngine(m, "cpu", trainer=_trainer(m), **kw)
+    tr = _trainer(m)
+    tr.force_dp = True
+    with pytest.raises(_lib.GMError, match="one GPU"):
+        tr.train(1)
+    m.layers[0].extra = torch.nn.Linear(2, 2)
+    with pytest.raises(_lib.GMError, match="general path"):
+        gmaf.MAFEngine(m, "cpu", trainer=_trainer(m))
+
+
+def test_checkpoint_config_is_checked_under_strict():
+    """The settings a checkpoint carries -- order, order_seed, alpha, levels, s_cap, seed -- are compared by configure()
+    before anything is allocated on a device or launched: a differing one is refused unless the load was lenient."""
+    m = maf.MAF(16, 8, 2, "random", 6)
+    tr = _trainer(m, alpha=0.1, levels=64, s_cap=3.0)
+    tr.seed = 9
+    eng = gmaf.MAFEngine(m, "cpu", trainer=tr)
+    now = eng._settings()
+    assert now == {"order": "random", "order_seed": 6, "alpha": 0.1, "levels": 64, "s_cap": 3.0, "seed": 9}
+    n = eng.fp.m.numel()
+    for key, other in (("order", "natural"), ("order_seed", 0), ("alpha", 0.05), ("levels", 256), ("s_cap", 2.0),
+                       ("seed", 0)):
+        saved = dict(now, B=8, lr=1e-3, weight_decay=0.0)
+        saved[key] = other
+        resume = {"m": torch.zeros(n), "v": torch.zeros(n), "step": 5, "config": saved}
+        with pytest.raises(_lib.GMError, match="different settings") as ei:
+            eng.configure(8, 5, 1e-3, 0.0, resume=resume)
+        assert key in str(ei.value)
+    src = inspect.getsource(maf.MAFTrainer.save_checkpoint)
+    assert "noise_steps" in src
+
+
+def test_reference_training_clears_the_learning_tests_bound():
+    """The GPU learning test's premise, checked on its reference: 150 Adam batches of 16 on the 4-pattern data take the
+    fp64 reference's validation NLL below the identity flow's on the same validation stream."""
+    D, H, K, b = 16, 8, 2, 16
+    cfg = dict(K=K, s_cap=2.0, alpha=0.05, levels=256)
+    x = R.pattern_data(64, D)
+    torch.manual_seed(1234)
+    m = maf.MAF(D, H, K)
+    noise = lambda tag, step, n: torch.from_numpy(gmaf.uniforms_reference(n, D, 5, step, tag).astype(np.float64))
+    P0 = R.f64(m.state_dict())
+    ident = np.mean([(R.nll_rows(P0, x[i:i + b].double(), noise(R.TAG_EVAL, i // b, b), cfg).mean()).item()
+                     for i in range(0, 64, b)])
+    P = R.params(P0)
+    opt = torch.optim.Adam([v for v in P.values() if v.is_floating_point()], lr=1e-3)
+    g = torch.Generator().manual_seed(0)
+    for step in range(150):
+        xb = x[torch.randperm(64, generator=g)[:b]].double()
+        opt.zero_grad()
+        (R.nll_rows(P, xb, noise(R.TAG_TRAIN, step, b), cfg).sum() / b).backward()
+        opt.step()
+    with torch.no_grad():
+        val = np.mean([(R.nll_rows(P, x[i:i + b].double(), noise(R.TAG_EVAL, i // b, b), cfg).mean()).item()
+                       for i in range(0, 64, b)])
+        for k in range(K):                           # masked entries never moved
+            M1, M2 = R.layer_masks(P, k)
+            assert not P["layers.%d.linear.weight" % k][M1 == 0].any() and not P["layers.%d.out.weight" % k][M2 == 0].any()
+    print("identity", ident, "trained", val)
+    assert val < ident

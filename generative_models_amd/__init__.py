@@ -85,8 +85,14 @@ def __getattr__(name):
     """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine, SNGAN / SNGANTrainer / SNGANEngine,
     DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine, NFVAE / NFVAETrainer / NFVAEEngine, CatVAE /
     CatVAETrainer / CatVAEEngine, RealNVP / RealNVPTrainer / RealNVPEngine, RBM / RBMTrainer / RBMEngine, VQVAE /
-    VQVAETrainer / VQVAEEngine and MAF / MAFTrainer / MAFEngine, imported on first use (importing the package stays free
-    of torch)."""
+    VQVAETrainer / VQVAEEngine, MAF / MAFTrainer / MAFEngine and IAFVAE / IAFVAETrainer / IAFVAEEngine, imported on first
+    use (importing the package stays free of torch)."""
+    if name in ("IAFVAE", "IAFVAETrainer"):
+        from . import iafvae
+        return getattr(iafvae, name)
+    if name == "IAFVAEEngine":
+        from . import engine
+        return engine.IAFVAEEngine
     if name in ("MAF", "MAFTrainer", "MAFEngine"):
         from . import maf
         return getattr(maf, name)

@@ -125,6 +125,9 @@ class CorruptArgs(ctypes.Structure):
 IWAE_TAG_TRAIN, IWAE_TAG_EVAL = 0x49574145, 0x49574556      # GM_IWAE_TAG_TRAIN / GM_IWAE_TAG_EVAL
 IWAE_MAX_K, IWAE_MAX_Z = 64, 32                             # GM_IWAE_MAX_K / GM_IWAE_MAX_Z
 FLOW_MAX_K, FLOW_PART_STRIDE = 32, 68                       # GM_FLOW_MAX_K / GM_FLOW_PART_STRIDE
+IAF_MIN_Z, IAF_MAX_Z, IAF_MAX_K, IAF_MIN_F, IAF_MAX_F, IAF_MAX_C = 2, 32, 8, 4, 64, 32     # GM_IAF_* (include/gm_hip.h)
+IAF_PART_ROWS = 64                                          # GM_IAF_PART_ROWS
+# (gm_iaf_params / gm_iaf_step_args travel by pointer; their ctypes forms live in ops_fused)
 CAT_TAG_TRAIN, CAT_TAG_EVAL = 0x43415454, 0x43415445        # GM_CAT_TAG_TRAIN / GM_CAT_TAG_EVAL
 CAT_MIN_C, CAT_MAX_C, CAT_MAX_NC = 2, 64, 1024              # GM_CAT_MIN_C / GM_CAT_MAX_C / GM_CAT_MAX_NC
 CAT_RELAXED, CAT_ST, CAT_DISCRETE, CAT_NOISE = 0, 1, 2, 3   # GM_CAT_RELAXED / _ST / _DISCRETE / _NOISE
@@ -400,6 +403,9 @@ _SIGNATURES = {
     "gm_flow_sample": (c_int, [_P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int]),
     "gm_flow_reduce": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int]),
     "gm_flow_step": (c_int, [_P, _P]),
+    "gm_iaf_sample": (c_int, [_P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int]),
+    "gm_iaf_reduce": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int]),
+    "gm_iaf_step": (c_int, [_P, _P]),
     "gm_cat_sample": (c_int, [_P, _P, _P]),
     "gm_cat_reduce": (c_int, [_P, _P, _P]),
     "gm_vq_quantise": (c_int, [_P, _P]),

@@ -895,6 +895,121 @@ def flow_step(part, B, u, w, b, moments, sched, sched_slot=NO_SLOT, grads=None, 
     _lib.call("gm_flow_step", stream or stream_ptr(), ctypes.byref(a))
 
 
+# ---- Inverse-autoregressive-flow posterior of the IAF-VAE (csrc/gm_iaf.hip; iafvae.py) -----------------------------
+class IafParams(ctypes.Structure):
+    """gm_iaf_params (include/gm_hip.h): the K layers' W1 [K, F, Z], U [K, F, C], b1 [K, F], W2 [K, 2Z, F], b2 [K, 2Z]."""
+    _fields_ = [("W1", ctypes.c_void_p), ("U", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("W2", ctypes.c_void_p),
+                ("b2", ctypes.c_void_p), ("K", ctypes.c_int), ("F", ctypes.c_int), ("C", ctypes.c_int)]
+
+
+class IafStepArgs(ctypes.Structure):
+    """gm_iaf_step_args (include/gm_hip.h): gm_iaf_step's arguments as one block."""
+    _fields_ = [("part", ctypes.c_void_p), ("nparts", ctypes.c_int), ("p", ctypes.c_void_p * 5),
+                ("g", ctypes.c_void_p * 5), ("m", ctypes.c_void_p * 5), ("v", ctypes.c_void_p * 5),
+                ("m_in", ctypes.c_void_p), ("sched", ctypes.c_void_p), ("sched_slot", _lib.Slot),
+                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("K", ctypes.c_int), ("Z", ctypes.c_int), ("F", ctypes.c_int),
+                ("C", ctypes.c_int)]
+
+
+def _iaf_f32(t, shape, what):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise _lib.GMError("%s must be a contiguous float32 device tensor of shape %s, got %s"
+                           % (what, tuple(shape), tuple(t.shape)))
+
+
+def iaf_shapes(K, Z, F, C):
+    """The shapes of (W1, U, b1, W2, b2); U's is None when C == 0."""
+    return (K, F, Z), ((K, F, C) if C else None), (K, F), (K, 2 * Z, F), (K, 2 * Z)
+
+
+def iaf_params(W1, U, b1, W2, b2):
+    """A gm_iaf_params block over the flow's stacked tensors (contiguous float32 device tensors that outlive every launch
+    and captured graph reading them); U is None when the flow has no context.  The block carries .Z beside K, F, C."""
+    K, F, Z = W1.shape
+    C = 0 if U is None else U.shape[2]
+    for t, shp, nm in zip((W1, U, b1, W2, b2), iaf_shapes(K, Z, F, C), ("W1", "U", "b1", "W2", "b2")):
+        if shp is not None:
+            _iaf_f32(t, shp, "iaf_params: " + nm)
+    blk = IafParams(W1.data_ptr(), U.data_ptr() if C else None, b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), K, F, C)
+    blk.Z = Z
+    return blk
+
+
+def iaf_part_stride(Z, F, C):
+    """Floats per layer of a partial block (GM_IAF_PART_STRIDE): [dW1 | dU | db1 | dW2 | db2]."""
+    return F * Z + F * C + F + 2 * Z * F + 2 * Z
+
+
+def iaf_nparts(B, k):
+    """Partial blocks of a batch of B images of k samples (GM_IAF_PARTS): a workgroup owns max(1, 64 // k) images."""
+    ipw = max(1, _lib.IAF_PART_ROWS // k)
+    return (B + ipw - 1) // ipw
+
+
+def iaf_parts(B, k, K, Z, F, C, device="cuda"):
+    """The partial-gradient buffer iaf_reduce fills and iaf_step sums: [iaf_nparts(B, k), K, iaf_part_stride(Z, F, C)]."""
+    return torch.zeros(iaf_nparts(B, k), K, iaf_part_stride(Z, F, C), device=device)
+
+
+def iaf_sample(ml, z, lp, noise, flow, B, k, Z, stream=None):
+    """z_K [B k, Z] and lp [B k] of the k samples of each of B images from ml [B, 2Z + C] = [mu | lv | h] through the
+    chain `flow` (an iaf_params block) (gm_iaf_sample)."""
+    if _rows2d(ml, "ml").shape[0] < B or ml.shape[1] < 2 * Z + flow.C or _rows2d(z, "z").shape[0] < B * k \
+            or z.shape[1] < Z or lp.numel() < B * k or not lp.is_contiguous() or flow.Z != Z:
+        raise _lib.GMError("iaf_sample: ml %s / z %s / lp %s do not fit B=%d, k=%d, Z=%d, C=%d"
+                           % (tuple(ml.shape), tuple(z.shape), tuple(lp.shape), B, k, Z, flow.C))
+    _lib.call("gm_iaf_sample", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(flow), ml.data_ptr(), _ld(ml),
+              z.data_ptr(), _ld(z), lp.data_ptr(), B, k, Z)
+
+
+def iaf_reduce(ml, wn, dzdec, dml, part, noise, flow, B, k, Z, stream=None):
+    """d loss / d [mu | lv | h] -> dml [B, 2Z + C] and the flow parameters' partial gradient blocks -> part (iaf_parts)
+    from dzdec [B k, Z] = dHdec Wd1 and the weights wn [B k] (gm_iaf_reduce)."""
+    W = 2 * Z + flow.C
+    if _rows2d(ml, "ml").shape[0] < B or ml.shape[1] < W or _rows2d(dzdec, "dzdec").shape[0] < B * k \
+            or dzdec.shape[1] < Z or _rows2d(dml, "dml").shape[0] < B or dml.shape[1] < W or wn.numel() < B * k \
+            or not wn.is_contiguous() or not part.is_contiguous() or flow.Z != Z \
+            or part.numel() < iaf_nparts(B, k) * flow.K * iaf_part_stride(Z, flow.F, flow.C):
+        raise _lib.GMError("iaf_reduce: the arrays do not fit B=%d, k=%d, Z=%d, K=%d, F=%d, C=%d"
+                           % (B, k, Z, flow.K, flow.F, flow.C))
+    _lib.call("gm_iaf_reduce", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(flow), ml.data_ptr(), _ld(ml),
+              wn.data_ptr(), dzdec.data_ptr(), _ld(dzdec), dml.data_ptr(), _ld(dml), part.data_ptr(), B, k, Z)
+
+
+def iaf_step(part, B, k, params, m_in, moments, sched, sched_slot=NO_SLOT, grads=None, betas=(0.9, 0.999), eps=1e-8,
+             weight_decay=0.0, stream=None):
+    """The flow's optimiser step (gm_iaf_step): iaf_reduce's blocks for a batch of B images of k samples summed, masked
+    entries left alone, the gradients written to grads when given, and one Adam step taken at the schedule's slot.
+    params = (W1, U, b1, W2, b2) with U None when C == 0; moments = ((m, v) per parameter, in that order, None for a
+    missing U); grads likewise; m_in [K, Z] int32 on the device."""
+    W1, U = params[0], params[1]
+    K, F, Z = W1.shape
+    C = 0 if U is None else U.shape[2]
+    shapes = iaf_shapes(K, Z, F, C)
+    nparts = iaf_nparts(B, k)
+    if part.numel() < nparts * K * iaf_part_stride(Z, F, C) or not part.is_contiguous():
+        raise _lib.GMError("iaf_step: %d partial blocks are needed" % nparts)
+    if not (m_in.is_cuda and m_in.dtype == torch.int32 and m_in.is_contiguous() and tuple(m_in.shape) == (K, Z)):
+        raise _lib.GMError("iaf_step: m_in must be a contiguous int32 device tensor of shape %s" % ((K, Z),))
+    arr = lambda: (ctypes.c_void_p * 5)()
+    ap, ag, am, av = arr(), arr(), arr(), arr()
+    for t, shp in enumerate(shapes):
+        if shp is None:
+            continue
+        n = params[t].numel()
+        _iaf_f32(params[t], shp, "iaf_step: a parameter")
+        ap[t] = params[t].data_ptr()
+        for dst, src in ((am, moments[t][0]), (av, moments[t][1])) + (((ag, grads[t]),) if grads is not None else ()):
+            if not (src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and src.numel() == n):
+                raise _lib.GMError("iaf_step: every moment and gradient must be a contiguous float32 device tensor "
+                                   "sized like its parameter")
+            dst[t] = src.data_ptr()
+    a = IafStepArgs(part.data_ptr(), nparts, ap, ag, am, av, m_in.data_ptr(), sched.data_ptr(), sched_slot, betas[0],
+                    betas[1], eps, weight_decay, K, Z, F, C)
+    _lib.call("gm_iaf_step", stream or stream_ptr(), ctypes.byref(a))
+
+
 # ---- Gumbel-Softmax posterior of the categorical VAE (csrc/gm_cat.hip; catvae.py) ----------------------------------
 class CatArgs(ctypes.Structure):
     """gm_cat_args (include/gm_hip.h): gm_cat_sample's and gm_cat_reduce's arguments as one block."""

@@ -1027,6 +1027,78 @@ class NFVAEEngine(IWAEEngine):
                       grads=self.Fgrads, weight_decay=self.wd, stream=st)
 
 
+class IAFVAEEngine(IWAEEngine):
+    """The inverse-autoregressive-flow VAE (iafvae.py holds the contract): IWAEEngine's batch with a chain of K masked
+    conditioners between z_0 and the decoder, and the encoder's head widened to [mu ; log_var ; context] (2Z + C rows:
+    launches 2, 11 and 12 carry the context and its gradient with no launch of their own).  13 launches per training
+    batch: the IWAE's 12 with launch 3 replaced by gm_iaf_sample (z_K, lp with the log-determinants) and launch 10 by
+    gm_iaf_reduce (d loss / d [mu | lv | h] and the flow's partial gradient blocks), and gm_iaf_step (the blocks' sum,
+    the masks, Adam on W1, U, b1, W2, b2 at the batch's schedule slot) behind gm_iaf_reduce, which is the last reader of
+    the flow's parameters.  The flow's parameters, gradients and moments are views of the engine's flat buffers like
+    every other parameter.  One GPU only."""
+
+    one_gpu = "the IAF-VAE engine"
+
+    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
+                 trainer=None):
+        self._refuse_dp(world_size, force_dp)
+        from .iafvae import _flow_stock, fused_sizes
+        sizes = tuple(int(getattr(model, n, -1)) for n in ("z_dim", "num_flows", "flow_hidden", "context_dim"))
+        if not (fused_sizes(*sizes) and _flow_stock(model)):
+            raise GMError("IAFVAEEngine: the fused kernels take 2 <= z_dim <= 32, 1 <= num_flows <= 8, 4 <= flow_hidden "
+                          "<= 64 in multiples of 4 and 0 <= context_dim <= 32 with IAFVAE's own flow (got %s); "
+                          "IAFVAETrainer trains these on the general path" % (sizes,))
+        self.K, self.F, self.C = sizes[1:]
+        super().__init__(model, device, use_graph=use_graph, trainer=trainer)
+        fp, fl = self.fp, model.flow
+        self.Fparams, self.Fgrads, self.Fmoments = [], [], []
+        seg = lambda buf, i: buf[fp.offsets[i]:fp.offsets[i] + fp.params[i].numel()]
+        for q in fl.tensors():                                   # W1, U (None when C = 0), b1, W2, b2
+            if q is None:
+                self.Fparams.append(None), self.Fgrads.append(None), self.Fmoments.append(None)
+                continue
+            i = [j for j, p in enumerate(fp.params) if p is q][0]
+            self.Fparams.append(fp.views[i])
+            self.Fgrads.append(seg(fp.grad, i))
+            self.Fmoments.append((seg(fp.m, i), seg(fp.v, i)))
+        self.m_in = fl.m_in.to(device).contiguous()
+
+    def _head(self, enc):
+        lins = [enc.mu, enc.log_var] + ([enc.context] if hasattr(enc, "context") else [])
+        return tuple(l.weight for l in lins), tuple(l.bias for l in lins), enc.mu.weight.shape[0]
+
+    def _extra_params(self, model):
+        return [p for p in model.flow.tensors() if p is not None]
+
+    def _settings(self):
+        return dict(num_flows=self.K, flow_hidden=self.F, context_dim=self.C, **super()._settings())
+
+    def _graph_args(self):
+        return (self.m_in.data_ptr(),)
+
+    def _alloc(self, B):
+        if self._bufB == B:
+            return
+        super()._alloc(B)
+        from . import ops_fused as of_
+        self.fpart = of_.iaf_parts(B, self.k, self.K, self.Z, self.F, self.C, device=self.device)
+
+    def _flow(self):
+        from . import ops_fused as of_
+        return of_.iaf_params(*self.Fparams)
+
+    def _sample(self, st, nz, b, t=0, train=True):
+        from . import ops_fused as of_
+        of_.iaf_sample(self.ml, self.Zs, self.lp, nz, self._flow(), b, self.k, self.Z, stream=st)
+
+    def _reduce(self, st, nz, b, adam):
+        from . import ops_fused as of_
+        of_.iaf_reduce(self.ml, self.wn, self.dzdec, self.dml, self.fpart, nz, self._flow(), b, self.k, self.Z,
+                       stream=st)
+        of_.iaf_step(self.fpart, b, self.k, self.Fparams, self.m_in, self.Fmoments, adam["sched"], adam["sched_slot"],
+                     grads=self.Fgrads, weight_decay=self.wd, stream=st)
+
+
 class CatVAEEngine(IWAEEngine):
     """The categorical VAE (catvae.py holds the contract): IWAEEngine's 12-launch batch at k = 1 with the `logits` layer
     (width N C) as the encoder's head instead of the packed [mu | log_var], launch 3 replaced by gm_cat_sample (the

@@ -1084,6 +1084,62 @@ typedef struct gm_flow_step_args {
  * constraint onto u and w, then gm_adam's step on u, w and b at the schedule's slot. */
 int gm_flow_step(void* stream, const gm_flow_step_args* a);
 
+/* ---- Inverse-autoregressive-flow posterior of the IAF-VAE (csrc/gm_iaf.hip; iafvae.py holds the contract, DESIGN.md
+ * section 31).  gm_iwae_sample / gm_iwae_reduce with a chain of K masked conditioners between z_0 = mu + eps exp(lv / 2)
+ * and the decoder; rows, noise block and the limit on k are the IWAE's.  ml [B, 2Z + C] = [mu | lv | h], h the context.
+ * Per layer and row: a = elu(W1 z + U h + b1) [F], m = W2[0:Z] a + b2[0:Z], s = W2[Z:2Z] a + b2[Z:2Z], g = sigmoid(s),
+ * logdet = -sum softplus(-s), z <- g z + (1 - g) m.  The parameters hold the masked values (MADE's degrees, iafvae.py);
+ * only gm_iaf_step reads the degrees.  Limits: 2 <= Z <= 32, 1 <= K <= 8, 4 <= F <= 64 with F % 4 == 0, 0 <= C <= 32,
+ * 1 <= k <= 64.  Fixed reduction orders, no atomics.  Out-of-range, NULL or aliased arguments return GM_EINVAL before
+ * any launch. */
+#define GM_IAF_MIN_Z 2
+#define GM_IAF_MAX_Z 32
+#define GM_IAF_MAX_K 8
+#define GM_IAF_MIN_F 4
+#define GM_IAF_MAX_F 64
+#define GM_IAF_MAX_C 32
+#define GM_IAF_PART_ROWS 64                    /* sample rows per workgroup of gm_iaf_reduce */
+/* floats per layer of a partial block: [d W1 (F Z) | d U (F C) | d b1 (F) | d W2 (2Z F) | d b2 (2Z)] */
+#define GM_IAF_PART_STRIDE(Z, F, C) ((F) * (Z) + (F) * (C) + (F) + 2 * (Z) * (F) + 2 * (Z))
+/* partial blocks of a batch: a workgroup of gm_iaf_reduce owns max(1, 64 / k) whole images */
+#define GM_IAF_PARTS(B, k) \
+    (((B) + (GM_IAF_PART_ROWS / (k) > 1 ? GM_IAF_PART_ROWS / (k) : 1) - 1) / (GM_IAF_PART_ROWS / (k) > 1 ? GM_IAF_PART_ROWS / (k) : 1))
+typedef struct gm_iaf_params {
+    const float* W1;                          /* [K, F, Z] contiguous */
+    const float* U;                           /* [K, F, C] contiguous; ignored (may be NULL) when C == 0 */
+    const float* b1;                          /* [K, F] */
+    const float* W2;                          /* [K, 2Z, F], 16-byte aligned: rows 0 .. Z-1 the shift m, Z .. 2Z-1 the gate s */
+    const float* b2;                          /* [K, 2Z] */
+    int K, F, C;
+} gm_iaf_params;
+/* z [B*k, Z] = z_K and lp[b k + j] = 1/2 |eps|^2 + 1/2 sum_c lv_c + sum_l logdet_l - 1/2 |z_K|^2; ldml >= 2Z + C. */
+int gm_iaf_sample(void* stream, const gm_iwae_noise* n, const gm_iaf_params* f, const float* ml, int64_t ldml,
+                  float* z, int64_t ldz, float* lp, int B, int k, int Z);
+/* The backward of gm_iaf_sample: eps and the chain rebuilt (the K layer inputs of the rows in flight kept in LDS), then
+ * walked back from g_K = wn_j z_K + dzdec_j with d loss / d logdet = -wn_j.  dml [B, 2Z + C] = [sum_j g_0 | sum_j g_0
+ * eps_j exp(lv / 2) / 2 - 1/2 | sum_j dh_j], j ascending.  part takes GM_IAF_PARTS(B, k) blocks of [K,
+ * GM_IAF_PART_STRIDE(Z, F, C)] floats, one per workgroup: the sums over its rows, ascending, of the five gradients
+ * (unmasked: gm_iaf_step applies the masks). */
+int gm_iaf_reduce(void* stream, const gm_iwae_noise* n, const gm_iaf_params* f, const float* ml, int64_t ldml,
+                  const float* wn, const float* dzdec, int64_t lddz, float* dml, int64_t lddml, float* part, int B,
+                  int k, int Z);
+typedef struct gm_iaf_step_args {
+    const float* part;                        /* gm_iaf_reduce's partial blocks */
+    int nparts;                               /* their number: GM_IAF_PARTS(B, k) */
+    float* p[5];                              /* W1, U, b1, W2, b2: stepped in place (U's entries ignored when C == 0) */
+    float* g[5];                              /* the gradients, written when not NULL (all or none) */
+    float* m[5]; float* v[5];                 /* Adam moments, laid out like their parameters */
+    const int32_t* m_in;                      /* [K, Z]: the layers' input degrees (the hidden ones follow MADE's rule) */
+    const float* sched;                       /* [steps, 2]: lr / (1 - b1^t), sqrt(1 - b2^t) (gm_adam's) */
+    gm_slot sched_slot;
+    double beta1, beta2, eps, weight_decay;
+    int K, Z, F, C;
+} gm_iaf_step_args;
+/* One thread per entry: the partial blocks summed in ascending order, then gm_adam's step at the schedule's slot.  A
+ * masked entry (W1 (j, i) with m_h[j] < m_in[i]; W2 (d, j) with m_in[d] <= m_h[j]; m_h[j] = 1 + j (Z - 1) / F) is
+ * skipped: it and its moments are left as they are (0.0), its gradient is written as 0.0. */
+int gm_iaf_step(void* stream, const gm_iaf_step_args* a);
+
 /* ---- Gumbel-Softmax posterior of the categorical VAE (csrc/gm_cat.hip; catvae.py holds the contract, DESIGN.md
  * section 23).  N categorical variables of C classes per sample row, rows image-major, gm_iwae_noise's counter layout
  * under the two tags below: element e = n C + c of noise row `row` is word e & 3 of Philox counter (q0 + (e >> 2), step,

@@ -454,6 +454,18 @@ def check_int(v, name, error=GMError):
     return int(v)
 
 
+def check_real(v, name, error=GMError):
+    """float(v) of a finite number (Python's or numpy's, no bool); else `error`."""
+    import math
+    import numpy as np
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise error("%s must be a number, got %r" % (name, v))
+    v = float(v)
+    if not math.isfinite(v):
+        raise error("%s must be finite, got %r" % (name, v))
+    return v
+
+
 def check_seed(seed, name="seed", error=GMError):
     """A counter-generator seed: an integer in [0, 2^64); else `error`."""
     seed = check_int(seed, name, error)

@@ -240,12 +240,8 @@ class CatVAETrainer(IWAETrainer):
 
     def viz_loss(self):
         """The training loss (sum_b -log w per batch) over the epochs."""
-        import matplotlib.pyplot as plt
-        plt.style.use("ggplot")
-        plt.plot(np.linspace(1, max(1, self.num_epochs), len(self.losses)), self.losses, "r")
-        plt.legend(["-log w"])
-        plt.title(self.name)
-        plt.show()
+        from . import viz
+        viz.one_loss_curve(self, "-log w")
 
     # ---- codes, samples ------------------------------------------------------------------------------------------------
     def decode(self, codes):

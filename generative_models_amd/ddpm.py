@@ -50,10 +50,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops, philox
+from . import _lib, ops, philox, viz
 from ._lib import (DDPM_MAX_E, DDPM_MAX_I, DDPM_MAX_T, DDPM_MIN_E, DDPM_TAG_E, DDPM_TAG_S, DDPM_TAG_T, DDPM_TAG_V,
                    DDPM_TAG_VE, GMError)
-from .trainers import FlatAdam, VAETrainer, _lin, _stock_module, stock, stock_model, to_cuda  # noqa: F401
+from .trainers import FlatAdam, OneLossTrainer, _lin, _stock_module, stock, stock_model, to_cuda  # noqa: F401
 from .engine import VAEEngine, _align4, _Linear
 
 TAG_T, TAG_E, TAG_V, TAG_VE, TAG_S = DDPM_TAG_T, DDPM_TAG_E, DDPM_TAG_V, DDPM_TAG_VE, DDPM_TAG_S
@@ -299,29 +299,22 @@ class DDPMEngine(VAEEngine):
 
 # ---- trainer ---------------------------------------------------------------------------------------------------------
 @stock
-class DDPMTrainer(VAETrainer):
+class DDPMTrainer(OneLossTrainer):
     """Trains a DDPM on L_simple and samples from it.  Histories: `losses` (one per training batch); the epoch line
     (mean training loss, validation loss); best_val_loss / best_model as the other VAE-family trainers; checkpoints
     (+ T, time_dim, seed in the optimizer state's config, checked under strict=True, and the number of training batches
     taken, so a resumed run continues the noise stream bit for bit).  One GPU only."""
-    _hook_names = ("compute_batch", "evaluate")
-    _series = (("losses", "recon"),)
-    _batch = "loss"
     _line = "Epoch[%d/%d], Loss: %.6f, Val Loss: %.6f"
     _one_gpu = "DDPMTrainer"
+    _error = DDPMError
+    _fused_ok = staticmethod(ddpm_fused_ok)
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, seed=0):
         self.seed = check_seed(seed)                 # before anything runs
         super().__init__(model, train_iter, val_iter, test_iter, viz=viz)
-        del self.kl_loss, self.recon_loss
-        self.losses = []
         self.noise_steps = 0                         # training batches taken: the next one's noise step
         self._eval_step = 0                          # batch index within an evaluate() call
         self._sampler = {}
-
-    def _stock(self):
-        return (self._hooks_stock() and ddpm_fused_ok(self.model) and self._loader_ok(self.train_iter)
-                and self._loader_ok(self.val_iter) and self.train_iter.batch_size == self.val_iter.batch_size)
 
     def _tables(self):
         from . import ops_fused as of_
@@ -333,26 +326,11 @@ class DDPMTrainer(VAETrainer):
         gm_ddpm_qsample on the contract's counter stream -- the training stream while the model trains, the validation
         one otherwise)."""
         from . import ops_fused as of_
-        images, _ = batch
-        x = to_cuda(images.view(images.shape[0], -1))
-        if not x.is_cuda:
-            raise GMError("generative_models_amd computes on MI355X only: no GPU is visible")
-        x = x.to(torch.float32).contiguous()
-        if self.model.training:
-            nz = of_.ddpm_noise(self.seed, True, step=self.noise_steps)
-            self.noise_steps += 1
-        else:
-            nz = of_.ddpm_noise(self.seed, False, step=self._eval_step)
-            self._eval_step += 1
-        xin, eps, _t = of_.ddpm_qsample(x, nz, self._tables())
+        x = self._flat_batch(batch)
+        train, step = self._noise_step()
+        xin, eps, _t = of_.ddpm_qsample(x, of_.ddpm_noise(self.seed, train, step=step), self._tables())
         out = self.model.denoiser(xin)
         return torch.sum((eps - out) ** 2) / (x.shape[0] * x.shape[1])
-
-    def evaluate(self, iterator):
-        """Mean over the batches of L_simple on the validation stream (batch i at noise step i)."""
-        self._eval_step = 0
-        with torch.no_grad():
-            return np.mean([self.compute_batch(batch).item() for batch in iterator])
 
     def _engine_class(self):
         import functools
@@ -463,17 +441,9 @@ class DDPMTrainer(VAETrainer):
     # ---- visualisation, checkpoints -----------------------------------------------------------------------------------
     viz_steps = 50               # sampler steps of the per-epoch sample grid (min(T, viz_steps))
 
-    def _viz_epoch(self, epoch):
-        if self.viz:
-            self.sample_images(epoch)
-
     def sample_images(self, epoch=-100, num_images=36, save=True):
-        from . import viz
         return viz.ddpm_sample_images(self, epoch, num_images, save, self.viz_dir,
                                       steps=min(self.model.T, self.viz_steps))
-
-    def generate_images(self, epoch=-100, num_outputs=36, save=True):
-        return self.sample_images(epoch, num_outputs, save)
 
     def log_likelihood(self, images=None, k=500, seed=0):
         raise GMError("log_likelihood needs vae.py's Encoder and Decoder unchanged (a DDPM has neither); parzen() "
@@ -483,12 +453,7 @@ class DDPMTrainer(VAETrainer):
         raise GMError("a DDPM has no encoder: denoise(images, t) returns the one-shot estimate of a noised image")
 
     def viz_loss(self):
-        import matplotlib.pyplot as plt
-        plt.style.use("ggplot")
-        plt.plot(np.linspace(1, max(1, self.num_epochs), len(self.losses)), self.losses, "r")
-        plt.legend(["L_simple"])
-        plt.title(self.name)
-        plt.show()
+        viz.one_loss_curve(self, "L_simple")
 
 
 __all__ = ["Denoiser", "DDPM", "DDPMTrainer", "DDPMEngine", "DDPMError", "tables", "reverse_table",

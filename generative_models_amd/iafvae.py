@@ -285,12 +285,8 @@ class IAFVAETrainer(IWAETrainer):
         b, k = x.shape[0], self.k
         mu, lv, h = self.model.encode(x)
         Z = mu.shape[1]
-        if self.model.training:
-            eps = of_.iwae_normals(b, k, Z, self.seed, self.noise_steps, TAG_TRAIN, device=x.device)
-            self.noise_steps += 1
-        else:
-            eps = of_.iwae_normals(b, k, Z, self.seed, self._eval_step, TAG_EVAL, device=x.device)
-            self._eval_step += 1
+        train, step = self._noise_step()
+        eps = of_.iwae_normals(b, k, Z, self.seed, step, TAG_TRAIN if train else TAG_EVAL, device=x.device)
         eps = eps.view(b, k, Z)
         z0 = mu[:, None, :] + eps * torch.exp(lv / 2)[:, None, :]
         hr = None if h is None else h[:, None, :].expand(b, k, h.shape[1]).reshape(b * k, -1)

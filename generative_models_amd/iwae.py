@@ -214,12 +214,8 @@ class IWAETrainer(VAETrainer):
         b, k = x.shape[0], self.k
         mu, lv = self.model.encoder(x)
         Z = mu.shape[1]
-        if self.model.training:
-            eps = of_.iwae_normals(b, k, Z, self.seed, self.noise_steps, TAG_TRAIN, device=x.device)
-            self.noise_steps += 1
-        else:
-            eps = of_.iwae_normals(b, k, Z, self.seed, self._eval_step, TAG_EVAL, device=x.device)
-            self._eval_step += 1
+        train, step = self._noise_step()
+        eps = of_.iwae_normals(b, k, Z, self.seed, step, TAG_TRAIN if train else TAG_EVAL, device=x.device)
         eps = eps.view(b, k, Z)
         z = mu[:, None, :] + eps * torch.exp(lv / 2)[:, None, :]
         xr = self.model.decoder(z.reshape(b * k, Z)).view(b, k, -1)
@@ -246,12 +242,8 @@ class IWAETrainer(VAETrainer):
 
     def viz_loss(self):
         """The training loss (sum_b -L_k per batch) over the epochs."""
-        import matplotlib.pyplot as plt
-        plt.style.use("ggplot")
-        plt.plot(np.linspace(1, max(1, self.num_epochs), len(self.losses)), self.losses, "r")
-        plt.legend(["-L_k"])
-        plt.title(self.name)
-        plt.show()
+        from . import viz
+        viz.one_loss_curve(self, "-L_k")
 
 
 __all__ = ["Encoder", "Decoder", "IWAE", "IWAETrainer", "IWAEError", "iwae_noise_reference", "iwae_reference",

@@ -37,9 +37,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops, philox
+from . import _lib, ops, philox, viz
 from ._lib import MADE_MAX_H, MADE_MAX_I, MADE_MIN_I, MADE_TAG_S, GMError
-from .trainers import FlatAdam, VAETrainer, _dataset_rows, _stock_module, stock, stock_model, to_cuda  # noqa: F401
+from .trainers import FlatAdam, OneLossTrainer, _dataset_rows, _stock_module, stock, stock_model  # noqa: F401
 from .engine import VAEEngine, _Linear
 
 TAG_MS = MADE_TAG_S
@@ -252,40 +252,21 @@ class MADEEngine(VAEEngine):
 
 # ---- trainer ---------------------------------------------------------------------------------------------------------
 @stock
-class MADETrainer(VAETrainer):
+class MADETrainer(OneLossTrainer):
     """Trains a MADE on its exact negative log-likelihood and samples from it.  Histories: `losses` (the NLL in nats per
     image, one per training batch); the epoch line (mean training NLL, validation NLL); best_val_loss / best_model as
     the other VAE-family trainers; checkpoints (+ order, order_seed in the optimizer state's config, checked under
     strict=True; resuming is bit-identical).  One GPU only."""
-    _hook_names = ("compute_batch", "evaluate")
-    _series = (("losses", "recon"),)
-    _batch = "loss"
     _line = "Epoch[%d/%d], NLL: %.6f, Val NLL: %.6f"
     _one_gpu = "MADETrainer"
-
-    def __init__(self, model, train_iter, val_iter, test_iter, viz=False):
-        super().__init__(model, train_iter, val_iter, test_iter, viz=viz)
-        del self.kl_loss, self.recon_loss
-        self.losses = []
-
-    def _stock(self):
-        return (self._hooks_stock() and made_fused_ok(self.model) and self._loader_ok(self.train_iter)
-                and self._loader_ok(self.val_iter) and self.train_iter.batch_size == self.val_iter.batch_size)
+    _error = MADEError
+    _fused_ok = staticmethod(made_fused_ok)
 
     def compute_batch(self, batch):
         """The batch's NLL in nats per image (general path: autograd over the fused linear kernels with weight *
         mask)."""
-        images, _ = batch
-        x = to_cuda(images.view(images.shape[0], -1))
-        if not x.is_cuda:
-            raise GMError("generative_models_amd computes on MI355X only: no GPU is visible")
-        x = x.to(torch.float32).contiguous()
+        x = self._flat_batch(batch)
         return nll_rows(self.model(x), x).sum() / x.shape[0]
-
-    def evaluate(self, iterator):
-        """Mean over the batches of the NLL in nats per image."""
-        with torch.no_grad():
-            return np.mean([self.compute_batch(batch).item() for batch in iterator])
 
     def _engine_class(self):
         return MADEEngine
@@ -362,31 +343,20 @@ class MADETrainer(VAETrainer):
         """images [n, pixels] with the pixels of degree <= n_known kept and the rest drawn by the sampler's rule;
         return_probs: (completed, the conditionals [n, I])."""
         n_known, seed = check_known(n_known, self.model.image_size), check_seed(seed)
-        x = images.reshape(images.shape[0], -1)
-        if x.shape[1] != self.model.image_size:
-            raise MADEError("images have %d pixels, the model %d" % (x.shape[1], self.model.image_size))
-        self._device()
-        x = to_cuda(x).to(torch.float32).contiguous()
+        x = self._rows(images)
         return self._draw(x.shape[0], seed, bool(return_probs), x, n_known)
 
     def log_likelihood(self, images=None, batch=1024):
         """The exact log p(x) of every image in nats (images=None: the whole test_iter) -> metrics.NLLResult(ll_mean,
         ll_stderr, n), from gm_made_bce's row partials."""
-        from . import metrics
-        ll = self.log_likelihood_rows(images, batch)
-        return metrics.NLLResult(float(ll.mean()), float(ll.std(unbiased=False)) / float(np.sqrt(ll.numel())),
-                                 int(ll.numel()))
+        return self._nll_result(self.log_likelihood_rows(images, batch))
 
     def log_likelihood_rows(self, images=None, batch=1024):
         """log p(x) per image, a float64 CPU tensor [n]."""
         from . import ops_fused as of_
-        dev = self._device()
-        x = _dataset_rows(self.test_iter) if images is None else images.reshape(images.shape[0], -1)
-        if x.shape[1] != self.model.image_size:
-            raise MADEError("images have %d pixels, the model %d" % (x.shape[1], self.model.image_size))
-        x = x.to(dev, torch.float32).contiguous()
+        x = self._rows(_dataset_rows(self.test_iter) if images is None else images)
         torch.cuda.synchronize()
-        part = torch.empty(x.shape[0], device=dev)
+        part = torch.empty(x.shape[0], device=x.device)
         for i in range(0, x.shape[0], batch):
             xb = x[i:i + batch]
             of_.made_bce(self._logits(xb), xb, part[i:], xb.shape[0], 1.0)
@@ -394,27 +364,14 @@ class MADETrainer(VAETrainer):
         return -part.double().cpu()
 
     # ---- visualisation, checkpoints -----------------------------------------------------------------------------------
-    def _viz_epoch(self, epoch):
-        if self.viz:
-            self.sample_images(epoch)
-
     def sample_images(self, epoch=-100, num_images=36, save=True):
-        from . import viz
         return viz.made_sample_images(self, epoch, num_images, save, self.viz_dir)
-
-    def generate_images(self, epoch=-100, num_outputs=36, save=True):
-        return self.sample_images(epoch, num_outputs, save)
 
     def reconstruct_images(self, images, epoch, save=True):
         raise GMError("a MADE has no latent code: complete(images, n_known) redraws the pixels after the first n_known")
 
     def viz_loss(self):
-        import matplotlib.pyplot as plt
-        plt.style.use("ggplot")
-        plt.plot(np.linspace(1, max(1, self.num_epochs), len(self.losses)), self.losses, "r")
-        plt.legend(["NLL (nats per image)"])
-        plt.title(self.name)
-        plt.show()
+        viz.one_loss_curve(self, "NLL (nats per image)")
 
 
 __all__ = ["MADE", "MADETrainer", "MADEEngine", "MADEError", "degrees", "masks", "inverse_order", "uniforms_reference",

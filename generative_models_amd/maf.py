@@ -49,7 +49,6 @@ launches plus the K transposed copies of linear.weight.  An overridden compute_b
 general loop -- autograd over ops.fused_linear with weight * mask and torch ops on the same u -- and a sampler of D passes
 per layer."""
 import functools
-import math
 
 import numpy as np
 import torch
@@ -57,7 +56,7 @@ import torch.nn as nn
 
 from . import _lib, made, ops, realnvp
 from ._lib import MAF_MAX_D, MAF_MAX_H, MAF_MAX_K, MAF_MIN_D, MAF_TAG_EVAL, MAF_TAG_TRAIN, GMError
-from .trainers import FlatAdam, VAETrainer, _dataset_rows, _stock_module, stock, stock_model, to_cuda  # noqa: F401
+from .trainers import FlatAdam, _stock_module, stock, stock_model  # noqa: F401
 from .engine import VAEEngine, _Linear
 
 TAG_TRAIN, TAG_EVAL, TAG_S = MAF_TAG_TRAIN, MAF_TAG_EVAL, realnvp.TAG_S
@@ -75,15 +74,6 @@ def _int(v, name):
 
 def check_seed(seed, name="seed"):
     return _lib.check_seed(seed, name, MAFError)
-
-
-def _real(v, name):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise MAFError("%s must be a number, got %r" % (name, v))
-    v = float(v)
-    if not math.isfinite(v):
-        raise MAFError("%s must be finite, got %r" % (name, v))
-    return v
 
 
 def check_config(image_size, hidden_dim, num_layers, order, order_seed):
@@ -105,14 +95,7 @@ def check_config(image_size, hidden_dim, num_layers, order, order_seed):
 
 def check_settings(alpha, levels, s_cap):
     """(alpha, levels, s_cap) of a trainer, validated against the kernels' limits; else MAFError."""
-    alpha, s_cap, levels = _real(alpha, "alpha"), _real(s_cap, "s_cap"), _int(levels, "levels")
-    if not (0.0 <= alpha < 0.5 and float(np.float32(alpha)) < 0.5):
-        raise MAFError("alpha must lie in [0, 0.5), got %r" % alpha)
-    if not 2 <= levels <= _lib.NVP_MAX_LEVELS:
-        raise MAFError("levels must lie in [2, %d], got %d" % (_lib.NVP_MAX_LEVELS, levels))
-    if not (0.0 < s_cap <= _lib.NVP_MAX_S_CAP and float(np.float32(s_cap)) > 0.0):
-        raise MAFError("s_cap must lie in (0, %d], got %r" % (_lib.NVP_MAX_S_CAP, s_cap))
-    return alpha, levels, s_cap
+    return realnvp.check_flow_settings(alpha, levels, s_cap, MAFError)
 
 
 # ---- the degrees and the masks in numpy (the tests' reference reads the same contract) ---------------------------------
@@ -363,26 +346,23 @@ class MAFEngine(VAEEngine):
 
 # ---- trainer ---------------------------------------------------------------------------------------------------------
 @stock
-class MAFTrainer(VAETrainer):
-    """Trains a MAF on its exact (dequantised) negative log-likelihood; samples, encodes and decodes.  Histories: `losses`
-    (the NLL in nats per image, one per training batch); the epoch line (mean training NLL, validation NLL);
-    best_val_loss / best_model as the other VAE-family trainers; checkpoints (+ order, order_seed, alpha, levels, s_cap,
-    seed in the optimizer state's config, checked under strict=True, and the number of training batches taken, so a
-    resumed run continues the noise stream bit for bit).  One GPU only."""
-    _hook_names = ("compute_batch", "evaluate")
-    _series = (("losses", "recon"),)
-    _batch = "loss"
-    _line = "Epoch[%d/%d], NLL: %.6f, Val NLL: %.6f"
+class MAFTrainer(realnvp.DequantFlowTrainer):
+    """Trains a MAF on its exact (dequantised) negative log-likelihood; samples, encodes and decodes: a
+    DequantFlowTrainer (realnvp.py) whose code is z itself and whose alpha, levels and s_cap are the trainer's
+    (sampling is K + 2 launches plus the K transposed copies for a stock model).  Histories: `losses` (the NLL in nats
+    per image, one per training batch); the epoch line (mean training NLL, validation NLL); best_val_loss / best_model
+    as the other VAE-family trainers; checkpoints (+ order, order_seed, alpha, levels, s_cap, seed in the optimizer
+    state's config, checked under strict=True, and the number of training batches taken, so a resumed run continues the
+    noise stream bit for bit).  One GPU only."""
     _one_gpu = "MAFTrainer"
+    _error = MAFError
+    _fused_ok = staticmethod(maf_fused_ok)
+    _tag_train, _tag_eval = TAG_TRAIN, TAG_EVAL
 
     def __init__(self, model, train_iter, val_iter, test_iter, seed=0, alpha=0.05, levels=256, s_cap=2.0, viz=False):
-        self.seed = check_seed(seed)                 # before anything runs
+        self.seed = check_seed(seed)                 # both before anything runs, the seed's refusal first
         self.alpha, self.levels, self.s_cap = check_settings(alpha, levels, s_cap)
-        super().__init__(model, train_iter, val_iter, test_iter, viz=viz)
-        del self.kl_loss, self.recon_loss
-        self.losses = []
-        self.noise_steps = 0                         # training batches taken: the next one's noise step
-        self._eval_step = 0                          # batch index within an evaluate() call
+        super().__init__(model, train_iter, val_iter, test_iter, viz=viz, seed=self.seed)
 
     def _settings_ok(self):
         try:
@@ -392,36 +372,13 @@ class MAFTrainer(VAETrainer):
             return False
 
     def _stock(self):
-        return (self._hooks_stock() and maf_fused_ok(self.model) and self._settings_ok()
-                and self._loader_ok(self.train_iter) and self._loader_ok(self.val_iter)
-                and self.train_iter.batch_size == self.val_iter.batch_size)
+        return super()._stock() and self._settings_ok()
 
-    def compute_batch(self, batch):
-        """The batch's NLL in nats per image (general path: autograd over the fused linear kernels with weight * mask; u
-        from gm_nvp_pre's NOISE mode on the contract's counter stream -- the training stream while the model trains, the
-        validation one otherwise)."""
-        from . import ops_fused as of_
-        images, _ = batch
-        x = to_cuda(images.view(images.shape[0], -1))
-        if not x.is_cuda:
-            raise GMError("generative_models_amd computes on MI355X only: no GPU is visible")
-        x = x.to(torch.float32).contiguous()
-        m = self.model
-        if m.training:
-            u = of_.nvp_uniforms(x.shape[0], x.shape[1], self.seed, TAG_TRAIN, step=self.noise_steps, device=x.device)
-            self.noise_steps += 1
-        else:
-            u = of_.nvp_uniforms(x.shape[0], x.shape[1], self.seed, TAG_EVAL, step=self._eval_step, device=x.device)
-            self._eval_step += 1
-        y, ld0 = preprocess(x, u, self.alpha, self.levels)
-        z, ld = m(y, self.s_cap)
-        return nll_rows(z, ld0, ld, x.shape[1], self.levels).sum() / x.shape[0]
+    def _flow_settings(self):
+        return self.alpha, self.levels, self.s_cap
 
-    def evaluate(self, iterator):
-        """Mean over the batches of the NLL in nats per image on the validation stream (batch i at noise step i)."""
-        self._eval_step = 0
-        with torch.no_grad():
-            return np.mean([self.compute_batch(batch).item() for batch in iterator])
+    def _model_flow(self, y):
+        return self.model(y, self.s_cap)
 
     def _engine_class(self):
         return functools.partial(MAFEngine, trainer=self)
@@ -432,12 +389,6 @@ class MAFTrainer(VAETrainer):
         return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
 
     # ---- the flow on device rows, no autograd --------------------------------------------------------------------------
-    def _rows(self, images):
-        x = images.reshape(images.shape[0], -1)
-        if x.shape[1] != self.model.image_size:
-            raise MAFError("images have %d pixels, the model %d" % (x.shape[1], self.model.image_size))
-        return x.to(self._device(), torch.float32).contiguous()
-
     def _forward_rows(self, x, seed, tag, step, row0=0):
         """(z [n, D], nll [n]) of device rows x under the noise of (seed, tag, step, row0 ..): the kernels for a stock
         model, the model's own forward on the same u otherwise."""
@@ -489,97 +440,13 @@ class MAFTrainer(VAETrainer):
         of_.nvp_post(*of_.maf_halves(y, D), x, y.shape[0], self.alpha, "half")
         return x
 
-    # ---- sampling and scoring ------------------------------------------------------------------------------------------
-    def sample(self, n, seed=0, temperature=1.0):
-        """n samples [n, D] float32 in [0, 1]: the contract's normals (indexed by row and element: rows 0 .. 4 of
-        sample(300) are sample(5)) times the temperature through the inverse flow -- K + 2 launches plus the K transposed
-        copies for a stock model.  Runs after a device synchronise; the global generator, the model's mode and the
-        parameters are untouched."""
+    def _prior(self, n, seed, temperature):
+        """The sampler's starting normals z [n, D]: gm_nvp_post's PRIOR mode under the HALF split."""
         from . import ops_fused as of_
-        n, seed, temperature = _int(n, "n"), check_seed(seed), _real(temperature, "temperature")
-        if not 1 <= n < 1 << 31:
-            raise MAFError("n must lie in [1, 2^31), got %d" % n)
-        if temperature < 0.0:
-            raise MAFError("temperature must be >= 0, got %r" % temperature)
-        dev, D = self._device(), self.model.image_size
-        torch.cuda.synchronize()
-        z = torch.empty(n, D, device=dev)
+        D = self.model.image_size
+        z = torch.empty(n, D, device=self._device())
         of_.nvp_prior(*of_.maf_halves(z, D), n, D, seed, "half", temperature=temperature)
-        x = self._inverse_rows(z)
-        torch.cuda.synchronize()
-        return x
-
-    def encode(self, images, seed=0, batch=1024):
-        """(z [n, D], log_px [n]): the latent code of every image under the validation stream's noise of `seed` (step 0,
-        row = the image's position in `images`) and the dequantisation bound on its log-probability in nats."""
-        seed = check_seed(seed)
-        x = self._rows(images)
-        torch.cuda.synchronize()
-        zs, lls = [], []
-        for i in range(0, x.shape[0], batch):
-            z, nll = self._forward_rows(x[i:i + batch], seed, TAG_EVAL, 0, row0=i)
-            zs.append(z)
-            lls.append(-nll)
-        torch.cuda.synchronize()
-        return torch.cat(zs), torch.cat(lls)
-
-    def decode(self, z, batch=1024):
-        """x [n, D] in [0, 1] of latent codes z [n, D]: encode's inverse (up to the dequantisation noise inside a grey
-        level)."""
-        z = z.reshape(z.shape[0], -1)
-        if z.shape[1] != self.model.image_size:
-            raise MAFError("codes have %d elements, the model %d" % (z.shape[1], self.model.image_size))
-        z = z.to(self._device(), torch.float32).contiguous()
-        torch.cuda.synchronize()
-        out = [self._inverse_rows(z[i:i + batch]) for i in range(0, z.shape[0], batch)]
-        torch.cuda.synchronize()
-        return torch.cat(out)
-
-    def log_likelihood_rows(self, images=None, seed=1, batch=1024):
-        """The bound on log p(x) per image in nats, a float64 CPU tensor [n]: batch i of `batch` rows at step i of the
-        validation stream under `seed`."""
-        seed = check_seed(seed)
-        x = self._rows(_dataset_rows(self.test_iter) if images is None else images)
-        torch.cuda.synchronize()
-        out = [-self._forward_rows(x[i:i + batch], seed, TAG_EVAL, i // batch)[1] for i in range(0, x.shape[0], batch)]
-        torch.cuda.synchronize()
-        return torch.cat(out).double().cpu()
-
-    def log_likelihood(self, images=None, seed=1, batch=1024):
-        """The dequantisation bound on log p(x) of every image in nats (images=None: the whole test_iter) ->
-        metrics.NLLResult(ll_mean, ll_stderr, n)."""
-        from . import metrics
-        ll = self.log_likelihood_rows(images, seed, batch)
-        return metrics.NLLResult(float(ll.mean()), float(ll.std(unbiased=False)) / float(np.sqrt(ll.numel())),
-                                 int(ll.numel()))
-
-    def bits_per_dim(self, res):
-        """A log_likelihood result (or a mean log-likelihood in nats) in bits per pixel."""
-        ll = res.ll_mean if hasattr(res, "ll_mean") else float(res)
-        return -ll / (self.model.image_size * math.log(2.0))
-
-    # ---- visualisation, checkpoints -----------------------------------------------------------------------------------
-    def _viz_epoch(self, epoch):
-        if self.viz:
-            self.sample_images(epoch)
-
-    def sample_images(self, epoch=-100, num_images=36, save=True):
-        from . import viz
-        return viz.realnvp_sample_images(self, epoch, num_images, save, self.viz_dir)
-
-    def generate_images(self, epoch=-100, num_outputs=36, save=True):
-        return self.sample_images(epoch, num_outputs, save)
-
-    def reconstruct_images(self, images, epoch, save=True):
-        raise GMError("a flow reconstructs exactly: decode(encode(images)[0]) returns the dequantised images")
-
-    def viz_loss(self):
-        import matplotlib.pyplot as plt
-        plt.style.use("ggplot")
-        plt.plot(np.linspace(1, max(1, self.num_epochs), len(self.losses)), self.losses, "r")
-        plt.legend(["NLL (nats per image)"])
-        plt.title(self.name)
-        plt.show()
+        return z
 
 
 __all__ = ["MAFLayer", "MAF", "MAFTrainer", "MAFEngine", "MAFError", "degrees", "masks", "inverse_order",

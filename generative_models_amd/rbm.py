@@ -32,9 +32,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops, philox
+from . import _lib, ops, philox, viz
 from ._lib import RBM_MAX_DIM, RBM_MAX_STEPS, RBM_TAG_D, RBM_TAG_H, RBM_TAG_V, GMError
-from .trainers import FlatAdam, VAETrainer, _dataset_rows, _stock_module, stock, stock_model, to_cuda  # noqa: F401
+from .trainers import FlatAdam, OneLossTrainer, _dataset_rows, _stock_module, stock, stock_model  # noqa: F401
 from .engine import VAEEngine, _Linear
 
 _M64 = (1 << 64) - 1
@@ -285,30 +285,23 @@ class RBMEngine(VAEEngine):
 
 # ---- trainer ---------------------------------------------------------------------------------------------------------
 @stock
-class RBMTrainer(VAETrainer):
+class RBMTrainer(OneLossTrainer):
     """Trains an RBM by CD-k or PCD-k and samples from it.  Histories: `losses` (the free-energy gap, one per training
     batch) and `recon_loss` (the validation pass' one-step reconstruction cross-entropy in nats per image, one per
     epoch); best_val_loss / best_model on the latter; checkpoints carry the weights, Adam's state, the counters and the
     PCD chains, and resuming is bit-identical.  One GPU only."""
-    _hook_names = ("compute_batch", "evaluate")
-    _series = (("losses", "recon"),)
     _history = ("recon_loss",)
-    _batch = "loss"
     _line = "Epoch[%d/%d], Free-energy gap: %.6f, Val recon CE: %.6f"
     _one_gpu = "RBMTrainer"
+    _error = RBMError
+    _fused_ok = staticmethod(rbm_fused_ok)
 
     def __init__(self, model, train_iter, val_iter, test_iter, seed=0, k=1, mode="cd", viz=False):
         self.seed = check_seed(seed)
         self.k, self.mode = check_k_mode(k, mode)
         super().__init__(model, train_iter, val_iter, test_iter, viz=viz)
-        del self.kl_loss
-        self.losses, self.recon_loss = [], []
         self.noise_steps = 0                         # training batches so far: the noise rule's batch step
         self._general_chains = None
-
-    def _stock(self):
-        return (self._hooks_stock() and rbm_fused_ok(self.model) and self._loader_ok(self.train_iter)
-                and self._loader_ok(self.val_iter) and self.train_iter.batch_size == self.val_iter.batch_size)
 
     # ---- the chain on either path ---------------------------------------------------------------------------------------
     def _weights(self):
@@ -361,21 +354,11 @@ class RBMTrainer(VAETrainer):
         torch.cuda.synchronize()
         return v, p
 
-    def _rows(self, images):
-        x = images.reshape(images.shape[0], -1)
-        if x.shape[1] != self.model.image_size:
-            raise RBMError("images have %d pixels, the model %d" % (x.shape[1], self.model.image_size))
-        return x.to(self._device(), torch.float32).contiguous()
-
     # ---- the general path's batch ---------------------------------------------------------------------------------------
     def compute_batch(self, batch, train=True):
         """The batch's free-energy gap (general path: autograd through the model's own layers; v0 and vk constants).
         Training batches advance the trainer's batch step and, under "pcd", its persistent chains."""
-        images, _ = batch
-        x = to_cuda(images.view(images.shape[0], -1))
-        if not x.is_cuda:
-            raise GMError("generative_models_amd computes on MI355X only: no GPU is visible")
-        x = x.to(torch.float32).contiguous()
+        x = self._flat_batch(batch)
         T = self.noise_steps + self._general_t
         if not train:
             r = self._chain_general(x, 1, (self.seed + EVAL_KEY) & _M64, dstep=self._general_t, g0=self._general_t)
@@ -531,27 +514,14 @@ class RBMTrainer(VAETrainer):
         return _parzen(self, n_samples, sigmas, n_val, seed)
 
     # ---- visualisation, checkpoints -----------------------------------------------------------------------------------
-    def _viz_epoch(self, epoch):
-        if self.viz:
-            self.sample_images(epoch)
-
     def sample_images(self, epoch=-100, num_images=36, save=True):
-        from . import viz
         return viz.made_sample_images(self, epoch, num_images, save, self.viz_dir)
-
-    def generate_images(self, epoch=-100, num_outputs=36, save=True):
-        return self.sample_images(epoch, num_outputs, save)
 
     def reconstruct_images(self, images, epoch, save=True):
         raise GMError("an RBM has no decoder: gibbs(images, steps) runs the chain from the images")
 
     def viz_loss(self):
-        import matplotlib.pyplot as plt
-        plt.style.use("ggplot")
-        plt.plot(np.linspace(1, max(1, self.num_epochs), len(self.losses)), self.losses, "r")
-        plt.legend(["free-energy gap"])
-        plt.title(self.name)
-        plt.show()
+        viz.one_loss_curve(self, "free-energy gap")
 
 
 __all__ = ["RBM", "RBMTrainer", "RBMEngine", "RBMError", "rbm_fused_ok", "uniforms_reference", "default_betas",

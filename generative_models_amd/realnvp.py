@@ -49,10 +49,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops, philox
+from . import _lib, ops, philox, viz
 from ._lib import (NVP_MAX_D, NVP_MAX_H, NVP_MAX_K, NVP_MAX_LEVELS, NVP_MAX_S_CAP, NVP_MIN_D, NVP_TAG_EVAL, NVP_TAG_S,
                    NVP_TAG_TRAIN, GMError)
-from .trainers import FlatAdam, VAETrainer, _dataset_rows, _stock_module, stock, stock_model, to_cuda  # noqa: F401
+from .trainers import FlatAdam, OneLossTrainer, _dataset_rows, _stock_module, stock, stock_model  # noqa: F401
 from .engine import VAEEngine, _Linear
 
 TAG_TRAIN, TAG_EVAL, TAG_S = NVP_TAG_TRAIN, NVP_TAG_EVAL, NVP_TAG_S
@@ -72,13 +72,18 @@ def check_seed(seed, name="seed"):
     return _lib.check_seed(seed, name, RealNVPError)
 
 
-def _real(v, name):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise RealNVPError("%s must be a number, got %r" % (name, v))
-    v = float(v)
-    if not math.isfinite(v):
-        raise RealNVPError("%s must be finite, got %r" % (name, v))
-    return v
+def check_flow_settings(alpha, levels, s_cap, error):
+    """(alpha, levels, s_cap) of a dequantising flow, validated against the gm_nvp kernels' limits -- in fp32 too, where
+    the kernels compute; else `error`."""
+    alpha, s_cap = _lib.check_real(alpha, "alpha", error), _lib.check_real(s_cap, "s_cap", error)
+    levels = _lib.check_int(levels, "levels", error)
+    if not (0.0 <= alpha < 0.5 and float(np.float32(alpha)) < 0.5):
+        raise error("alpha must lie in [0, 0.5), got %r" % alpha)
+    if not 2 <= levels <= NVP_MAX_LEVELS:
+        raise error("levels must lie in [2, %d], got %d" % (NVP_MAX_LEVELS, levels))
+    if not (0.0 < s_cap <= NVP_MAX_S_CAP and float(np.float32(s_cap)) > 0.0):
+        raise error("s_cap must lie in (0, %d], got %r" % (NVP_MAX_S_CAP, s_cap))
+    return alpha, levels, s_cap
 
 
 def check_config(image_size, hidden_dim, num_couplings, mask, alpha, levels, s_cap):
@@ -92,14 +97,7 @@ def check_config(image_size, hidden_dim, num_couplings, mask, alpha, levels, s_c
         raise RealNVPError("num_couplings must lie in [1, %d], got %d" % (NVP_MAX_K, K))
     if not isinstance(mask, str) or mask not in MASKS:
         raise RealNVPError("mask must be one of %s, got %r" % (MASKS, mask))
-    alpha, s_cap, levels = _real(alpha, "alpha"), _real(s_cap, "s_cap"), _int(levels, "levels")
-    if not (0.0 <= alpha < 0.5 and float(np.float32(alpha)) < 0.5):
-        raise RealNVPError("alpha must lie in [0, 0.5), got %r" % alpha)
-    if not 2 <= levels <= NVP_MAX_LEVELS:
-        raise RealNVPError("levels must lie in [2, %d], got %d" % (NVP_MAX_LEVELS, levels))
-    if not (0.0 < s_cap <= NVP_MAX_S_CAP and float(np.float32(s_cap)) > 0.0):
-        raise RealNVPError("s_cap must lie in (0, %d], got %r" % (NVP_MAX_S_CAP, s_cap))
-    return D, H, K, mask, alpha, levels, s_cap
+    return (D, H, K, mask) + check_flow_settings(alpha, levels, s_cap, RealNVPError)
 
 
 # ---- the split and the noise rules in numpy (the tests' reference reads the same contract) ----------------------------
@@ -376,56 +374,151 @@ class RealNVPEngine(VAEEngine):
 
 # ---- trainer ---------------------------------------------------------------------------------------------------------
 @stock
-class RealNVPTrainer(VAETrainer):
-    """Trains a RealNVP on its exact (dequantised) negative log-likelihood; samples, encodes and decodes.  Histories:
-    `losses` (the NLL in nats per image, one per training batch); the epoch line (mean training NLL, validation NLL);
-    best_val_loss / best_model as the other VAE-family trainers; checkpoints (+ mask, alpha, levels, s_cap, seed in the
-    optimizer state's config, checked under strict=True, and the number of training batches taken, so a resumed run
-    continues the noise stream bit for bit).  One GPU only."""
-    _hook_names = ("compute_batch", "evaluate")
-    _series = (("losses", "recon"),)
-    _batch = "loss"
+class DequantFlowTrainer(OneLossTrainer):
+    """What the trainers of the two flows over dequantised grey-level images share (RealNVP here, MAF in maf.py): one
+    protocol around two sets of kernels.  Rows are dequantised and taken to logit space under the contract's Philox
+    noise -- the training stream at step `noise_steps` while the model trains, the validation stream at the batch's
+    index otherwise; encode runs at step 0 with row0 = the image's position; log_likelihood_rows runs batch i at step i;
+    sample is the prior's normals times the temperature through the inverse flow, between two synchronises.
+
+    A latent travels between the hooks as a `code`: z [n, D] itself by default, the pair of halves for RealNVP, which
+    merges and splits only where a public method takes or returns z.  A subclass names _tag_train, _tag_eval and _error
+    and supplies _flow_settings() -> (alpha, levels, s_cap), _model_flow(y) -> (z, logdet) by autograd-able ops,
+    _forward_rows(x, seed, tag, step, row0) -> (code, nll [n]), _inverse_rows(code) -> x and _prior(n, seed,
+    temperature) -> code."""
     _line = "Epoch[%d/%d], NLL: %.6f, Val NLL: %.6f"
-    _one_gpu = "RealNVPTrainer"
+    _tag_train = _tag_eval = None
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, seed=0):
-        self.seed = check_seed(seed)                 # before anything runs
+        self.seed = self._check_seed(seed)           # before anything runs
         super().__init__(model, train_iter, val_iter, test_iter, viz=viz)
-        del self.kl_loss, self.recon_loss
-        self.losses = []
         self.noise_steps = 0                         # training batches taken: the next one's noise step
         self._eval_step = 0                          # batch index within an evaluate() call
 
-    def _stock(self):
-        return (self._hooks_stock() and realnvp_fused_ok(self.model) and self._loader_ok(self.train_iter)
-                and self._loader_ok(self.val_iter) and self.train_iter.batch_size == self.val_iter.batch_size)
+    def _check_seed(self, seed):
+        return _lib.check_seed(seed, "seed", self._error)
+
+    def _code_to_z(self, code):
+        return code
+
+    def _z_to_code(self, z):
+        return z
 
     def compute_batch(self, batch):
         """The batch's NLL in nats per image (general path: autograd over the fused linear kernels; u from gm_nvp_pre's
         NOISE mode on the contract's counter stream -- the training stream while the model trains, the validation one
         otherwise)."""
         from . import ops_fused as of_
-        images, _ = batch
-        x = to_cuda(images.view(images.shape[0], -1))
-        if not x.is_cuda:
-            raise GMError("generative_models_amd computes on MI355X only: no GPU is visible")
-        x = x.to(torch.float32).contiguous()
-        m = self.model
-        if m.training:
-            u = of_.nvp_uniforms(x.shape[0], x.shape[1], self.seed, TAG_TRAIN, step=self.noise_steps, device=x.device)
-            self.noise_steps += 1
-        else:
-            u = of_.nvp_uniforms(x.shape[0], x.shape[1], self.seed, TAG_EVAL, step=self._eval_step, device=x.device)
-            self._eval_step += 1
-        y, ld0 = preprocess(x, u, m.alpha, m.levels)
-        z, ld = m(y)
-        return nll_rows(z, ld0, ld, x.shape[1], m.levels).sum() / x.shape[0]
+        x = self._flat_batch(batch)
+        alpha, levels, _ = self._flow_settings()
+        train, step = self._noise_step()
+        u = of_.nvp_uniforms(x.shape[0], x.shape[1], self.seed, self._tag_train if train else self._tag_eval, step=step,
+                             device=x.device)
+        y, ld0 = preprocess(x, u, alpha, levels)
+        z, ld = self._model_flow(y)
+        return nll_rows(z, ld0, ld, x.shape[1], levels).sum() / x.shape[0]
 
-    def evaluate(self, iterator):
-        """Mean over the batches of the NLL in nats per image on the validation stream (batch i at noise step i)."""
-        self._eval_step = 0
-        with torch.no_grad():
-            return np.mean([self.compute_batch(batch).item() for batch in iterator])
+    # ---- sampling and scoring ------------------------------------------------------------------------------------------
+    def sample(self, n, seed=0, temperature=1.0):
+        """n samples [n, D] float32 in [0, 1]: the contract's normals (indexed by row and element: rows 0 .. 4 of
+        sample(300) are sample(5)) times the temperature through the inverse flow.  Runs after a device synchronise; the
+        global generator, the model's mode and the parameters are untouched."""
+        E = self._error
+        n, seed = _lib.check_int(n, "n", E), self._check_seed(seed)
+        temperature = _lib.check_real(temperature, "temperature", E)
+        if not 1 <= n < 1 << 31:
+            raise E("n must lie in [1, 2^31), got %d" % n)
+        if temperature < 0.0:
+            raise E("temperature must be >= 0, got %r" % temperature)
+        self._device()
+        torch.cuda.synchronize()
+        x = self._inverse_rows(self._prior(n, seed, temperature))
+        torch.cuda.synchronize()
+        return x
+
+    def encode(self, images, seed=0, batch=1024):
+        """(z [n, D], log_px [n]): the latent code of every image under the validation stream's noise of `seed` (step 0,
+        row = the image's position in `images`) and the dequantisation bound on its log-probability in nats."""
+        seed = self._check_seed(seed)
+        x = self._rows(images)
+        torch.cuda.synchronize()
+        zs, lls = [], []
+        for i in range(0, x.shape[0], batch):
+            code, nll = self._forward_rows(x[i:i + batch], seed, self._tag_eval, 0, row0=i)
+            zs.append(self._code_to_z(code))
+            lls.append(-nll)
+        torch.cuda.synchronize()
+        return torch.cat(zs), torch.cat(lls)
+
+    def decode(self, z, batch=1024):
+        """x [n, D] in [0, 1] of latent codes z [n, D]: encode's inverse (up to the dequantisation noise inside a
+        grey level)."""
+        z = z.reshape(z.shape[0], -1)
+        if z.shape[1] != self.model.image_size:
+            raise self._error("codes have %d elements, the model %d" % (z.shape[1], self.model.image_size))
+        z = z.to(self._device(), torch.float32).contiguous()
+        torch.cuda.synchronize()
+        out = [self._inverse_rows(self._z_to_code(z[i:i + batch])) for i in range(0, z.shape[0], batch)]
+        torch.cuda.synchronize()
+        return torch.cat(out)
+
+    def log_likelihood_rows(self, images=None, seed=1, batch=1024):
+        """The bound on log p(x) per image in nats, a float64 CPU tensor [n]: batch i of `batch` rows at step i of the
+        validation stream under `seed`."""
+        seed = self._check_seed(seed)
+        x = self._rows(_dataset_rows(self.test_iter) if images is None else images)
+        torch.cuda.synchronize()
+        out = [-self._forward_rows(x[i:i + batch], seed, self._tag_eval, i // batch)[1]
+               for i in range(0, x.shape[0], batch)]
+        torch.cuda.synchronize()
+        return torch.cat(out).double().cpu()
+
+    def log_likelihood(self, images=None, seed=1, batch=1024):
+        """The dequantisation bound on log p(x) of every image in nats (images=None: the whole test_iter) ->
+        metrics.NLLResult(ll_mean, ll_stderr, n)."""
+        return self._nll_result(self.log_likelihood_rows(images, seed, batch))
+
+    def bits_per_dim(self, res):
+        """A log_likelihood result (or a mean log-likelihood in nats) in bits per pixel."""
+        ll = res.ll_mean if hasattr(res, "ll_mean") else float(res)
+        return -ll / (self.model.image_size * math.log(2.0))
+
+    # ---- visualisation ---------------------------------------------------------------------------------------------------
+    def sample_images(self, epoch=-100, num_images=36, save=True):
+        return viz.realnvp_sample_images(self, epoch, num_images, save, self.viz_dir)
+
+    def reconstruct_images(self, images, epoch, save=True):
+        raise GMError("a flow reconstructs exactly: decode(encode(images)[0]) returns the dequantised images")
+
+    def viz_loss(self):
+        viz.one_loss_curve(self, "NLL (nats per image)")
+
+
+@stock
+class RealNVPTrainer(DequantFlowTrainer):
+    """Trains a RealNVP on its exact (dequantised) negative log-likelihood; samples, encodes and decodes: a
+    DequantFlowTrainer whose code is the pair of halves (sampling is 3 K + 2 launches for a stock model).  Histories:
+    `losses` (the NLL in nats per image, one per training batch); the epoch line (mean training NLL, validation NLL);
+    best_val_loss / best_model as the other VAE-family trainers; checkpoints (+ mask, alpha, levels, s_cap, seed in the
+    optimizer state's config, checked under strict=True, and the number of training batches taken, so a resumed run
+    continues the noise stream bit for bit).  One GPU only."""
+    _one_gpu = "RealNVPTrainer"
+    _error = RealNVPError
+    _fused_ok = staticmethod(realnvp_fused_ok)
+    _tag_train, _tag_eval = TAG_TRAIN, TAG_EVAL
+
+    def _flow_settings(self):
+        m = self.model
+        return m.alpha, m.levels, m.s_cap
+
+    def _model_flow(self, y):
+        return self.model(y)
+
+    def _code_to_z(self, code):
+        return self.model.merge(*code)
+
+    def _z_to_code(self, z):
+        return self.model.split(z)
 
     def _engine_class(self):
         import functools
@@ -436,12 +529,6 @@ class RealNVPTrainer(VAETrainer):
         return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
 
     # ---- the flow on device rows, no autograd --------------------------------------------------------------------------
-    def _rows(self, images):
-        x = images.reshape(images.shape[0], -1)
-        if x.shape[1] != self.model.image_size:
-            raise RealNVPError("images have %d pixels, the model %d" % (x.shape[1], self.model.image_size))
-        return x.to(self._device(), torch.float32).contiguous()
-
     def _st(self, k, xc):
         """ST of coupling k on device rows xc: the two GEMM launches."""
         c = self.model.couplings[k]
@@ -452,8 +539,8 @@ class RealNVPTrainer(VAETrainer):
         return st
 
     def _forward_rows(self, x, seed, tag, step, row0=0):
-        """(za, zb, nll [n]) of device rows x under the noise of (seed, tag, step, row0 ..): the kernels for a stock model,
-        the model's own forward on the same u otherwise."""
+        """((za, zb), nll [n]) of device rows x under the noise of (seed, tag, step, row0 ..): the kernels for a stock
+        model, the model's own forward on the same u otherwise."""
         from . import ops_fused as of_
         m, n = self.model, x.shape[0]
         with torch.no_grad():
@@ -461,8 +548,7 @@ class RealNVPTrainer(VAETrainer):
                 u = of_.nvp_uniforms(n, m.image_size, seed, tag, step=step, row0=row0, device=x.device)
                 y, ld0 = preprocess(x, u, m.alpha, m.levels)
                 z, ld = m(y)
-                a, b = m.split(z)
-                return a, b, nll_rows(z, ld0, ld, m.image_size, m.levels)
+                return m.split(z), nll_rows(z, ld0, ld, m.image_size, m.levels)
             h = [torch.empty(n, m.Da, device=x.device), torch.empty(n, m.Db, device=x.device)]
             logdet, part = torch.empty(n, device=x.device), torch.empty(n, device=x.device)
             of_.nvp_pre(x, h[0], h[1], logdet, n, seed, tag, m.alpha, m.levels, m.mask, step=step, row0=row0)
@@ -472,11 +558,12 @@ class RealNVPTrainer(VAETrainer):
                 of_.nvp_couple(self._st(k, h[1 - t]), h[t], out, n, h[t].shape[1], m.s_cap, logdet=logdet)
                 h[t] = out
             of_.nvp_loss(h[0], h[1], logdet, part, n, float(np.float32(nll_constant(m.image_size, m.levels))))
-            return h[0], h[1], part
+            return (h[0], h[1]), part
 
-    def _inverse_rows(self, za, zb):
-        """x [n, D] in [0, 1] of latent halves: the couplings inverted last to first, then gm_nvp_post."""
+    def _inverse_rows(self, code):
+        """x [n, D] in [0, 1] of latent halves (za, zb): the couplings inverted last to first, then gm_nvp_post."""
         from . import ops_fused as of_
+        za, zb = code
         m, n = self.model, za.shape[0]
         with torch.no_grad():
             if not realnvp_fused_ok(m):
@@ -491,52 +578,13 @@ class RealNVPTrainer(VAETrainer):
             of_.nvp_post(h[0], h[1], x, n, m.alpha, m.mask)
             return x
 
-    # ---- sampling and scoring ------------------------------------------------------------------------------------------
-    def sample(self, n, seed=0, temperature=1.0):
-        """n samples [n, D] float32 in [0, 1]: the contract's normals (indexed by row and element: rows 0 .. 4 of
-        sample(300) are sample(5)) times the temperature through the inverse flow -- 3 K + 2 launches for a stock model.
-        Runs after a device synchronise; the global generator, the model's mode and the parameters are untouched."""
+    def _prior(self, n, seed, temperature):
+        """The sampler's starting halves (za, zb): gm_nvp_post's PRIOR mode."""
         from . import ops_fused as of_
-        n, seed, temperature = _int(n, "n"), check_seed(seed), _real(temperature, "temperature")
-        if not 1 <= n < 1 << 31:
-            raise RealNVPError("n must lie in [1, 2^31), got %d" % n)
-        if temperature < 0.0:
-            raise RealNVPError("temperature must be >= 0, got %r" % temperature)
         dev, m = self._device(), self.model
-        torch.cuda.synchronize()
         za, zb = torch.empty(n, m.Da, device=dev), torch.empty(n, m.Db, device=dev)
         of_.nvp_prior(za, zb, n, m.image_size, seed, m.mask, temperature=temperature)
-        x = self._inverse_rows(za, zb)
-        torch.cuda.synchronize()
-        return x
-
-    def encode(self, images, seed=0, batch=1024):
-        """(z [n, D], log_px [n]): the latent code of every image under the validation stream's noise of `seed` (step 0,
-        row = the image's position in `images`) and the dequantisation bound on its log-probability in nats."""
-        seed = check_seed(seed)
-        x = self._rows(images)
-        m = self.model
-        torch.cuda.synchronize()
-        zs, lls = [], []
-        for i in range(0, x.shape[0], batch):
-            a, b, nll = self._forward_rows(x[i:i + batch], seed, TAG_EVAL, 0, row0=i)
-            zs.append(m.merge(a, b))
-            lls.append(-nll)
-        torch.cuda.synchronize()
-        return torch.cat(zs), torch.cat(lls)
-
-    def decode(self, z, batch=1024):
-        """x [n, D] in [0, 1] of latent codes z [n, D]: encode's inverse (up to the dequantisation noise inside a
-        grey level)."""
-        z = z.reshape(z.shape[0], -1)
-        m = self.model
-        if z.shape[1] != m.image_size:
-            raise RealNVPError("codes have %d elements, the model %d" % (z.shape[1], m.image_size))
-        z = z.to(self._device(), torch.float32).contiguous()
-        torch.cuda.synchronize()
-        out = [self._inverse_rows(*m.split(z[i:i + batch])) for i in range(0, z.shape[0], batch)]
-        torch.cuda.synchronize()
-        return torch.cat(out)
+        return za, zb
 
     def interpolate(self, a, b, steps=8, seed=0):
         """[steps, D]: the decoded line from image a to image b in z."""
@@ -546,52 +594,6 @@ class RealNVPTrainer(VAETrainer):
         z, _ = self.encode(torch.stack([a.reshape(-1), b.reshape(-1)]), seed=seed)
         w = torch.linspace(0.0, 1.0, steps, device=z.device)[:, None]
         return self.decode((1.0 - w) * z[0:1] + w * z[1:2])
-
-    def log_likelihood_rows(self, images=None, seed=1, batch=1024):
-        """The bound on log p(x) per image in nats, a float64 CPU tensor [n]: batch i of `batch` rows at step i of the
-        validation stream under `seed`."""
-        seed = check_seed(seed)
-        x = self._rows(_dataset_rows(self.test_iter) if images is None else images)
-        torch.cuda.synchronize()
-        out = [-self._forward_rows(x[i:i + batch], seed, TAG_EVAL, i // batch)[2] for i in range(0, x.shape[0], batch)]
-        torch.cuda.synchronize()
-        return torch.cat(out).double().cpu()
-
-    def log_likelihood(self, images=None, seed=1, batch=1024):
-        """The dequantisation bound on log p(x) of every image in nats (images=None: the whole test_iter) ->
-        metrics.NLLResult(ll_mean, ll_stderr, n)."""
-        from . import metrics
-        ll = self.log_likelihood_rows(images, seed, batch)
-        return metrics.NLLResult(float(ll.mean()), float(ll.std(unbiased=False)) / float(np.sqrt(ll.numel())),
-                                 int(ll.numel()))
-
-    def bits_per_dim(self, res):
-        """A log_likelihood result (or a mean log-likelihood in nats) in bits per pixel."""
-        ll = res.ll_mean if hasattr(res, "ll_mean") else float(res)
-        return -ll / (self.model.image_size * math.log(2.0))
-
-    # ---- visualisation, checkpoints -----------------------------------------------------------------------------------
-    def _viz_epoch(self, epoch):
-        if self.viz:
-            self.sample_images(epoch)
-
-    def sample_images(self, epoch=-100, num_images=36, save=True):
-        from . import viz
-        return viz.realnvp_sample_images(self, epoch, num_images, save, self.viz_dir)
-
-    def generate_images(self, epoch=-100, num_outputs=36, save=True):
-        return self.sample_images(epoch, num_outputs, save)
-
-    def reconstruct_images(self, images, epoch, save=True):
-        raise GMError("a flow reconstructs exactly: decode(encode(images)[0]) returns the dequantised images")
-
-    def viz_loss(self):
-        import matplotlib.pyplot as plt
-        plt.style.use("ggplot")
-        plt.plot(np.linspace(1, max(1, self.num_epochs), len(self.losses)), self.losses, "r")
-        plt.legend(["NLL (nats per image)"])
-        plt.title(self.name)
-        plt.show()
 
 
 __all__ = ["Coupling", "RealNVP", "RealNVPTrainer", "RealNVPEngine", "RealNVPError", "split_indices", "philox_words",

@@ -797,10 +797,23 @@ class VAETrainer:
         self.best_val_loss = 1e10
         self.debugging_image, _ = next(iter(test_iter))          # vae.py:120 (consumes RNG)
         self.viz = viz
-        self.kl_loss, self.recon_loss = [], []
+        self._new_histories()
         self.num_epochs = 0
         self._engine = None
         self.use_graph = True
+
+    def _new_histories(self):
+        """The empty loss histories a constructor leaves."""
+        self.kl_loss, self.recon_loss = [], []
+
+    def _noise_step(self):
+        """(training stream?, step) of a device-noise trainer's next general-path batch: the count of training batches
+        taken while the model trains, the batch's index in the evaluate() pass otherwise; advances the one it read."""
+        train = self.model.training
+        name = "noise_steps" if train else "_eval_step"
+        step = getattr(self, name)
+        setattr(self, name, step + 1)
+        return train, step
 
     def compute_batch(self, batch):
         """vae.py:193-208 (general path: autograd over the fused linear kernels)."""
@@ -1072,6 +1085,60 @@ class VAETrainer:
         """strict: refuse a checkpoint whose run settings (batch size, D_steps, learning rates ...)
         differ from the next train() call's."""
         _load_checkpoint(self, loadpath, strict)
+
+
+@stock
+class OneLossTrainer(VAETrainer):
+    """What the trainers that record one scalar loss per batch in `losses` share (MADE, MAF, RealNVP, DDPM, RBM): the
+    histories a constructor leaves, path selection on the model's own fused-path test, the general path's batch
+    preparation and evaluate(), the pixel-count check of images handed to a sampling or scoring method, and
+    generate_images; the per-epoch sample grid is VAETrainer's _viz_epoch.  A subclass names its _fused_ok, _error, _line
+    and _one_gpu and supplies compute_batch, sample_images, viz_loss and its engine."""
+    _hook_names = ("compute_batch", "evaluate")
+    _series = (("losses", "recon"),)
+    _batch = "loss"
+    _error = GMError            # the subclass's own refusal class
+    _fused_ok = None            # staticmethod(<module>.<model>_fused_ok): the model is the shipped one, unchanged
+
+    def _new_histories(self):
+        """`losses`, and the RBM's per-epoch `recon_loss`: no kl_loss / recon_loss pair."""
+        for name in tuple(n for n, _ in self._series) + self._history:
+            setattr(self, name, [])
+
+    def _stock(self):
+        return (self._hooks_stock() and self._fused_ok(self.model) and self._loader_ok(self.train_iter)
+                and self._loader_ok(self.val_iter) and self.train_iter.batch_size == self.val_iter.batch_size)
+
+    def _flat_batch(self, batch):
+        """A loader's batch as fp32 contiguous device rows [b, pixels]: where a general-path compute_batch starts."""
+        images, _ = batch
+        x = to_cuda(images.view(images.shape[0], -1))
+        if not x.is_cuda:
+            raise GMError("generative_models_amd computes on MI355X only: no GPU is visible")
+        return x.to(torch.float32).contiguous()
+
+    def evaluate(self, iterator):
+        """Mean over the batches of compute_batch's loss, batch i at noise step i of the validation stream."""
+        self._eval_step = 0
+        with torch.no_grad():
+            return np.mean([self.compute_batch(batch).item() for batch in iterator])
+
+    def _rows(self, images):
+        """images as fp32 contiguous rows [n, pixels] on the model's device; _error when the pixel count is not the
+        model's."""
+        x = images.reshape(images.shape[0], -1)
+        if x.shape[1] != self.model.image_size:
+            raise self._error("images have %d pixels, the model %d" % (x.shape[1], self.model.image_size))
+        return x.to(self._device(), torch.float32).contiguous()
+
+    def _nll_result(self, ll):
+        """metrics.NLLResult(ll_mean, ll_stderr, n) of per-image log-likelihoods ll [n]."""
+        from . import metrics
+        return metrics.NLLResult(float(ll.mean()), float(ll.std(unbiased=False)) / float(np.sqrt(ll.numel())),
+                                 int(ll.numel()))
+
+    def generate_images(self, epoch=-100, num_outputs=36, save=True):
+        return self.sample_images(epoch, num_outputs, save)
 
 
 # ============================================================================================

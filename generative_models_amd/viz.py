@@ -163,6 +163,16 @@ def vae_viz_loss(trainer, second="kl_loss"):
     plt.show()
 
 
+def one_loss_curve(trainer, label):
+    """The trainer's `losses` history over its epochs, in red, under the legend `label`."""
+    import matplotlib.pyplot as plt
+    plt.style.use("ggplot")
+    plt.plot(np.linspace(1, max(1, trainer.num_epochs), len(trainer.losses)), trainer.losses, "r")
+    plt.legend([label])
+    plt.title(trainer.name)
+    plt.show()
+
+
 def ddpm_sample_images(trainer, epoch=-100, num_images=36, save=True, outdir=None, steps=None):
     """A grid of trainer.sample(num_images, seed=max(epoch, 0), steps) -- drawn on the device from the sampler's own
     counter stream, so the global CPU generator stays where it is -- written as ../viz/<name>/sample_<epoch>.png."""

@@ -1,0 +1,211 @@
+"""The shared bases of the one-loss trainers without a GPU: OneLossTrainer (MADE, MAF, RealNVP, DDPM, RBM) and
+DequantFlowTrainer (MAF, RealNVP) define each shared method once, both carry the stock mark on the class itself so path
+selection still sees an overridden hook, every constructor leaves exactly the attributes it left before the bases existed,
+the noise-step clock, and the validators raise the caller's error class with the messages they always had."""
+import os
+import sys
+
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+
+from generative_models_amd import _lib, ddpm, iwae, made, maf, realnvp, rbm, trainers  # noqa: E402
+from generative_models_amd.realnvp import DequantFlowTrainer  # noqa: E402
+from generative_models_amd.trainers import OneLossTrainer, VAETrainer  # noqa: E402
+
+FIVE = (made.MADETrainer, maf.MAFTrainer, realnvp.RealNVPTrainer, ddpm.DDPMTrainer, rbm.RBMTrainer)
+FLOW_SHARED = ("compute_batch", "evaluate", "sample", "encode", "decode", "log_likelihood_rows", "log_likelihood",
+               "bits_per_dim", "sample_images", "generate_images", "reconstruct_images")
+ALL_SHARED = ("_stock", "_flat_batch", "_rows", "_viz_epoch", "generate_images")
+
+# What every trainer's constructor leaves, recorded by running the constructors before the shared bases existed.
+BASE_VARS = {"_engine", "best_val_loss", "debugging_image", "model", "name", "num_epochs", "test_iter", "train_iter",
+             "use_graph", "val_iter", "viz"}
+VARS = {
+    "MADETrainer": BASE_VARS | {"losses"},
+    "MAFTrainer": BASE_VARS | {"losses", "seed", "noise_steps", "_eval_step", "alpha", "levels", "s_cap"},
+    "RealNVPTrainer": BASE_VARS | {"losses", "seed", "noise_steps", "_eval_step"},
+    "DDPMTrainer": BASE_VARS | {"losses", "seed", "noise_steps", "_eval_step", "_sampler"},
+    "RBMTrainer": BASE_VARS | {"losses", "recon_loss", "seed", "noise_steps", "k", "mode", "_general_chains"},
+    "IWAETrainer": BASE_VARS | {"losses", "ess", "recon_loss", "kl_loss", "k", "seed", "noise_steps", "_eval_step"},
+    "VAETrainer": BASE_VARS | {"recon_loss", "kl_loss"},
+}
+MODELS = {
+    "MADETrainer": (made.MADETrainer, lambda: made.MADE(16, 8)),
+    "MAFTrainer": (maf.MAFTrainer, lambda: maf.MAF(16, 8, 2)),
+    "RealNVPTrainer": (realnvp.RealNVPTrainer, lambda: realnvp.RealNVP(16, 8, 2)),
+    "DDPMTrainer": (ddpm.DDPMTrainer, lambda: ddpm.DDPM(16, 8, 4, 10)),
+    "RBMTrainer": (rbm.RBMTrainer, lambda: rbm.RBM(16, 8)),
+    "IWAETrainer": (iwae.IWAETrainer, lambda: iwae.IWAE(16, 8, 2)),
+    "VAETrainer": (VAETrainer, lambda: trainers.VAE(16, 8, 2)),
+}
+
+
+def _loaders(n=12, batch=4, side=4):
+    x = torch.rand(n, 1, side, side)
+    ds = torch.utils.data.TensorDataset(x, torch.zeros(n, dtype=torch.int64))
+    dl = lambda: torch.utils.data.DataLoader(ds, batch_size=batch, shuffle=True)
+    return dl(), dl(), dl()
+
+
+def _bare(cls, model):
+    tr = object.__new__(cls)                     # selection runs before anything touches a GPU
+    tr.model, tr.train_iter, tr.val_iter, tr.test_iter = model, *_loaders()
+    tr.seed, tr.noise_steps, tr._engine = 0, 0, None
+    tr.alpha, tr.levels, tr.s_cap = 0.05, 256, 2.0
+    return tr
+
+
+def test_every_shared_method_is_defined_once():
+    M, N = maf.MAFTrainer, realnvp.RealNVPTrainer
+    for name in FLOW_SHARED:
+        assert getattr(M, name) is getattr(N, name), name
+        assert name not in M.__dict__ and name not in N.__dict__, name
+    for name in ALL_SHARED:
+        for T in FIVE:
+            if (T, name) == (M, "_stock"):       # MAF's: the shared selection and its settings' check, nothing else
+                assert M.__dict__["_stock"].__code__.co_names == ("super", "_stock", "_settings_ok")
+                continue
+            assert getattr(T, name) is getattr(made.MADETrainer, name), (T.__name__, name)
+            assert name not in T.__dict__, (T.__name__, name)
+    for T in FIVE + (iwae.IWAETrainer,):
+        assert T._noise_step is VAETrainer._noise_step and "_noise_step" not in T.__dict__
+    for T in FIVE:
+        assert issubclass(T, OneLossTrainer)
+        assert T._hook_names == ("compute_batch", "evaluate") and T._series == (("losses", "recon"),)
+        assert T._batch == "loss" and "_hook_names" not in T.__dict__ and "_series" not in T.__dict__
+    for T in (made.MADETrainer, maf.MAFTrainer, realnvp.RealNVPTrainer, ddpm.DDPMTrainer):
+        assert T.evaluate is OneLossTrainer.evaluate
+    assert issubclass(M, DequantFlowTrainer) and issubclass(N, DequantFlowTrainer)
+    assert "train" in M.__dict__ and "train" in N.__dict__ and "interpolate" in N.__dict__
+    assert (made.MADETrainer._error, M._error, N._error, ddpm.DDPMTrainer._error, rbm.RBMTrainer._error) == (
+        made.MADEError, maf.MAFError, realnvp.RealNVPError, ddpm.DDPMError, rbm.RBMError)
+    # the RBM keeps its own batch contract
+    assert "compute_batch" in rbm.RBMTrainer.__dict__ and "evaluate" in rbm.RBMTrainer.__dict__
+
+
+@pytest.mark.parametrize("name", ["MADETrainer", "MAFTrainer", "RealNVPTrainer", "DDPMTrainer", "RBMTrainer"])
+def test_bases_are_stock_and_an_overridden_hook_leaves_the_fused_path(name):
+    for base in (OneLossTrainer, DequantFlowTrainer):
+        assert base.__dict__.get("_gm_stock_class") is True
+    cls, model = MODELS[name]
+    assert _bare(cls, model())._stock() is True
+
+    class Mine(cls):
+        def compute_batch(self, batch, *a, **kw):
+            return super().compute_batch(batch, *a, **kw)
+
+    assert _bare(Mine, model())._stock() is False
+
+    class Scored(cls):
+        def evaluate(self, iterator):
+            return super().evaluate(iterator)
+
+    assert _bare(Scored, model())._stock() is False
+
+
+@pytest.mark.parametrize("name", ["MADETrainer", "MAFTrainer", "RealNVPTrainer", "DDPMTrainer", "RBMTrainer"])
+def test_rows_refuses_a_wrong_pixel_count_as_the_trainers_own_error(name):
+    cls, model = MODELS[name]
+    tr = _bare(cls, model())
+    with pytest.raises(cls._error) as e:
+        tr._rows(torch.zeros(2, 1, 5))
+    assert str(e.value) == "images have 5 pixels, the model 16" and type(e.value) is cls._error
+
+
+def test_maf_settings_still_gate_the_fused_path():
+    tr = _bare(maf.MAFTrainer, maf.MAF(16, 8, 2))
+    tr.alpha = 0.5
+    assert tr._stock() is False
+
+
+@pytest.mark.parametrize("name", sorted(VARS))
+def test_constructor_leaves_the_same_attributes(name, monkeypatch):
+    monkeypatch.setattr(trainers, "to_cuda", lambda x: x)
+    cls, model = MODELS[name]
+    tr = cls(model(), *_loaders())
+    assert set(vars(tr)) == VARS[name]
+    for hist in ("losses", "recon_loss", "kl_loss", "ess"):
+        if hist in VARS[name]:
+            assert getattr(tr, hist) == []
+    assert not hasattr(tr, "kl_loss") or name in ("IWAETrainer", "VAETrainer")
+
+
+def test_noise_step_clock():
+    for cls in (iwae.IWAETrainer, ddpm.DDPMTrainer, maf.MAFTrainer, realnvp.RealNVPTrainer):
+        tr = object.__new__(cls)
+        tr.model = torch.nn.Linear(1, 1)
+        tr.noise_steps, tr._eval_step = 5, 2
+        tr.model.train()
+        assert tr._noise_step() == (True, 5) and tr._noise_step() == (True, 6)
+        assert (tr.noise_steps, tr._eval_step) == (7, 2)
+        tr.model.eval()
+        assert tr._noise_step() == (False, 2) and tr._noise_step() == (False, 3)
+        assert (tr.noise_steps, tr._eval_step) == (7, 4)
+
+
+def test_evaluate_starts_its_pass_at_step_zero():
+    seen = []
+
+    class Probe(OneLossTrainer):
+        def compute_batch(self, batch):
+            assert not torch.is_grad_enabled()
+            seen.append(self._noise_step())
+            return torch.tensor(float(batch))
+
+    tr = object.__new__(Probe)
+    tr.model = torch.nn.Linear(1, 1).eval()
+    tr.noise_steps, tr._eval_step = 3, 7
+    assert tr.evaluate([1.0, 2.0, 6.0]) == 3.0
+    assert seen == [(False, 0), (False, 1), (False, 2)] and tr.noise_steps == 3
+    tr.evaluate([4.0])
+    assert seen[-1] == (False, 0)
+
+
+ERRORS = (maf.MAFError, realnvp.RealNVPError, made.MADEError)
+
+
+@pytest.mark.parametrize("error", ERRORS)
+def test_check_real_raises_the_callers_error_with_the_old_messages(error):
+    for bad, text in ((True, "alpha must be a number, got True"), ("x", "alpha must be a number, got 'x'"),
+                      (None, "alpha must be a number, got None"), (float("nan"), "alpha must be finite, got nan"),
+                      (float("inf"), "alpha must be finite, got inf"), (-float("inf"), "alpha must be finite, got -inf")):
+        with pytest.raises(error) as e:
+            _lib.check_real(bad, "alpha", error)
+        assert str(e.value) == text and type(e.value) is error
+    import numpy as np
+    assert _lib.check_real(np.float32(0.25), "alpha", error) == 0.25 and _lib.check_real(2, "alpha", error) == 2.0
+    assert type(_lib.check_real(np.int64(3), "alpha", error)) is float
+
+
+SETTINGS = [
+    (dict(alpha=True), "alpha must be a number, got True"),
+    (dict(alpha="x"), "alpha must be a number, got 'x'"),
+    (dict(alpha=float("nan")), "alpha must be finite, got nan"),
+    (dict(s_cap=float("inf")), "s_cap must be finite, got inf"),
+    (dict(alpha=0.5), "alpha must lie in [0, 0.5), got 0.5"),
+    (dict(alpha=0.49999999), "alpha must lie in [0, 0.5), got 0.49999999"),          # 0.5 once rounded to fp32
+    (dict(levels=1), "levels must lie in [2, 65536], got 1"),
+    (dict(levels=256.0), "levels must be an integer, got 256.0"),
+    (dict(s_cap=0), "s_cap must lie in (0, 8], got 0.0"),
+    (dict(s_cap=1e-50), "s_cap must lie in (0, 8], got 1e-50"),                      # 0 once rounded to fp32
+]
+
+
+@pytest.mark.parametrize("kw,text", SETTINGS)
+def test_shared_settings_check_keeps_every_message(kw, text):
+    args = dict(alpha=0.05, levels=256, s_cap=2.0)
+    args.update(kw)
+    calls = ((maf.MAFError, lambda: maf.check_settings(**args)),
+             (maf.MAFError, lambda: maf.MAFTrainer(maf.MAF(16, 8, 2), None, None, None, **args)),
+             (realnvp.RealNVPError, lambda: realnvp.check_config(16, 8, 2, "checker", **args)),
+             (realnvp.RealNVPError, lambda: realnvp.RealNVP(16, 8, 2, **args)),
+             (made.MADEError, lambda: realnvp.check_flow_settings(error=made.MADEError, **args)))
+    for error, call in calls:
+        with pytest.raises(error) as e:
+            call()
+        assert str(e.value) == text and type(e.value) is error
+    assert maf.check_settings(0.0, 2, 8) == (0.0, 2, 8.0)
+    assert realnvp.check_config(16, 8, 2, "half", 0.4999, 65536, 1e-3) == (16, 8, 2, "half", 0.4999, 65536, 1e-3)

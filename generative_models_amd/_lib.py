@@ -406,6 +406,10 @@ _SIGNATURES = {
     "gm_iaf_sample": (c_int, [_P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int]),
     "gm_iaf_reduce": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int, c_int, c_int]),
     "gm_iaf_step": (c_int, [_P, _P]),
+    "gm_tc_sample": (c_int, [_P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64, _P, _P, c_float, c_float, c_float,
+                             c_float, c_int, c_int, c_int]),
+    "gm_tc_reduce": (c_int, [_P, _P, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_float,
+                             c_float, c_float, c_int, c_int, c_int]),
     "gm_cat_sample": (c_int, [_P, _P, _P]),
     "gm_cat_reduce": (c_int, [_P, _P, _P]),
     "gm_vq_quantise": (c_int, [_P, _P]),

@@ -1,6 +1,6 @@
 // Philox4x32-10 (Salmon et al., SC'11; the Random123 constants) and the one home of the device noise rule (DESIGN.md
 // section 27): the step clock, the uniform / normal mappings and the sample-noise block.  Shared by every kernel that
-// draws on the device: gm_bgan.hip, gm_dvae.h, gm_ddpm.h, gm_iwae.hip, gm_flow.hip, gm_iaf.hip, gm_cat.hip, gm_nvp.hip, gm_made.h,
+// draws on the device: gm_bgan.hip, gm_dvae.h, gm_ddpm.h, gm_iwae.hip, gm_flow.hip, gm_iaf.hip, gm_tc.hip, gm_cat.hip, gm_nvp.hip, gm_made.h,
 // gm_rbm.h.
 //
 // A stream is the counter (q, step, row, tag) under key (seed mod 2^32, seed >> 32): q the block of four elements

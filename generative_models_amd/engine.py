@@ -1632,5 +1632,5 @@ class GANEngine(CriticStep, InfoQStep, GeneratorStep, PenaltySteps):
 
 
 # the engines built on this module's pieces (imported last: they import FlatParams / GANEngine ... from here)
-from .vae_engine import AAEEngine, AEEngine, BIRVAEEngine, CatVAEEngine, CVAEEngine, DVAEEngine, IAFVAEEngine, IWAEEngine, NFVAEEngine, VAEEngine, VQVAEEngine, validate_labels  # noqa: E402,F401,E501
+from .vae_engine import AAEEngine, AEEngine, BIRVAEEngine, CatVAEEngine, CVAEEngine, DVAEEngine, IAFVAEEngine, IWAEEngine, NFVAEEngine, TCVAEEngine, VAEEngine, VQVAEEngine, validate_labels  # noqa: E402,F401,E501
 from .began_engine import BEGANEngine                          # noqa: E402,F401

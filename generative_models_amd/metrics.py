@@ -30,6 +30,10 @@ AISResult = collections.namedtuple("AISResult", "ll_mean ll_stderr log_z log_z_s
 # the codes' bits; ll_mean = recon_mean + prior_mean
 VQResult = collections.namedtuple("VQResult", "ll_mean ll_stderr recon_mean prior_mean n")
 
+# tcvae.TCVAETrainer.decomposition: the KL's three terms (index-code mutual information, total correlation, dimension-wise
+# KL) and the reconstruction error, per image, over n rows
+TCResult = collections.namedtuple("TCResult", "mi tc dw_kl recon n")
+
 
 def default_sigmas():
     """numpy.logspace(-1, 0, 10): the sigma grid of the evaluation."""

@@ -819,6 +819,50 @@ def iwae_normals(n_images, k, Z, seed, step, tag, device="cuda"):
     return out.view(n_images * k, Z)
 
 
+# ---- beta-TCVAE (csrc/gm_tc.hip; tcvae.py) -------------------------------------------------------------------------
+def _tc_vec(t, n, who, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+            and t.numel() >= n):
+        raise _lib.GMError("%s: %s must be a contiguous float32 device tensor of at least %d values" % (who, name, n))
+    return t
+
+
+def tc_records(B, Z, device="cuda"):
+    """(lse_joint [B], lse_dim [B, Z], tc [B]): what tc_sample leaves for tc_reduce and for the batch's second sum."""
+    z = lambda *s: torch.zeros(*s, device=device)
+    return z(B), z(B, Z), z(B)
+
+
+def tc_sample(ml, z, lp, lse_joint, lse_dim, tc, noise, alpha, beta, gamma, log_nm, B, Z, terms=None, stream=None):
+    """z [B, Z], lp [B], the two logsumexp records, the tc row and (given) terms [B, 3] = (mi, tc, dwkl) of B images at
+    k = 1 from ml [B, 2Z] (gm_tc_sample); noise: an iwae_noise block with k_total = 1; log_nm = log(N B)."""
+    if _rows2d(ml, "ml").shape[0] < B or ml.shape[1] < 2 * Z or _rows2d(z, "z").shape[0] < B or z.shape[1] < Z \
+            or _rows2d(lse_dim, "lse_dim").shape[0] < B or lse_dim.shape[1] < Z:
+        raise _lib.GMError("tc_sample: ml %s / z %s / lse_dim %s do not fit B=%d, Z=%d"
+                           % (tuple(ml.shape), tuple(z.shape), tuple(lse_dim.shape), B, Z))
+    for t, nm in ((lp, "lp"), (lse_joint, "lse_joint"), (tc, "tc")):
+        _tc_vec(t, B, "tc_sample", nm)
+    if terms is not None:
+        _tc_vec(terms, 3 * B, "tc_sample", "terms")
+    _lib.call("gm_tc_sample", stream or stream_ptr(), ctypes.byref(noise), ml.data_ptr(), _ld(ml), z.data_ptr(), _ld(z),
+              lp.data_ptr(), lse_joint.data_ptr(), lse_dim.data_ptr(), _ld(lse_dim), tc.data_ptr(),
+              terms.data_ptr() if terms is not None else None, float(alpha), float(beta), float(gamma), float(log_nm),
+              B, 1, Z)
+
+
+def tc_reduce(ml, z, lse_joint, lse_dim, wn, dzdec, dml, noise, alpha, beta, gamma, B, Z, stream=None):
+    """d loss / d [mu | lv] -> dml [B, 2Z] from tc_sample's z and records, the weights wn [B] and dzdec [B, Z] = dHdec
+    Wd1 (gm_tc_reduce); noise: tc_sample's block."""
+    for t, w, nm in ((ml, 2 * Z, "ml"), (z, Z, "z"), (lse_dim, Z, "lse_dim"), (dzdec, Z, "dzdec"), (dml, 2 * Z, "dml")):
+        if _rows2d(t, nm).shape[0] < B or t.shape[1] < w:
+            raise _lib.GMError("tc_reduce: %s %s does not fit B=%d, Z=%d" % (nm, tuple(t.shape), B, Z))
+    for t, nm in ((lse_joint, "lse_joint"), (wn, "wn")):
+        _tc_vec(t, B, "tc_reduce", nm)
+    _lib.call("gm_tc_reduce", stream or stream_ptr(), ctypes.byref(noise), ml.data_ptr(), _ld(ml), z.data_ptr(), _ld(z),
+              lse_joint.data_ptr(), lse_dim.data_ptr(), _ld(lse_dim), wn.data_ptr(), dzdec.data_ptr(), _ld(dzdec),
+              dml.data_ptr(), _ld(dml), float(alpha), float(beta), float(gamma), B, 1, Z)
+
+
 # ---- Planar-flow posterior of the normalizing-flow VAE (csrc/gm_flow.hip; nfvae.py) --------------------------------
 class FlowParams(ctypes.Structure):
     """gm_flow_params (include/gm_hip.h): the K planar layers' u [K, Z], w [K, Z], b [K]."""

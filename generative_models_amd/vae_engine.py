@@ -1099,6 +1099,64 @@ class IAFVAEEngine(IWAEEngine):
                      grads=self.Fgrads, weight_decay=self.wd, stream=st)
 
 
+class TCVAEEngine(IWAEEngine):
+    """The beta-TCVAE (tcvae.py holds the contract): IWAEEngine's 12-launch batch at k = 1 with
+    launch 3 replaced by gm_tc_sample (z, lp = -(alpha mi + beta tc + gamma dwkl) from every pair of the batch, the two
+    logsumexp records and the per-image tc) and launch 10 by gm_tc_reduce (d loss / d [mu | lv] through the sample and
+    through every partner's parameters).  The finalize block sums -log w (-> `recon`) and tc / b (-> `kl`).  log(N b) is
+    a launch argument: N the trainer's dataset_size for a training batch, the pass's own dataset for a validation batch
+    (a graph is keyed by its batch size, its kind and its dataset, so each holds one value).  One GPU only."""
+
+    one_gpu = "the TCVAE engine"
+
+    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
+                 trainer=None):
+        self._refuse_dp(world_size, force_dp)
+        super().__init__(model, device, use_graph=use_graph, trainer=trainer)
+
+    def _check_limits(self, model, k):
+        from ._lib import IWAE_MAX_Z
+        Z = model.encoder.mu.weight.shape[0]
+        if k != 1 or not 1 <= Z <= IWAE_MAX_Z:
+            raise GMError("TCVAEEngine: k = 1 and 1 <= z_dim <= %d (got k=%d, z_dim=%d); TCVAETrainer trains these on "
+                          "the general path" % (IWAE_MAX_Z, k, Z))
+
+    def _alloc(self, B):
+        if self._bufB == B:
+            return
+        super()._alloc(B)
+        from . import ops_fused as of_
+        self.lse_joint, self.lse_dim, self.tcrow = of_.tc_records(B, self.Z, device=self.device)
+
+    def _settings(self):
+        tr = self.trainer
+        return dict(alpha=float(tr.alpha), beta=float(tr.beta), gamma=float(tr.gamma),
+                    dataset_size=int(tr.dataset_size), **super()._settings())
+
+    def _second_sum(self, b):
+        return self.tcrow, 1.0 / b
+
+    def _coef(self):
+        tr = self.trainer
+        return float(tr.alpha), float(tr.beta), float(tr.gamma)
+
+    def _log_nm(self, b, train):
+        """log(N b): N the training set's size (the trainer's dataset_size) or the size of the pass's own dataset."""
+        import math
+        n = int(self.trainer.dataset_size) if train else int(self.data.shape[0])
+        return math.log(n * b)
+
+    def _sample(self, st, nz, b, t=0, train=True):
+        from . import ops_fused as of_
+        of_.tc_sample(self.ml, self.Zs, self.lp, self.lse_joint, self.lse_dim, self.tcrow, nz, *self._coef(),
+                      self._log_nm(b, train), b, self.Z, stream=st)
+
+    def _reduce(self, st, nz, b, adam):
+        from . import ops_fused as of_
+        of_.tc_reduce(self.ml, self.Zs, self.lse_joint, self.lse_dim, self.wn, self.dzdec, self.dml, nz, *self._coef(),
+                      b, self.Z, stream=st)
+
+
 class CatVAEEngine(IWAEEngine):
     """The categorical VAE (catvae.py holds the contract): IWAEEngine's 12-launch batch at k = 1 with the `logits` layer
     (width N C) as the encoder's head instead of the packed [mu | log_var], launch 3 replaced by gm_cat_sample (the

@@ -1140,6 +1140,33 @@ typedef struct gm_iaf_step_args {
  * skipped: it and its moments are left as they are (0.0), its gradient is written as 0.0. */
 int gm_iaf_step(void* stream, const gm_iaf_step_args* a);
 
+/* ---- beta-TCVAE (csrc/gm_tc.hip; tcvae.py holds the contract).  gm_iwae_sample / gm_iwae_reduce at
+ * k = 1 with the KL term decomposed by minibatch-weighted sampling over every pair (sample i, posterior j) of the batch.
+ * With l'(i, j, d) = -1/2 (lv_jd + (z_id - mu_jd)^2 exp(-lv_jd)) (log N(z_id; mu_jd, exp lv_jd) without -1/2 log 2 pi,
+ * which cancels out of every term below), L = log_nm = log(N M), all sums over j including j = i:
+ *   J_i = logsumexp_j sum_d l'(i, j, d)            D_id = logsumexp_j l'(i, j, d)
+ *   mi_i = sum_d l'(i, i, d) - J_i + L             tc_i = J_i - sum_d D_id + (Z - 1) L
+ *   dwkl_i = sum_d D_id - Z L + 1/2 |z_i|^2        lp_i = -(alpha mi_i + beta tc_i + gamma dwkl_i)
+ * Rows and the noise block are the IWAE's (the IWAE's two tags: z is gm_iwae_sample's bit for bit).  No [B, B] or
+ * [B, B, Z] array is formed; fixed reduction orders, no atomics.  Limits: k = 1, 1 <= Z <= GM_IWAE_MAX_Z, B >= 1,
+ * alpha, beta, gamma finite and >= 0; outside them, or with a NULL or aliased array, both return GM_EINVAL before any
+ * launch. */
+/* z [B, Z], lp [B], the records lse_joint [B] = J and lse_dim [B, Z] = D for gm_tc_reduce, tc [B], and, where not NULL,
+ * terms [B, 3] = (mi, tc, dwkl).  One launch, no dependency across the grid: an owner row reads its own z and every
+ * row's [mu | lv].  Called from vae_engine.TCVAEEngine._sample (launch 3) and ops_fused.tc_sample. */
+int gm_tc_sample(void* stream, const gm_iwae_noise* n, const float* ml, int64_t ldml, float* z, int64_t ldz, float* lp,
+                 float* lse_joint, float* lse_dim, int64_t ldd, float* tc, float* terms, float alpha, float beta,
+                 float gamma, float log_nm, int B, int k, int Z);
+/* The backward of gm_tc_sample: dml [B, 2Z] = d sum_i (-wn_i lp_i) / d [mu | lv] + the reparameterised dzdec.  The
+ * coefficient of l'(i, j, d) is wn_i ((beta - alpha) a_ij + (gamma - beta) c_ijd), a_i. = softmax_j sum_d l' (from J),
+ * c_i.d = softmax_j l' (from D); row r sums its terms as sample i = r into dz_r and as posterior j = r (z read from z
+ * [B, Z]) into dmu_r, dlv_r in one workgroup, then dz_r + gamma wn_r z_r + dzdec_r goes through the reparameterisation
+ * (eps rebuilt from the counter) and the alpha term leaves -alpha wn_r / 2 on lv.  One writer per element.  Called from
+ * vae_engine.TCVAEEngine._reduce (launch 10) and ops_fused.tc_reduce. */
+int gm_tc_reduce(void* stream, const gm_iwae_noise* n, const float* ml, int64_t ldml, const float* z, int64_t ldz,
+                 const float* lse_joint, const float* lse_dim, int64_t ldd, const float* wn, const float* dzdec,
+                 int64_t lddz, float* dml, int64_t lddml, float alpha, float beta, float gamma, int B, int k, int Z);
+
 /* ---- Gumbel-Softmax posterior of the categorical VAE (csrc/gm_cat.hip; catvae.py holds the contract, DESIGN.md
  * section 23).  N categorical variables of C classes per sample row, rows image-major, gm_iwae_noise's counter layout
  * under the two tags below: element e = n C + c of noise row `row` is word e & 3 of Philox counter (q0 + (e >> 2), step,

@@ -26,11 +26,12 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import guarded  # noqa: E402
 import linear_path_cases as lp  # noqa: E402
 from generative_models_amd import ops  # noqa: E402
 
 DEV = "cuda:0"
-NAN_BITS = 0x7FC0DEAD                    # a quiet NaN no arithmetic produces
+NAN_BITS = guarded.NAN_BITS              # a quiet NaN no arithmetic produces
 VECTORS = ("bias", "db", "pb", "mb", "vb", "sched")
 WORST = {"ratio": 0.0, "case": None}     # the largest e_hip / bound of the session (printed with every case)
 
@@ -86,33 +87,9 @@ def expression_flags(c):
     return tuple(sorted((k, v) for k, v in c.flags.items() if k in ("bias", "act", "epi", "add", "accumulate")))
 
 
-# ---- guarded placement ------------------------------------------------------------------------------------------------
-class Placed:
-    def __init__(self, a, values):
-        guard = lp.GUARD_FLOATS if a.name in VECTORS else lp.GUARD_ROWS * a.ld
-        guard += lp.pad4(guard)
-        stride = lp.ring_stride(a) if a.ring > 1 else 0
-        span = a.ring * stride if a.ring > 1 else a.rows * a.ld
-        self.buf = torch.empty(guard + a.off + span + guard + 4, device=DEV)
-        assert self.buf.data_ptr() % 16 == 0
-        self.buf.view(torch.int32).fill_(NAN_BITS)
-        base = guard + a.off
-        shape, strides, start = (a.rows, a.width), (a.ld, 1), base + lp.RING_PICK * stride
-        self.view = self.buf.as_strided(shape, strides, start)
-        if values is not None:
-            self.view.copy_(values.reshape(shape))
-        self.inside = torch.zeros(self.buf.numel(), dtype=torch.bool, device=DEV)
-        self.inside.as_strided(shape, strides, start).fill_(True)
-        self.ptr = self.buf.data_ptr() + 4 * base
-        assert self.ptr % 16 == 4 * a.off
-        self.before = self.buf.view(torch.int32).clone()
-        self.array = a
-
-    def untouched_outside(self):
-        after = self.buf.view(torch.int32)
-        if self.array.role == "in":
-            return torch.equal(after, self.before)
-        return torch.equal(after[~self.inside], self.before[~self.inside])
+# ---- guarded placement (tests/guarded.py) ------------------------------------------------------------------------------
+def Placed(a, values):
+    return guarded.Placed(a, values, vector=a.name in VECTORS, pick=lp.RING_PICK, dev=DEV)
 
 
 def cpu_below(c, t):

@@ -37,6 +37,7 @@
 #include "gm_ldsdma.h"
 
 #include <cstdlib>
+#include <cassert>
 #include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -782,62 +783,6 @@ inline int lds_pick_cfg(int M, int N) {
     return pick;
 }
 
-// ---- launch-plan query (gm_linear_plan, gm_hip.h).  While plan_rec points at a plan on this thread, every launch site
-// of this file's host side RECORDS what it would launch -- from the template arguments it names -- instead of launching,
-// and GM_GEMM_RET returns without asking the runtime: the query is the dispatch itself, run dry.  The launch path pays
-// one test of a thread-local pointer per launch.
-thread_local int32_t* plan_rec = nullptr;
-
-inline void plan_launch(dim3 grid, dim3 block) {
-    plan_rec[GM_PLAN_F_LAUNCHES] += 1;
-    plan_rec[GM_PLAN_F_GRID_X] = (int32_t)grid.x; plan_rec[GM_PLAN_F_GRID_Y] = (int32_t)grid.y;
-    plan_rec[GM_PLAN_F_BLOCK] = (int32_t)block.x;
-    if (!plan_rec[GM_PLAN_F_FAMILY]) plan_rec[GM_PLAN_F_FAMILY] = GM_PLAN_RIDING;   // (a plain site names its family first)
-}
-inline void plan_kernel(int family, int mode, int mi, int ni, int lds_cfg, int lds_stages, bool vec, bool xv, int vec_epi,
-                        bool dma, bool slots) {
-    int32_t* r = plan_rec;
-    r[GM_PLAN_F_FAMILY] = family; r[GM_PLAN_F_MODE] = mode; r[GM_PLAN_F_MI] = mi; r[GM_PLAN_F_NI] = ni;
-    r[GM_PLAN_F_LDS_CFG] = lds_cfg; r[GM_PLAN_F_LDS_STAGES] = lds_stages; r[GM_PLAN_F_VEC] = vec; r[GM_PLAN_F_XV] = xv;
-    r[GM_PLAN_F_VEC_EPI] = vec_epi; r[GM_PLAN_F_DMA] = dma; r[GM_PLAN_F_SLOTS] = slots;
-}
-// hipLaunchKernelGGL, or its record; GM_LAUNCH_AS: a plain launch site, NOTE = the plan_kernel call that describes KERNEL
-#define GM_LAUNCH(KERNEL, GRID, BLOCK, ...)                                         \
-    do {                                                                            \
-        if (plan_rec) plan_launch(GRID, BLOCK);                                     \
-        else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, __VA_ARGS__);                  \
-    } while (0)
-#define GM_LAUNCH_AS(NOTE, KERNEL, GRID, BLOCK, ...)                                \
-    do {                                                                            \
-        if (plan_rec) { NOTE; plan_launch(GRID, BLOCK); }                           \
-        else hipLaunchKernelGGL(KERNEL, GRID, BLOCK, __VA_ARGS__);                  \
-    } while (0)
-#define GM_GEMM_RET()                                                               \
-    do {                                                                            \
-        if (plan_rec) return 0;                                                     \
-        GM_LAUNCH_RET();                                                            \
-    } while (0)
-
-template <int MODE, int BM, int BN, int WTM, int WTN, int WK, int KU, int PD>
-int launch_lds_cfg(hipStream_t s, GemmP p) {
-    using C = LdsCfg<MODE, BM, BN, WTM, WTN, WK, KU>;
-    const int tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
-    p.lds_tm = tm; p.tn = tn; p.lds_mpx = (tm + 7) / 8;
-    const dim3 grid(8 * p.lds_mpx * tn), block(C::NT);
-    // fully unrolled instantiations for the reduction lengths of this model (784, 400: image and
-    // hidden widths); anything else takes the runtime loop
-    constexpr int NS784 = (784 + C::BK - 1) / C::BK, NS400 = (400 + C::BK - 1) / C::BK;
-    const int S = (p.K + C::BK - 1) / C::BK;
-#define GM_LLDS(NS_)                                                                                                  \
-    GM_LAUNCH_AS(plan_kernel(GM_PLAN_LDS, MODE, 0, 0, BM == 64 ? 1 : 2, NS_, true, MODE == MODE_DX, p.vec_epi, false, false), \
-                 (gemm_lds_kernel<MODE, BM, BN, WTM, WTN, WK, KU, PD, NS_>), grid, block, 0, s, p)
-    if (S == NS784) GM_LLDS(NS784);
-    else if (S == NS400) GM_LLDS(NS400);
-    else GM_LLDS(0);
-#undef GM_LLDS
-    GM_GEMM_RET();
-}
-
 // Tile configuration of the LDS kernel for this forward / input-gradient launch, or 0 when the launch is not for it
 // (the caller continues with the split-reduction kernels).  1: 64x64 tile = 2 x 1 waves of 32x64 (two accumulators
 // each) x 4 reduction groups, BK = 32; 2: 32x64 tile = 1 x 2 waves of 32x32 x 4 reduction groups.
@@ -849,16 +794,6 @@ int lds_cfg_for(const GemmP& p, bool vec, bool xv) {
     constexpr int min_m = 1024;                              // (ops.lds_min_m() mirrors it on the host side)
     if (p.M < min_m || p.K < 64 || !vec || (MODE == MODE_DX && !xv) || p.N < 32) return 0;
     return lds_pick_cfg(p.M, p.N);
-}
-
-template <int MODE>
-int launch_lds(hipStream_t s, const GemmP& p, int cfg) {
-    // (round 6, profiles/r06_experiments.md section 3: BK = 64 (13 barriers instead of 25), 2 x 2 waves x 2 k-groups (half the
-    // partial tiles in the epilogue) and 2 register stages instead of 4 all measured level or slower than this --
-    // 20.0 / 19.9 / 20.0 against 19.7 us on 2048 x 784 -> 400: the stages run at 1 150 - 1 210 cycles against 1 024 of
-    // MFMA issue, what the launch loses it loses to tile quantisation, profiles/r06_ns_b1024_wave_timeline.md)
-    if (cfg == 1) return launch_lds_cfg<MODE, 64, 64, 32, 64, 4, 1, 4>(s, p);
-    return launch_lds_cfg<MODE, 32, 64, 32, 32, 4, 1, 4>(s, p);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2038,15 +1973,6 @@ struct Rider {
     const L1RideP* l1 = nullptr;         // MODE_DW pair: the next iteration's first layer from the second GEMM's W1, b1
 };
 
-// A rider's batch gather as a launch of its own (4 waves per workgroup), for the configurations that cannot carry it.
-inline void launch_gather_alone(hipStream_t s, const Rider& r) {
-    const GatherP& gp = *r.gather;
-    if (r.corrupt)
-        GM_LAUNCH(gather_rows_corrupt_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp, *r.corrupt);
-    else
-        GM_LAUNCH(gather_rows_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp);
-}
-
 // Tile shapes of the 16-wave kernels, as sub-tiles (16 x 16) per wave: MI x NI
 enum { T22 = 0, T24, T42, T12, T23, T32 };       // 32x32, 32x64, 64x32, 16x32, 32x48, 48x32
 inline int tile_mi(int t) { return t == T42 ? 4 : t == T32 ? 3 : t == T12 ? 1 : 2; }
@@ -2076,32 +2002,87 @@ int pick_tile(const GemmP& p) {
     return t;
 }
 
-// LAUNCH(MI, NI, DMA) for the tile `tile`; the LDS-DMA instantiations exist for the 48-wide weight-gradient tiles
-#define GM_TILE_SWITCH(tile, dma, LAUNCH)                                           \
-    do {                                                                            \
-        switch (tile) {                                                             \
-        case T24: LAUNCH(2, 4, false); break;                                       \
-        case T42: LAUNCH(4, 2, false); break;                                       \
-        case T12: LAUNCH(1, 2, false); break;                                       \
-        case T23: if (dma) LAUNCH(2, 3, true); else LAUNCH(2, 3, false); break;     \
-        case T32: if (dma) LAUNCH(3, 2, true); else LAUNCH(3, 2, false); break;     \
-        default: LAUNCH(2, 2, false); break;                                        \
-        }                                                                           \
-    } while (0)
+// ---- host dispatch.  decide<MODE> turns a call into a Plan -- pure host arithmetic that carries every rule of this file --
+// and issue() launches a Plan: the only place on the host side that names a kernel.  gm_linear_plan reads the same Plan.
+enum Family {       // (the first three ARE gm_hip.h's; before F_LABEL: a stamp slot in the GM_STAMPS build; the last three: no GemmP)
+    F_LDS = GM_PLAN_LDS, F_K32 = GM_PLAN_K32, F_SPLIT = GM_PLAN_SPLIT, F_FWD_BITS, F_DW_HEAD_BITS, F_DW_HEAD, F_DW_HEAD_TP,
+    F_DX_HEAD, F_DX_GATHER, F_FWD_GATHER, F_PAIR, F_PAIR_L1, F_LABEL, F_HEAD, F_GATHER, F_FIN2
+};
+static_assert(F_FWD_BITS == GM_PLAN_RIDING, "every family past the plain three reports as GM_PLAN_RIDING");
+
+struct Step {
+    int family, mode;           // Family; MODE_* of its kernel (a weight-gradient plan may end in the layer-1 forward)
+    int mi, ni;                 // tile of the 16-wave kernels, in 16 x 16 sub-tiles per wave (0: the family has one shape)
+    bool vec, xv, of, folded, dma, sl, slb, gather, corrupt, fin;   // the compile-time switches its family takes
+    int lds_cfg, lds_ns;        // F_LDS: tile configuration, stages of the unrolled instantiation (0: runtime loop)
+    dim3 grid, block;
+    int gemm;                   // runs on Plan::g[gemm] (the pairs: and on g[gemm + 1])
+    int r0, r1, r2;             // rider counts: hrows, hblocks / grows, gblocks / na, tna, tnb
+};
+struct Plan {
+    int n = 0, ng = 0;
+    Step step[4];               // (the longest: single GEMM, single GEMM, loss sums)
+    GemmP g[3];                 // first, second (pair), derived layer-1 forward -- as decided (vec_epi, dma, LDS tiling)
+};
+
+// The LDS kernel's two tile configurations (lds_cfg_for).
+// (round 6, profiles/r06_experiments.md section 3: BK = 64 (13 barriers instead of 25), 2 x 2 waves x 2 k-groups (half the
+// partial tiles in the epilogue) and 2 register stages instead of 4 all measured level or slower than this --
+// 20.0 / 19.9 / 20.0 against 19.7 us on 2048 x 784 -> 400: the stages run at 1 150 - 1 210 cycles against 1 024 of
+// MFMA issue, what the launch loses it loses to tile quantisation, profiles/r06_ns_b1024_wave_timeline.md)
+template <int MODE, int CFG>
+using LdsOf = std::conditional_t<CFG == 1, LdsCfg<MODE, 64, 64, 32, 64, 4, 1>, LdsCfg<MODE, 32, 64, 32, 32, 4, 1>>;
+constexpr int LDS_NT = LdsOf<MODE_FWD, 1>::NT, LDS_BK = LdsOf<MODE_FWD, 1>::BK;
+static_assert(LdsOf<MODE_DX, 2>::NT == LDS_NT && LdsOf<MODE_DX, 2>::BK == LDS_BK, "one block size, one stage depth");
+// fully unrolled instantiations for the reduction lengths of this model (784, 400: image and
+// hidden widths); anything else takes the runtime loop
+constexpr int LDS_NS784 = (784 + LDS_BK - 1) / LDS_BK, LDS_NS400 = (400 + LDS_BK - 1) / LDS_BK;
 
 template <int MODE>
-int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const Rider& rider = Rider()) {
+int decide(const GemmP& p_in, bool vec, bool xvec, const Rider& rider, Plan* plan) {
+    const int gi = plan->ng++;
+    GemmP& p = plan->g[gi];
+    p = p_in;
+    auto add = [&](int family, dim3 grid, int block) -> Step& {
+        assert(plan->n < 4);
+        Step& st = (plan->step[plan->n++] = Step{});
+        st.family = family; st.mode = MODE; st.grid = grid; st.block = dim3(block); st.gemm = gi;
+        return st;
+    };
+    auto tiled = [&](int family, int tile, dim3 grid) -> Step& {         // a step of the 16-wave kernels
+        Step& st = add(family, grid, 1024);
+        st.mi = tile_mi(tile); st.ni = tile_ni(tile);
+        return st;
+    };
+    auto tile_grid = [](const GemmP& q, int t) {
+        return dim3((q.N + 16 * tile_ni(t) - 1) / (16 * tile_ni(t)), (q.M + 16 * tile_mi(t) - 1) / (16 * tile_mi(t))); };
+    auto ride = [](Step& st, int blocks) {                    // rider workgroups in rows [0, r0) of the step's grid
+        st.r1 = blocks; st.r0 = (blocks + (int)st.grid.x - 1) / (int)st.grid.x;
+        st.grid.y += st.r0;
+    };
+    auto dma48 = [](const GemmP& q, int tile) { return q.dma && (tile == T23 || tile == T32); };   // (see on_tile)
+    // The plain 16-wave launch of g[g]; template arguments: MODE, VEC, waves, G, XV, MI, NI, DMA, SL
+    auto split = [&](int g, bool v, bool x) {
+        const GemmP& q = plan->g[g];
+        const int t = pick_tile<MODE>(q);
+        Step& st = tiled(F_SPLIT, t, tile_grid(q, t));
+        st.gemm = g; st.vec = v; st.xv = x; st.dma = dma48(q, t);
+        st.sl = MODE != MODE_DX && (has_slot(q.a_slot) || has_slot(q.b_slot));
+    };
+    if constexpr (MODE == MODE_FWD) {
+        // The class-conditional forward: every shape through the 16-wave split-reduction kernel (its tile choice) -- the
+        // label term lives in that kernel's epilogue only.
+        if (p.lb_E) {
+            const int t = pick_tile<MODE_FWD>(p);
+            tiled(F_LABEL, t, tile_grid(p, t)).vec = vec;
+            return 0;
+        }
+    }
     const HeadBwdP* head = rider.head;
     // folded critic head: the head workgroups AND the GEMM's A operand depend on the fold -- only the riding launches
     // below implement it; every other configuration is refused, never silently run without it
     const bool folded = head && head->fold.enabled;
-    GemmP p = p_in;
     p.vec_epi = vec_epi_ok<MODE>(p);
-#ifdef GM_STAMPS
-    p.stamp.slot = gm_stamps::host_buf ? gm_stamps::host_buf + (size_t)(gm_stamps::host_next++ % gm_stamps::SLOTS) * gm_stamps::SLOT_WORDS
-                                       : nullptr;
-    p.stamp.tile = gm_stamps::host_tile;
-#endif
     const bool xv = xvec && MODE != MODE_FWD;
     // ring slots on the operands (the generator's first layer on the noise ring): the slot-resolving instantiations of
     // the plain / gather / pair kernels; the head-riding, bit-packed and LDS macro-tile kernels are compiled without
@@ -2111,6 +2092,9 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
         return GM_EINVAL;
     }
     const bool ride_head = head && !slots;                   // (else the head workgroups get their own launch below)
+    auto head_alone = [&] { add(F_HEAD, dim3(gm_head_bwd_blocks(*head)), 1024); };
+    // A rider's batch gather as a launch of its own (4 waves per workgroup), for the configurations that cannot carry it.
+    auto gather_alone = [&] { add(F_GATHER, dim3(gm_gather_blocks(*rider.gather, 4)), 256).corrupt = rider.corrupt != nullptr; };
     // weight gradients over >= GM_DW_DMA_MIN_K rows on 16-byte aligned operands: chunks by LDS-DMA (gemm16_dw_dma).
     // Measured (profiles/r04_experiments.md): 2048 rows 26.0 -> 24.2 us, 1024 rows 15.3 -> 15.2, 768 rows 12.2 -> 11.9;
     // below that the extra hop through LDS costs more than the load instructions it saves (512 rows 9.0 -> 9.2, 256
@@ -2129,9 +2113,8 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
                 gm_set_error("bit-packed rows: the forward needs 16-byte aligned operands and the folded head's partial dots");
                 return GM_EINVAL;
             }
-            const dim3 bgrid((p.N + 31) / 32, (p.M + 31) / 32);
-            GM_LAUNCH(gemm16_fwd_bits_kernel, bgrid, dim3(1024), 0, s, p);
-            GM_GEMM_RET();
+            add(F_FWD_BITS, dim3((p.N + 31) / 32, (p.M + 31) / 32), 1024);
+            return 0;
         } else if constexpr (MODE == MODE_DW) {
             if (!head || !folded || head->fold.enabled != 1 || !xv || p.ones_from > 0 || rider.pair) {
                 gm_set_error("bit-packed rows: the weight gradient needs the folded head of a separable loss and "
@@ -2139,12 +2122,8 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
                 return GM_EINVAL;
             }
             p.dma = false;                                   // operands through registers (the expansion lives there)
-            const dim3 bgrid((p.N + 47) / 48, (p.M + 31) / 32);
-            const int hblocks = gm_head_bwd_blocks(*head);
-            const int hrows = (hblocks + (int)bgrid.x - 1) / (int)bgrid.x;
-            GM_LAUNCH(gemm16_dw_head_bits_kernel, dim3(bgrid.x, bgrid.y + hrows), dim3(1024), 0, s, p, *head,
-                               hrows, hblocks);
-            GM_GEMM_RET();
+            ride(add(F_DW_HEAD_BITS, dim3((p.N + 47) / 48, (p.M + 31) / 32), 1024), gm_head_bwd_blocks(*head));
+            return 0;
         } else {
             gm_set_error("bit-packed rows: forward and weight gradient only");
             return GM_EINVAL;
@@ -2156,92 +2135,57 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
         if (!rider.pair && !folded && !p.hd_part && !p.sq_part && !slots) {
             const int cfg = lds_cfg_for<MODE>(p, vec, xv);
             if (cfg) {
-                if (head) GM_LAUNCH(head_bwd_kernel, dim3(gm_head_bwd_blocks(*head)), dim3(1024), 0, s, *head);
-                if (rider.gather) launch_gather_alone(s, rider);
-                return launch_lds<MODE>(s, p, cfg);
+                if (head) head_alone();
+                if (rider.gather) gather_alone();
+                const int BM = cfg == 1 ? 64 : 32, BN = 64;
+                const int tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
+                p.lds_tm = tm; p.tn = tn; p.lds_mpx = (tm + 7) / 8;
+                const int S = (p.K + LDS_BK - 1) / LDS_BK;
+                Step& st = add(F_LDS, dim3(8 * p.lds_mpx * tn), LDS_NT);
+                st.lds_cfg = cfg; st.lds_ns = S == LDS_NS784 || S == LDS_NS400 ? S : 0;
+                st.vec = true; st.xv = MODE == MODE_DX;
+                return 0;
             }
         }
     }
     // forwards over a reduction of at most 32: one wave per 16 x 32 piece, no cross-wave reduction (gemm16_k32_fwd_kernel)
     if constexpr (MODE == MODE_FWD) {
         if (vec && p.K <= 32 && !head && !p.hd_part && !p.sq_part) {
-            const dim3 kgrid((p.N + 63) / 64, (p.M + 31) / 32);
-            if (rider.gather && rider.corrupt) {                 // the corrupting gather is not compiled into this kernel
-                launch_gather_alone(s, rider);
-                if (slots) GM_LAUNCH((gemm16_k32_fwd_kernel<true, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0);
-                else GM_LAUNCH((gemm16_k32_fwd_kernel<false, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0);
-            } else if (rider.gather) {
-                const GatherP& gp = *rider.gather;
-                const int gblocks = gm_gather_blocks(gp, 4);
-                const int grows = (gblocks + (int)kgrid.x - 1) / (int)kgrid.x;
-                const dim3 ggrid(kgrid.x, kgrid.y + grows);
-                if (slots) GM_LAUNCH((gemm16_k32_fwd_kernel<true, true>), ggrid, dim3(256), 0, s, p, gp, grows, gblocks);
-                else GM_LAUNCH((gemm16_k32_fwd_kernel<false, true>), ggrid, dim3(256), 0, s, p, gp, grows, gblocks);
-            } else {
-#define GM_LK32(SL_)                                                                                             \
-    GM_LAUNCH_AS(plan_kernel(GM_PLAN_K32, MODE, 0, 0, 0, 0, true, false, p.vec_epi, false, SL_),                \
-                 (gemm16_k32_fwd_kernel<SL_, false>), kgrid, dim3(256), 0, s, p, GatherP{}, 0, 0)
-                if (slots) GM_LK32(true);
-                else GM_LK32(false);
-#undef GM_LK32
-            }
-            GM_GEMM_RET();
+            const bool rides = rider.gather && !rider.corrupt;   // the corrupting gather is not compiled into this kernel
+            if (rider.gather && !rides) gather_alone();
+            Step& st = add(F_K32, dim3((p.N + 63) / 64, (p.M + 31) / 32), 256);
+            st.vec = true; st.sl = slots; st.gather = rides;
+            if (rides) ride(st, gm_gather_blocks(*rider.gather, 4));
+            return 0;
         }
     }
     const int tile = pick_tile<MODE>(p);
-    const int mi = tile_mi(tile), ni = tile_ni(tile);
-    const dim3 grid((p.N + 16 * ni - 1) / (16 * ni), (p.M + 16 * mi - 1) / (16 * mi));
+    const int ni = tile_ni(tile);
+    const dim3 grid = tile_grid(p, tile);
     if constexpr (MODE == MODE_DW) {
         if (ride_head) {                 // the critic head's backward workgroups ride in rows [0, hrows) of the grid
-            const int hblocks = gm_head_bwd_blocks(*head);
-            const int hrows = (hblocks + (int)grid.x - 1) / (int)grid.x;
-            const dim3 hgrid(grid.x, grid.y + hrows);
             if (folded && (!xv || p.ones_from > 0)) {
                 gm_set_error("folded head: the weight gradient needs 16-byte aligned operands and no stacked rows");
                 return GM_EINVAL;
             }
+            // RaGAN / Fisher (fold 2): operands through registers (the two-phase prologue's scratch and the DMA form's
+            // chunk buffers would share LDS)
+            const bool tp = folded && head->fold.enabled == 2;
+            if (tp) p.dma = false;
             // template arguments: VEC (a k-contiguous notion: false), G, XV, MI, NI, OF (ones column with a row offset:
             // WGAN-GP's stacked gradient), FOLDED, DMA
-#define GM_LH(X, OFV, FD) GM_TILE_SWITCH(tile, p.dma && (X), GM_LH1_##X##_##OFV##_##FD)
-#define GM_LHK(X, OFV, FD, MI_, NI_, D_) GM_LAUNCH((gemm16_dw_head_kernel<false, 1, X, MI_, NI_, OFV, FD, ((X) && (D_))>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks)
-#define GM_LH1_true_false_true(MI_, NI_, D_) GM_LHK(true, false, true, MI_, NI_, D_)
-#define GM_LH1_true_true_false(MI_, NI_, D_) GM_LHK(true, true, false, MI_, NI_, D_)
-#define GM_LH1_true_false_false(MI_, NI_, D_) GM_LHK(true, false, false, MI_, NI_, D_)
-#define GM_LH1_false_true_false(MI_, NI_, D_) GM_LHK(false, true, false, MI_, NI_, D_)
-#define GM_LH1_false_false_false(MI_, NI_, D_) GM_LHK(false, false, false, MI_, NI_, D_)
-            if (folded && head->fold.enabled == 2) {
-                // RaGAN / Fisher: operands through registers (the two-phase prologue's scratch and the DMA form's
-                // chunk buffers would share LDS)
-                p.dma = false;
-#define GM_LHTP(MI_, NI_, D_) GM_LAUNCH((gemm16_dw_head_tp_kernel<MI_, NI_>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks)
-                GM_TILE_SWITCH(tile, false, GM_LHTP);
-#undef GM_LHTP
-            } else if (folded) GM_LH(true, false, true);
-            else if (xv) { if (p.ones_from > 0) GM_LH(true, true, false); else GM_LH(true, false, false); }
-            else { if (p.ones_from > 0) GM_LH(false, true, false); else GM_LH(false, false, false); }
-#undef GM_LH1_false_false_false
-#undef GM_LH1_false_true_false
-#undef GM_LH1_true_false_false
-#undef GM_LH1_true_true_false
-#undef GM_LH1_true_false_true
-#undef GM_LHK
-#undef GM_LH
-            GM_GEMM_RET();
+            Step& st = tiled(tp ? F_DW_HEAD_TP : F_DW_HEAD, tile, grid);
+            st.xv = xv; st.of = p.ones_from > 0; st.folded = folded; st.dma = dma48(p, tile);
+            ride(st, gm_head_bwd_blocks(*head));
+            return 0;
         }
     }
     if constexpr (MODE == MODE_DX) {
         if (ride_head && vec && xv && (tile == T22 || tile == T12)) {   // the generator-mode head's scalar workgroup rides along
-            const int hblocks = gm_head_bwd_blocks(*head);
-            const int hrows = (hblocks + (int)grid.x - 1) / (int)grid.x;
-            const dim3 hgrid(grid.x, grid.y + hrows);
-            if (tile == T12) {
-                if (folded) GM_LAUNCH((gemm16_dx_head_kernel<1, 1, 2, true>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
-                else GM_LAUNCH((gemm16_dx_head_kernel<1, 1, 2, false>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
-            } else {
-                if (folded) GM_LAUNCH((gemm16_dx_head_kernel<1, 2, 2, true>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
-                else GM_LAUNCH((gemm16_dx_head_kernel<1, 2, 2, false>), hgrid, dim3(1024), 0, s, p, *head, hrows, hblocks);
-            }
-            GM_GEMM_RET();
+            Step& st = tiled(F_DX_HEAD, tile, grid);
+            st.vec = st.xv = true; st.folded = folded;
+            ride(st, gm_head_bwd_blocks(*head));
+            return 0;
         }
     }
     if (folded) {
@@ -2249,133 +2193,203 @@ int launch(hipStream_t s, const GemmP& p_in, bool vec, bool xvec = false, const 
                      "aligned operands)");
         return GM_EINVAL;
     }
-    if (head)        // this configuration cannot carry the head workgroups: separate launch
-        GM_LAUNCH(head_bwd_kernel, dim3(gm_head_bwd_blocks(*head)), dim3(1024), 0, s, *head);
-    if constexpr (MODE == MODE_DX) {
+    if (head) head_alone();      // this configuration cannot carry the head workgroups: separate launch
+    if constexpr (MODE != MODE_DW) {
         if (rider.gather) {
-            const GatherP& gp = *rider.gather;
-            if (vec && xv && (tile == T22 || tile == T12)) {     // the batch gather rides in rows [0, grows) of the grid
-                const int gblocks = gm_gather_blocks(gp, 16);
-                const int grows = (gblocks + (int)grid.x - 1) / (int)grid.x;
-                const dim3 ggrid(grid.x, grid.y + grows);
-                if (tile == T12) GM_LAUNCH((gemm16_dx_gather_kernel<true, true, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
-                else GM_LAUNCH((gemm16_dx_gather_kernel<true, true, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
-                GM_GEMM_RET();
+            if (vec && (xv || MODE == MODE_FWD) && (tile == T22 || tile == T12)) {   // the batch gather rides in rows [0, grows) of the grid
+                Step& st = tiled(MODE == MODE_FWD ? F_FWD_GATHER : F_DX_GATHER, tile, grid);
+                st.vec = true; st.xv = xv; st.corrupt = rider.corrupt != nullptr;
+                ride(st, gm_gather_blocks(*rider.gather, 16));
+                return 0;
             }
-            GM_LAUNCH(gather_rows_kernel, dim3(gm_gather_blocks(gp, 4)), dim3(256), 0, s, gp);
-        }
-    }
-    if constexpr (MODE == MODE_FWD) {
-        if (rider.gather) {
-            const GatherP& gp = *rider.gather;
-            if (vec && (tile == T22 || tile == T12)) {           // the batch gather rides in rows [0, grows) of the grid
-                const int gblocks = gm_gather_blocks(gp, 16);
-                const int grows = (gblocks + (int)grid.x - 1) / (int)grid.x;
-                const dim3 ggrid(grid.x, grid.y + grows);
-                if (rider.corrupt) {
-                    const CorruptP& cp = *rider.corrupt;
-                    if (tile == T12) GM_LAUNCH((gemm16_fwd_gather_corrupt_kernel<true, 1, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, cp, grows, gblocks);
-                    else GM_LAUNCH((gemm16_fwd_gather_corrupt_kernel<true, 1, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, cp, grows, gblocks);
-                    GM_GEMM_RET();
-                }
-                if (tile == T12) GM_LAUNCH((gemm16_fwd_gather_kernel<true, 1, 1, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
-                else GM_LAUNCH((gemm16_fwd_gather_kernel<true, 1, 2, 2>), ggrid, dim3(1024), 0, s, p, gp, grows, gblocks);
-                GM_GEMM_RET();
-            }
-            launch_gather_alone(s, rider);
+            gather_alone();
         }
     }
     if constexpr (MODE == MODE_DW) {
         if (rider.pair) {
-            GemmP pb = *rider.pair;
+            GemmP& pb = plan->g[plan->ng++];
+            pb = *rider.pair;
             pb.vec_epi = vec_epi_ok<MODE_DW>(pb);
             const bool pairable = xv && rider.pair_xvec && tile != T12 && pb.K == p.K;
+            const bool dma = p.dma && dma_ok(pb, true);      // both GEMMs on one tile shape; LDS-DMA only when both may take it
             // the next iteration's first layer rides on the second GEMM's 16-row tiles (gemm16_dw_pair_l1_kernel): the
             // pair through registers, no slots on the first GEMM, Adam in the epilogue, [W1 | b1] in one column tile
             // (and the forward's operands as gemm16_k32_fwd_kernel takes them: K <= 32, 16-byte rows of z)
-            const bool l1_rides = rider.l1 && pairable && !(p.dma && dma_ok(pb, true)) && !slots && !rider.fin &&
+            const bool l1_rides = rider.l1 && pairable && !dma && !slots && !rider.fin &&
                                   pb.adam.enabled && pb.db && pb.n_real + 1 <= 16 * ni && pb.n_real <= 32 &&
                                   pb.n_real % 4 == 0 && aligned16(rider.l1->z) && rider.l1->ldz % 4 == 0 &&
                                   rider.l1->z_slot.stride % 4 == 0;
-            if (rider.l1 && !l1_rides) {            // the pair as it would run alone, then the forward on its own
-                Rider r2 = rider;
-                r2.l1 = nullptr;
-                const int rc = launch<MODE_DW>(s, p_in, vec, xvec, r2);
-                if (rc) return rc;
-                const L1RideP& l = *rider.l1;
-                GemmP f{};
-                f.A = l.z; f.B = pb.adam.pW; f.C = l.H; f.M = l.rows; f.N = pb.M; f.K = pb.n_real;
-                f.lda = l.ldz; f.ldb = pb.ldc; f.ldc = l.ldh; f.bias = pb.adam.pb; f.epi = GM_ACT_RELU;
-                f.a_slot = l.z_slot; f.b_slot = gm_slot{};
-                const bool fvec = aligned16(l.z) && aligned16(pb.adam.pW) && (l.ldz % 4 == 0) && (f.K % 4 == 0) &&
-                                  (pb.ldc % 4 == 0) && (l.z_slot.stride % 4 == 0);
-                return launch<MODE_FWD>(s, f, fvec);
+            const int tna = (int)grid.x, na = (int)(grid.x * grid.y);
+            if (pairable) p.dma = pb.dma = dma;
+            if (l1_rides) {
+                Step& st = tiled(F_PAIR_L1, tile, dim3(na + (pb.M + 15) / 16));
+                st.xv = true; st.r0 = na; st.r1 = tna;
+                return 0;
             }
             if (pairable) {
-                // both GEMMs on one tile shape; LDS-DMA only when both may take it
-                const bool dma = p.dma && dma_ok(pb, true);
-                p.dma = pb.dma = dma;
-                const int tna = (int)grid.x, na = (int)(grid.x * grid.y);
-                if (l1_rides) {
-                    const dim3 lgrid(na + (pb.M + 15) / 16);
-#define GM_LL1(MI_, NI_, D_) GM_LAUNCH((gemm16_dw_pair_l1_kernel<MI_, NI_>), lgrid, dim3(1024), 0, s, p, pb, na, tna, *rider.l1)
-                    GM_TILE_SWITCH(tile, false, GM_LL1);
-#undef GM_LL1
-                    GM_GEMM_RET();
-                }
-                const int tnb = (pb.N + 16 * ni - 1) / (16 * ni), tmb = (pb.M + 16 * mi - 1) / (16 * mi);
-                const dim3 pgrid(na + tnb * tmb);
-                const bool sl_b = has_slot(pb.a_slot) || has_slot(pb.b_slot);
-#define GM_LP2(K_, GRID_, MI_, NI_, D_, ...)                                                                              \
-    do {                                                                                                                  \
-        if (slots) GM_LAUNCH((K_<1, true, MI_, NI_, D_, true, true>), GRID_, dim3(1024), 0, s, __VA_ARGS__);     \
-        else if (sl_b) GM_LAUNCH((K_<1, true, MI_, NI_, D_, false, true>), GRID_, dim3(1024), 0, s, __VA_ARGS__); \
-        else GM_LAUNCH((K_<1, true, MI_, NI_, D_, false, false>), GRID_, dim3(1024), 0, s, __VA_ARGS__);         \
-    } while (0)
-#define GM_LP(MI_, NI_, D_) GM_LP2(gemm16_dw_pair_kernel, pgrid, MI_, NI_, D_, p, pb, na, tna, tnb)
-#define GM_LPF(MI_, NI_, D_) GM_LP2(gemm16_dw_pair_fin_kernel, dim3(pgrid.x + 1), MI_, NI_, D_, p, pb, na, tna, tnb, *rider.fin)
-                if (rider.fin) GM_TILE_SWITCH(tile, dma, GM_LPF);
-                else GM_TILE_SWITCH(tile, dma, GM_LP);
-#undef GM_LP2
-#undef GM_LPF
-#undef GM_LP
-                GM_GEMM_RET();
+                const dim3 gb = tile_grid(pb, tile);
+                Step& st = tiled(F_PAIR, tile, dim3(na + gb.x * gb.y + (rider.fin ? 1 : 0)));    // fin: one more workgroup
+                st.xv = true; st.fin = rider.fin != nullptr; st.dma = dma48(p, tile);
+                st.sl = slots; st.slb = slots || has_slot(pb.a_slot) || has_slot(pb.b_slot);
+                st.r0 = na; st.r1 = tna; st.r2 = (int)gb.x;
+            } else {
+                // not pairable in this configuration: the second GEMM gets its own launch afterwards (and the sums theirs)
+                split(gi, vec, xv);
+                pb.dma = dma_ok(pb, rider.pair_xvec);
+                split(gi + 1, false, rider.pair_xvec);
+                if (rider.fin) add(F_FIN2, dim3(0), 0);
             }
-            // not pairable in this configuration: the second GEMM gets its own launch afterwards (and the sums theirs)
-            Rider none;
-            int rc = launch<MODE_DW>(s, p_in, vec, xvec, none);
-            if (rc) return rc;
-            rc = launch<MODE_DW>(s, pb, false, rider.pair_xvec, none);
-            if (rc || !rider.fin) return rc;
-            const gm_fin2& f = *rider.fin;
-            if (plan_rec) { gm_set_error("launch-plan query: the pair's loss sums are not reported"); return GM_EUNSUPPORTED; }
-            return gm_sum_finalize2_tick(s, f.pa, f.na, f.sa, f.oa, f.slot_a, f.pb, f.nb, f.sb, f.ob, f.slot_b, f.tick);
+            if (!rider.l1) return 0;
+            // the layer-1 rider cannot ride: the pair as it runs alone (above), then the forward on its own
+            const L1RideP& l = *rider.l1;
+            GemmP f{};
+            f.A = l.z; f.B = pb.adam.pW; f.C = l.H; f.M = l.rows; f.N = pb.M; f.K = pb.n_real;
+            f.lda = l.ldz; f.ldb = pb.ldc; f.ldc = l.ldh; f.bias = pb.adam.pb; f.epi = GM_ACT_RELU;
+            f.a_slot = l.z_slot; f.b_slot = gm_slot{};
+            const bool fvec = aligned16(l.z) && aligned16(pb.adam.pW) && (l.ldz % 4 == 0) && (f.K % 4 == 0) &&
+                              (pb.ldc % 4 == 0) && (l.z_slot.stride % 4 == 0);
+            return decide<MODE_FWD>(f, fvec, false, Rider(), plan);
         }
     }
-    // template arguments: MODE, VEC, waves, G, XV, MI, NI, DMA
     // (ring slots exist on the batch-row operand of forward and weight-gradient launches only: gm_hip.h)
     if (MODE == MODE_DX && slots) { gm_set_error("ring slots: forward and weight-gradient operands only"); return GM_EINVAL; }
-#define GM_L16K1(V, X, MI_, NI_, DMA_, SL_)                                                                                  \
-    GM_LAUNCH_AS(plan_kernel(GM_PLAN_SPLIT, MODE, MI_, NI_, 0, 0, V, X, p.vec_epi, DMA_, SL_),                               \
-                 (gemm16_kernel<MODE, V, 16, 1, X, MI_, NI_, DMA_, SL_>), grid, dim3(1024), 0, s, p)
-#define GM_L16K(V, X, MI_, NI_, D_)                                                                                          \
-    do {                                                                                                                     \
-        if (MODE != MODE_DX && slots) GM_L16K1(V, X, MI_, NI_, (MODE == MODE_DW && (X) && (D_)), (MODE != MODE_DX));          \
-        else GM_L16K1(V, X, MI_, NI_, (MODE == MODE_DW && (X) && (D_)), false);                                              \
-    } while (0)
-#define GM_L16_tt(MI_, NI_, D_) GM_L16K(true, true, MI_, NI_, D_)
-#define GM_L16_tf(MI_, NI_, D_) GM_L16K(true, false, MI_, NI_, D_)
-#define GM_L16_ft(MI_, NI_, D_) GM_L16K(false, true, MI_, NI_, D_)
-#define GM_L16_ff(MI_, NI_, D_) GM_L16K(false, false, MI_, NI_, D_)
-    if (xv) { if (vec) GM_TILE_SWITCH(tile, p.dma, GM_L16_tt); else GM_TILE_SWITCH(tile, p.dma, GM_L16_ft); }
-    else    { if (vec) GM_TILE_SWITCH(tile, false, GM_L16_tf); else GM_TILE_SWITCH(tile, false, GM_L16_ff); }
-#undef GM_L16_ff
-#undef GM_L16_ft
-#undef GM_L16_tf
-#undef GM_L16_tt
-#undef GM_L16K
-#undef GM_L16K1
-    GM_GEMM_RET();
+    split(gi, vec, xv);
+    return 0;
+}
+
+// ---- issue: one runtime-to-compile-time switch per kernel family ----
+template <bool B> using BoolC = std::integral_constant<bool, B>;
+template <int I> using IntC = std::integral_constant<int, I>;
+#define GM_CV(c) (decltype(c)::value)
+template <class F> inline void on_bool(bool b, F&& f) { if (b) f(BoolC<true>{}); else f(BoolC<false>{}); }
+// f(MI, NI, DMA) for the step's tile; the LDS-DMA instantiations exist for the 48-wide weight-gradient tiles
+template <class F> inline void on_tile(const Step& st, F&& f) {
+    switch (10 * st.mi + st.ni) {
+    case 24: f(IntC<2>{}, IntC<4>{}, BoolC<false>{}); break;
+    case 42: f(IntC<4>{}, IntC<2>{}, BoolC<false>{}); break;
+    case 12: f(IntC<1>{}, IntC<2>{}, BoolC<false>{}); break;
+    case 23: on_bool(st.dma, [&](auto D) { f(IntC<2>{}, IntC<3>{}, D); }); break;
+    case 32: on_bool(st.dma, [&](auto D) { f(IntC<3>{}, IntC<2>{}, D); }); break;
+    default: f(IntC<2>{}, IntC<2>{}, BoolC<false>{}); break;
+    }
+}
+// f(MI) for the families that exist on 16x32 and 32x32 tiles only
+template <class F> inline void on_small_tile(const Step& st, F&& f) { if (st.mi == 1) f(IntC<1>{}); else f(IntC<2>{}); }
+
+int issue(hipStream_t s, const Plan& plan, const Rider& r) {
+    for (int i = 0; i < plan.n; ++i) {
+        const Step& st = plan.step[i];
+        const dim3 g = st.grid, b = st.block;
+        GemmP p = plan.g[st.gemm];
+#ifdef GM_STAMPS
+        if (st.family < F_LABEL) {
+            p.stamp.slot = gm_stamps::host_buf ? gm_stamps::host_buf + (size_t)(gm_stamps::host_next++ % gm_stamps::SLOTS) * gm_stamps::SLOT_WORDS : nullptr;
+            p.stamp.tile = gm_stamps::host_tile;
+        }
+#endif
+        switch (st.family) {
+        case F_HEAD: hipLaunchKernelGGL(head_bwd_kernel, g, b, 0, s, *r.head); break;
+        case F_GATHER:
+            if (st.corrupt) hipLaunchKernelGGL(gather_rows_corrupt_kernel, g, b, 0, s, *r.gather, *r.corrupt);
+            else hipLaunchKernelGGL(gather_rows_kernel, g, b, 0, s, *r.gather);
+            break;
+        case F_FWD_BITS: hipLaunchKernelGGL(gemm16_fwd_bits_kernel, g, b, 0, s, p); break;
+        case F_DW_HEAD_BITS: hipLaunchKernelGGL(gemm16_dw_head_bits_kernel, g, b, 0, s, p, *r.head, st.r0, st.r1); break;
+        case F_LDS:
+            on_bool(st.mode == MODE_DX, [&](auto DX) { on_bool(st.lds_cfg == 1, [&](auto BIG) {
+                constexpr int MODE = GM_CV(DX) ? MODE_DX : MODE_FWD, BM = GM_CV(BIG) ? 64 : 32, WTN = GM_CV(BIG) ? 64 : 32;
+                auto go = [&](auto NS) { hipLaunchKernelGGL((gemm_lds_kernel<MODE, BM, 64, 32, WTN, 4, 1, 4, GM_CV(NS)>), g, b, 0, s, p); };
+                if (st.lds_ns == LDS_NS784) go(IntC<LDS_NS784>{});
+                else if (st.lds_ns == LDS_NS400) go(IntC<LDS_NS400>{});
+                else go(IntC<0>{});
+            }); });
+            break;
+        case F_K32:
+            on_bool(st.sl, [&](auto SL) {
+                if (st.gather) hipLaunchKernelGGL((gemm16_k32_fwd_kernel<GM_CV(SL), true>), g, b, 0, s, p, *r.gather, st.r0, st.r1);
+                else hipLaunchKernelGGL((gemm16_k32_fwd_kernel<GM_CV(SL), false>), g, b, 0, s, p, GatherP{}, 0, 0);
+            });
+            break;
+        case F_SPLIT: {
+            auto go = [&](auto M) { on_bool(st.vec, [&](auto V) { on_bool(st.xv, [&](auto X) { on_bool(st.sl, [&](auto SL) {
+                on_tile(st, [&](auto MI, auto NI, auto D) {
+                    constexpr int MODE = GM_CV(M);
+                    hipLaunchKernelGGL((gemm16_kernel<MODE, GM_CV(V), 16, 1, GM_CV(X), GM_CV(MI), GM_CV(NI),
+                                                      (MODE == MODE_DW && GM_CV(X) && GM_CV(D)), (MODE != MODE_DX && GM_CV(SL))>),
+                                       g, b, 0, s, p);
+                }); }); }); }); };
+            st.mode == MODE_FWD ? go(IntC<MODE_FWD>{}) : st.mode == MODE_DX ? go(IntC<MODE_DX>{}) : go(IntC<MODE_DW>{});
+            break;
+        }
+        case F_LABEL:
+            on_bool(st.vec, [&](auto V) { on_tile(st, [&](auto MI, auto NI, auto) {
+                hipLaunchKernelGGL((gemm16_fwd_label_kernel<GM_CV(V), GM_CV(MI), GM_CV(NI)>), g, b, 0, s, p);
+            }); });
+            break;
+        case F_DW_HEAD: {       // (X, OF, FOLDED): folded needs X and takes no row offset
+            auto go = [&](auto X, auto OF, auto FD) { on_tile(st, [&](auto MI, auto NI, auto D) {
+                hipLaunchKernelGGL((gemm16_dw_head_kernel<false, 1, GM_CV(X), GM_CV(MI), GM_CV(NI), GM_CV(OF), GM_CV(FD),
+                                                          (GM_CV(X) && GM_CV(D))>), g, b, 0, s, p, *r.head, st.r0, st.r1);
+            }); };
+            if (st.folded) go(BoolC<true>{}, BoolC<false>{}, BoolC<true>{});
+            else on_bool(st.xv, [&](auto X) { on_bool(st.of, [&](auto OF) { go(X, OF, BoolC<false>{}); }); });
+            break;
+        }
+        case F_DW_HEAD_TP:
+            on_tile(st, [&](auto MI, auto NI, auto) {
+                hipLaunchKernelGGL((gemm16_dw_head_tp_kernel<GM_CV(MI), GM_CV(NI)>), g, b, 0, s, p, *r.head, st.r0, st.r1);
+            });
+            break;
+        case F_DX_HEAD:
+            on_small_tile(st, [&](auto MI) { on_bool(st.folded, [&](auto FD) {
+                hipLaunchKernelGGL((gemm16_dx_head_kernel<1, GM_CV(MI), 2, GM_CV(FD)>), g, b, 0, s, p, *r.head, st.r0, st.r1);
+            }); });
+            break;
+        case F_DX_GATHER:
+            on_small_tile(st, [&](auto MI) {
+                hipLaunchKernelGGL((gemm16_dx_gather_kernel<true, true, GM_CV(MI), 2>), g, b, 0, s, p, *r.gather, st.r0, st.r1);
+            });
+            break;
+        case F_FWD_GATHER:
+            on_small_tile(st, [&](auto MI) {
+                if (st.corrupt) hipLaunchKernelGGL((gemm16_fwd_gather_corrupt_kernel<true, 1, GM_CV(MI), 2>), g, b, 0, s, p, *r.gather, *r.corrupt, st.r0, st.r1);
+                else hipLaunchKernelGGL((gemm16_fwd_gather_kernel<true, 1, GM_CV(MI), 2>), g, b, 0, s, p, *r.gather, st.r0, st.r1);
+            });
+            break;
+        case F_PAIR_L1:
+            on_tile(st, [&](auto MI, auto NI, auto) {
+                hipLaunchKernelGGL((gemm16_dw_pair_l1_kernel<GM_CV(MI), GM_CV(NI)>), g, b, 0, s, p, plan.g[st.gemm + 1], st.r0, st.r1, *r.l1);
+            });
+            break;
+        case F_PAIR: {          // (SLA, SLB): which of the two resolves ring slots
+            auto go = [&](auto SLA, auto SLB) { on_tile(st, [&](auto MI, auto NI, auto D) {
+                const GemmP& pb = plan.g[st.gemm + 1];
+                if (st.fin) hipLaunchKernelGGL((gemm16_dw_pair_fin_kernel<1, true, GM_CV(MI), GM_CV(NI), GM_CV(D), GM_CV(SLA), GM_CV(SLB)>),
+                                               g, b, 0, s, p, pb, st.r0, st.r1, st.r2, *r.fin);
+                else hipLaunchKernelGGL((gemm16_dw_pair_kernel<1, true, GM_CV(MI), GM_CV(NI), GM_CV(D), GM_CV(SLA), GM_CV(SLB)>),
+                                        g, b, 0, s, p, pb, st.r0, st.r1, st.r2);
+            }); };
+            st.sl ? go(BoolC<true>{}, BoolC<true>{}) : st.slb ? go(BoolC<false>{}, BoolC<true>{}) : go(BoolC<false>{}, BoolC<false>{});
+            break;
+        }
+        default: break;         // F_FIN2: below, behind the launches' error check
+        }
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { gm_set_error(hipGetErrorString(e)); return -(int)e; }
+    if (plan.n && plan.step[plan.n - 1].family == F_FIN2) {
+        const gm_fin2& f = *r.fin;
+        return gm_sum_finalize2_tick(s, f.pa, f.na, f.sa, f.oa, f.slot_a, f.pb, f.nb, f.sb, f.ob, f.slot_b, f.tick);
+    }
+    return 0;
+}
+
+// One call: decide, then issue -- or hand the Plan to the launch-plan query instead of issuing it.
+template <int MODE>
+int run(void* stream, const GemmP& p, bool vec, bool xvec, const Rider& r, Plan* query) {
+    Plan own, *plan = query ? query : &own;
+    const int rc = decide<MODE>(p, vec, xvec, r, plan);
+    return (rc || query) ? rc : issue((hipStream_t)stream, *plan, r);
 }
 
 inline gm_slot no_slot() { gm_slot z; z.ctr = nullptr; z.mul = 0; z.add = 0; z.ring = 0; z.stride = 0; return z; }
@@ -2414,9 +2428,7 @@ static int gather_from_args(const gm_gather_args& a, bool forward, GatherP* g, C
 
 static bool slot_is_zero(const gm_slot& s) { return !s.ctr && !s.mul && !s.add && !s.ring && !s.stride; }
 
-static int fwd_label_launch(hipStream_t s, const GemmP& p, bool vec);
-
-static int fwd_impl(void* stream, const gm_fwd_args* args) {
+static int fwd_impl(void* stream, const gm_fwd_args* args, Plan* query = nullptr) {
     GM_CHECK_ARG(args);
     const gm_fwd_args& a = *args;
     GM_CHECK_ARG(a.X && a.W && a.Y && a.M > 0 && a.K > 0 && a.N > 0 && a.ldx >= a.K && a.ldy >= a.N);
@@ -2468,8 +2480,7 @@ static int fwd_impl(void* stream, const gm_fwd_args* args) {
         p.sq_ldp = a.sq_ldp;
     } else if (label) {
         GM_CHECK_ARG(a.lb_E && a.lb.labels && a.lb_C > 0 && a.lb_C <= 32);
-        p.lb = a.lb; p.lb_E = a.lb_E; p.lb_C = a.lb_C;
-        return fwd_label_launch((hipStream_t)stream, p, vec);
+        p.lb = a.lb; p.lb_E = a.lb_E; p.lb_C = a.lb_C;     // (decide: the label kernels, whatever the shape)
     } else if (a.gather) {
         const float* gout = nullptr;
         const int rc = gather_from_args(*a.gather, true, &g, &c, &r.corrupt, &gout);
@@ -2479,22 +2490,7 @@ static int fwd_impl(void* stream, const gm_fwd_args* args) {
         GM_CHECK_ARG(!r.corrupt || (c.out_c != a.Y && (const float*)c.out_c != a.X));
         r.gather = &g;
     }
-    return launch<MODE_FWD>((hipStream_t)stream, p, vec, false, r);
-}
-
-// The class-conditional forward: every shape through the 16-wave split-reduction kernel (its tile choice) -- the label
-// term lives in that kernel's epilogue only.
-static int fwd_label_launch(hipStream_t s, const GemmP& p, bool vec) {
-    const int tile = pick_tile<MODE_FWD>(p);
-    const dim3 grid((p.N + 16 * tile_ni(tile) - 1) / (16 * tile_ni(tile)), (p.M + 16 * tile_mi(tile) - 1) / (16 * tile_mi(tile)));
-#define GM_LBL(MI_, NI_, D_)                                                                                \
-    do {                                                                                                    \
-        if (vec) GM_LAUNCH((gemm16_fwd_label_kernel<true, MI_, NI_>), grid, dim3(1024), 0, s, p);  \
-        else GM_LAUNCH((gemm16_fwd_label_kernel<false, MI_, NI_>), grid, dim3(1024), 0, s, p);     \
-    } while (0)
-    GM_TILE_SWITCH(tile, false, GM_LBL);
-#undef GM_LBL
-    GM_GEMM_RET();
+    return run<MODE_FWD>(stream, p, vec, false, r, query);
 }
 
 extern "C" int gm_linear_fwd(void* stream, const float* X, int64_t ldx, gm_slot x_slot, const float* W,
@@ -2507,7 +2503,7 @@ extern "C" int gm_linear_fwd(void* stream, const float* X, int64_t ldx, gm_slot 
 
 extern "C" int gm_linear_fwd_ex(void* stream, const gm_fwd_args* a) { return fwd_impl(stream, a); }
 
-static int dx_impl(void* stream, const gm_dx_args* args) {
+static int dx_impl(void* stream, const gm_dx_args* args, Plan* query = nullptr) {
     GM_CHECK_ARG(args);
     const gm_dx_args& a = *args;
     GM_CHECK_ARG(a.dA && a.W && a.dX && a.M > 0 && a.K > 0 && a.N > 0 && a.lda >= a.N && a.ldx >= a.K);
@@ -2564,7 +2560,7 @@ static int dx_impl(void* stream, const gm_dx_args* args) {
     }
     const bool vec = aligned16(a.dA) && (a.lda % 4 == 0) && (a.N % 4 == 0) && (!p.fold_w2 || aligned16(p.fold_w2));
     const bool xvec = aligned16(a.W) && (a.K % 4 == 0);
-    return launch<MODE_DX>((hipStream_t)stream, p, vec, xvec, r);
+    return run<MODE_DX>(stream, p, vec, xvec, r, query);
 }
 
 extern "C" int gm_linear_bwd_dx(void* stream, const float* dA, int64_t lda, const float* W, float* dX, int64_t ldx,
@@ -2601,7 +2597,8 @@ static int dw_fill(const gm_dw_adam_args& a, GemmP* out, bool* xvec_out) {
     return 0;
 }
 
-static int dw_impl(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second, const gm_dw_tail* tail) {
+static int dw_impl(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_args* second, const gm_dw_tail* tail,
+                   Plan* query = nullptr) {
     GM_CHECK_ARG(first);
     const gm_dw_adam_args& a = *first;
     if (second && (a.head || second->head)) {
@@ -2657,7 +2654,7 @@ static int dw_impl(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_
             if (!aligned16(a.fold->snap)) xa = false;
         }
         pa.pk_bits = a.xbits; pa.pk_wpr = a.xbits ? a.xbits_wpr : 0; pa.pk_rows = a.xbits ? a.xbits_rows : 0;
-        return launch<MODE_DW>((hipStream_t)stream, pa, false, xa, r);
+        return run<MODE_DW>(stream, pa, false, xa, r, query);
     }
     const gm_dw_adam_args& b = *second;
     L1RideP l{};
@@ -2689,7 +2686,7 @@ static int dw_impl(void* stream, const gm_dw_adam_args* first, const gm_dw_adam_
     if (rc) return rc;
     r.pair = &pb;
     r.pair_xvec = xb;
-    return launch<MODE_DW>((hipStream_t)stream, pa, false, xa, r);
+    return run<MODE_DW>(stream, pa, false, xa, r, query);
 }
 
 extern "C" int gm_linear_bwd_dw(void* stream, const float* dA, int64_t lda, const float* X, int64_t ldx,
@@ -2705,7 +2702,7 @@ extern "C" int gm_linear_bwd_dw_ex(void* stream, const gm_dw_adam_args* first, c
     return dw_impl(stream, first, second, tail);
 }
 
-// The launch-plan query (gm_hip.h): the entry point's own checks and dispatch with this thread's launch sites recording.
+// The launch-plan query (gm_hip.h): the entry point's own checks and decide<MODE>; the Plan is reported, not issued.
 extern "C" int gm_linear_plan(int mode, const void* args, int32_t* plan) {
     GM_CHECK_ARG(args && plan && mode >= GM_PLAN_MODE_FWD && mode <= GM_PLAN_MODE_DW);
     bool riding = false;
@@ -2724,20 +2721,19 @@ extern "C" int gm_linear_plan(int mode, const void* args, int32_t* plan) {
         gm_set_error("launch-plan query: plain launches only (this descriptor carries a riding block)");
         return GM_EUNSUPPORTED;
     }
-    int32_t rec[GM_PLAN_FIELDS] = {0};
-    rec[GM_PLAN_F_MODE] = mode;
-    struct Recording {          // the launch sites record while this lives, whichever way the dispatch returns
-        explicit Recording(int32_t* r) { plan_rec = r; }
-        ~Recording() { plan_rec = nullptr; }
-    };
+    Plan pl;
     int rc;
-    {
-        Recording on(rec);
-        if (mode == GM_PLAN_MODE_FWD) rc = fwd_impl(nullptr, static_cast<const gm_fwd_args*>(args));
-        else if (mode == GM_PLAN_MODE_DX) rc = dx_impl(nullptr, static_cast<const gm_dx_args*>(args));
-        else rc = dw_impl(nullptr, static_cast<const gm_dw_adam_args*>(args), nullptr, nullptr);
-    }
+    if (mode == GM_PLAN_MODE_FWD) rc = fwd_impl(nullptr, static_cast<const gm_fwd_args*>(args), &pl);
+    else if (mode == GM_PLAN_MODE_DX) rc = dx_impl(nullptr, static_cast<const gm_dx_args*>(args), &pl);
+    else rc = dw_impl(nullptr, static_cast<const gm_dw_adam_args*>(args), nullptr, nullptr, &pl);
     if (rc) return rc;
-    for (int i = 0; i < GM_PLAN_FIELDS; ++i) plan[i] = rec[i];
+    const Step& st = pl.step[pl.n - 1];
+    for (int i = 0; i < GM_PLAN_FIELDS; ++i) plan[i] = 0;
+    plan[GM_PLAN_F_FAMILY] = st.family < GM_PLAN_RIDING ? st.family : GM_PLAN_RIDING;
+    plan[GM_PLAN_F_MODE] = st.mode; plan[GM_PLAN_F_MI] = st.mi; plan[GM_PLAN_F_NI] = st.ni;
+    plan[GM_PLAN_F_LDS_CFG] = st.lds_cfg; plan[GM_PLAN_F_LDS_STAGES] = st.lds_ns; plan[GM_PLAN_F_VEC] = st.vec; plan[GM_PLAN_F_XV] = st.xv;
+    plan[GM_PLAN_F_VEC_EPI] = pl.g[st.gemm].vec_epi; plan[GM_PLAN_F_DMA] = st.dma; plan[GM_PLAN_F_SLOTS] = st.sl;
+    plan[GM_PLAN_F_LAUNCHES] = pl.n;                         // grid and block: of the last launch
+    plan[GM_PLAN_F_GRID_X] = (int32_t)st.grid.x; plan[GM_PLAN_F_GRID_Y] = (int32_t)st.grid.y; plan[GM_PLAN_F_BLOCK] = (int32_t)st.block.x;
     return 0;
 }

@@ -951,8 +951,8 @@ int gm_linear_bwd_dw_ex(void* stream, const gm_dw_adam_args* first, const gm_dw_
 
 /* ---- launch-plan query: what gm_linear_fwd_ex / gm_linear_bwd_dx_ex / gm_linear_bwd_dw_ex WOULD launch for a
  * descriptor, without launching and without a call into the HIP runtime (works on a host without a GPU; the pointers
- * are only looked at for their alignment).  The query runs the entry point's own argument checks and dispatch with the
- * launch sites switched to recording, so it cannot disagree with the launch.
+ * are only looked at for their alignment).  The query runs the entry point's own argument checks and the same pure
+ * decision (decide<MODE>: call -> launch plan) whose plan the entry point issues, so it cannot disagree with the launch.
  *   mode: GM_PLAN_MODE_FWD / _DX / _DW; args: a gm_fwd_args / gm_dx_args / gm_dw_adam_args (single gradient);
  *   plan: GM_PLAN_FIELDS ints, written on success (indices below).
  * Plain launches only (for the input gradient with or without `add`, for the weight gradient with or without Adam):

@@ -1,5 +1,6 @@
-"""Which kernel every case of tests/linear_path_cases.py reaches, pinned against the library's own dispatch run dry
-(gm_linear_plan: the launch sites record instead of launching -- no GPU, no HIP call).  Two things are asserted:
+"""Which kernel every case of tests/linear_path_cases.py reaches, pinned against the library's own dispatch
+(gm_linear_plan: the launch plan that decide<MODE> makes of the call, read instead of issued -- no GPU, no HIP call).
+Two things are asserted:
 every case resolves to the plan written next to it, and the plans of the table are EXACTLY the plans a plain launch can
 reach -- listed here family by family, and checked against a sweep of the query over shapes, alignments and ring slots.
 A retuned threshold moves cases onto other plans and fails the first test by name; a new instantiation the dispatch can
@@ -45,7 +46,7 @@ REACHABLE = set(
      for x in B for e in B for s in B] +
     [lp.split("dw", t, 0, 1, e, 1, s) for t in ("32x48", "48x32") for e in B for s in B])
 
-# Instantiations the library compiles (GM_TILE_SWITCH expands every tile for every mode) that NO plain call reaches, and
+# Instantiations the library compiles (on_tile expands every tile for every mode) that NO plain call reaches, and
 # why; the sweep below backs each line -- none of these plans may ever come out of the query.
 UNREACHABLE = {
     "fwd split 32x48": "pick_tile turns 32x64 into 32x48 for weight gradients only",

@@ -85,8 +85,12 @@ def __getattr__(name):
     """PDWGAN / PDWGANTrainer / PDWGANEngine, IWAE / IWAETrainer / IWAEEngine, SNGAN / SNGANTrainer / SNGANEngine,
     DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine, NFVAE / NFVAETrainer / NFVAEEngine, CatVAE /
     CatVAETrainer / CatVAEEngine, RealNVP / RealNVPTrainer / RealNVPEngine, RBM / RBMTrainer / RBMEngine, VQVAE /
-    VQVAETrainer / VQVAEEngine, MAF / MAFTrainer / MAFEngine, IAFVAE / IAFVAETrainer / IAFVAEEngine and TCVAE /
-    TCVAETrainer / TCVAEEngine, imported on first use (importing the package stays free of torch)."""
+    VQVAETrainer / VQVAEEngine, MAF / MAFTrainer / MAFEngine, IAFVAE / IAFVAETrainer / IAFVAEEngine, TCVAE /
+    TCVAETrainer / TCVAEEngine and GMMN / GMMNTrainer / GMMNEngine, imported on first use (importing the package stays
+    free of torch)."""
+    if name in ("GMMN", "GMMNTrainer", "GMMNEngine"):
+        from . import gmmn
+        return getattr(gmmn, name)
     if name in ("TCVAE", "TCVAETrainer"):
         from . import tcvae
         return getattr(tcvae, name)

@@ -138,6 +138,8 @@ CAT_RELAXED, CAT_ST, CAT_DISCRETE, CAT_NOISE = 0, 1, 2, 3   # GM_CAT_RELAXED / _
 
 DDPM_TAG_T, DDPM_TAG_E, DDPM_TAG_V, DDPM_TAG_VE, DDPM_TAG_S = 0x44445054, 0x4444504D, 0x44445056, 0x44445057, 0x44445053
 DDPM_MAX_I, DDPM_MIN_E, DDPM_MAX_E, DDPM_MAX_T = 8192, 4, 128, 4096      # GM_DDPM_* (include/gm_hip.h)
+GMMN_TAG_T, GMMN_TAG_V, GMMN_TAG_S = 0x474D4D54, 0x474D4D56, 0x474D4D53    # GM_GMMN_TAG_* ("GMMT", "GMMV", "GMMS")
+MMD_MAX_SIGMAS, MMD_MAX_I, MMD_CHUNK, GMMN_MAX_Z, GMMN_MAX_B = 16, 8192, 128, 8192, 2048    # GM_MMD_* / GM_GMMN_*
 # (gm_ddpm_noise / _tables / _out / _reverse_args travel by pointer; their ctypes forms live in ops_fused)
 
 MADE_TAG_S = 0x4D414453                                     # GM_MADE_TAG_S ("MADS")
@@ -410,6 +412,11 @@ _SIGNATURES = {
                              c_float, c_int, c_int, c_int]),
     "gm_tc_reduce": (c_int, [_P, _P, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, _P, c_int64, _P, c_int64, c_float,
                              c_float, c_float, c_int, c_int, c_int]),
+    "gm_mmd_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "gm_gmmn_prior": (c_int, [_P, _P, _P, c_int64, c_int, c_int]),
+    "gm_mmd_pairs": (c_int, [_P, _P, c_int64, c_int, _P, c_int64, c_int, c_int, _P, c_int, _P, c_int64, _P, _P, c_int64]),
+    "gm_mmd_finalize": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int64, _P, _P, _P]),
+    "gm_mmd_grad": (c_int, [_P, _P, c_int64, _P, _P, c_int64, _P, _P, c_float, c_int, _P, c_int64, c_int, c_int]),
     "gm_cat_sample": (c_int, [_P, _P, _P]),
     "gm_cat_reduce": (c_int, [_P, _P, _P]),
     "gm_vq_quantise": (c_int, [_P, _P]),

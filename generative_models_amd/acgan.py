@@ -337,6 +337,12 @@ class ACGANTrainer(GANTrainer):
         """Parzen-window log-likelihood of the test images under n_samples class-balanced samples."""
         return _parzen(self, n_samples, sigmas, n_val, seed)
 
+    def mmd(self, n_samples=10000, sigmas=None, seed=0):
+        """Kernel maximum mean discrepancy (metrics.mmd) between sample(n_samples, seed) and the test images ->
+        metrics.MMDResult; sigmas None: the GMMN paper's data-space bandwidths; the unbiased statistic."""
+        from .trainers import _mmd
+        return _mmd(self, n_samples, sigmas, seed)
+
     def generate_images(self, epoch, num_outputs=36, save=True, labels=None):
         """ns_gan.py:228-262 for chosen classes (None: arange(num_outputs) % num_classes): compute_noise's draw from
         the global generator, saved as ../viz/<name>/reconst_<epoch>.png."""

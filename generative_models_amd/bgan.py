@@ -423,6 +423,12 @@ class BayesGANTrainer(GANTrainer):
         """Parzen-window log-likelihood of the test images under the mixture's samples (metrics.parzen_evaluate)."""
         return _parzen(self, n_samples, sigmas, n_val, seed)
 
+    def mmd(self, n_samples=10000, sigmas=None, seed=0):
+        """Kernel maximum mean discrepancy (metrics.mmd) between sample(n_samples, seed) and the test images ->
+        metrics.MMDResult; sigmas None: the GMMN paper's data-space bandwidths; the unbiased statistic."""
+        from .trainers import _mmd
+        return _mmd(self, n_samples, sigmas, seed)
+
     def generate_images(self, epoch, num_outputs=36, save=True):
         """A grid of mixture samples (sample(num_outputs, seed=epoch): no global draw), saved as
         ../viz/<name>/reconst_<epoch>.png."""

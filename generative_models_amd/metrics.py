@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from ._lib import GMError
 
-MAX_SIGMAS = 16
+MAX_SIGMAS = 16                      # also the kernel MMD's (GM_MMD_MAX_SIGMAS)
 
 ParzenResult = collections.namedtuple("ParzenResult", "sigma ll_mean ll_stderr val_means")
 # VAETrainer.log_likelihood (iwae.py): the importance-weighted estimate of log p(x) over n rows from k samples each
@@ -93,3 +93,32 @@ def parzen_evaluate(samples, val, test, sigmas=None):
     ll = parzen_log_likelihood(samples, test, sig[k:k + 1])[0].double()
     return ParzenResult(float(sig[k]), float(ll.mean()), float(ll.std(unbiased=False)) / np.sqrt(ll.numel()),
                         val_means)
+
+
+# ---- kernel maximum mean discrepancy (gm_mmd_pairs / gm_mmd_finalize, csrc/gm_gmmn.hip; gmmn.py holds the contract) ------
+# mmd2 of n_samples generated rows against n_data data rows under k(a, b) = sum_s exp(-|a - b|^2 / (2 sigma_s^2));
+# mmd = sqrt(max(mmd2, 0)).  A two-sample statistic: no bandwidth is picked on validation rows.
+MMDResult = collections.namedtuple("MMDResult", "mmd2 mmd n_samples n_data")
+MMD_SIGMAS = (2.0, 5.0, 10.0, 20.0, 40.0, 80.0)      # the GMMN paper's data-space bandwidths (arXiv 1502.02761)
+
+
+def mmd(samples, data, sigmas=None, unbiased=True):
+    """The kernel MMD between `samples` [N, ...] and `data` [M, ...] (float32 tensors on the MI355X) -> MMDResult.
+    unbiased (needs N, M >= 2): the U-statistic -- the xx and yy sums without their diagonals over N (N - 1) and
+    M (M - 1); else the V-statistic of gmmn.py's loss, diagonals in.  Nothing of size N x M is stored."""
+    from . import ops_fused as of_
+    s, q = _rows(samples, "samples"), _rows(data, "data")
+    if s.shape[1] != q.shape[1]:
+        raise GMError("mmd: samples have %d values per row, data %d" % (s.shape[1], q.shape[1]))
+    n, m = s.shape[0], q.shape[0]
+    if min(n, m) < (2 if unbiased else 1):
+        raise GMError("mmd: %d samples and %d data rows; the %s statistic needs at least %d of each"
+                      % (n, m, "unbiased" if unbiased else "biased", 2 if unbiased else 1))
+    with torch.cuda.device(q.device):
+        sig = of_.mmd_sigmas(MMD_SIGMAS if sigmas is None else sigmas, q.device, "mmd")
+        st = of_.mmd_stats(s, q, sig).cpu().tolist()             # the one sync
+    if unbiased:
+        mmd2 = st[6] / (n * (n - 1.0)) - 2.0 * st[4] / (float(n) * m) + st[7] / (m * (m - 1.0))
+    else:
+        mmd2 = st[0]
+    return MMDResult(mmd2, float(np.sqrt(max(mmd2, 0.0))), n, m)

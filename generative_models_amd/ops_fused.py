@@ -1823,3 +1823,157 @@ def maf_invert(u, W2, b2, W1T, b1, m_h, inv_order, s_cap, n=None, y=None, s=None
     a.s_cap, a.n, a.D, a.H = float(s_cap), n, D, H
     _lib.call("gm_maf_invert", stream or stream_ptr(), ctypes.byref(a))
     return y
+
+
+# ---- Generative moment matching network / kernel MMD (csrc/gm_gmmn.hip; gmmn.py, metrics.mmd) ----------------------
+def gmmn_noise(seed, tag, step=0, step_ctr=None, step_base=None, row0=0):
+    """The prior's noise block (a gm_iwae_noise at k = 1): stream (seed, tag) at step = *step_ctr + *step_base + step,
+    the call's row b draws noise row row0 + b."""
+    return iwae_noise(seed, tag, 1, j0=row0, step=step, step_ctr=step_ctr, step_base=step_base)
+
+
+def gmmn_prior(z, noise, B=None, Z=None, stream=None):
+    """z [B, Z] = 2 u - 1, u the uniforms of the noise block's rows (gm_gmmn_prior)."""
+    B = z.shape[0] if B is None else int(B)
+    Z = z.shape[1] if Z is None else int(Z)
+    if _rows2d(z, "z").shape[0] < B or z.shape[1] < Z:
+        raise _lib.GMError("gmmn_prior: z %s does not fit B=%d, Z=%d" % (tuple(z.shape), B, Z))
+    _lib.call("gm_gmmn_prior", stream or stream_ptr(), ctypes.byref(noise), z.data_ptr(), _ld(z), B, Z)
+    return z
+
+
+def mmd_sigmas(sigmas, device="cuda", who="mmd", error=None):
+    """The bandwidths as a float32 device vector: 1 to GM_MMD_MAX_SIGMAS finite values > 0, else `error` (GMError)."""
+    import numpy as np
+    error = error or _lib.GMError
+    try:
+        s = np.asarray(sigmas, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise error("%s: sigmas must be numbers, got %r" % (who, sigmas))
+    if not 1 <= s.size <= _lib.MMD_MAX_SIGMAS:
+        raise error("%s: 1 to %d bandwidths, got %d" % (who, _lib.MMD_MAX_SIGMAS, s.size))
+    if not (np.all(np.isfinite(s)) and np.all(s > 0)):
+        raise error("%s: every sigma must be finite and > 0, got %s" % (who, s.tolist()))
+    return torch.from_numpy(s.astype(np.float32)).to(device) if device is not None else s
+
+
+def mmd_workspace(N, M, grad, device="cuda"):
+    """The device workspace of mmd_pairs / mmd_finalize for N generated and M data rows (gm_mmd_workspace_bytes)."""
+    n = _lib.load().gm_mmd_workspace_bytes(int(N), int(M), 1 if grad else 0)
+    if n < 0:
+        _lib.check(int(n), "gm_mmd_workspace_bytes")
+    return torch.empty(int(n) // 8 + 1, dtype=torch.float64, device=device)
+
+
+def mmd_pairs(X, Y, sig, ws, C=None, Rc=None, N=None, M=None, stream=None):
+    """Every tile's pairs of X [N, I] and Y [M, I] under the bandwidths sig (gm_mmd_pairs): the block sums (and, with C
+    [N, >= N + M], the coefficients and the shares of r) are left in ws for mmd_finalize; Rc (contiguous, >= N + M rows of
+    I; None: a new tensor) takes the rows less X's first row, what the distances and the product C (R - mu) are formed
+    from."""
+    N = X.shape[0] if N is None else int(N)
+    M = Y.shape[0] if M is None else int(M)
+    I = X.shape[1]
+    if _rows2d(X, "X").shape[0] < N or _rows2d(Y, "Y").shape[0] < M or Y.shape[1] != I:
+        raise _lib.GMError("mmd_pairs: X %s / Y %s do not fit N=%d, M=%d" % (tuple(X.shape), tuple(Y.shape), N, M))
+    if C is not None and (_rows2d(C, "C").shape[0] < N or C.shape[1] < N + M):
+        raise _lib.GMError("mmd_pairs: C %s does not fit [%d, %d]" % (tuple(C.shape), N, N + M))
+    if Rc is None:
+        Rc = torch.empty(N + M, I, device=X.device)
+    if not (_rows2d(Rc, "Rc").is_contiguous() and Rc.shape[0] >= N + M and Rc.shape[1] == I):
+        raise _lib.GMError("mmd_pairs: Rc %s must be contiguous [>= %d, %d]" % (tuple(Rc.shape), N + M, I))
+    _tc_vec(sig, 1, "mmd_pairs", "sig")
+    _lib.call("gm_mmd_pairs", stream or stream_ptr(), X.data_ptr(), _ld(X), N, Y.data_ptr(), _ld(Y), M, I,
+              sig.data_ptr(), sig.numel(), C.data_ptr() if C is not None else None, _ld(C) if C is not None else 0,
+              Rc.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size())
+
+
+def mmd_finalize(N, M, n_sigma, sqrt_loss, ws, stats, r=None, loss_out=None, stream=None):
+    """stats [10] float64 (mmd2, loss, 1 / (2 loss), the block sums; include/gm_hip.h) and, given r [N], the row sums
+    of C, from the workspace mmd_pairs filled (gm_mmd_finalize).  loss_out: a float32 tensor taking the loss."""
+    if not (stats.is_cuda and stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() >= 10):
+        raise _lib.GMError("mmd_finalize: stats must be a contiguous float64 device tensor of 10 values")
+    if r is not None:
+        _tc_vec(r, N, "mmd_finalize", "r")
+    if loss_out is not None:
+        _tc_vec(loss_out, 1, "mmd_finalize", "loss_out")
+    _lib.call("gm_mmd_finalize", stream or stream_ptr(), int(N), int(M), int(n_sigma), 1 if sqrt_loss else 0,
+              1 if r is not None else 0, ws.data_ptr(), ws.numel() * ws.element_size(), stats.data_ptr(),
+              r.data_ptr() if r is not None else None, loss_out.data_ptr() if loss_out is not None else None)
+
+
+def mmd_grad(X, P, r, stats, dA, N=None, sigmoid=True, gscale=1.0, mu=None, stream=None):
+    """dA [N, I] = gscale stats[2] (r_i (x - mu) - P) (sigmoid: times x (1 - x)) with P = C (R - mu) (gm_mmd_grad); mu: a
+    row of I values (mmd_pairs' Rc is centred on X[0]), None: 0."""
+    N = X.shape[0] if N is None else int(N)
+    I = X.shape[1]
+    for t, nm in ((X, "X"), (P, "P"), (dA, "dA")):
+        if _rows2d(t, nm).shape[0] < N or t.shape[1] != I:
+            raise _lib.GMError("mmd_grad: %s %s does not fit [%d, %d]" % (nm, tuple(t.shape), N, I))
+    _tc_vec(r, N, "mmd_grad", "r")
+    if mu is not None:
+        _tc_vec(mu[0] if mu.dim() == 2 else mu, I, "mmd_grad", "mu")
+    _lib.call("gm_mmd_grad", stream or stream_ptr(), X.data_ptr(), _ld(X), mu.data_ptr() if mu is not None else None,
+              P.data_ptr(), _ld(P), r.data_ptr(),
+              stats.data_ptr(), float(gscale), 1 if sigmoid else 0, dA.data_ptr(), _ld(dA), N, I)
+
+
+def mmd_stats(samples, data, sig, sqrt_loss=False):
+    """stats [10] (float64, device) of the rows `samples` against `data`: pairs without C, then finalize."""
+    N, M = samples.shape[0], data.shape[0]
+    ws = mmd_workspace(N, M, False, samples.device)
+    stats = torch.zeros(10, dtype=torch.float64, device=samples.device)
+    mmd_pairs(samples, data, sig, ws)
+    mmd_finalize(N, M, sig.numel(), sqrt_loss, ws, stats)
+    return stats
+
+
+class _MMDLoss(torch.autograd.Function):
+    """mmd_loss below: pairs + finalize forward; C (R - mu) through the GEMM kernels and gm_mmd_grad backward."""
+
+    @staticmethod
+    def forward(ctx, samples, data, sig, sqrt_loss):
+        N, M, I = samples.shape[0], data.shape[0], samples.shape[1]
+        grad = ctx.needs_input_grad[0]
+        dev = samples.device
+        R = torch.cat([samples.detach(), data.detach()], 0).contiguous()
+        ws = mmd_workspace(N, M, grad, dev)
+        stats = torch.zeros(10, dtype=torch.float64, device=dev)
+        C = torch.empty(N, (N + M + 3) // 4 * 4, device=dev) if grad else None
+        r = torch.empty(N, device=dev) if grad else None
+        loss = torch.empty(1, device=dev)
+        Rc = torch.empty_like(R)
+        mmd_pairs(R[:N], R[N:], sig, ws, C=C, Rc=Rc)
+        mmd_finalize(N, M, sig.numel(), sqrt_loss, ws, stats, r=r, loss_out=loss)
+        if grad:
+            ctx.save_for_backward(R, Rc, C, r, stats)
+        ctx.shape = (N, M, I)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import ops
+        R, Rc, C, r, stats = ctx.saved_tensors
+        N, M, I = ctx.shape
+        P = torch.empty(N, I, device=R.device)
+        dX = torch.empty(N, I, device=R.device)
+        ops.linear_bwd_dx(C[:, :N + M], Rc, P, M=N)
+        mmd_grad(R[:N], P, r, stats, dX, sigmoid=False, mu=R[:1])
+        return dX * g, None, None, None
+
+
+def mmd_loss(samples, data, sigmas, sqrt_loss=True):
+    """The kernel MMD of gmmn.py's contract between samples [N, I] and data [M, I] (float32 device rows) as a
+    differentiable scalar: sqrt(mmd2 + 1e-8) (sqrt_loss) or mmd2, the biased statistic.  The gradient is with respect
+    to `samples` only: data.requires_grad raises.  sigmas: numbers, or the float32 device vector of mmd_sigmas."""
+    if data.requires_grad:
+        raise _lib.GMError("mmd_loss differentiates with respect to samples only: data.requires_grad is set")
+    for t, nm in ((samples, "samples"), (data, "data")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2):
+            raise _lib.GMError("mmd_loss: %s must be a 2-D float32 tensor on the MI355X; there is no CPU fallback" % nm)
+    if samples.shape[1] != data.shape[1] or not 1 <= samples.shape[1] <= _lib.MMD_MAX_I:
+        raise _lib.GMError("mmd_loss: rows of %d and %d values (1 to %d, equal)"
+                           % (samples.shape[1], data.shape[1], _lib.MMD_MAX_I))
+    if samples.shape[0] < 1 or data.shape[0] < 1 or samples.shape[0] > 65535:
+        raise _lib.GMError("mmd_loss: 1 to 65535 sample rows and at least one data row")
+    sig = sigmas if isinstance(sigmas, torch.Tensor) else mmd_sigmas(sigmas, samples.device, "mmd_loss")
+    return _MMDLoss.apply(samples.contiguous(), data.contiguous(), sig, bool(sqrt_loss))

@@ -513,6 +513,12 @@ class RBMTrainer(OneLossTrainer):
         from .trainers import _parzen
         return _parzen(self, n_samples, sigmas, n_val, seed)
 
+    def mmd(self, n_samples=10000, sigmas=None, seed=0):
+        """Kernel maximum mean discrepancy (metrics.mmd) between sample(n_samples, seed) and the test images ->
+        metrics.MMDResult; sigmas None: the GMMN paper's data-space bandwidths; the unbiased statistic."""
+        from .trainers import _mmd
+        return _mmd(self, n_samples, sigmas, seed)
+
     # ---- visualisation, checkpoints -----------------------------------------------------------------------------------
     def sample_images(self, epoch=-100, num_images=36, save=True):
         return viz.made_sample_images(self, epoch, num_images, save, self.viz_dir)

@@ -230,6 +230,14 @@ def _parzen(trainer, n_samples, sigmas, n_val, seed):
     return metrics.parzen_evaluate(samples, val, test, sigmas)
 
 
+def _mmd(trainer, n_samples, sigmas, seed):
+    """metrics.mmd (unbiased) of trainer.sample(n_samples, seed) against the test_iter images."""
+    from . import metrics
+    samples = trainer.sample(n_samples, seed)
+    test = _dataset_rows(trainer.test_iter).to(samples.device, torch.float32).contiguous()
+    return metrics.mmd(samples, test, sigmas, unbiased=True)
+
+
 def _decode_rows(net, z, batch=1024):
     """net(z) in batches, after every launch already queued (the engines' last Adam step included: the parameters
     are views of their flat buffers) -- no autograd, no mode change, no RNG use."""
@@ -555,6 +563,11 @@ class GANTrainer:
         """Parzen-window log-likelihood of the test images under n_samples generator samples, sigma chosen on the
         first n_val validation images (metrics.parzen_evaluate) -> metrics.ParzenResult."""
         return _parzen(self, n_samples, sigmas, n_val, seed)
+
+    def mmd(self, n_samples=10000, sigmas=None, seed=0):
+        """Kernel maximum mean discrepancy (metrics.mmd) between sample(n_samples, seed) and the test images ->
+        metrics.MMDResult; sigmas None: the GMMN paper's data-space bandwidths; the unbiased statistic."""
+        return _mmd(self, n_samples, sigmas, seed)
 
     def _viz_epoch(self, epoch):
         if self.viz:
@@ -1021,6 +1034,11 @@ class VAETrainer:
         the first n_val validation images (metrics.parzen_evaluate) -> metrics.ParzenResult."""
         return _parzen(self, n_samples, sigmas, n_val, seed)
 
+    def mmd(self, n_samples=10000, sigmas=None, seed=0):
+        """Kernel maximum mean discrepancy (metrics.mmd) between sample(n_samples, seed) and the test images ->
+        metrics.MMDResult; sigmas None: the GMMN paper's data-space bandwidths; the unbiased statistic."""
+        return _mmd(self, n_samples, sigmas, seed)
+
     def log_likelihood(self, images=None, k=500, seed=0):
         """Importance-weighted estimate of log p(x) from k samples per image (iwae.log_likelihood; images=None: the
         whole test_iter) -> metrics.IWAEResult.  For models built of vae.py's Encoder and Decoder unchanged (VAE, DVAE,
@@ -1342,6 +1360,9 @@ class AutoencoderTrainer(VAETrainer):
 
     def parzen(self, n_samples=10000, sigmas=None, n_val=10000, seed=0):
         raise GMError("an Autoencoder has no prior to sample: sample() / parzen() need a VAE or a GAN")
+
+    def mmd(self, n_samples=10000, sigmas=None, seed=0):
+        raise GMError("an Autoencoder has no prior to sample: sample() / parzen() / mmd() need a VAE or a GAN")
 
     def compute_batch(self, batch):
         """ae.py:147-160 (general path: autograd over the fused linear kernels)."""

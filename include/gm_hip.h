@@ -1604,6 +1604,53 @@ typedef struct gm_vq_step_args {
  * alone.  Then gm_adam's step on E_k at the schedule's slot.  Launch it behind the last reader of E. */
 int gm_vq_step(void* stream, const gm_vq_step_args* a);
 
+/* ---- Generative moment matching network (csrc/gm_gmmn.hip; gmmn.py holds the contract).  The
+ * kernel maximum mean discrepancy of generated rows X [N, I] and data rows Y [M, I] (each with a leading dimension of
+ * its own) under k(a, b) = sum_s exp(-|a - b|^2 / (2 sigma_s^2)), R = [X; Y], T = N + M:
+ *   mmd2 = sum_ij k(x_i, x_j) / N^2 - 2 sum_ij k(x_i, y_j) / (N M) + sum_jl k(y_j, y_l) / M^2        (diagonals in)
+ *   w(d2) = sum_s exp(-d2 / (2 sigma_s^2)) / sigma_s^2
+ *   C[i, j] = -(2 / N^2) w(|x_i - x_j|^2), j < N;   C[i, N + j] = +(2 / (N M)) w(|x_i - y_j|^2);   r_i = sum_j C[i, j]
+ *   d mmd2 / d x_i = r_i x_i - (C R)_i.
+ * d^2 = |a|^2 + |b|^2 - 2 a.b comes from the Gram form on v_mfma_f32_32x32x2_f32 (fp32 operands, fp32 accumulate) over
+ * the rows less X's first row, each norm formed by the same MFMA sequence as the dot products; it is clamped at 0 and is
+ * exactly 0 for a row against itself and for any two equal rows.  Every sum of kernel values or coefficients is fp64 in
+ * a fixed order; no atomics, one writer per element.  Limits: N, M >= 1, N + M < 2^31, 1 <= I <= GM_MMD_MAX_I,
+ * 1 <= n_sigma <= GM_MMD_MAX_SIGMAS, leading dimensions >= the row length; outside them, or with a NULL array or a
+ * workspace that is too small or not 8-byte aligned, every entry point returns GM_EINVAL before any launch. */
+#define GM_MMD_CHUNK 128                       /* partner rows per workgroup */
+#define GM_MMD_MAX_SIGMAS 16
+#define GM_MMD_MAX_I 8192
+#define GM_GMMN_MAX_Z 8192
+#define GM_GMMN_MAX_B 2048                     /* training batch: C [B, 2B] is 32 MB there */
+#define GM_GMMN_TAG_T 0x474D4D54u              /* "GMMT": the training prior */
+#define GM_GMMN_TAG_V 0x474D4D56u              /* "GMMV": the validation prior */
+#define GM_GMMN_TAG_S 0x474D4D53u              /* "GMMS": sample(n, seed) */
+/* Bytes of caller-owned device workspace of gm_mmd_pairs / gm_mmd_finalize:
+ *     40 * ceil(T / 256) * ceil(T / GM_MMD_CHUNK) + (grad ? 8 * ceil(T / GM_MMD_CHUNK) * N : 0) + 4 * 256 * (T / 256 + 1)
+ * (T / 256 the integer quotient: the row norms, padded with zeros past every tile of the grid). */
+int64_t gm_mmd_workspace_bytes(int N, int M, int grad);
+/* z [B, Z] = fmaf(2, u, -1): u the uniform of word e & 3 of Philox block (q0 + (e >> 2), step, b * k_total + j0, tag) of
+ * the noise block (gm_iwae_noise's layout with k_total = 1 and j0 the first row's position).  1 <= Z <= GM_GMMN_MAX_Z. */
+int gm_gmmn_prior(void* stream, const gm_iwae_noise* n, float* z, int64_t ldz, int B, int Z);
+/* Two launches: the row norms, then every tile's pairs.  Leaves the block sums (and, with C, the chunk shares of r) in the
+ * workspace for gm_mmd_finalize.  C [N, >= T] (NULL: no gradient; nothing of size N x M is written) takes the
+ * coefficients; with ldc % 4 == 0 and C 16-byte aligned they are stored four at a time.  Rc [T, I] (contiguous, caller-
+ * owned) takes the centred rows R - mu, mu = X's first row, which both the distances and the product with C are formed
+ * from: distances do not change under the shift, r_i x_i - (C R)_i = r_i (x_i - mu) - (C (R - mu))_i about any origin, and
+ * about a generated row the sums that cancel in either stay small when the generator has collapsed. */
+int gm_mmd_pairs(void* stream, const float* X, int64_t ldx, int N, const float* Y, int64_t ldy, int M, int I,
+                 const float* sigmas, int n_sigma, float* C, int64_t ldc, float* Rc, void* workspace, int64_t ws_bytes);
+/* stats [10] (fp64, device): mmd2, loss = sqrt(mmd2 + 1e-8) (sqrt_loss) or mmd2, 1 / (2 loss) (or 1), the three block sums
+ * xx, xy, yy with their diagonals, xx and yy without them, the xx and yy diagonals (N n_sigma and M n_sigma exactly).
+ * grad: r [N] as well (the workspace is the one gm_mmd_pairs filled with a C).  loss_out (may be NULL): the loss as a
+ * float. */
+int gm_mmd_finalize(void* stream, int N, int M, int n_sigma, int sqrt_loss, int grad, const void* workspace,
+                    int64_t ws_bytes, double* stats, float* r, float* loss_out);
+/* dA [N, I] = gscale stats[2] (r_i (x - mu) - P) (sigmoid: times x (1 - x), the gradient entering the generator's output
+ * layer), P = C (R - mu); mu [I] (NULL: 0, P = C R).  N <= 65535. */
+int gm_mmd_grad(void* stream, const float* X, int64_t ldx, const float* mu, const float* P, int64_t ldp, const float* r,
+                const double* stats, float gscale, int sigmoid, float* dA, int64_t lda, int N, int I);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

@@ -141,6 +141,10 @@ DDPM_MAX_I, DDPM_MIN_E, DDPM_MAX_E, DDPM_MAX_T = 8192, 4, 128, 4096      # GM_DD
 GMMN_TAG_T, GMMN_TAG_V, GMMN_TAG_S = 0x474D4D54, 0x474D4D56, 0x474D4D53    # GM_GMMN_TAG_* ("GMMT", "GMMV", "GMMS")
 MMD_MAX_SIGMAS, MMD_MAX_I, MMD_CHUNK, GMMN_MAX_Z, GMMN_MAX_B = 16, 8192, 128, 8192, 2048    # GM_MMD_* / GM_GMMN_*
 # (gm_ddpm_noise / _tables / _out / _reverse_args travel by pointer; their ctypes forms live in ops_fused)
+# GM_FM_TAG_* ("FMTD", "FMTT", "FMTN": training dequantisation / time / normals; "FMVD", "FMVT", "FMVN": validation)
+FM_TAG_D, FM_TAG_T, FM_TAG_N, FM_TAG_VD, FM_TAG_VT, FM_TAG_VN = (0x464D5444, 0x464D5454, 0x464D544E, 0x464D5644,
+                                                                 0x464D5654, 0x464D564E)
+FM_MAX_H = 1024                                                          # GM_FM_MAX_H
 
 MADE_TAG_S = 0x4D414453                                     # GM_MADE_TAG_S ("MADS")
 MADE_MIN_I, MADE_MAX_I, MADE_MAX_H = 2, 8192, 1024          # GM_MADE_* (include/gm_hip.h)
@@ -428,6 +432,11 @@ _SIGNATURES = {
     "gm_ddpm_loss": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_float, c_int, c_int]),
     "gm_ddpm_reverse": (c_int, [_P, _P]),
     "gm_ddpm_prior": (c_int, [_P, _P, c_int64, _P, ctypes.c_uint64, c_int64, c_int, _P, c_int, c_int, c_int, c_int]),
+    "gm_fm_qsample": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int]),
+    "gm_gather_rows_fm_qsample": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
+    "gm_gather_rows_bits_fm_qsample": (c_int, [_P, _P, _P, _P, _P, c_int, c_int64, _P, Slot, _P, c_int64, c_int, c_int]),
+    "gm_fm_div": (c_int, [_P, _P]),
+    "gm_fm_stage": (c_int, [_P, _P]),
     "gm_made_bce": (c_int, [_P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_float, c_int, c_int]),
     "gm_made_mask": (c_int, [_P, _P]),
     "gm_made_sample": (c_int, [_P, _P]),

@@ -1977,3 +1977,178 @@ def mmd_loss(samples, data, sigmas, sqrt_loss=True):
         raise _lib.GMError("mmd_loss: 1 to 65535 sample rows and at least one data row")
     sig = sigmas if isinstance(sigmas, torch.Tensor) else mmd_sigmas(sigmas, samples.device, "mmd_loss")
     return _MMDLoss.apply(samples.contiguous(), data.contiguous(), sig, bool(sqrt_loss))
+
+
+# ---- Flow matching (csrc/gm_fm.hip, gm_fm.h; flowmatch.py) ------------------------------------------------------------
+class FmNoise(ctypes.Structure):
+    """gm_fm_noise (include/gm_hip.h)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("tag_d", ctypes.c_uint32), ("tag_t", ctypes.c_uint32),
+                ("tag_n", ctypes.c_uint32), ("step_ctr", ctypes.c_void_p), ("step_base", ctypes.c_void_p),
+                ("step_add", ctypes.c_int64), ("row0", ctypes.c_int64)]
+
+
+class FmTables(ctypes.Structure):
+    """gm_fm_tables (include/gm_hip.h)."""
+    _fields_ = [("tt", ctypes.c_void_p), ("tc", ctypes.c_void_p), ("temb", ctypes.c_void_p), ("T", ctypes.c_int),
+                ("E", ctypes.c_int)]
+
+
+class FmOut(ctypes.Structure):
+    """gm_fm_out (include/gm_hip.h)."""
+    _fields_ = [("xin", ctypes.c_void_p), ("ldin", ctypes.c_int64), ("u", ctypes.c_void_p), ("ldu", ctypes.c_int64),
+                ("logdet", ctypes.c_void_p), ("j", ctypes.c_void_p), ("y1", ctypes.c_void_p), ("ldy1", ctypes.c_int64),
+                ("y0", ctypes.c_void_p), ("ldy0", ctypes.c_int64), ("alpha", ctypes.c_float), ("levels", ctypes.c_int)]
+
+
+class FmDivArgs(ctypes.Structure):
+    """gm_fm_div_args (include/gm_hip.h)."""
+    _fields_ = [("H1", ctypes.c_void_p), ("ld1", ctypes.c_int64), ("H2", ctypes.c_void_p), ("ld2", ctypes.c_int64),
+                ("Q", ctypes.c_void_p), ("ldq", ctypes.c_int64), ("part", ctypes.c_void_p),
+                ("part_floats", ctypes.c_int64), ("div", ctypes.c_void_p), ("B", ctypes.c_int), ("H", ctypes.c_int)]
+
+
+class FmStageArgs(ctypes.Structure):
+    """gm_fm_stage_args (include/gm_hip.h): one solver stage."""
+    _fields_ = [("k", ctypes.c_void_p), ("ldk", ctypes.c_int64), ("base", ctypes.c_void_p), ("ldb", ctypes.c_int64),
+                ("acc", ctypes.c_void_p), ("lda", ctypes.c_int64), ("xin", ctypes.c_void_p), ("ldin", ctypes.c_int64),
+                ("L", ctypes.c_void_p), ("div", ctypes.c_void_p), ("div_stride", ctypes.c_int64),
+                ("div_parts", ctypes.c_int), ("tab", ctypes.c_void_p), ("slot", _lib.Slot), ("temb", ctypes.c_void_p),
+                ("traj", ctypes.c_void_p), ("traj_stride", ctypes.c_int64), ("tick", ctypes.c_void_p),
+                ("done", ctypes.c_void_p), ("rows", ctypes.c_int), ("I", ctypes.c_int), ("E", ctypes.c_int),
+                ("T", ctypes.c_int), ("S", ctypes.c_int), ("stages", ctypes.c_int)]
+
+
+def fm_noise(seed, train=True, step=0, step_ctr=None, step_base=None, row0=0):
+    """A gm_fm_noise block: the training stream (tags FMTD / FMTT / FMTN) or the validation one (FMVD / FMVT / FMVN) at
+    step = *step_ctr + *step_base + step (int64 device tensors, or None for 0).  The tensors must outlive every launch
+    (and every captured graph) that reads them."""
+    tags = (_lib.FM_TAG_D, _lib.FM_TAG_T, _lib.FM_TAG_N) if train else (_lib.FM_TAG_VD, _lib.FM_TAG_VT, _lib.FM_TAG_VN)
+    return FmNoise(_seed64("fm_noise", seed), *tags, *_clock("fm_noise", step, step_ctr, step_base), int(row0))
+
+
+def fm_tables(tt, tc, temb):
+    """A gm_fm_tables block over the model's fp32 device buffers tt [T + 1], tc [T + 1], temb [T + 1, E]."""
+    for t, nm in ((tt, "tt"), (tc, "tc"), (temb, "temb")):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise _lib.GMError("fm_tables: %s must be a contiguous float32 device tensor" % nm)
+    T1, E = temb.shape
+    if tt.numel() != T1 or tc.numel() != T1:
+        raise _lib.GMError("fm_tables: tt and tc hold one float per grid point")
+    tab = FmTables(tt.data_ptr(), tc.data_ptr(), temb.data_ptr(), T1 - 1, E)
+    tab.keep = (tt, tc, temb)
+    return tab
+
+
+def _fm_out(xin, u, logdet, j, rows, I, E, alpha, levels, y1=None, y0=None):
+    _nvp_rows(xin, rows, I + E, "xin"), _nvp_rows(u, rows, I, "u"), _nvp_vec(logdet, rows, "logdet")
+    if j is not None and not (j.is_cuda and j.dtype == torch.int32 and j.is_contiguous() and j.numel() >= rows):
+        raise _lib.GMError("fm q-sample: j must be a contiguous int32 device tensor of %d elements" % rows)
+    o = FmOut(xin.data_ptr(), _ld(xin), u.data_ptr(), _ld(u), logdet.data_ptr(), j.data_ptr() if j is not None else None)
+    if y1 is not None:
+        o.y1, o.ldy1 = _nvp_rows(y1, rows, I, "y1").data_ptr(), _ld(y1)
+    if y0 is not None:
+        o.y0, o.ldy0 = _nvp_rows(y0, rows, I, "y0").data_ptr(), _ld(y0)
+    o.alpha, o.levels = float(alpha), int(levels)
+    return o
+
+
+def fm_qsample(x, noise, tables, alpha, levels, xin=None, u=None, logdet=None, j=None, y1=None, y0=None, stream=None):
+    """(xin, u, logdet, j) of the image rows x [n, I] in [0, 1] (gm_fm_qsample): xin [n, I + E] = [y_t | temb[j]], u
+    [n, I] = y1 - y0, logdet [n] the preprocessing log-determinant, j [n] int32 the grid index; y1 / y0 [n, I]
+    (optional) take the preprocessed rows and the normals.  Missing outputs are allocated."""
+    n, I = _rows2d(x, "x").shape
+    E = tables.E
+    xin = torch.empty(n, I + E, device=x.device) if xin is None else xin
+    u = torch.empty(n, I, device=x.device) if u is None else u
+    logdet = torch.empty(n, device=x.device) if logdet is None else logdet
+    j = torch.empty(n, dtype=torch.int32, device=x.device) if j is None else j
+    if n:
+        o = _fm_out(xin, u, logdet, j, n, I, E, alpha, levels, y1, y0)
+        _lib.call("gm_fm_qsample", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(tables), ctypes.byref(o),
+                  x.data_ptr(), x.stride(0), n, I)
+    return xin, u, logdet, j
+
+
+def gather_rows_fm_qsample(data, idx, out, xin, u, logdet, j, noise, tables, alpha, levels, B=None, idx_slot=NO_SLOT,
+                           y1=None, y0=None, stream=None):
+    """ops.gather_rows(data, idx, out) and the path sample of every gathered row in one launch
+    (gm_gather_rows[_bits]_fm_qsample)."""
+    from .ops import PackedData
+    n_rows, row = data.shape
+    B = out.shape[0] if B is None else B
+    if not (idx.dtype == torch.int64 and idx.is_cuda):
+        raise _lib.GMError("gather_rows_fm_qsample: idx must be an int64 device tensor")
+    _nvp_rows(out, B, row, "out")
+    o = _fm_out(xin, u, logdet, j, B, row, tables.E, alpha, levels, y1, y0)
+    if isinstance(data, PackedData):
+        _lib.call("gm_gather_rows_bits_fm_qsample", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(tables),
+                  ctypes.byref(o), data.data_ptr(), data.wpr, n_rows, idx.data_ptr(), idx_slot, out.data_ptr(),
+                  _ld(out), B, row)
+    else:
+        _lib.call("gm_gather_rows_fm_qsample", stream or stream_ptr(), ctypes.byref(noise), ctypes.byref(tables),
+                  ctypes.byref(o), _rows2d(data, "data").data_ptr(), n_rows, idx.data_ptr(), idx_slot, out.data_ptr(),
+                  _ld(out), B, row)
+    return out
+
+
+def fm_div_tiles(H):
+    """The number of partials per row gm_fm_div writes: one per 32 hidden units."""
+    return (int(H) + 31) // 32
+
+
+def fm_div(H1, H2, Q, B=None, part=None, div=None, finish=True, stream=None):
+    """div [B] = sum_{i, j} [H2[b, i] > 0] Q[i, j] [H1[b, j] > 0] (gm_fm_div).  part [tiles, B] takes the tiles'
+    partials; finish=False leaves them for gm_fm_stage to add and returns part."""
+    H = Q.shape[0]
+    B = H1.shape[0] if B is None else B
+    if Q.dim() != 2 or Q.shape[1] != H or not 1 <= H <= _lib.FM_MAX_H:
+        raise _lib.GMError("fm_div: Q must be [H, H] with 1 <= H <= %d, got %s" % (_lib.FM_MAX_H, tuple(Q.shape)))
+    _nvp_rows(H1, B, H, "H1"), _nvp_rows(H2, B, H, "H2"), _nvp_rows(Q, H, H, "Q")
+    tiles = fm_div_tiles(H)
+    part = torch.empty(tiles, B, device=H1.device) if part is None else part
+    if not (part.is_cuda and part.dtype == torch.float32 and part.is_contiguous() and part.numel() >= tiles * B):
+        raise _lib.GMError("fm_div: part must be a contiguous float32 device tensor of %d elements" % (tiles * B))
+    a = FmDivArgs(H1.data_ptr(), _ld(H1), H2.data_ptr(), _ld(H2), Q.data_ptr(), _ld(Q), part.data_ptr(), part.numel())
+    if finish:
+        div = torch.empty(B, device=H1.device) if div is None else div
+        a.div = _nvp_vec(div, B, "div").data_ptr()
+    a.B, a.H = B, H
+    _lib.call("gm_fm_div", stream or stream_ptr(), ctypes.byref(a))
+    return div if finish else part
+
+
+def fm_stage(k, base, acc, xin, tab, temb, I, stages, L=None, div=None, div_parts=1, slot=None, step=0, traj=None,
+             tick=None, done=None, rows=None, stream=None):
+    """One solver stage in place (gm_fm_stage): the coefficients are row `slot` (a gm_slot of stride 8 over a device
+    counter) or row `step` of tab [S, 8]; div [div_parts, rows] the divergence's partials (None: sampling, L is left
+    alone); traj [S / stages + 1, rows, I] takes a step's result at index step + 1; tick (with done, one zeroed int32)
+    is advanced by the launch."""
+    T1, E = temb.shape
+    S = tab.shape[0]
+    rows = xin.shape[0] if rows is None else rows
+    _nvp_rows(k, rows, I, "k"), _nvp_rows(base, rows, I, "base"), _nvp_rows(acc, rows, I, "acc")
+    _nvp_rows(xin, rows, I + E, "xin")
+    if tuple(tab.shape) != (S, 8) or not (tab.is_cuda and tab.dtype == torch.float32 and tab.is_contiguous()) \
+            or not temb.is_contiguous():
+        raise _lib.GMError("fm_stage: tab must be a contiguous float32 device tensor [S, 8]")
+    if traj is not None and not (traj.is_contiguous() and tuple(traj.shape) == (S // stages + 1, rows, I)):
+        raise _lib.GMError("fm_stage: traj must be a contiguous [%d, %d, %d] tensor" % (S // stages + 1, rows, I))
+    if done is not None and not (done.dtype == torch.int32 and done.is_cuda):
+        raise _lib.GMError("fm_stage: done must be an int32 device tensor")
+    a = FmStageArgs()
+    a.k, a.ldk, a.base, a.ldb, a.acc, a.lda = k.data_ptr(), _ld(k), base.data_ptr(), _ld(base), acc.data_ptr(), _ld(acc)
+    a.xin, a.ldin = xin.data_ptr(), _ld(xin)
+    if div is not None:
+        if L is None or not (L.is_cuda and L.dtype == torch.float32 and L.is_contiguous() and L.numel() >= 2 * rows):
+            raise _lib.GMError("fm_stage: the divergence needs L, a contiguous float32 device tensor [rows, 2]")
+        if not (div.is_cuda and div.dtype == torch.float32 and div.is_contiguous() and div.numel() >= div_parts * rows):
+            raise _lib.GMError("fm_stage: div must be a contiguous float32 device tensor [div_parts, rows]")
+        a.L, a.div, a.div_stride, a.div_parts = L.data_ptr(), div.data_ptr(), rows, int(div_parts)
+    a.tab, a.slot, a.temb = tab.data_ptr(), (slot if slot is not None else _lib.slot(0, 0, int(step), 0, 8)), \
+        temb.data_ptr()
+    if traj is not None:
+        a.traj, a.traj_stride = traj.data_ptr(), rows * I
+    a.tick = tick.data_ptr() if tick is not None else None
+    a.done = done.data_ptr() if done is not None else None
+    a.rows, a.I, a.E, a.T, a.S, a.stages = rows, I, E, T1 - 1, S, int(stages)
+    _lib.call("gm_fm_stage", stream or stream_ptr(), ctypes.byref(a))

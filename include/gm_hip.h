@@ -1651,6 +1651,92 @@ int gm_mmd_finalize(void* stream, int N, int M, int n_sigma, int sqrt_loss, int 
 int gm_mmd_grad(void* stream, const float* X, int64_t ldx, const float* mu, const float* P, int64_t ldp, const float* r,
                 const double* stats, float gscale, int sigmoid, float* dA, int64_t lda, int N, int I);
 
+/* ---- Flow matching: a continuous normalizing flow trained by velocity regression, with an exact-divergence likelihood
+ * (csrc/gm_fm.hip, gm_fm.h; flowmatch.py holds the contract).  The row kernels run one 256-thread
+ * workgroup per row with fixed reduction orders; nothing uses floating-point atomics.  Noise: Philox4x32-10 with key
+ * (seed mod 2^32, seed >> 32), batch row `row` = row0 + the row's position in the call, step as in gm_ddpm_noise:
+ *   dequantisation uniform of pixel e: word e & 3 of counter (e >> 2, step, row, tag_d) (gm_nvp_pre's rule and bits);
+ *   grid index: j = mulhi(word 0 of counter (0, step, row, tag_t), T + 1);
+ *   y0 of pixels 4q .. 4q + 3: counter (q, step, row, tag_n) through gm_philox_normal's Box-Muller mapping;
+ *   y_t = fmaf(tt[j], y1, tc[j] * y0),  u = y1 - y0.
+ * Limits: gm_ddpm's on I, E and T, 1 <= H <= GM_FM_MAX_H; outside them, or with a NULL array, every entry point
+ * returns GM_EINVAL before any launch. */
+#define GM_FM_TAG_D 0x464D5444u                /* "FMTD": training, dequantisation */
+#define GM_FM_TAG_T 0x464D5454u                /* "FMTT": training, time */
+#define GM_FM_TAG_N 0x464D544Eu                /* "FMTN": training, normals */
+#define GM_FM_TAG_VD 0x464D5644u               /* "FMVD": validation, dequantisation */
+#define GM_FM_TAG_VT 0x464D5654u               /* "FMVT": validation, time */
+#define GM_FM_TAG_VN 0x464D564Eu               /* "FMVN": validation, normals */
+#define GM_FM_MAX_H 1024
+typedef struct gm_fm_noise {
+    uint64_t seed;
+    uint32_t tag_d, tag_t, tag_n;
+    const int64_t* step_ctr;                  /* device counter or NULL */
+    const int64_t* step_base;                 /* device base or NULL */
+    int64_t step_add;
+    int64_t row0;                             /* batch position of the first row (>= 0) */
+} gm_fm_noise;
+typedef struct gm_fm_tables {                 /* fp32 device tables over the grid t_j = j / T, j = 0 .. T */
+    const float* tt; const float* tc;         /* [T + 1]: j / T and (T - j) / T */
+    const float* temb;                        /* [T + 1, E] */
+    int T, E;
+} gm_fm_tables;
+typedef struct gm_fm_out {
+    float* xin; int64_t ldin;                 /* [rows, >= I + E]: row = [y_t | temb[j]], the field's input */
+    float* u; int64_t ldu;                    /* [rows, >= I]: the regression target y1 - y0 */
+    float* logdet;                            /* [rows]: the preprocessing log-determinant (gm_nvp_pre's) */
+    int32_t* j;                               /* [rows]: the grid index (may be NULL) */
+    float* y1; int64_t ldy1;                  /* [rows, >= I] (may be NULL): the preprocessed rows */
+    float* y0; int64_t ldy0;                  /* [rows, >= I] (may be NULL): the normals */
+    float alpha; int levels;                  /* gm_nvp_pre's settings */
+} gm_fm_out;
+/* The path sample of `rows` image rows x in [0, 1] (ldx floats apart). */
+int gm_fm_qsample(void* stream, const gm_fm_noise* n, const gm_fm_tables* s, const gm_fm_out* o, const float* x,
+                  int64_t ldx, int64_t rows, int I);
+/* gm_gather_rows / gm_gather_rows_bits and the path sample of every gathered row in one launch. */
+int gm_gather_rows_fm_qsample(void* stream, const gm_fm_noise* n, const gm_fm_tables* s, const gm_fm_out* o,
+                              const float* data, int64_t n_rows, const int64_t* idx, gm_slot idx_slot, float* out,
+                              int64_t ld_out, int B, int row_elems);
+int gm_gather_rows_bits_fm_qsample(void* stream, const gm_fm_noise* n, const gm_fm_tables* s, const gm_fm_out* o,
+                                   const uint32_t* bits, int words_per_row, int64_t n_rows, const int64_t* idx,
+                                   gm_slot idx_slot, float* out, int64_t ld_out, int B, int row_elems);
+/* The exact divergence of the three-layer field from the ReLU patterns of its forward pass:
+ *   div[b] = sum_{i, j} [H2[b, i] > 0] Q[i, j] [H1[b, j] > 0]        (-0.0, 0.0 and NaN are not lit)
+ * on v_mfma_f32_32x32x2_f32 (exact fp32).  One wave owns 32 rows b and 32 indices i (tile t = i / 32) over all j and
+ * writes part[t * B + b]; tiles = ceil(H / 32).  div (may be NULL) = the tiles' partials added in order by a second
+ * launch; with div NULL gm_fm_stage adds them.  One writer per output, no atomics, no workgroup waits on another.
+ * 1 <= B <= 2^30.  Q must be finite: an entry meets the 0 / 1 pattern as a product inside the MFMA, so a NaN or an
+ * infinity in Q reaches every row's result, unlit units included (0 * inf = NaN). */
+typedef struct gm_fm_div_args {
+    const float* H1; int64_t ld1;             /* [B, >= H] */
+    const float* H2; int64_t ld2;             /* [B, >= H] */
+    const float* Q; int64_t ldq;              /* [H, >= H] */
+    float* part; int64_t part_floats;         /* >= ceil(H / 32) * B floats */
+    float* div;                               /* [B] or NULL */
+    int B, H;
+} gm_fm_div_args;
+int gm_fm_div(void* stream, const gm_fm_div_args* a);
+/* One solver stage on `rows` rows, its coefficients row s = slot's index of the table tab [S, 8] = (h a, h b, first,
+ * last, j_next or -1, j_eval, 0, 0); k the field at this evaluation, d = sum_p div[p * div_stride + row] its divergence:
+ *   acc = first ? hb k : fmaf(hb, k, acc);   last: base += acc, y = base;   otherwise: y = fmaf(ha, k, base);
+ * y goes to xin[:, :I]; (lbase, lacc) = L[row, 0 .. 1] follow the same rule with d (div NULL: L is left alone);
+ * temb[j_next] goes into the rows' tails (j_next < 0: the tail stays).  traj (may be NULL): on a step's last stage y
+ * also to traj + (s / stages + 1) traj_stride, rows I floats apart.  done / tick as in gm_ddpm_reverse. */
+typedef struct gm_fm_stage_args {
+    const float* k; int64_t ldk;              /* [rows, >= I] */
+    float* base; int64_t ldb;                 /* [rows, >= I] */
+    float* acc; int64_t lda;                  /* [rows, >= I] */
+    float* xin; int64_t ldin;                 /* [rows, >= I + E] */
+    float* L;                                 /* [rows, 2] (needed with div) */
+    const float* div; int64_t div_stride; int div_parts;
+    const float* tab; gm_slot slot;           /* slot.stride == 8 */
+    const float* temb;                        /* [T + 1, E] */
+    float* traj; int64_t traj_stride;
+    int64_t* tick; unsigned int* done;
+    int rows, I, E, T, S, stages;
+} gm_fm_stage_args;
+int gm_fm_stage(void* stream, const gm_fm_stage_args* a);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

@@ -86,8 +86,11 @@ def __getattr__(name):
     DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine, NFVAE / NFVAETrainer / NFVAEEngine, CatVAE /
     CatVAETrainer / CatVAEEngine, RealNVP / RealNVPTrainer / RealNVPEngine, RBM / RBMTrainer / RBMEngine, VQVAE /
     VQVAETrainer / VQVAEEngine, MAF / MAFTrainer / MAFEngine, IAFVAE / IAFVAETrainer / IAFVAEEngine, TCVAE /
-    TCVAETrainer / TCVAEEngine, GMMN / GMMNTrainer / GMMNEngine and FlowMatching / FlowMatchTrainer / FlowMatchEngine,
-    imported on first use (importing the package stays free of torch)."""
+    TCVAETrainer / TCVAEEngine, GMMN / GMMNTrainer / GMMNEngine, SWG / SWGTrainer / SWGEngine and FlowMatching /
+    FlowMatchTrainer / FlowMatchEngine, imported on first use (importing the package stays free of torch)."""
+    if name in ("SWG", "SWGTrainer", "SWGEngine"):
+        from . import swg
+        return getattr(swg, name)
     if name in ("FlowMatching", "FlowMatchTrainer", "FlowMatchEngine"):
         from . import flowmatch
         return getattr(flowmatch, name)

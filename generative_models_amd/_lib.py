@@ -140,6 +140,9 @@ DDPM_TAG_T, DDPM_TAG_E, DDPM_TAG_V, DDPM_TAG_VE, DDPM_TAG_S = 0x44445054, 0x4444
 DDPM_MAX_I, DDPM_MIN_E, DDPM_MAX_E, DDPM_MAX_T = 8192, 4, 128, 4096      # GM_DDPM_* (include/gm_hip.h)
 GMMN_TAG_T, GMMN_TAG_V, GMMN_TAG_S = 0x474D4D54, 0x474D4D56, 0x474D4D53    # GM_GMMN_TAG_* ("GMMT", "GMMV", "GMMS")
 MMD_MAX_SIGMAS, MMD_MAX_I, MMD_CHUNK, GMMN_MAX_Z, GMMN_MAX_B = 16, 8192, 128, 8192, 2048    # GM_MMD_* / GM_GMMN_*
+SWG_TAG_T, SWG_TAG_V, SWG_TAG_S = 0x53574754, 0x53574756, 0x53574753         # GM_SWG_TAG_* ("SWGT", "SWGV", "SWGS")
+SWG_TAG_DT, SWG_TAG_DV, SWG_TAG_DM = 0x53574454, 0x53574456, 0x5357444D      # the directions ("SWDT", "SWDV", "SWDM")
+SW_MAX_P, SW_MAX_B, SW_MAX_ROWS = 8192, 2048, 16384                          # GM_SW_* (include/gm_hip.h)
 # (gm_ddpm_noise / _tables / _out / _reverse_args travel by pointer; their ctypes forms live in ops_fused)
 # GM_FM_TAG_* ("FMTD", "FMTT", "FMTN": training dequantisation / time / normals; "FMVD", "FMVT", "FMVN": validation)
 FM_TAG_D, FM_TAG_T, FM_TAG_N, FM_TAG_VD, FM_TAG_VT, FM_TAG_VN = (0x464D5444, 0x464D5454, 0x464D544E, 0x464D5644,
@@ -421,6 +424,10 @@ _SIGNATURES = {
     "gm_mmd_pairs": (c_int, [_P, _P, c_int64, c_int, _P, c_int64, c_int, c_int, _P, c_int, _P, c_int64, _P, _P, c_int64]),
     "gm_mmd_finalize": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int64, _P, _P, _P]),
     "gm_mmd_grad": (c_int, [_P, _P, c_int64, _P, _P, c_int64, _P, _P, c_float, c_int, _P, c_int64, c_int, c_int]),
+    "gm_sw_workspace_bytes": (c_int64, [c_int]),
+    "gm_sw_directions": (c_int, [_P, _P, _P, c_int64, c_int, c_int]),
+    "gm_sw_sort": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, c_int64, _P, c_int64]),
+    "gm_sw_finalize": (c_int, [_P, c_int, c_int, c_int, _P, c_int64, _P, _P]),
     "gm_cat_sample": (c_int, [_P, _P, _P]),
     "gm_cat_reduce": (c_int, [_P, _P, _P]),
     "gm_vq_quantise": (c_int, [_P, _P]),

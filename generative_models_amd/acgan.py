@@ -343,6 +343,12 @@ class ACGANTrainer(GANTrainer):
         from .trainers import _mmd
         return _mmd(self, n_samples, sigmas, seed)
 
+    def swd(self, n_samples=10000, n_projections=1024, seed=0):
+        """Sliced Wasserstein distance (metrics.sliced_wasserstein) between sample(n_samples, seed) and the test images
+        over n_projections random unit directions -> metrics.SWDResult."""
+        from .trainers import _swd
+        return _swd(self, n_samples, n_projections, seed)
+
     def generate_images(self, epoch, num_outputs=36, save=True, labels=None):
         """ns_gan.py:228-262 for chosen classes (None: arange(num_outputs) % num_classes): compute_noise's draw from
         the global generator, saved as ../viz/<name>/reconst_<epoch>.png."""

@@ -122,3 +122,46 @@ def mmd(samples, data, sigmas=None, unbiased=True):
     else:
         mmd2 = st[0]
     return MMDResult(mmd2, float(np.sqrt(max(mmd2, 0.0))), n, m)
+
+
+# ---- sliced Wasserstein distance (gm_sw_directions / gm_sw_sort / gm_sw_finalize, csrc/gm_sw.hip; swg.py holds the
+# contract) ----  swd2 = the mean over n_projections random unit directions of the squared 2-Wasserstein distance between
+# the projected samples and the projected data; swd = sqrt(swd2).
+SWDResult = collections.namedtuple("SWDResult", "swd2 swd n_projections n_samples n_data")
+SWD_BLOCK = 256                      # projections per launch: nothing larger than [256, N + M] is stored
+SWD_GROUP = 64                       # gm_sw_finalize adds ws in groups of 64 consecutive projections, in ascending order
+assert SWD_BLOCK % SWD_GROUP == 0    # so a block is whole groups, and the block sums close in block order
+
+
+def sliced_wasserstein(samples, data, n_projections=1024, seed=0):
+    """The sliced Wasserstein distance between `samples` [N, ...] and `data` [M, ...] (float32 tensors on the MI355X) ->
+    SWDResult.  Any 1 <= N, M <= GM_SW_MAX_ROWS (16384), N != M included; the directions are rows 0 .. n_projections - 1
+    of the stream (seed, step 0, "SWDM").  Projections run in blocks of at most SWD_BLOCK; every projection's sum lands in
+    one fp64 array and one launch closes it in a fixed order (groups of 64 in ascending order, so block after block)."""
+    from . import ops, ops_fused as of_
+    s, q = _rows(samples, "samples"), _rows(data, "data")
+    if s.shape[1] != q.shape[1] or not 1 <= s.shape[1] <= _lib.MMD_MAX_I:
+        raise GMError("sliced_wasserstein: samples have %d values per row, data %d (1 to %d, equal)"
+                      % (s.shape[1], q.shape[1], _lib.MMD_MAX_I))
+    n, m, I = s.shape[0], q.shape[0], s.shape[1]
+    if not (1 <= n <= _lib.SW_MAX_ROWS and 1 <= m <= _lib.SW_MAX_ROWS):
+        raise GMError("sliced_wasserstein: %d samples and %d data rows; each projection is sorted in LDS, which holds 1 to "
+                      "%d rows a side (a radix sort for more is not implemented)" % (n, m, _lib.SW_MAX_ROWS))
+    P = _lib.check_int(n_projections, "n_projections")
+    if not 1 <= P <= _lib.SW_MAX_P:
+        raise GMError("sliced_wasserstein: n_projections must lie in [1, %d], got %d" % (_lib.SW_MAX_P, P))
+    seed = _lib.check_seed(seed)
+    with torch.cuda.device(q.device):
+        R = torch.cat([s, q], 0).contiguous()
+        pb = min(P, SWD_BLOCK)
+        theta, Pr = torch.empty(pb, I, device=q.device), torch.empty(pb, n + m, device=q.device)
+        ws = of_.sw_workspace(P, q.device)
+        stats = torch.zeros(2, dtype=torch.float64, device=q.device)
+        for p0 in range(0, P, SWD_BLOCK):
+            k = min(SWD_BLOCK, P - p0)
+            of_.sw_directions(theta, of_.sw_noise(seed, _lib.SWG_TAG_DM, row0=p0), P=k)
+            ops.linear_fwd(theta[:k], R, None, Pr[:k], "id")
+            of_.sw_sort(Pr, n, m, ws[p0:p0 + k], P=k)
+        of_.sw_finalize(P, n, m, ws, stats)
+        st = stats.cpu().tolist()                                    # the one sync
+    return SWDResult(st[0], st[1], P, n, m)

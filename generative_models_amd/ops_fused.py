@@ -1979,6 +1979,115 @@ def mmd_loss(samples, data, sigmas, sqrt_loss=True):
     return _MMDLoss.apply(samples.contiguous(), data.contiguous(), sig, bool(sqrt_loss))
 
 
+# ---- Sliced Wasserstein distance (csrc/gm_sw.hip; swg.py, metrics.sliced_wasserstein) ------------------------------
+def sw_noise(seed, tag, step=0, step_ctr=None, step_base=None, row0=0):
+    """The noise block of the SWG's prior or directions (a gm_iwae_noise at k = 1): stream (seed, tag) at step =
+    *step_ctr + *step_base + step, the call's row p draws noise row row0 + p."""
+    return iwae_noise(seed, tag, 1, j0=row0, step=step, step_ctr=step_ctr, step_base=step_base)
+
+
+def sw_directions(theta, noise, P=None, I=None, stream=None):
+    """theta [P, I]: the noise block's rows of normals, each scaled to unit 2-norm (gm_sw_directions)."""
+    P = theta.shape[0] if P is None else int(P)
+    I = theta.shape[1] if I is None else int(I)
+    if _rows2d(theta, "theta").shape[0] < P or theta.shape[1] < I:
+        raise _lib.GMError("sw_directions: theta %s does not fit P=%d, I=%d" % (tuple(theta.shape), P, I))
+    _lib.call("gm_sw_directions", stream or stream_ptr(), ctypes.byref(noise), theta.data_ptr(), _ld(theta), P, I)
+    return theta
+
+
+def sw_workspace(P, device="cuda"):
+    """The device workspace of sw_sort / sw_finalize for P projections: the column sums (gm_sw_workspace_bytes)."""
+    n = _lib.load().gm_sw_workspace_bytes(int(P))
+    if n < 0:
+        _lib.check(int(n), "gm_sw_workspace_bytes")
+    return torch.empty(int(n) // 8, dtype=torch.float64, device=device)
+
+
+def _sw_ws(ws, P, who):
+    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.float64 and ws.is_contiguous()
+            and ws.numel() >= P):
+        raise _lib.GMError("%s: ws must be a contiguous float64 device tensor of at least %d values" % (who, P))
+    return ws
+
+
+def sw_sort(Pr, N, M, ws, Ct=None, P=None, stream=None):
+    """Every projection's two columns sorted and matched by rank (gm_sw_sort): Pr [P, >= N + M] holds a_p in columns
+    [0, N) and b_p in [N, N + M); ws[p] = W_p N M; Ct [P, >= N] (None: no gradient, up to SW_MAX_ROWS rows a side) takes
+    d swd2 / d a at the rows' original positions."""
+    P = Pr.shape[0] if P is None else int(P)
+    N, M = int(N), int(M)
+    if _rows2d(Pr, "Pr").shape[0] < P or Pr.shape[1] < N + M:
+        raise _lib.GMError("sw_sort: Pr %s does not fit P=%d, N + M=%d" % (tuple(Pr.shape), P, N + M))
+    if Ct is not None and (_rows2d(Ct, "Ct").shape[0] < P or Ct.shape[1] < N):
+        raise _lib.GMError("sw_sort: Ct %s does not fit [%d, %d]" % (tuple(Ct.shape), P, N))
+    _sw_ws(ws, P, "sw_sort")
+    _lib.call("gm_sw_sort", stream or stream_ptr(), Pr.data_ptr(), _ld(Pr), P, N, M,
+              Ct.data_ptr() if Ct is not None else None, _ld(Ct) if Ct is not None else 0, ws.data_ptr(), 8 * ws.numel())
+
+
+def sw_finalize(P, N, M, ws, stats, loss_out=None, stream=None):
+    """stats [2] float64 = (swd2, sqrt(swd2)) from the column sums sw_sort left in ws (gm_sw_finalize).  loss_out: a
+    float32 tensor taking swd2."""
+    if not (stats.is_cuda and stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() >= 2):
+        raise _lib.GMError("sw_finalize: stats must be a contiguous float64 device tensor of 2 values")
+    if loss_out is not None:
+        _tc_vec(loss_out, 1, "sw_finalize", "loss_out")
+    _sw_ws(ws, int(P), "sw_finalize")
+    _lib.call("gm_sw_finalize", stream or stream_ptr(), int(P), int(N), int(M), ws.data_ptr(), 8 * ws.numel(),
+              stats.data_ptr(), loss_out.data_ptr() if loss_out is not None else None)
+
+
+class _SWLoss(torch.autograd.Function):
+    """sw_loss below: the projection GEMM, sort and finalize forward; Ct^T Theta through the GEMM kernels backward."""
+
+    @staticmethod
+    def forward(ctx, samples, data, theta):
+        from . import ops
+        N, M, P = samples.shape[0], data.shape[0], theta.shape[0]
+        grad = ctx.needs_input_grad[0]
+        dev = samples.device
+        R = torch.cat([samples.detach(), data.detach()], 0).contiguous()
+        Pr = torch.empty(P, N + M, device=dev)
+        ops.linear_fwd(theta, R, None, Pr, "id")                  # [P, N + M]: a projection's values are contiguous
+        ws = sw_workspace(P, dev)
+        stats = torch.zeros(2, dtype=torch.float64, device=dev)
+        Ct = torch.empty(P, N, device=dev) if grad else None
+        loss = torch.empty(1, device=dev)
+        sw_sort(Pr, N, M, ws, Ct=Ct)
+        sw_finalize(P, N, M, ws, stats, loss_out=loss)
+        if grad:
+            ctx.save_for_backward(Ct, theta)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import ops
+        Ct, theta = ctx.saved_tensors
+        dX = torch.empty(Ct.shape[1], theta.shape[1], device=Ct.device)
+        ops.linear_bwd_dw(Ct, theta, dX, None)                    # dX [N, I] = Ct^T Theta
+        return dX * g, None, None
+
+
+def sw_loss(samples, data, theta):
+    """swd2 of swg.py's contract between samples [N, I] and data [M, I] (float32 device rows, at most SW_MAX_B each) over
+    the unit directions theta [P, I], as a differentiable scalar.  The gradient is with respect to `samples` only."""
+    if data.requires_grad or theta.requires_grad:
+        raise _lib.GMError("sw_loss differentiates with respect to samples only: data or theta requires grad")
+    for t, nm in ((samples, "samples"), (data, "data"), (theta, "theta")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2):
+            raise _lib.GMError("sw_loss: %s must be a 2-D float32 tensor on the MI355X; there is no CPU fallback" % nm)
+    I = samples.shape[1]
+    if data.shape[1] != I or theta.shape[1] != I or not 1 <= I <= _lib.MMD_MAX_I:
+        raise _lib.GMError("sw_loss: rows of %d, %d and %d values (1 to %d, equal)"
+                           % (I, data.shape[1], theta.shape[1], _lib.MMD_MAX_I))
+    if not (1 <= samples.shape[0] <= _lib.SW_MAX_B and 1 <= data.shape[0] <= _lib.SW_MAX_B):
+        raise _lib.GMError("sw_loss: 1 to %d sample rows and data rows" % _lib.SW_MAX_B)
+    if not 1 <= theta.shape[0] <= _lib.SW_MAX_P:
+        raise _lib.GMError("sw_loss: 1 to %d directions" % _lib.SW_MAX_P)
+    return _SWLoss.apply(samples.contiguous(), data.contiguous(), theta.contiguous())
+
+
 # ---- Flow matching (csrc/gm_fm.hip, gm_fm.h; flowmatch.py) ------------------------------------------------------------
 class FmNoise(ctypes.Structure):
     """gm_fm_noise (include/gm_hip.h)."""

@@ -519,6 +519,12 @@ class RBMTrainer(OneLossTrainer):
         from .trainers import _mmd
         return _mmd(self, n_samples, sigmas, seed)
 
+    def swd(self, n_samples=10000, n_projections=1024, seed=0):
+        """Sliced Wasserstein distance (metrics.sliced_wasserstein) between sample(n_samples, seed) and the test images
+        over n_projections random unit directions -> metrics.SWDResult."""
+        from .trainers import _swd
+        return _swd(self, n_samples, n_projections, seed)
+
     # ---- visualisation, checkpoints -----------------------------------------------------------------------------------
     def sample_images(self, epoch=-100, num_images=36, save=True):
         return viz.made_sample_images(self, epoch, num_images, save, self.viz_dir)

@@ -238,6 +238,15 @@ def _mmd(trainer, n_samples, sigmas, seed):
     return metrics.mmd(samples, test, sigmas, unbiased=True)
 
 
+def _swd(trainer, n_samples, n_projections, seed):
+    """metrics.sliced_wasserstein of trainer.sample(n_samples, seed) against the test_iter images, directions under
+    `seed`."""
+    from . import metrics
+    samples = trainer.sample(n_samples, seed)
+    test = _dataset_rows(trainer.test_iter).to(samples.device, torch.float32).contiguous()
+    return metrics.sliced_wasserstein(samples, test, n_projections, seed)
+
+
 def _decode_rows(net, z, batch=1024):
     """net(z) in batches, after every launch already queued (the engines' last Adam step included: the parameters
     are views of their flat buffers) -- no autograd, no mode change, no RNG use."""
@@ -568,6 +577,11 @@ class GANTrainer:
         """Kernel maximum mean discrepancy (metrics.mmd) between sample(n_samples, seed) and the test images ->
         metrics.MMDResult; sigmas None: the GMMN paper's data-space bandwidths; the unbiased statistic."""
         return _mmd(self, n_samples, sigmas, seed)
+
+    def swd(self, n_samples=10000, n_projections=1024, seed=0):
+        """Sliced Wasserstein distance (metrics.sliced_wasserstein) between sample(n_samples, seed) and the test images
+        over n_projections random unit directions -> metrics.SWDResult."""
+        return _swd(self, n_samples, n_projections, seed)
 
     def _viz_epoch(self, epoch):
         if self.viz:
@@ -1039,6 +1053,11 @@ class VAETrainer:
         metrics.MMDResult; sigmas None: the GMMN paper's data-space bandwidths; the unbiased statistic."""
         return _mmd(self, n_samples, sigmas, seed)
 
+    def swd(self, n_samples=10000, n_projections=1024, seed=0):
+        """Sliced Wasserstein distance (metrics.sliced_wasserstein) between sample(n_samples, seed) and the test images
+        over n_projections random unit directions -> metrics.SWDResult."""
+        return _swd(self, n_samples, n_projections, seed)
+
     def log_likelihood(self, images=None, k=500, seed=0):
         """Importance-weighted estimate of log p(x) from k samples per image (iwae.log_likelihood; images=None: the
         whole test_iter) -> metrics.IWAEResult.  For models built of vae.py's Encoder and Decoder unchanged (VAE, DVAE,
@@ -1363,6 +1382,9 @@ class AutoencoderTrainer(VAETrainer):
 
     def mmd(self, n_samples=10000, sigmas=None, seed=0):
         raise GMError("an Autoencoder has no prior to sample: sample() / parzen() / mmd() need a VAE or a GAN")
+
+    def swd(self, n_samples=10000, n_projections=1024, seed=0):
+        raise GMError("an Autoencoder has no prior to sample: sample() / parzen() / mmd() / swd() need a VAE or a GAN")
 
     def compute_batch(self, batch):
         """ae.py:147-160 (general path: autograd over the fused linear kernels)."""

@@ -1737,6 +1737,39 @@ typedef struct gm_fm_stage_args {
 } gm_fm_stage_args;
 int gm_fm_stage(void* stream, const gm_fm_stage_args* a);
 
+/* ---- Sliced Wasserstein distance (csrc/gm_sw.hip; swg.py holds the contract).  For each of P unit
+ * directions theta_p the projections a = X theta_p [N] of the generated rows and b = Y theta_p [M] of the data rows are
+ * sorted ascending and matched by rank:
+ *   W_p = (1 / (N M)) sum_ij w_ij (a_(i) - b_(j))^2,   w_ij = max(0, min((i+1) M, (j+1) N) - max(i M, j N))
+ *   swd2 = (1 / P) sum_p W_p,   d swd2 / d a_i = (2 / (P N M)) sum_j w_ij (a_(i) - b_(j))
+ * Elements compare by (value, original row) lexicographically: the order is numpy's stable argsort and unique.  The
+ * sort is a data-oblivious compare-exchange network in LDS; padding up to a power of two compares above every real
+ * element and is never written out.  Differences are fp32, their squares and every sum fp64 in a fixed order; no
+ * atomics, one writer per element.  Outside the limits, with a NULL array, a leading dimension below the width, a short
+ * workspace or a misaligned fp64 pointer every entry point returns GM_EINVAL before any launch. */
+#define GM_SW_MAX_P 8192                       /* projections per call */
+#define GM_SW_MAX_B 2048                       /* rows per side with a gradient: (value, row) pairs, 32 KiB of LDS */
+#define GM_SW_MAX_ROWS 16384                   /* rows per side without one: values only, 128 KiB of LDS */
+#define GM_SWG_TAG_T 0x53574754u               /* "SWGT": the training prior */
+#define GM_SWG_TAG_V 0x53574756u               /* "SWGV": the validation prior */
+#define GM_SWG_TAG_S 0x53574753u               /* "SWGS": sample(n, seed) */
+#define GM_SWG_TAG_DT 0x53574454u              /* "SWDT": the training directions */
+#define GM_SWG_TAG_DV 0x53574456u              /* "SWDV": the validation directions */
+#define GM_SWG_TAG_DM 0x5357444Du              /* "SWDM": the metric's directions */
+/* Bytes of caller-owned device workspace of gm_sw_sort / gm_sw_finalize: 8 P, the column sums. */
+int64_t gm_sw_workspace_bytes(int P);
+/* Theta [P, I]: row p is the I normals of Philox blocks (q0 + (e >> 2), step, j0 + p, tag) of the noise block
+ * (gm_iwae_noise's layout with k_total = 1 and j0 the first row's position; Box-Muller pairs as everywhere), scaled to unit
+ * 2-norm; the norm is summed in fp64 in a fixed order, and a row whose norm is 0 is left at 0.  1 <= I <= GM_MMD_MAX_I. */
+int gm_sw_directions(void* stream, const gm_iwae_noise* n, float* Theta, int64_t ldt, int P, int I);
+/* Pr [P, >= N + M]: row p holds a_p in columns [0, N) and b_p in [N, N + M).  ws[p] = W_p N M.  Ct [P, >= N] (NULL: no
+ * gradient, values only) takes d swd2 / d a_i at Ct[p, i], the row's original position; nothing else of Ct is touched.
+ * With Ct 1 <= N, M <= GM_SW_MAX_B, without 1 <= N, M <= GM_SW_MAX_ROWS.  ws is the same, bit for bit, either way. */
+int gm_sw_sort(void* stream, const float* Pr, int64_t ldp, int P, int N, int M, float* Ct, int64_t ldc, void* ws,
+               int64_t ws_bytes);
+/* stats [2] (fp64, device): swd2 = sum_p ws[p] / (P N M) and sqrt(swd2).  loss_out (may be NULL): swd2 as a float. */
+int gm_sw_finalize(void* stream, int P, int N, int M, const void* ws, int64_t ws_bytes, double* stats, float* loss_out);
+
 /* ---- graph capture helpers (HIP graphs instead of a tracing compiler) ------------------ */
 int gm_graph_begin(void* stream);
 int gm_graph_end(void* stream, void** graph_exec_out);

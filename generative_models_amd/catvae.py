@@ -200,9 +200,8 @@ class CatVAETrainer(IWAETrainer):
                 and self.train_iter.batch_size == self.val_iter.batch_size)
 
     def _engine_class(self):
-        import functools
         from .engine import CatVAEEngine
-        return functools.partial(CatVAEEngine, trainer=self)
+        return CatVAEEngine
 
     def train(self, num_epochs, lr=1e-3, weight_decay=1e-5, tau0=1.0, tau_min=0.5, anneal_rate=3e-5, quiet=False):
         """vae.py's train loop on the relaxed (hard=True: straight-through) bound; batch t of the trainer's life runs at

@@ -54,7 +54,7 @@ from . import _lib, ops, philox, viz
 from ._lib import (DDPM_MAX_E, DDPM_MAX_I, DDPM_MAX_T, DDPM_MIN_E, DDPM_TAG_E, DDPM_TAG_S, DDPM_TAG_T, DDPM_TAG_V,
                    DDPM_TAG_VE, GMError)
 from .trainers import FlatAdam, OneLossTrainer, _lin, _stock_module, stock, stock_model, to_cuda  # noqa: F401
-from .engine import VAEEngine, _align4, _Linear
+from .engine import TimeRegressionEngine, _align4
 
 TAG_T, TAG_E, TAG_V, TAG_VE, TAG_S = DDPM_TAG_T, DDPM_TAG_E, DDPM_TAG_V, DDPM_TAG_VE, DDPM_TAG_S
 BETA_MAX = 0.999                 # cap of the scaled linear schedule (reached below T = 21 only)
@@ -212,7 +212,7 @@ def ddpm_fused_ok(model):
 
 
 # ---- engine ----------------------------------------------------------------------------------------------------------
-class DDPMEngine(VAEEngine):
+class DDPMEngine(TimeRegressionEngine):
     """The DDPM on the VAE engine's epoch machinery (index ring, multi-batch hipGraphs over a device counter).  Per
     training batch, 10 launches: 1. gm_gather_rows[_bits]_qsample (clean rows, [x_t | temb[t]], eps, t);  2.-4. the three
     forwards;  5. gm_ddpm_loss (dA, row partials);  6. dH2 = dA Wout [H2 > 0];  7. dH1 = dH2 Whid [H1 > 0];  8. the
@@ -223,78 +223,21 @@ class DDPMEngine(VAEEngine):
     into a graph), of a validation batch ctr (the batch's index in the pass).  No host noise ring, every batch its own
     gather.  One GPU only."""
 
-    has_eps = False
     one_gpu = "the DDPM engine"
-
-    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
-                 trainer=None):
-        self._refuse_dp(world_size, force_dp)
-        if not ddpm_fused_ok(model):
-            raise GMError("DDPMEngine: the model is not ddpm.DDPM with its Denoiser unchanged; DDPMTrainer trains "
-                          "such models on the general path")
-        d = model.denoiser
-        self._init_flat(model, device, use_graph,
-                        [d.linear.weight, d.linear.bias, d.hidden.weight, d.hidden.bias, d.out.weight, d.out.bias])
-        self._bind_trainer(trainer)                  # seed and noise_steps are read from it
-        self.L1, self.L2, self.L3 = _Linear(self.fp, d.linear), _Linear(self.fp, d.hidden), _Linear(self.fp, d.out)
-        self.I, self.E, self.T, self.H = model.image_size, model.time_dim, model.T, d.linear.weight.shape[0]
-
-    def _alloc(self, B):
-        if self._bufB == B:
-            return
-        I, E, H = self.I, self.E, self.H
-        z = lambda *s: torch.zeros(*s, device=self.device)
-        self.X, self.Xin_full, self.Eps = z(B, I), z(B, _align4(I + E)), z(B, I)
-        self.Xin = self.Xin_full[:, :I + E]          # the first layer's operand: K = I + E, rows _align4(I + E) apart
-        self.tq = torch.zeros(B, dtype=torch.int32, device=self.device)
-        self.H1, self.H2, self.Out = z(B, H), z(B, H), z(B, I)
-        self.dA, self.dH2, self.dH1 = z(B, I), z(B, H), z(B, H)
-        self.part = z(B)
-        self._bufB = B
-        self.graphs = {}
+    fused_ok = staticmethod(ddpm_fused_ok)
+    refusal = ("DDPM", "ddpm.DDPM", "Denoiser")  # the trainer: seed and noise_steps
+    net, tables = "denoiser", ("sa", "s1", "temb")
+    table_builder, noise_builder = "ddpm_tables", "ddpm_noise"
+    target, steps = "Eps", "tq"
 
     def _settings(self):
         m = self.model
         return {"T": int(m.T), "time_dim": int(m.time_dim), "seed": int(self.trainer.seed)}
 
-    def _graph_args(self):
-        m = self.model
-        return tuple(t.data_ptr() for t in (m.sa, m.s1, m.temb))     # the tables are launch arguments of the graphs
-
-    def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
-        super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
+    def _gather_sample(self, st, b, noise, idx_slot):
         from . import ops_fused as of_
-        m = self.model
-        self.tab = of_.ddpm_tables(m.sa, m.s1, m.temb)
-
-    def _noise(self, t, train):
-        from . import ops_fused as of_
-        return of_.ddpm_noise(self.trainer.seed, train, **self._clock(t, train))
-
-    def _issue(self, st, t, b, train, pos=0, of=1):
-        """One batch of size b: q-sample, forward, L_simple (+ backward + Adam when train)."""
-        from . import ops_fused as of_
-        L1, L2, L3 = self.L1, self.L2, self.L3
-        idx_slot = self._slot(t, 1, 0, self.R, self.B)
-        loss_slot = self._slot(t, 1, 0, 0, 1)
-        of_.gather_rows_qsample(self.data, self.idx_ring.view(-1), self.X, self.Xin_full, self.Eps, self.tq,
-                                self._noise(t, train), self.tab, B=b, idx_slot=idx_slot, stream=st)
-        ops.linear_fwd(self.Xin, L1.W, L1.b, self.H1, "relu", M=b, stream=st)
-        ops.linear_fwd(self.H1, L2.W, L2.b, self.H2, "relu", M=b, stream=st)
-        ops.linear_fwd(self.H2, L3.W, L3.b, self.Out, "id", M=b, stream=st)
-        scale = float(np.float32(1.0 / (b * self.I)))
-        of_.ddpm_loss(self.Out, self.Eps, self.part, b, scale, dA=self.dA if train else None, stream=st)
-        if train:
-            adam = dict(sched=self.sched, sched_slot=self._slot(t, 1, 0, 0, 1))
-            # every dX reads a layer's weights BEFORE that layer's dW(+Adam) launch updates them
-            ops.linear_bwd_dx(self.dA, L3.W, self.dH2, below=self.H2, epi="relu", M=b, stream=st)
-            ops.linear_bwd_dx(self.dH2, L2.W, self.dH1, below=self.H1, epi="relu", M=b, stream=st)
-            ops.linear_bwd_dw_adam_pair(dict(dA=self.dA, X=self.H2, lin=L3, adam=adam, M=b),
-                                        dict(dA=self.dH2, X=self.H1, lin=L2, adam=adam, M=b),
-                                        weight_decay=self.wd, stream=st)
-            ops.linear_bwd_dw_adam(self.dH1, self.Xin, L1, adam, M=b, weight_decay=self.wd, stream=st)
-        of_.sum_finalize(self.part, b, self.recon if train else self.vrecon, scale=scale, out_slot=loss_slot,
-                         tick=self.ctr if self.use_graph else None, stream=st)
+        of_.gather_rows_qsample(self.data, self.idx_ring.view(-1), self.X, self.Xin_full, self.Eps, self.tq, noise,
+                                self.tab, B=b, idx_slot=idx_slot, stream=st)
 
 
 # ---- trainer ---------------------------------------------------------------------------------------------------------
@@ -306,6 +249,7 @@ class DDPMTrainer(OneLossTrainer):
     taken, so a resumed run continues the noise stream bit for bit).  One GPU only."""
     _line = "Epoch[%d/%d], Loss: %.6f, Val Loss: %.6f"
     _one_gpu = "DDPMTrainer"
+    _engine_reads_trainer = True
     _error = DDPMError
     _fused_ok = staticmethod(ddpm_fused_ok)
 
@@ -333,8 +277,7 @@ class DDPMTrainer(OneLossTrainer):
         return torch.sum((eps - out) ** 2) / (x.shape[0] * x.shape[1])
 
     def _engine_class(self):
-        import functools
-        return functools.partial(DDPMEngine, trainer=self)
+        return DDPMEngine
 
     def train(self, num_epochs, lr=2e-4, weight_decay=0.0, quiet=False):
         """VAETrainer.train with this model's defaults."""

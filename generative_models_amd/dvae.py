@@ -120,6 +120,7 @@ class DVAETrainer(VAETrainer):
     training batches taken, so a resumed run continues the noise stream).  One GPU only."""
 
     _one_gpu = "DVAETrainer"
+    _engine_reads_trainer = True
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, noise="salt_pepper", level=0.25, seed=0):
         self.noise, self.level, self.seed = check_noise(noise, level, seed)     # before anything runs
@@ -139,9 +140,8 @@ class DVAETrainer(VAETrainer):
         return recon_loss, self.kl_divergence(mu, log_var)
 
     def _engine_class(self):
-        import functools
         from .engine import DVAEEngine
-        return functools.partial(DVAEEngine, trainer=self)
+        return DVAEEngine
 
     def denoise(self, images, batch=1024):
         """(noisy, recon): noisy = the corruption of `images` as training batch step 0 sees it (corrupt(images, ...,

@@ -20,8 +20,8 @@ step, D gradients during the G step); every observable -- parameters, loss lists
 position -- matches the reference.
 
 This module: the shared pieces (FlatParams, host RNG replay) and the GAN engine's CORE; what a GAN iteration launches is
-gan_steps.py (mix-ins), BEGAN's overrides began_engine.py, the VAE / AE / BIR-VAE engines vae_engine.py (all re-exported
-here)."""
+gan_steps.py (mix-ins), BEGAN's overrides began_engine.py, the VAE / AE / BIR-VAE engines vae_engine.py, the one-network
+engines' bases onenet_engine.py (all re-exported here)."""
 import numpy as np
 import torch
 
@@ -1634,3 +1634,4 @@ class GANEngine(CriticStep, InfoQStep, GeneratorStep, PenaltySteps):
 # the engines built on this module's pieces (imported last: they import FlatParams / GANEngine ... from here)
 from .vae_engine import AAEEngine, AEEngine, BIRVAEEngine, CatVAEEngine, CVAEEngine, DVAEEngine, IAFVAEEngine, IWAEEngine, NFVAEEngine, TCVAEEngine, VAEEngine, VQVAEEngine, validate_labels  # noqa: E402,F401,E501
 from .began_engine import BEGANEngine                          # noqa: E402,F401
+from .onenet_engine import GeneratorMatchEngine, OneNetEngine, TimeRegressionEngine  # noqa: E402,F401

@@ -68,7 +68,7 @@ from . import _lib, ops, philox, realnvp
 from ._lib import (DDPM_MAX_E, DDPM_MAX_I, DDPM_MAX_T, DDPM_MIN_E, FM_MAX_H, FM_TAG_D, FM_TAG_N, FM_TAG_T, FM_TAG_VD,
                    FM_TAG_VN, FM_TAG_VT, GMError)
 from .trainers import FlatAdam, _dataset_rows, _lin, _stock_module, stock, stock_model  # noqa: F401
-from .engine import VAEEngine, _align4, _Linear
+from .engine import TimeRegressionEngine, _align4
 from .realnvp import nll_constant, nll_rows, postprocess, preprocess  # noqa: F401
 
 TAG_D, TAG_T, TAG_N, TAG_VD, TAG_VT, TAG_VN = FM_TAG_D, FM_TAG_T, FM_TAG_N, FM_TAG_VD, FM_TAG_VT, FM_TAG_VN
@@ -253,7 +253,7 @@ def flowmatch_fused_ok(model):
 
 
 # ---- engine ----------------------------------------------------------------------------------------------------------
-class FlowMatchEngine(VAEEngine):
+class FlowMatchEngine(TimeRegressionEngine):
     """Flow matching on the VAE engine's epoch machinery (index ring, multi-batch hipGraphs over a device counter), the
     DDPM engine's launch shape.  Per training batch, 10 launches: 1. gm_gather_rows[_bits]_fm_qsample (clean rows,
     [y_t | temb[j]], u, logdet_pre, j);  2.-4. the three forwards;  5. gm_ddpm_loss with eps := u (dA, row partials);
@@ -264,80 +264,23 @@ class FlowMatchEngine(VAEEngine):
     training batches, so the step is never baked into a graph), of a validation batch ctr (the batch's index in the
     pass).  One GPU only."""
 
-    has_eps = False
     one_gpu = "the flow-matching engine"
-
-    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
-                 trainer=None):
-        self._refuse_dp(world_size, force_dp)
-        if not flowmatch_fused_ok(model):
-            raise GMError("FlowMatchEngine: the model is not flowmatch.FlowMatching with its VelocityField unchanged; "
-                          "FlowMatchTrainer trains such models on the general path")
-        f = model.field
-        self._init_flat(model, device, use_graph,
-                        [f.linear.weight, f.linear.bias, f.hidden.weight, f.hidden.bias, f.out.weight, f.out.bias])
-        self._bind_trainer(trainer)                  # seed, alpha, levels and noise_steps are read from it
-        self.L1, self.L2, self.L3 = _Linear(self.fp, f.linear), _Linear(self.fp, f.hidden), _Linear(self.fp, f.out)
-        self.I, self.E, self.T, self.H = model.image_size, model.time_dim, model.T, model.hidden_dim
-
-    def _alloc(self, B):
-        if self._bufB == B:
-            return
-        I, E, H = self.I, self.E, self.H
-        z = lambda *s: torch.zeros(*s, device=self.device)
-        self.X, self.Xin_full, self.U = z(B, I), z(B, _align4(I + E)), z(B, I)
-        self.Xin = self.Xin_full[:, :I + E]          # the first layer's operand: K = I + E, rows _align4(I + E) apart
-        self.jq = torch.zeros(B, dtype=torch.int32, device=self.device)
-        self.H1, self.H2, self.Out = z(B, H), z(B, H), z(B, I)
-        self.dA, self.dH2, self.dH1 = z(B, I), z(B, H), z(B, H)
-        self.logdet, self.part = z(B), z(B)
-        self._bufB = B
-        self.graphs = {}
+    fused_ok = staticmethod(flowmatch_fused_ok)
+    refusal = ("FlowMatch", "flowmatch.FlowMatching", "VelocityField")   # the trainer: seed, alpha, levels, noise_steps
+    net, tables = "field", ("tt", "tc", "temb")
+    table_builder, noise_builder = "fm_tables", "fm_noise"
+    target, steps, rows = "U", "jq", ("logdet",)
 
     def _settings(self):
         m, tr = self.model, self.trainer
         return {"T": int(m.T), "time_dim": int(m.time_dim), "alpha": float(tr.alpha), "levels": int(tr.levels),
                 "seed": int(tr.seed)}
 
-    def _graph_args(self):
-        m = self.model
-        return tuple(t.data_ptr() for t in (m.tt, m.tc, m.temb))     # the tables are launch arguments of the graphs
-
-    def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
-        super().configure(B, n_train_steps, lr, weight_decay, resume=resume)
+    def _gather_sample(self, st, b, noise, idx_slot):
         from . import ops_fused as of_
-        m = self.model
-        self.tab = of_.fm_tables(m.tt, m.tc, m.temb)
-
-    def _noise(self, t, train):
-        from . import ops_fused as of_
-        return of_.fm_noise(self.trainer.seed, train, **self._clock(t, train))
-
-    def _issue(self, st, t, b, train, pos=0, of=1):
-        """One batch of size b: the path sample, forward, the regression loss (+ backward + Adam when train)."""
-        from . import ops_fused as of_
-        L1, L2, L3, tr = self.L1, self.L2, self.L3, self.trainer
-        idx_slot = self._slot(t, 1, 0, self.R, self.B)
-        loss_slot = self._slot(t, 1, 0, 0, 1)
+        tr = self.trainer
         of_.gather_rows_fm_qsample(self.data, self.idx_ring.view(-1), self.X, self.Xin_full, self.U, self.logdet,
-                                   self.jq, self._noise(t, train), self.tab, tr.alpha, tr.levels, B=b,
-                                   idx_slot=idx_slot, stream=st)
-        ops.linear_fwd(self.Xin, L1.W, L1.b, self.H1, "relu", M=b, stream=st)
-        ops.linear_fwd(self.H1, L2.W, L2.b, self.H2, "relu", M=b, stream=st)
-        ops.linear_fwd(self.H2, L3.W, L3.b, self.Out, "id", M=b, stream=st)
-        scale = float(np.float32(1.0 / (b * self.I)))
-        of_.ddpm_loss(self.Out, self.U, self.part, b, scale, dA=self.dA if train else None, stream=st)
-        if train:
-            adam = dict(sched=self.sched, sched_slot=self._slot(t, 1, 0, 0, 1))
-            # every dX reads a layer's weights BEFORE that layer's dW(+Adam) launch updates them
-            ops.linear_bwd_dx(self.dA, L3.W, self.dH2, below=self.H2, epi="relu", M=b, stream=st)
-            ops.linear_bwd_dx(self.dH2, L2.W, self.dH1, below=self.H1, epi="relu", M=b, stream=st)
-            ops.linear_bwd_dw_adam_pair(dict(dA=self.dA, X=self.H2, lin=L3, adam=adam, M=b),
-                                        dict(dA=self.dH2, X=self.H1, lin=L2, adam=adam, M=b),
-                                        weight_decay=self.wd, stream=st)
-            ops.linear_bwd_dw_adam(self.dH1, self.Xin, L1, adam, M=b, weight_decay=self.wd, stream=st)
-        of_.sum_finalize(self.part, b, self.recon if train else self.vrecon, scale=scale, out_slot=loss_slot,
-                         tick=self.ctr if self.use_graph else None, stream=st)
+                                   self.jq, noise, self.tab, tr.alpha, tr.levels, B=b, idx_slot=idx_slot, stream=st)
 
 
 # ---- trainer ---------------------------------------------------------------------------------------------------------
@@ -394,8 +337,7 @@ class FlowMatchTrainer(realnvp.DequantFlowTrainer):
         return torch.sum((u - out) ** 2) / (x.shape[0] * x.shape[1])
 
     def _engine_class(self):
-        import functools
-        return functools.partial(FlowMatchEngine, trainer=self)
+        return FlowMatchEngine
 
     def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
         """VAETrainer.train with this model's defaults."""

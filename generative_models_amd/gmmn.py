@@ -47,7 +47,7 @@ import torch.nn as nn
 from . import _lib, ops, philox, viz
 from ._lib import GMMN_MAX_B, GMMN_MAX_Z, GMMN_TAG_S, GMMN_TAG_T, GMMN_TAG_V, MMD_MAX_I, MMD_MAX_SIGMAS, GMError
 from .trainers import FlatAdam, Generator, OneLossTrainer, _stock_module, stock, stock_model  # noqa: F401
-from .engine import VAEEngine, _align4, _Linear
+from .engine import GeneratorMatchEngine, _align4
 
 TAG_T, TAG_V, TAG_S = GMMN_TAG_T, GMMN_TAG_V, GMMN_TAG_S
 SIGMAS = (2.0, 5.0, 10.0, 20.0, 40.0, 80.0)      # the paper's data-space bandwidths (= metrics.MMD_SIGMAS)
@@ -77,15 +77,21 @@ def check_sigmas(sigmas):
     return tuple(float(s) for s in of_.mmd_sigmas(sigmas, None, "GMMN", GMMNError))
 
 
-def check_shape(image_size, hidden_dim, z_dim):
-    I, H, Z = _int(image_size, "image_size"), _int(hidden_dim, "hidden_dim"), _int(z_dim, "z_dim")
+def generator_shape(image_size, hidden_dim, z_dim, error):
+    """(I, H, Z) of a generator-matching model validated against the kernels' limits; else `error`."""
+    I, H, Z = (_lib.check_int(v, n, error) for v, n in ((image_size, "image_size"), (hidden_dim, "hidden_dim"),
+                                                        (z_dim, "z_dim")))
     if not 1 <= I <= MMD_MAX_I:
-        raise GMMNError("image_size must lie in [1, %d], got %d" % (MMD_MAX_I, I))
+        raise error("image_size must lie in [1, %d], got %d" % (MMD_MAX_I, I))
     if H < 1:
-        raise GMMNError("hidden_dim must be >= 1, got %d" % H)
+        raise error("hidden_dim must be >= 1, got %d" % H)
     if not 1 <= Z <= GMMN_MAX_Z:
-        raise GMMNError("z_dim must lie in [1, %d], got %d" % (GMMN_MAX_Z, Z))
+        raise error("z_dim must lie in [1, %d], got %d" % (GMMN_MAX_Z, Z))
     return I, H, Z
+
+
+def check_shape(image_size, hidden_dim, z_dim):
+    return generator_shape(image_size, hidden_dim, z_dim, GMMNError)
 
 
 def check_batch(b):
@@ -103,13 +109,14 @@ def uniforms_reference(n_rows, Z, seed, step, tag=TAG_T, row0=0):
 
 
 # ---- modules ---------------------------------------------------------------------------------------------------------
-@stock_model
-class GMMN(nn.Module):
-    """One Generator: z in (-1, 1)^Z -> relu -> sigmoid -> I pixels."""
+class GeneratorModel(nn.Module):
+    """One Generator: z in (-1, 1)^Z -> relu -> sigmoid -> I pixels.  GMMN below and swg.SWG are this model, each under its
+    own name, stock mark and error class."""
+    _error = GMError
 
     def __init__(self, image_size=784, hidden_dim=400, z_dim=20):
         super().__init__()
-        self.image_size, self.hidden_dim, self.z_dim = check_shape(image_size, hidden_dim, z_dim)
+        self.image_size, self.hidden_dim, self.z_dim = generator_shape(image_size, hidden_dim, z_dim, self._error)
         self.G = Generator(self.image_size, self.hidden_dim, self.z_dim)
         self.shape = int(self.image_size ** 0.5)
 
@@ -117,8 +124,15 @@ class GMMN(nn.Module):
         return self.G(z)
 
 
-def gmmn_fused_ok(model):
-    """True iff the model is GMMN itself with its Generator unchanged and consistent shapes."""
+@stock_model
+class GMMN(GeneratorModel):
+    """One Generator: z in (-1, 1)^Z -> relu -> sigmoid -> I pixels."""
+    _error = GMMNError
+
+
+def generator_fused_ok(model):
+    """True iff the model is a shipped generator-matching model itself (GMMN, swg.SWG) with its Generator unchanged and
+    consistent shapes."""
     g = getattr(model, "G", None)
     if not (type(model).__dict__.get("_gm_stock_model", False) and type(g) is Generator and _stock_module(g, 2)):
         return False
@@ -128,36 +142,28 @@ def gmmn_fused_ok(model):
             and 1 <= Z <= GMMN_MAX_Z)
 
 
+gmmn_fused_ok = generator_fused_ok
+
+
 # ---- engine ----------------------------------------------------------------------------------------------------------
-class GMMNEngine(VAEEngine):
+class GMMNEngine(GeneratorMatchEngine):
     """The GMMN on the VAE engine's epoch machinery (index ring, multi-batch hipGraphs over a device counter).  Per
     training batch, 12 launches: 1. gm_gather_rows[_bits] (Y, the lower half of R);  2. gm_gmmn_prior (z);  3.-4. the two
     generator forwards (X, the upper half of R);  5.-6. gm_mmd_pairs (row norms, then every tile: block sums, C, the
     shares of r; the norms launch also leaves the centred rows R - mu, mu = x_1);  7. gm_mmd_finalize (mmd2, loss,
     1 / (2 loss), r);  8. P = C (R - mu) through ops.linear_bwd_dx (reduction length 2b, output width I);
     9. gm_mmd_grad (dA);  10. dH = dA Wgen [H > 0];  11. the two weight gradients + Adam as a pair;  12. the loss record
-    with the counter tick.  Every input gradient is issued before the launch that steps the weights it reads.  A validation batch is launches 1-7 without C and r, and the record.  The noise step of a
-    training batch is ctr + nbase (DDPMEngine's scheme), of a validation batch ctr.  One GPU only."""
+    with the counter tick.  Every input gradient is issued before the launch that steps the weights it reads.  A
+    validation batch is launches 1-7 without C and r, and the record.  The noise step of a training batch is ctr + nbase
+    (DDPMEngine's scheme), of a validation batch ctr.  One GPU only."""
 
-    has_eps = False
     one_gpu = "the GMMN engine"
+    fused_ok = staticmethod(gmmn_fused_ok)
+    refusal = ("GMMN", "gmmn.GMMN", "Generator")     # the trainer: seed, sigmas, sqrt_loss and noise_steps
+    noise_builder, tags = "gmmn_noise", (TAG_T, TAG_V)
+    sig = None
 
-    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
-                 trainer=None):
-        self._refuse_dp(world_size, force_dp)
-        if not gmmn_fused_ok(model):
-            raise GMError("GMMNEngine: the model is not gmmn.GMMN with its Generator unchanged; GMMNTrainer trains "
-                          "such models on the general path")
-        g = model.G
-        self._init_flat(model, device, use_graph, [g.linear.weight, g.linear.bias, g.generate.weight, g.generate.bias])
-        self._bind_trainer(trainer)                  # seed, sigmas, sqrt_loss and noise_steps are read from it
-        self.L1, self.L2 = _Linear(self.fp, g.linear), _Linear(self.fp, g.generate)
-        self.I, self.H, self.Z = model.image_size, model.hidden_dim, model.z_dim
-        self.sig = None
-
-    def _alloc(self, B):
-        if self._bufB == B:
-            return
+    def _buffers(self, B):
         from . import ops_fused as of_
         check_batch(B)
         I, H, Z = self.I, self.H, self.Z
@@ -170,8 +176,6 @@ class GMMNEngine(VAEEngine):
         self.r, self.lossf = z(B), z(1)
         self.stats = torch.zeros(10, dtype=torch.float64, device=self.device)
         self.ws = of_.mmd_workspace(B, B, True, self.device)
-        self._bufB = B
-        self.graphs = {}
 
     def _settings(self):
         t = self.trainer
@@ -191,34 +195,85 @@ class GMMNEngine(VAEEngine):
     def _issue(self, st, t, b, train, pos=0, of=1):
         """One batch of size b: Y, z, X, the statistic (+ its gradient, the backward and Adam when train)."""
         from . import ops_fused as of_
-        L1, L2, tr = self.L1, self.L2, self.trainer
-        idx_slot = self._slot(t, 1, 0, self.R, self.B)
-        loss_slot = self._slot(t, 1, 0, 0, 1)
-        X, Y = self.Rb[:b], self.Rb[b:2 * b]
-        ops.gather_rows(self.data, self.idx_ring.view(-1), Y, B=b, idx_slot=idx_slot, stream=st)
-        of_.gmmn_prior(self.Zb, of_.gmmn_noise(tr.seed, TAG_T if train else TAG_V, **self._clock(t, train)), B=b,
-                       Z=self.Z, stream=st)
-        ops.linear_fwd(self.Zb, L1.W, L1.b, self.Hg, "relu", M=b, stream=st)
-        ops.linear_fwd(self.Hg, L2.W, L2.b, X, "sigmoid", M=b, stream=st)
+        X, Y = self._forward(st, t, b, train)
         of_.mmd_pairs(X, Y, self.sig, self.ws, C=self.C if train else None, Rc=self.Rc, N=b, M=b, stream=st)
-        of_.mmd_finalize(b, b, self.sig.numel(), tr.sqrt_loss, self.ws, self.stats, r=self.r if train else None,
-                         loss_out=self.lossf, stream=st)
+        of_.mmd_finalize(b, b, self.sig.numel(), self.trainer.sqrt_loss, self.ws, self.stats,
+                         r=self.r if train else None, loss_out=self.lossf, stream=st)
         if train:
-            adam = dict(sched=self.sched, sched_slot=self._slot(t, 1, 0, 0, 1))
             ops.linear_bwd_dx(self.C[:b, :2 * b], self.Rc[:2 * b], self.P, M=b, stream=st)
             of_.mmd_grad(X, self.P, self.r, self.stats, self.dA, N=b, sigmoid=True, mu=X[:1], stream=st)
-            # dH reads the output layer's weights BEFORE the pair's Adam updates them
-            ops.linear_bwd_dx(self.dA, L2.W, self.dH, below=self.Hg, epi="relu", M=b, stream=st)
-            ops.linear_bwd_dw_adam_pair(dict(dA=self.dA, X=self.Hg, lin=L2, adam=adam, M=b),
-                                        dict(dA=self.dH, X=self.Zb, lin=L1, adam=adam, M=b),
-                                        weight_decay=self.wd, stream=st)
-        of_.sum_finalize(self.lossf, 1, self.recon if train else self.vrecon, out_slot=loss_slot,
-                         tick=self.ctr if self.use_graph else None, stream=st)
+        self._tail(st, t, b, train)
 
 
-# ---- trainer ---------------------------------------------------------------------------------------------------------
+# ---- trainers --------------------------------------------------------------------------------------------------------
 @stock
-class GMMNTrainer(OneLossTrainer):
+class GeneratorMatchTrainer(OneLossTrainer):
+    """What the trainers of the two generator-matching models share (GMMN here, SWG in swg.py): the prior under the
+    contract's Philox noise, the sampler, the constructor's batch-size check and step counters, and the refusals of a
+    likelihood and a reconstruction.  A subclass names its engine, _error, _check_batch, the ops_fused builder of its
+    noise, its sampling tag and the two refusals' words, and supplies compute_batch and viz_loss."""
+    _engine_reads_trainer = True
+    _engine_type = None         # the engine class
+    _check_batch = None         # staticmethod(<module>.check_batch)
+    _noise_builder = _tag_sample = None
+    _no_likelihood = _no_encoder = None
+
+    def __init__(self, model, train_iter, val_iter, test_iter, viz=False):
+        if getattr(train_iter, "batch_size", None) is not None:
+            self._check_batch(train_iter.batch_size)
+        super().__init__(model, train_iter, val_iter, test_iter, viz=viz)
+        self.noise_steps = 0                         # training batches taken: the next one's noise step
+        self._eval_step = 0                          # batch index within an evaluate() call
+
+    def _noise(self, seed, tag, step, row0=0):
+        from . import ops_fused as of_
+        return getattr(of_, self._noise_builder)(self.seed if seed is None else seed, tag, step=step, row0=row0)
+
+    def prior(self, n, step, tag, seed=None, row0=0):
+        """The prior rows [n, Z] of (seed, step, tag) on the model's device (gm_gmmn_prior)."""
+        from . import ops_fused as of_
+        z = torch.empty(n, self.model.z_dim, device=self._device())
+        return of_.gmmn_prior(z, self._noise(seed, tag, step, row0))
+
+    def _engine_class(self):
+        return self._engine_type
+
+    def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
+        """VAETrainer.train with these models' defaults."""
+        return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
+
+    # ---- sampling ---------------------------------------------------------------------------------------------------
+    SAMPLE_BLOCK = 1024          # sample() runs the generator on whole blocks of this many rows
+
+    def sample(self, n, seed=0):
+        """n samples [n, I] in [0, 1]: row r is the generator on the prior row r of (seed, the sampling tag, step 0),
+        whatever n -- the generator always runs on whole blocks of SAMPLE_BLOCK rows (the last one is cut after the fact),
+        so a row's launches, and its bits, do not depend on n.  Runs after a device synchronise; the global generator,
+        the model's mode and the parameters are untouched."""
+        n, seed = _lib.check_int(n, "n", self._error), _lib.check_seed(seed, error=self._error)
+        if n < 1:
+            raise self._error("n must be >= 1, got %d" % n)
+        self._device()
+        torch.cuda.synchronize()                     # after the engine's last Adam step
+        out = []
+        with torch.no_grad():
+            for lo in range(0, n, self.SAMPLE_BLOCK):
+                out.append(self.model(self.prior(self.SAMPLE_BLOCK, 0, self._tag_sample, seed=seed, row0=lo)))
+        return torch.cat(out)[:n].contiguous()
+
+    # ---- visualisation ----------------------------------------------------------------------------------------------
+    def sample_images(self, epoch=-100, num_images=36, save=True):
+        return viz.made_sample_images(self, epoch, num_images, save, self.viz_dir)
+
+    def log_likelihood(self, images=None, k=500, seed=0):
+        raise GMError(self._no_likelihood)
+
+    def reconstruct_images(self, images, epoch, save=True):
+        raise GMError(self._no_encoder)
+
+
+@stock
+class GMMNTrainer(GeneratorMatchTrainer):
     """Trains a GMMN on the kernel MMD and samples from it.  Histories: `losses` (one per training batch); the epoch line
     (mean training loss, validation loss); best_val_loss / best_model as the other one-loss trainers; checkpoints
     (+ sigmas, sqrt_loss, seed in the optimizer state's config, checked under strict=True, and the number of training
@@ -227,6 +282,11 @@ class GMMNTrainer(OneLossTrainer):
     _one_gpu = "GMMNTrainer"
     _error = GMMNError
     _fused_ok = staticmethod(gmmn_fused_ok)
+    _engine_type = GMMNEngine
+    _check_batch = staticmethod(check_batch)
+    _noise_builder, _tag_sample = "gmmn_noise", TAG_S
+    _no_likelihood = "a GMMN has no likelihood and no encoder; parzen() and mmd() score its samples"
+    _no_encoder = "a GMMN has no encoder"
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, sigmas=None, sqrt_loss=True, seed=0):
         self.seed = check_seed(seed)                 # before anything runs
@@ -234,17 +294,7 @@ class GMMNTrainer(OneLossTrainer):
         if isinstance(sqrt_loss, (bool, np.bool_)) is False:
             raise GMMNError("sqrt_loss must be a bool, got %r" % (sqrt_loss,))
         self.sqrt_loss = bool(sqrt_loss)
-        if getattr(train_iter, "batch_size", None) is not None:
-            check_batch(train_iter.batch_size)
         super().__init__(model, train_iter, val_iter, test_iter, viz=viz)
-        self.noise_steps = 0                         # training batches taken: the next one's noise step
-        self._eval_step = 0                          # batch index within an evaluate() call
-
-    def prior(self, n, step, tag, seed=None, row0=0):
-        """The prior rows [n, Z] of (seed, step, tag) on the model's device (gm_gmmn_prior)."""
-        from . import ops_fused as of_
-        z = torch.empty(n, self.model.z_dim, device=self._device())
-        return of_.gmmn_prior(z, of_.gmmn_noise(self.seed if seed is None else seed, tag, step=step, row0=row0))
 
     def compute_batch(self, batch):
         """The MMD loss of a batch against as many samples (general path: autograd over the fused linear kernels and
@@ -255,43 +305,6 @@ class GMMNTrainer(OneLossTrainer):
         train, step = self._noise_step()
         z = self.prior(check_batch(x.shape[0]), step, TAG_T if train else TAG_V)
         return of_.mmd_loss(self.model(z), x, self.sigmas, self.sqrt_loss)
-
-    def _engine_class(self):
-        import functools
-        return functools.partial(GMMNEngine, trainer=self)
-
-    def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
-        """VAETrainer.train with this model's defaults."""
-        return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
-
-    # ---- sampling ---------------------------------------------------------------------------------------------------
-    SAMPLE_BLOCK = 1024          # sample() runs the generator on whole blocks of this many rows
-
-    def sample(self, n, seed=0):
-        """n samples [n, I] in [0, 1]: row r is the generator on the prior row r of (seed, TAG_S, step 0), whatever n --
-        the generator always runs on whole blocks of SAMPLE_BLOCK rows (the last one is cut after the fact), so a row's
-        launches, and its bits, do not depend on n.  Runs after a device synchronise; the global generator, the model's
-        mode and the parameters are untouched."""
-        n, seed = _int(n, "n"), check_seed(seed)
-        if n < 1:
-            raise GMMNError("n must be >= 1, got %d" % n)
-        self._device()
-        torch.cuda.synchronize()                     # after the engine's last Adam step
-        out = []
-        with torch.no_grad():
-            for lo in range(0, n, self.SAMPLE_BLOCK):
-                out.append(self.model(self.prior(self.SAMPLE_BLOCK, 0, TAG_S, seed=seed, row0=lo)))
-        return torch.cat(out)[:n].contiguous()
-
-    # ---- visualisation ----------------------------------------------------------------------------------------------
-    def sample_images(self, epoch=-100, num_images=36, save=True):
-        return viz.made_sample_images(self, epoch, num_images, save, self.viz_dir)
-
-    def log_likelihood(self, images=None, k=500, seed=0):
-        raise GMError("a GMMN has no likelihood and no encoder; parzen() and mmd() score its samples")
-
-    def reconstruct_images(self, images, epoch, save=True):
-        raise GMError("a GMMN has no encoder")
 
     def viz_loss(self):
         viz.one_loss_curve(self, "MMD loss")

@@ -270,9 +270,8 @@ class IAFVAETrainer(IWAETrainer):
                 and self.train_iter.batch_size == self.val_iter.batch_size)
 
     def _engine_class(self):
-        import functools
         from .engine import IAFVAEEngine
-        return functools.partial(IAFVAEEngine, trainer=self)
+        return IAFVAEEngine
 
     def compute_batch(self, batch):
         """(sum_b -L_k, mean ess) of a batch (general path: autograd over the fused linear kernels and iaf_chain, eps from

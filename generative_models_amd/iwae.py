@@ -191,6 +191,7 @@ class IWAETrainer(VAETrainer):
     _batch = "loss+stat"
     _line = "Epoch[%d/%d], Loss: %.4f, ESS: %.4f, Val Loss: %.4f"
     _one_gpu = "IWAETrainer"
+    _engine_reads_trainer = True
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, k=5, seed=0):
         self.k, self.seed = check_k_seed(k, seed)              # before anything runs
@@ -236,9 +237,8 @@ class IWAETrainer(VAETrainer):
         return FlatAdam(self.model.parameters(), lr, weight_decay=weight_decay)
 
     def _engine_class(self):
-        import functools
         from .engine import IWAEEngine
-        return functools.partial(IWAEEngine, trainer=self)
+        return IWAEEngine
 
     def viz_loss(self):
         """The training loss (sum_b -L_k per batch) over the epochs."""

@@ -40,7 +40,7 @@ import torch.nn as nn
 from . import _lib, ops, philox, viz
 from ._lib import MADE_MAX_H, MADE_MAX_I, MADE_MIN_I, MADE_TAG_S, GMError
 from .trainers import FlatAdam, OneLossTrainer, _dataset_rows, _stock_module, stock, stock_model  # noqa: F401
-from .engine import VAEEngine, _Linear
+from .engine import OneNetEngine, _Linear
 
 TAG_MS = MADE_TAG_S
 ORDERS = ("natural", "random")
@@ -182,7 +182,7 @@ def nll_rows(logits, x):
 
 
 # ---- engine ----------------------------------------------------------------------------------------------------------
-class MADEEngine(VAEEngine):
+class MADEEngine(OneNetEngine):
     """MADE on the VAE engine's epoch machinery (index ring, multi-batch hipGraphs over a device counter).  Per training
     batch, 8 launches: 1. gm_gather_rows[_bits];  2. H1 = relu(linear(X));  3. A = out(H1);  4. gm_made_bce (dA, row
     partials);  5. dH = dA Wout [H1 > 0], before the launch that steps Wout;  6. both weight gradients + Adam as a pair;
@@ -192,27 +192,22 @@ class MADEEngine(VAEEngine):
     launch arguments: the graphs are dropped when the model's buffers move.  No eps ring, every batch its own gather.
     One GPU only."""
 
-    has_eps = False
     one_gpu = "the MADE engine"
+    fused_ok = staticmethod(made_fused_ok)
+    refusal = ("MADE", "made.MADE", "layers")
+    binds_trainer = False       # no noise: nothing to read from the trainer
 
-    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False):
-        self._refuse_dp(world_size, force_dp)
-        if not made_fused_ok(model):
-            raise GMError("MADEEngine: the model is not made.MADE with its layers unchanged; MADETrainer trains such "
-                          "models on the general path")
-        self._init_flat(model, device, use_graph,
-                        [model.linear.weight, model.linear.bias, model.out.weight, model.out.bias])
+    def _params(self, model):
+        return [model.linear.weight, model.linear.bias, model.out.weight, model.out.bias]
+
+    def _setup(self, model):
         self.L1, self.L2 = _Linear(self.fp, model.linear), _Linear(self.fp, model.out)
         self.I, self.H = model.image_size, model.hidden_dim
 
-    def _alloc(self, B):
-        if self._bufB == B:
-            return
+    def _buffers(self, B):
         z = lambda *s: torch.zeros(*s, device=self.device)
         self.X, self.H1, self.A = z(B, self.I), z(B, self.H), z(B, self.I)
         self.dA, self.dH, self.part = z(B, self.I), z(B, self.H), z(B)
-        self._bufB = B
-        self.graphs = {}
 
     def _settings(self):
         return {"order": str(self.model.order), "order_seed": int(self.model.order_seed)}

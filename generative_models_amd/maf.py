@@ -48,8 +48,6 @@ gm_maf_mask) and the loss sum with the counter tick: 8 K + 3 launches.  Sampling
 launches plus the K transposed copies of linear.weight.  An overridden compute_batch / evaluate or an edited model: the
 general loop -- autograd over ops.fused_linear with weight * mask and torch ops on the same u -- and a sampler of D passes
 per layer."""
-import functools
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -57,7 +55,7 @@ import torch.nn as nn
 from . import _lib, made, ops, realnvp
 from ._lib import MAF_MAX_D, MAF_MAX_H, MAF_MAX_K, MAF_MIN_D, MAF_TAG_EVAL, MAF_TAG_TRAIN, GMError
 from .trainers import FlatAdam, _stock_module, stock, stock_model  # noqa: F401
-from .engine import VAEEngine, _Linear
+from .engine import OneNetEngine, _Linear
 
 TAG_TRAIN, TAG_EVAL, TAG_S = MAF_TAG_TRAIN, MAF_TAG_EVAL, realnvp.TAG_S
 ORDERS = made.ORDERS
@@ -244,7 +242,7 @@ def maf_fused_ok(model):
 
 
 # ---- engine ----------------------------------------------------------------------------------------------------------
-class MAFEngine(VAEEngine):
+class MAFEngine(OneNetEngine):
     """MAF on the VAE engine's epoch machinery (index ring, multi-batch hipGraphs over a device counter).  Per training
     batch: 1. gm_gather_rows[_bits];  2. gm_nvp_pre (the HALF split with both halves inside Y[0]);  3. K x (H1 =
     relu(linear(Y[k])), MA = out(H1), gm_maf_couple -> Y[k + 1]);  4. gm_nvp_loss (dZ, row partials);  5. for k = K - 1 ..
@@ -256,27 +254,19 @@ class MAFEngine(VAEEngine):
     of a training batch is ctr + nbase, of a validation batch ctr (the batch's index in the pass).  The degree vectors
     are launch arguments: the graphs are dropped when the model's buffers move.  One GPU only."""
 
-    has_eps = False
     one_gpu = "the MAF engine"
+    fused_ok = staticmethod(maf_fused_ok)
+    refusal = ("MAF", "maf.MAF", "layers")       # the trainer: seed, alpha, levels, s_cap and noise_steps
 
-    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
-                 trainer=None):
-        self._refuse_dp(world_size, force_dp)
-        if not maf_fused_ok(model):
-            raise GMError("MAFEngine: the model is not maf.MAF with its layers unchanged; MAFTrainer trains such models "
-                          "on the general path")
-        plist = []
-        for c in model.layers:
-            plist += [c.linear.weight, c.linear.bias, c.out.weight, c.out.bias]
-        self._init_flat(model, device, use_graph, plist)
-        self._bind_trainer(trainer)                  # seed, alpha, levels, s_cap and noise_steps are read from it
+    def _params(self, model):
+        return [p for c in model.layers for p in (c.linear.weight, c.linear.bias, c.out.weight, c.out.bias)]
+
+    def _setup(self, model):
         self.C = [(_Linear(self.fp, c.linear), _Linear(self.fp, c.out)) for c in model.layers]
         self.D, self.H, self.K = model.image_size, model.hidden_dim, model.num_layers
         self.I = self.D
 
-    def _alloc(self, B):
-        if self._bufB == B:
-            return
+    def _buffers(self, B):
         z = lambda *s: torch.zeros(*s, device=self.device)
         D, H, K = self.D, self.H, self.K
         self.X = z(B, D)
@@ -286,8 +276,6 @@ class MAFEngine(VAEEngine):
         self.logdet, self.part = z(B), z(B)
         self.dZ, self.dOUT, self.dH, self.dY = z(B, D), z(B, 2 * D), z(B, H), z(B, D)
         self.G = (z(B, D), z(B, D))                  # the cotangent of layer k's input lives in G[k % 2]
-        self._bufB = B
-        self.graphs = {}
 
     def _settings(self):
         m, tr = self.model, self.trainer
@@ -381,7 +369,7 @@ class MAFTrainer(realnvp.DequantFlowTrainer):
         return self.model(y, self.s_cap)
 
     def _engine_class(self):
-        return functools.partial(MAFEngine, trainer=self)
+        return MAFEngine
 
     def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
         """VAETrainer.train with this model's defaults (general path: weight * mask in the forward keeps every masked

@@ -132,9 +132,8 @@ class NFVAETrainer(IWAETrainer):
         return (_flow_stock(self.model) and 1 <= self.model.flow.u.shape[0] <= FLOW_MAX_K and super()._stock())
 
     def _engine_class(self):
-        import functools
         from .engine import NFVAEEngine
-        return functools.partial(NFVAEEngine, trainer=self)
+        return NFVAEEngine
 
     def compute_batch(self, batch):
         """(sum_b -L_k, mean ess) of a batch (general path: autograd over the fused linear kernels and the chain in

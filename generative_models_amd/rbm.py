@@ -35,7 +35,7 @@ import torch.nn as nn
 from . import _lib, ops, philox, viz
 from ._lib import RBM_MAX_DIM, RBM_MAX_STEPS, RBM_TAG_D, RBM_TAG_H, RBM_TAG_V, GMError
 from .trainers import FlatAdam, OneLossTrainer, _dataset_rows, _stock_module, stock, stock_model  # noqa: F401
-from .engine import VAEEngine, _Linear
+from .engine import OneNetEngine, _Linear
 
 _M64 = (1 << 64) - 1
 MODES = ("cd", "pcd")
@@ -163,7 +163,7 @@ def rbm_fused_ok(model):
 
 
 # ---- engine ----------------------------------------------------------------------------------------------------------
-class RBMEngine(VAEEngine):
+class RBMEngine(OneNetEngine):
     """The RBM on the VAE engine's epoch machinery (index ring, multi-batch hipGraphs over a device counter).  A CD-k
     training batch is 8 launches: 1. gm_gather_rows[_bits];  2. gm_rbm_chain: v0 and vk into the stacked V = [v0; vk]
     [2b, I];  3. pre = linear(V), one forward GEMM over 2b rows;  4. gm_rbm_grad: dA = [-p0; +pk] / b and the signed
@@ -177,34 +177,27 @@ class RBMEngine(VAEEngine):
     writes from the trainer's count of training batches, so a graph captured in one train() call serves the next.
     No eps ring.  One GPU only."""
 
-    has_eps = False
     one_gpu = "the RBM engine"
+    fused_ok = staticmethod(rbm_fused_ok)
+    refusal = ("RBM", "rbm.RBM", "layer")        # the trainer: k, mode, seed and noise_steps
 
-    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
-                 trainer=None):
-        self._refuse_dp(world_size, force_dp)
-        if not rbm_fused_ok(model):
-            raise GMError("RBMEngine: the model is not rbm.RBM with its layer unchanged; RBMTrainer trains such models "
-                          "on the general path")
-        self._init_flat(model, device, use_graph, [model.linear.weight, model.linear.bias, model.vbias])
-        self._bind_trainer(trainer)                  # k, mode, seed and noise_steps are read from it
+    def _params(self, model):
+        return [model.linear.weight, model.linear.bias, model.vbias]
+
+    def _setup(self, model):
         self.L = _Linear(self.fp, model.linear)
         self.I, self.H = model.image_size, model.hidden_dim
         o = self.fp.offsets[2]
         self.vb, self.m_vb, self.v_vb = self.fp.views[2], self.fp.m[o:o + self.I], self.fp.v[o:o + self.I]
-        self.WT = torch.zeros(self.I, self.H, device=device)
+        self.WT = torch.zeros(self.I, self.H, device=self.device)
         self.pcd_ready = False
 
-    def _alloc(self, B):
-        if self._bufB == B:
-            return
+    def _buffers(self, B):
         z = lambda *s: torch.zeros(*s, device=self.device)
         self.X, self.V, self.PRE, self.dA = z(B, self.I), z(2 * B, self.I), z(2 * B, self.H), z(2 * B, self.H)
         self.part, self.A, self.Vv, self.vpart = z(2 * B), z(B, self.I), z(B, self.I), z(B)
         self.P = z(B, self.I)                        # the persistent chains (mode "pcd")
         self.pcd_ready = False
-        self._bufB = B
-        self.graphs = {}
 
     def configure(self, B, n_train_steps, lr, weight_decay, resume=None):
         from . import ops_fused as of_
@@ -293,6 +286,7 @@ class RBMTrainer(OneLossTrainer):
     _history = ("recon_loss",)
     _line = "Epoch[%d/%d], Free-energy gap: %.6f, Val recon CE: %.6f"
     _one_gpu = "RBMTrainer"
+    _engine_reads_trainer = True
     _error = RBMError
     _fused_ok = staticmethod(rbm_fused_ok)
 
@@ -384,9 +378,6 @@ class RBMTrainer(OneLossTrainer):
 
     def _engine_class(self):
         return RBMEngine
-
-    def _engine_kwargs(self):
-        return {"trainer": self}
 
     def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
         """VAETrainer.train with this model's defaults."""

@@ -53,7 +53,7 @@ from . import _lib, ops, philox, viz
 from ._lib import (NVP_MAX_D, NVP_MAX_H, NVP_MAX_K, NVP_MAX_LEVELS, NVP_MAX_S_CAP, NVP_MIN_D, NVP_TAG_EVAL, NVP_TAG_S,
                    NVP_TAG_TRAIN, GMError)
 from .trainers import FlatAdam, OneLossTrainer, _dataset_rows, _stock_module, stock, stock_model  # noqa: F401
-from .engine import VAEEngine, _Linear
+from .engine import OneNetEngine, _Linear
 
 TAG_TRAIN, TAG_EVAL, TAG_S = NVP_TAG_TRAIN, NVP_TAG_EVAL, NVP_TAG_S
 MASKS = ("checker", "half")
@@ -261,7 +261,7 @@ def nll_rows(z, logdet_pre, logdet, D, levels):
 
 
 # ---- engine ----------------------------------------------------------------------------------------------------------
-class RealNVPEngine(VAEEngine):
+class RealNVPEngine(OneNetEngine):
     """RealNVP on the VAE engine's epoch machinery (index ring, multi-batch hipGraphs over a device counter).  Per
     training batch: 1. gm_gather_rows[_bits];  2. gm_nvp_pre;  3. K x (H1 = relu(linear(x_c)), ST = out(H1),
     gm_nvp_couple);  4. gm_nvp_loss (dZ, row partials);  5. for k = K - 1 .. 0: gm_nvp_couple_bwd, dH = dST Wout [H1 > 0],
@@ -272,20 +272,14 @@ class RealNVPEngine(VAEEngine):
     scheme), of a validation batch ctr (the batch's index in the pass).  No host noise ring, every batch its own gather.
     One GPU only."""
 
-    has_eps = False
     one_gpu = "the RealNVP engine"
+    fused_ok = staticmethod(realnvp_fused_ok)
+    refusal = ("RealNVP", "realnvp.RealNVP", "couplings")        # the trainer: seed and noise_steps
 
-    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
-                 trainer=None):
-        self._refuse_dp(world_size, force_dp)
-        if not realnvp_fused_ok(model):
-            raise GMError("RealNVPEngine: the model is not realnvp.RealNVP with its couplings unchanged; RealNVPTrainer "
-                          "trains such models on the general path")
-        plist = []
-        for c in model.couplings:
-            plist += [c.linear.weight, c.linear.bias, c.out.weight, c.out.bias]
-        self._init_flat(model, device, use_graph, plist)
-        self._bind_trainer(trainer)                  # seed and noise_steps are read from it
+    def _params(self, model):
+        return [p for c in model.couplings for p in (c.linear.weight, c.linear.bias, c.out.weight, c.out.bias)]
+
+    def _setup(self, model):
         self.C = [(_Linear(self.fp, c.linear), _Linear(self.fp, c.out)) for c in model.couplings]
         self.D, self.H, self.K = model.image_size, model.hidden_dim, model.num_couplings
         self.Da, self.Db = model.Da, model.Db
@@ -294,9 +288,7 @@ class RealNVPEngine(VAEEngine):
     def _dt(self, k):
         return self.Db if k % 2 == 0 else self.Da
 
-    def _alloc(self, B):
-        if self._bufB == B:
-            return
+    def _buffers(self, B):
         z = lambda *s: torch.zeros(*s, device=self.device)
         D, H, K, Da, Db = self.D, self.H, self.K, self.Da, self.Db
         self.X, self.Y0 = z(B, D), (z(B, Da), z(B, Db))
@@ -309,8 +301,6 @@ class RealNVPEngine(VAEEngine):
         self.dH = z(B, H)
         self.dX = [z(B, self._dt(k)) if k >= 2 else None for k in range(K)]          # d loss / d (coupling k's input)
         self.G = [z(B, self._dt(k - 1)) if k >= 1 else None for k in range(K)]       # cotangent of coupling k's x_c
-        self._bufB = B
-        self.graphs = {}
 
     def _settings(self):
         m = self.model
@@ -388,6 +378,7 @@ class DequantFlowTrainer(OneLossTrainer):
     temperature) -> code."""
     _line = "Epoch[%d/%d], NLL: %.6f, Val NLL: %.6f"
     _tag_train = _tag_eval = None
+    _engine_reads_trainer = True
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, seed=0):
         self.seed = self._check_seed(seed)           # before anything runs
@@ -521,8 +512,7 @@ class RealNVPTrainer(DequantFlowTrainer):
         return self.model.split(z)
 
     def _engine_class(self):
-        import functools
-        return functools.partial(RealNVPEngine, trainer=self)
+        return RealNVPEngine
 
     def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
         """VAETrainer.train with this model's defaults."""

@@ -53,13 +53,13 @@ overridden compute_batch / evaluate or an edited model: the general loop -- auto
 ops_fused.sw_loss on the same noise."""
 import numpy as np
 import torch
-import torch.nn as nn
 
 from . import _lib, ops, philox, viz
-from ._lib import (GMMN_MAX_Z, MMD_MAX_I, SW_MAX_B, SW_MAX_P, SW_MAX_ROWS, SWG_TAG_DM, SWG_TAG_DT, SWG_TAG_DV, SWG_TAG_S,
-                   SWG_TAG_T, SWG_TAG_V, GMError)
-from .trainers import FlatAdam, Generator, OneLossTrainer, _stock_module, stock, stock_model  # noqa: F401
-from .engine import VAEEngine, _align4, _Linear
+from ._lib import (SW_MAX_B, SW_MAX_P, SW_MAX_ROWS, SWG_TAG_DM, SWG_TAG_DT, SWG_TAG_DV, SWG_TAG_S, SWG_TAG_T, SWG_TAG_V,
+                   GMError)
+from .trainers import FlatAdam, Generator, stock, stock_model  # noqa: F401
+from .engine import GeneratorMatchEngine, _align4
+from .gmmn import GeneratorMatchTrainer, GeneratorModel, generator_fused_ok, generator_shape
 from .gmmn import uniforms_reference  # noqa: F401  (the prior's rule)
 
 TAG_T, TAG_V, TAG_S = SWG_TAG_T, SWG_TAG_V, SWG_TAG_S
@@ -89,14 +89,7 @@ def check_projections(P):
 
 
 def check_shape(image_size, hidden_dim, z_dim):
-    I, H, Z = _int(image_size, "image_size"), _int(hidden_dim, "hidden_dim"), _int(z_dim, "z_dim")
-    if not 1 <= I <= MMD_MAX_I:
-        raise SWGError("image_size must lie in [1, %d], got %d" % (MMD_MAX_I, I))
-    if H < 1:
-        raise SWGError("hidden_dim must be >= 1, got %d" % H)
-    if not 1 <= Z <= GMMN_MAX_Z:
-        raise SWGError("z_dim must lie in [1, %d], got %d" % (GMMN_MAX_Z, Z))
-    return I, H, Z
+    return generator_shape(image_size, hidden_dim, z_dim, SWGError)
 
 
 def check_batch(b):
@@ -117,32 +110,16 @@ def directions_reference(P, I, seed, step, tag=TAG_DT, row0=0):
 
 # ---- modules ---------------------------------------------------------------------------------------------------------
 @stock_model
-class SWG(nn.Module):
+class SWG(GeneratorModel):
     """One Generator: z in (-1, 1)^Z -> relu -> sigmoid -> I pixels."""
-
-    def __init__(self, image_size=784, hidden_dim=400, z_dim=20):
-        super().__init__()
-        self.image_size, self.hidden_dim, self.z_dim = check_shape(image_size, hidden_dim, z_dim)
-        self.G = Generator(self.image_size, self.hidden_dim, self.z_dim)
-        self.shape = int(self.image_size ** 0.5)
-
-    def forward(self, z):
-        return self.G(z)
+    _error = SWGError
 
 
-def swg_fused_ok(model):
-    """True iff the model is SWG itself with its Generator unchanged and consistent shapes."""
-    g = getattr(model, "G", None)
-    if not (type(model).__dict__.get("_gm_stock_model", False) and type(g) is Generator and _stock_module(g, 2)):
-        return False
-    I, H, Z = model.image_size, model.hidden_dim, model.z_dim
-    return (tuple(g.linear.weight.shape) == (H, Z) and tuple(g.generate.weight.shape) == (I, H)
-            and g.linear.bias is not None and g.generate.bias is not None and 1 <= I <= MMD_MAX_I
-            and 1 <= Z <= GMMN_MAX_Z)
+swg_fused_ok = generator_fused_ok
 
 
 # ---- engine ----------------------------------------------------------------------------------------------------------
-class SWGEngine(VAEEngine):
+class SWGEngine(GeneratorMatchEngine):
     """The SWG on the VAE engine's epoch machinery (index ring, multi-batch hipGraphs over a device counter).  Per
     training batch, 13 launches: 1. gm_gather_rows[_bits] (Y, the lower half of R);  2. gm_gmmn_prior (z);  3.-4. the two
     generator forwards (X, the upper half of R);  5. gm_sw_directions (Theta);  6. Pr = Theta R^T through ops.linear_fwd
@@ -153,29 +130,19 @@ class SWGEngine(VAEEngine):
     without Ct, and the record.  The noise step of a training batch is ctr + nbase (DDPMEngine's scheme), of a
     validation batch ctr.  One GPU only."""
 
-    has_eps = False
     one_gpu = "the SWG engine"
+    fused_ok = staticmethod(swg_fused_ok)
+    refusal = ("SWG", "swg.SWG", "Generator")        # the trainer: seed, num_projections and noise_steps
+    noise_builder, tags = "sw_noise", (TAG_T, TAG_V)
+    _bufP = None
 
-    def __init__(self, model, device, use_graph=True, world_size=1, rank=0, process_group=None, force_dp=False,
-                 trainer=None):
-        self._refuse_dp(world_size, force_dp)
-        if not swg_fused_ok(model):
-            raise GMError("SWGEngine: the model is not swg.SWG with its Generator unchanged; SWGTrainer trains "
-                          "such models on the general path")
-        g = model.G
-        self._init_flat(model, device, use_graph, [g.linear.weight, g.linear.bias, g.generate.weight, g.generate.bias])
-        self._bind_trainer(trainer)                  # seed, num_projections and noise_steps are read from it
-        self.L1, self.L2 = _Linear(self.fp, g.linear), _Linear(self.fp, g.generate)
-        self.I, self.H, self.Z = model.image_size, model.hidden_dim, model.z_dim
-        self._bufP = None
+    def _alloc_key(self, B):
+        return B, check_projections(self.trainer.num_projections)
 
-    def _alloc(self, B):
-        P = check_projections(self.trainer.num_projections)
-        if self._bufB == B and self._bufP == P:
-            return
+    def _buffers(self, B):
         from . import ops_fused as of_
         check_batch(B)
-        I, H, Z = self.I, self.H, self.Z
+        I, H, Z, P = self.I, self.H, self.Z, int(self.trainer.num_projections)
         z = lambda *s: torch.zeros(*s, device=self.device)
         self.Rb = z(2 * B, I)                        # R = [X; Y]: a batch of b rows uses rows [0, b) and [b, 2b)
         self.Zb, self.Hg = z(B, Z), z(B, H)
@@ -186,8 +153,7 @@ class SWGEngine(VAEEngine):
         self.lossf = z(1)
         self.stats = torch.zeros(2, dtype=torch.float64, device=self.device)
         self.ws = of_.sw_workspace(P, self.device)
-        self._bufB, self._bufP = B, P
-        self.graphs = {}
+        self._bufP = P
 
     def _settings(self):
         t = self.trainer
@@ -202,15 +168,8 @@ class SWGEngine(VAEEngine):
         """One batch of size b: Y, z, X, the directions, the statistic (+ its gradient, the backward and Adam when
         train)."""
         from . import ops_fused as of_
-        L1, L2, tr, P = self.L1, self.L2, self.trainer, self._bufP
-        idx_slot = self._slot(t, 1, 0, self.R, self.B)
-        loss_slot = self._slot(t, 1, 0, 0, 1)
-        X, Y = self.Rb[:b], self.Rb[b:2 * b]
-        ops.gather_rows(self.data, self.idx_ring.view(-1), Y, B=b, idx_slot=idx_slot, stream=st)
-        of_.gmmn_prior(self.Zb, of_.sw_noise(tr.seed, TAG_T if train else TAG_V, **self._clock(t, train)), B=b, Z=self.Z,
-                       stream=st)
-        ops.linear_fwd(self.Zb, L1.W, L1.b, self.Hg, "relu", M=b, stream=st)
-        ops.linear_fwd(self.Hg, L2.W, L2.b, X, "sigmoid", M=b, stream=st)
+        tr, P = self.trainer, self._bufP
+        X, Y = self._forward(st, t, b, train)
         of_.sw_directions(self.Theta, of_.sw_noise(tr.seed, TAG_DT if train else TAG_DV, **self._clock(t, train)),
                           stream=st)
         Pr = self.Pr[:, :2 * b]
@@ -218,21 +177,14 @@ class SWGEngine(VAEEngine):
         of_.sw_sort(Pr, b, b, self.ws, Ct=self.Ct if train else None, stream=st)
         of_.sw_finalize(P, b, b, self.ws, self.stats, loss_out=self.lossf, stream=st)
         if train:
-            adam = dict(sched=self.sched, sched_slot=self._slot(t, 1, 0, 0, 1))
             ops.linear_bwd_dw(self.Ct[:, :b], self.Theta, self.dX[:b], None, stream=st)
             ops.act_bwd(self.dX[:b], X, self.dA[:b], "sigmoid", stream=st)
-            # dH reads the output layer's weights BEFORE the pair's Adam updates them
-            ops.linear_bwd_dx(self.dA, L2.W, self.dH, below=self.Hg, epi="relu", M=b, stream=st)
-            ops.linear_bwd_dw_adam_pair(dict(dA=self.dA, X=self.Hg, lin=L2, adam=adam, M=b),
-                                        dict(dA=self.dH, X=self.Zb, lin=L1, adam=adam, M=b),
-                                        weight_decay=self.wd, stream=st)
-        of_.sum_finalize(self.lossf, 1, self.recon if train else self.vrecon, out_slot=loss_slot,
-                         tick=self.ctr if self.use_graph else None, stream=st)
+        self._tail(st, t, b, train)
 
 
 # ---- trainer ---------------------------------------------------------------------------------------------------------
 @stock
-class SWGTrainer(OneLossTrainer):
+class SWGTrainer(GeneratorMatchTrainer):
     """Trains an SWG on the sliced Wasserstein distance and samples from it.  Histories: `losses` (one per training
     batch); the epoch line (mean training loss, validation loss); best_val_loss / best_model as the other one-loss
     trainers; checkpoints (+ num_projections, seed in the optimizer state's config, checked under strict=True, and the
@@ -241,27 +193,22 @@ class SWGTrainer(OneLossTrainer):
     _one_gpu = "SWGTrainer"
     _error = SWGError
     _fused_ok = staticmethod(swg_fused_ok)
+    _engine_type = SWGEngine
+    _check_batch = staticmethod(check_batch)
+    _noise_builder, _tag_sample = "sw_noise", TAG_S
+    _no_likelihood = "an SWG has no likelihood and no encoder; parzen(), mmd() and swd() score its samples"
+    _no_encoder = "an SWG has no encoder"
 
     def __init__(self, model, train_iter, val_iter, test_iter, viz=False, *, num_projections=NUM_PROJECTIONS, seed=0):
         self.seed = check_seed(seed)                 # before anything runs
         self.num_projections = check_projections(num_projections)
-        if getattr(train_iter, "batch_size", None) is not None:
-            check_batch(train_iter.batch_size)
         super().__init__(model, train_iter, val_iter, test_iter, viz=viz)
-        self.noise_steps = 0                         # training batches taken: the next one's noise step
-        self._eval_step = 0                          # batch index within an evaluate() call
-
-    def prior(self, n, step, tag, seed=None, row0=0):
-        """The prior rows [n, Z] of (seed, step, tag) on the model's device (gm_gmmn_prior)."""
-        from . import ops_fused as of_
-        z = torch.empty(n, self.model.z_dim, device=self._device())
-        return of_.gmmn_prior(z, of_.sw_noise(self.seed if seed is None else seed, tag, step=step, row0=row0))
 
     def directions(self, step, tag, seed=None, P=None, row0=0):
         """The unit directions [P, I] of (seed, step, tag) on the model's device (gm_sw_directions)."""
         from . import ops_fused as of_
         th = torch.empty(self.num_projections if P is None else P, self.model.image_size, device=self._device())
-        return of_.sw_directions(th, of_.sw_noise(self.seed if seed is None else seed, tag, step=step, row0=row0))
+        return of_.sw_directions(th, self._noise(seed, tag, step, row0))
 
     def compute_batch(self, batch):
         """The sliced Wasserstein loss of a batch against as many samples (general path: autograd over the fused linear
@@ -272,43 +219,6 @@ class SWGTrainer(OneLossTrainer):
         train, step = self._noise_step()
         z = self.prior(check_batch(x.shape[0]), step, TAG_T if train else TAG_V)
         return of_.sw_loss(self.model(z), x, self.directions(step, TAG_DT if train else TAG_DV))
-
-    def _engine_class(self):
-        import functools
-        return functools.partial(SWGEngine, trainer=self)
-
-    def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
-        """VAETrainer.train with this model's defaults."""
-        return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
-
-    # ---- sampling ---------------------------------------------------------------------------------------------------
-    SAMPLE_BLOCK = 1024          # sample() runs the generator on whole blocks of this many rows
-
-    def sample(self, n, seed=0):
-        """n samples [n, I] in [0, 1]: row r is the generator on the prior row r of (seed, TAG_S, step 0), whatever n --
-        the generator always runs on whole blocks of SAMPLE_BLOCK rows (the last one is cut after the fact), so a row's
-        launches, and its bits, do not depend on n.  Runs after a device synchronise; the global generator, the model's
-        mode and the parameters are untouched."""
-        n, seed = _int(n, "n"), check_seed(seed)
-        if n < 1:
-            raise SWGError("n must be >= 1, got %d" % n)
-        self._device()
-        torch.cuda.synchronize()                     # after the engine's last Adam step
-        out = []
-        with torch.no_grad():
-            for lo in range(0, n, self.SAMPLE_BLOCK):
-                out.append(self.model(self.prior(self.SAMPLE_BLOCK, 0, TAG_S, seed=seed, row0=lo)))
-        return torch.cat(out)[:n].contiguous()
-
-    # ---- visualisation ----------------------------------------------------------------------------------------------
-    def sample_images(self, epoch=-100, num_images=36, save=True):
-        return viz.made_sample_images(self, epoch, num_images, save, self.viz_dir)
-
-    def log_likelihood(self, images=None, k=500, seed=0):
-        raise GMError("an SWG has no likelihood and no encoder; parzen(), mmd() and swd() score its samples")
-
-    def reconstruct_images(self, images, epoch, save=True):
-        raise GMError("an SWG has no encoder")
 
     def viz_loss(self):
         viz.one_loss_curve(self, "SWD loss")

@@ -138,9 +138,8 @@ class TCVAETrainer(IWAETrainer):
         self._eval_n = None              # the dataset size of the evaluate() pass under way
 
     def _engine_class(self):
-        import functools
         from .engine import TCVAEEngine
-        return functools.partial(TCVAEEngine, trainer=self)
+        return TCVAEEngine
 
     def _stock(self):
         return self.k == 1 and super()._stock()

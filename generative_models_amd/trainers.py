@@ -996,9 +996,11 @@ class VAETrainer:
         from .engine import VAEEngine
         return VAEEngine
 
+    _engine_reads_trainer = False    # the engine draws its noise on the device: seed, settings, noise_steps from here
+
     def _engine_kwargs(self):
         """Constructor arguments of the engine beside the model, the device, use_graph and the data-parallel group."""
-        return {}
+        return {"trainer": self} if self._engine_reads_trainer else {}
 
     def _new_engine(self, dev):
         kw = self._engine_kwargs()
@@ -1126,10 +1128,10 @@ class VAETrainer:
 
 @stock
 class OneLossTrainer(VAETrainer):
-    """What the trainers that record one scalar loss per batch in `losses` share (MADE, MAF, RealNVP, DDPM, RBM): the
-    histories a constructor leaves, path selection on the model's own fused-path test, the general path's batch
-    preparation and evaluate(), the pixel-count check of images handed to a sampling or scoring method, and
-    generate_images; the per-epoch sample grid is VAETrainer's _viz_epoch.  A subclass names its _fused_ok, _error, _line
+    """What the eight trainers that record one scalar loss per batch in `losses` share (MADE, MAF, RealNVP, DDPM, RBM,
+    GMMN, flow matching, SWG): the histories a constructor leaves, path selection on the model's own fused-path test,
+    the general path's batch preparation and evaluate(), the pixel-count check of images handed to a sampling or
+    scoring method, and generate_images; the per-epoch sample grid is VAETrainer's _viz_epoch.  A subclass names its _fused_ok, _error, _line
     and _one_gpu and supplies compute_batch, sample_images, viz_loss and its engine."""
     _hook_names = ("compute_batch", "evaluate")
     _series = (("losses", "recon"),)

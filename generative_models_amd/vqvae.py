@@ -220,9 +220,8 @@ class VQVAETrainer(IWAETrainer):
                 and self.train_iter.batch_size == self.val_iter.batch_size)
 
     def _engine_class(self):
-        import functools
         from .engine import VQVAEEngine
-        return functools.partial(VQVAEEngine, trainer=self)
+        return VQVAEEngine
 
     def train(self, num_epochs, lr=1e-3, weight_decay=1e-5, quiet=False):
         """vae.py's train loop on the quantised bound; the codebook steps with every other parameter."""

@@ -69,7 +69,10 @@ def test_module_surface_and_state_dict_keys():
     assert pkg.DDPM is gddpm.DDPM and pkg.DDPMTrainer is gddpm.DDPMTrainer and pkg.DDPMEngine is gddpm.DDPMEngine
     from generative_models_amd.engine import VAEEngine
     assert issubclass(gddpm.DDPMEngine, VAEEngine)
-    for f in ("_alloc", "_issue", "configure"):
+    from generative_models_amd.engine import TimeRegressionEngine
+    for f in ("_buffers", "_issue", "configure"):              # the step body it shares with the flow-matching engine
+        assert getattr(gddpm.DDPMEngine, f) is getattr(TimeRegressionEngine, f)
+    for f in ("_settings", "_gather_sample"):
         assert f in gddpm.DDPMEngine.__dict__
     # the forward is the contract's composition (fp64, CPU: plain matmuls on the module's own tensors)
     P = R.f64(m.state_dict())
@@ -361,7 +364,8 @@ def test_fused_and_general_path_selection():
     class MyDDPM(ddpm.DDPM):
         pass
     assert not _trainer(MyDDPM(16, 8, 8, 50))._stock()
-    assert _trainer(mk())._engine_class().func is gddpm.DDPMEngine
+    tr = _trainer(mk())
+    assert tr._engine_class() is gddpm.DDPMEngine and tr._engine_kwargs() == {"trainer": tr}
     with pytest.raises(_lib.GMError):
         gddpm.DDPMEngine(m, "cpu", trainer=_trainer(m))        # the engine itself refuses an edited model
 

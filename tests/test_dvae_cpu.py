@@ -239,7 +239,8 @@ def test_fused_and_general_path_selection():
         pass
     assert not _trainer(MyDVAE(16, 8, 4))._stock()
     from generative_models_amd.engine import DVAEEngine
-    assert _trainer(mk())._engine_class().func is DVAEEngine
+    tr = _trainer(mk())
+    assert tr._engine_class() is DVAEEngine and tr._engine_kwargs() == {"trainer": tr}
 
 
 def test_data_parallelism_is_refused():

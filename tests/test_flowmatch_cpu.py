@@ -228,7 +228,8 @@ def test_module_surface_and_exports():
     assert (p["seed"].default, p["batch"].default, p["steps"].default, p["solver"].default) == (0, 1024, 100, "rk4")
     from generative_models_amd import engine, realnvp
     assert issubclass(T, realnvp.DequantFlowTrainer) and T._series == (("losses", "recon"),)
-    assert issubclass(gfm.FlowMatchEngine, engine.VAEEngine) and "_issue" in gfm.FlowMatchEngine.__dict__
+    assert issubclass(gfm.FlowMatchEngine, engine.VAEEngine) and "_gather_sample" in gfm.FlowMatchEngine.__dict__
+    assert gfm.FlowMatchEngine._issue is engine.TimeRegressionEngine._issue        # the DDPM engine's step body
     for name in ("sample", "encode", "decode", "log_likelihood", "log_likelihood_rows", "bits_per_dim", "velocity",
                  "divergence", "parzen", "mmd", "save_checkpoint", "load_checkpoint"):
         assert callable(getattr(T, name)), name

@@ -270,7 +270,8 @@ def test_fused_and_general_path_selection():
         pass
     assert not _trainer(MyIWAE(16, 8, 4))._stock()
     from generative_models_amd.engine import IWAEEngine
-    assert _trainer(mk())._engine_class().func is IWAEEngine
+    tr = _trainer(mk())
+    assert tr._engine_class() is IWAEEngine and tr._engine_kwargs() == {"trainer": tr}
 
 
 def test_data_parallelism_and_out_of_scope_models_are_refused():

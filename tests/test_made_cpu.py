@@ -70,7 +70,7 @@ def test_module_surface_and_state_dict_keys():
     from generative_models_amd.engine import VAEEngine
     from generative_models_amd.trainers import VAETrainer
     assert issubclass(gmade.MADEEngine, VAEEngine) and issubclass(gmade.MADETrainer, VAETrainer)
-    for f in ("_alloc", "_issue", "configure"):
+    for f in ("_buffers", "_issue", "configure"):    # _alloc, the guard around _buffers, is the shared base's
         assert f in gmade.MADEEngine.__dict__
     # a checkpoint carries the order: the degrees travel in the state_dict
     m2 = made.MADE(16, 12, order="random", order_seed=3)

@@ -78,7 +78,7 @@ def test_module_surface_and_state_dict_keys():
     assert pkg.MAF is gmaf.MAF and pkg.MAFTrainer is T and pkg.MAFEngine is gmaf.MAFEngine
     assert issubclass(T, VAETrainer) and "train" in T.__dict__ and "_train_fused" not in T.__dict__   # the shared loop
     assert issubclass(gmaf.MAFEngine, VAEEngine) and gmaf.MAFEngine.has_eps is False
-    for f in ("_alloc", "_issue", "configure"):
+    for f in ("_buffers", "_issue", "configure"):    # _alloc, the guard around _buffers, is the shared base's
         assert f in gmaf.MAFEngine.__dict__, f
     assert gmaf.__doc__ and "The contract" in gmaf.__doc__ and "MAFD" in gmaf.__doc__
     tr = _trainer(m)

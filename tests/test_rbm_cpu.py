@@ -69,7 +69,7 @@ def test_module_surface_and_state_dict_keys():
     from generative_models_amd.engine import VAEEngine
     from generative_models_amd.trainers import VAETrainer
     assert issubclass(grbm.RBMEngine, VAEEngine) and issubclass(grbm.RBMTrainer, VAETrainer)
-    for f in ("_alloc", "_issue", "configure", "optim_state"):
+    for f in ("_buffers", "_issue", "configure", "optim_state"):     # _alloc, the guard around _buffers: the shared base's
         assert f in grbm.RBMEngine.__dict__
 
 

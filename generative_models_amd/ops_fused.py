@@ -4,7 +4,12 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import NO_SLOT
+from ._abi import (NO_SLOT, SN_MAX_H, SN_MAX_I, SN_NR, SN_NT, SN_NW2, SN_SIGMA, STD_WS_BYTES,  # noqa: F401
+                   ACGANHeadsArgs, CatArgs, DdpmNoise, DdpmOut, DdpmReverseArgs, DdpmTables, FlowParams, FlowStepArgs,
+                   FmDivArgs, FmNoise, FmOut, FmStageArgs, FmTables, IafParams, IafStepArgs, IwaeNoise, MadeMaskArgs,
+                   MadeSampleArgs, MafCoupleArgs, MafCoupleBwdArgs, MafInvertArgs, MafMaskArgs, NvpCoupleArgs,
+                   NvpCoupleBwdArgs, NvpLossArgs, NvpPostArgs, NvpPreArgs, RbmChainArgs, RbmVbiasArgs, SNGradArgs,
+                   SNHeadArgs, SNPowerArgs, VqArgs, VqStepArgs)
 from .ops import _ld, stream_ptr
 
 
@@ -207,9 +212,6 @@ def began_update(state, dstate, istate, gamma, lam, patience, tick, stream=None)
               istate.data_ptr(), gamma, lam, patience, tick.data_ptr() if tick is not None else None)
 
 
-STD_WS_BYTES = 1088                  # include/gm_hip.h GM_STD_WS_BYTES
-
-
 def std_workspace(device):
     """Zeroed workspace of the multi-workgroup std kernels (allocate once, outside graph capture)."""
     import torch
@@ -316,20 +318,6 @@ def aae_gen_mid(z, He, W1, b1, w2, b2, Wz, dz, dHe, loss_part, B, stream=None):
 
 
 # ---- auxiliary-classifier GAN (csrc/gm_acgan.hip; acgan.py) ---------------------------------------------------------
-class ACGANHeadsArgs(ctypes.Structure):
-    """gm_acgan_heads_args (include/gm_hip.h): the AC-GAN critic's two heads, forward and backward."""
-    _fields_ = [("H", ctypes.c_void_p), ("ldh", ctypes.c_int64), ("rows", ctypes.c_int), ("B", ctypes.c_int), ("Hd", ctypes.c_int), ("C", ctypes.c_int),
-                ("gen_mode", ctypes.c_int), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p), ("Wc", ctypes.c_void_p), ("bc", ctypes.c_void_p),
-                ("lab", _lib.LabelSrc), ("class_weight", ctypes.c_float), ("da2", ctypes.c_void_p), ("dq", ctypes.c_void_p), ("lddq", ctypes.c_int64),
-                ("loss_out", ctypes.c_void_p), ("loss_slot", _lib.Slot), ("ce_out", ctypes.c_void_p), ("ce_slot", _lib.Slot),
-                ("acc_out", ctypes.c_void_p), ("acc_slot", _lib.Slot), ("dPre", ctypes.c_void_p), ("ldp", ctypes.c_int64),
-                ("gw2", ctypes.c_void_p), ("gb2", ctypes.c_void_p), ("gWc", ctypes.c_void_p), ("gbc", ctypes.c_void_p),
-                ("mw2", ctypes.c_void_p), ("vw2", ctypes.c_void_p), ("mb2", ctypes.c_void_p), ("vb2", ctypes.c_void_p),
-                ("mWc", ctypes.c_void_p), ("vWc", ctypes.c_void_p), ("mbc", ctypes.c_void_p), ("vbc", ctypes.c_void_p),
-                ("sched", ctypes.c_void_p), ("sched_slot", _lib.Slot), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
-                ("eps", ctypes.c_double), ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_int64)]
-
-
 def _acgan_shape(rows, Hd, C):
     if not (rows >= 1 and 1 <= C <= 32 and 4 <= Hd <= 1024 and Hd % 4 == 0):
         raise _lib.GMError("the AC-GAN head kernels take 1 <= C <= 32 and 4 <= Hd <= 1024 with Hd %% 4 == 0 (got "
@@ -403,34 +391,6 @@ def acgan_heads_bwd(H, w2, b2, Wc, bc, B, gen_mode, da2, dq, dPre, ws, grads=Non
 
 
 # ---- spectrally normalised hinge GAN (csrc/gm_sn.hip; sngan.py) -----------------------------------------------------
-SN_MAX_H, SN_MAX_I = 1024, 8192                     # GM_SN_MAX_H / GM_SN_MAX_I
-SN_SIGMA, SN_NW2, SN_NT, SN_NR = 0, 1, 2, 3        # GM_SN_STAT_*
-
-
-class SNPowerArgs(ctypes.Structure):
-    """gm_sn_power_args (include/gm_hip.h): the power-iteration stage in front of a critic forward."""
-    _fields_ = [("W", ctypes.c_void_p), ("H", ctypes.c_int), ("I", ctypes.c_int), ("u", ctypes.c_void_p),
-                ("v", ctypes.c_void_p), ("Wbar", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("w2bar", ctypes.c_void_p),
-                ("stats", ctypes.c_void_p), ("update_u", ctypes.c_int), ("ws", ctypes.c_void_p),
-                ("ws_bytes", ctypes.c_int64)]
-
-
-class SNHeadArgs(ctypes.Structure):
-    """gm_sn_head_args (include/gm_hip.h): the hinge head on the normalised w2, forward and backward."""
-    _fields_ = [("H", ctypes.c_void_p), ("ldh", ctypes.c_int64), ("rows", ctypes.c_int), ("B", ctypes.c_int),
-                ("Hd", ctypes.c_int), ("gen_mode", ctypes.c_int), ("w2bar", ctypes.c_void_p), ("b2", ctypes.c_void_p),
-                ("s", ctypes.c_void_p), ("ds", ctypes.c_void_p), ("loss_out", ctypes.c_void_p), ("loss_slot", _lib.Slot),
-                ("dPre", ctypes.c_void_p), ("ldp", ctypes.c_int64), ("stats", ctypes.c_void_p), ("gw2", ctypes.c_void_p),
-                ("gb2", ctypes.c_void_p), ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_int64)]
-
-
-class SNGradArgs(ctypes.Structure):
-    """gm_sn_grad_args (include/gm_hip.h): d loss / d Wbar carried back to W."""
-    _fields_ = [("G", ctypes.c_void_p), ("Wbar", ctypes.c_void_p), ("H", ctypes.c_int), ("I", ctypes.c_int),
-                ("u", ctypes.c_void_p), ("v", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("gW", ctypes.c_void_p),
-                ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_int64)]
-
-
 def _sn_w_shape(H, I):
     if not (4 <= H <= SN_MAX_H and H % 4 == 0 and 1 <= I <= SN_MAX_I):
         raise _lib.GMError("the spectral-norm kernels take 4 <= H <= 1024 with H %% 4 == 0 and 1 <= I <= 8192 (got "
@@ -747,13 +707,6 @@ def pdw_dir(g, x, xr, n, gamma, pen, lam, inv_b, stream=None):
 
 
 # ---- Importance-weighted autoencoder (csrc/gm_iwae.hip; iwae.py) ---------------------------------------------------
-class IwaeNoise(ctypes.Structure):
-    """gm_iwae_noise (include/gm_hip.h): the IWAE's noise stream -- seed, tag, step and the sample rows of the call."""
-    _fields_ = [("seed", ctypes.c_uint64), ("tag", ctypes.c_uint32), ("step_ctr", ctypes.c_void_p),
-                ("step_base", ctypes.c_void_p), ("step_add", ctypes.c_int64), ("k_total", ctypes.c_int64),
-                ("j0", ctypes.c_int64), ("q0", ctypes.c_int64)]
-
-
 def iwae_noise(seed, tag, k_total, j0=0, step=0, step_ctr=None, step_base=None, q0=0):
     """A gm_iwae_noise block: the stream (seed, tag) at step = *step_ctr + *step_base + step (int64 device tensors, or
     None for 0); the call's sample j of image b draws noise row b * k_total + j0 + j.  The tensors must outlive every
@@ -864,21 +817,6 @@ def tc_reduce(ml, z, lse_joint, lse_dim, wn, dzdec, dml, noise, alpha, beta, gam
 
 
 # ---- Planar-flow posterior of the normalizing-flow VAE (csrc/gm_flow.hip; nfvae.py) --------------------------------
-class FlowParams(ctypes.Structure):
-    """gm_flow_params (include/gm_hip.h): the K planar layers' u [K, Z], w [K, Z], b [K]."""
-    _fields_ = [("u", ctypes.c_void_p), ("w", ctypes.c_void_p), ("b", ctypes.c_void_p), ("K", ctypes.c_int)]
-
-
-class FlowStepArgs(ctypes.Structure):
-    """gm_flow_step_args (include/gm_hip.h): gm_flow_step's arguments as one block."""
-    _fields_ = [("part", ctypes.c_void_p), ("nparts", ctypes.c_int), ("u", ctypes.c_void_p), ("w", ctypes.c_void_p),
-                ("b", ctypes.c_void_p), ("gu", ctypes.c_void_p), ("gw", ctypes.c_void_p), ("gb", ctypes.c_void_p),
-                ("mu", ctypes.c_void_p), ("vu", ctypes.c_void_p), ("mw", ctypes.c_void_p), ("vw", ctypes.c_void_p),
-                ("mb", ctypes.c_void_p), ("vb", ctypes.c_void_p), ("sched", ctypes.c_void_p), ("sched_slot", _lib.Slot),
-                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
-                ("weight_decay", ctypes.c_double), ("K", ctypes.c_int), ("Z", ctypes.c_int)]
-
-
 def flow_params(u, w, b):
     """A gm_flow_params block over u [K, Z], w [K, Z], b [K] (contiguous float32 device tensors that outlive every
     launch and captured graph reading them)."""
@@ -940,22 +878,6 @@ def flow_step(part, B, u, w, b, moments, sched, sched_slot=NO_SLOT, grads=None, 
 
 
 # ---- Inverse-autoregressive-flow posterior of the IAF-VAE (csrc/gm_iaf.hip; iafvae.py) -----------------------------
-class IafParams(ctypes.Structure):
-    """gm_iaf_params (include/gm_hip.h): the K layers' W1 [K, F, Z], U [K, F, C], b1 [K, F], W2 [K, 2Z, F], b2 [K, 2Z]."""
-    _fields_ = [("W1", ctypes.c_void_p), ("U", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("W2", ctypes.c_void_p),
-                ("b2", ctypes.c_void_p), ("K", ctypes.c_int), ("F", ctypes.c_int), ("C", ctypes.c_int)]
-
-
-class IafStepArgs(ctypes.Structure):
-    """gm_iaf_step_args (include/gm_hip.h): gm_iaf_step's arguments as one block."""
-    _fields_ = [("part", ctypes.c_void_p), ("nparts", ctypes.c_int), ("p", ctypes.c_void_p * 5),
-                ("g", ctypes.c_void_p * 5), ("m", ctypes.c_void_p * 5), ("v", ctypes.c_void_p * 5),
-                ("m_in", ctypes.c_void_p), ("sched", ctypes.c_void_p), ("sched_slot", _lib.Slot),
-                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
-                ("weight_decay", ctypes.c_double), ("K", ctypes.c_int), ("Z", ctypes.c_int), ("F", ctypes.c_int),
-                ("C", ctypes.c_int)]
-
-
 def _iaf_f32(t, shape, what):
     if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
         raise _lib.GMError("%s must be a contiguous float32 device tensor of shape %s, got %s"
@@ -1055,16 +977,6 @@ def iaf_step(part, B, k, params, m_in, moments, sched, sched_slot=NO_SLOT, grads
 
 
 # ---- Gumbel-Softmax posterior of the categorical VAE (csrc/gm_cat.hip; catvae.py) ----------------------------------
-class CatArgs(ctypes.Structure):
-    """gm_cat_args (include/gm_hip.h): gm_cat_sample's and gm_cat_reduce's arguments as one block."""
-    _fields_ = [("logits", ctypes.c_void_p), ("ldl", ctypes.c_int64), ("tau_tab", ctypes.c_void_p),
-                ("tau_slot", _lib.Slot), ("tau", ctypes.c_float), ("B", ctypes.c_int), ("k", ctypes.c_int),
-                ("N", ctypes.c_int), ("C", ctypes.c_int), ("mode", ctypes.c_int), ("y", ctypes.c_void_p),
-                ("ldy", ctypes.c_int64), ("lp", ctypes.c_void_p), ("kl", ctypes.c_void_p), ("codes", ctypes.c_void_p),
-                ("dzdec", ctypes.c_void_p), ("lddz", ctypes.c_int64), ("wn", ctypes.c_void_p),
-                ("dlogits", ctypes.c_void_p), ("lddl", ctypes.c_int64)]
-
-
 def _cat_f32(t, name):
     if not (t.is_cuda and t.dtype == torch.float32):
         raise _lib.GMError("%s must be a float32 device tensor (got %s on %s)" % (name, t.dtype, t.device))
@@ -1146,25 +1058,6 @@ def catvae_gumbels(n_images, k, N, C, seed, step, tag, device="cuda"):
 
 
 # ---- Vector quantisation of the VQ-VAE (csrc/gm_vq.hip; vqvae.py) --------------------------------------------------
-class VqArgs(ctypes.Structure):
-    """gm_vq_args (include/gm_hip.h): gm_vq_quantise's and gm_vq_reduce's arguments as one block."""
-    _fields_ = [("ze", ctypes.c_void_p), ("ldz", ctypes.c_int64), ("E", ctypes.c_void_p), ("lde", ctypes.c_int64),
-                ("codes", ctypes.c_void_p), ("ldc", ctypes.c_int64), ("beta", ctypes.c_float), ("B", ctypes.c_int),
-                ("N", ctypes.c_int), ("D", ctypes.c_int), ("K", ctypes.c_int), ("zq", ctypes.c_void_p),
-                ("ldq", ctypes.c_int64), ("qerr", ctypes.c_void_p), ("lp", ctypes.c_void_p), ("dzdec", ctypes.c_void_p),
-                ("lddz", ctypes.c_int64), ("wn", ctypes.c_void_p), ("dml", ctypes.c_void_p), ("lddml", ctypes.c_int64)]
-
-
-class VqStepArgs(ctypes.Structure):
-    """gm_vq_step_args (include/gm_hip.h): gm_vq_step's arguments as one block."""
-    _fields_ = [("ze", ctypes.c_void_p), ("ldz", ctypes.c_int64), ("codes", ctypes.c_void_p), ("ldc", ctypes.c_int64),
-                ("E", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("grad", ctypes.c_void_p),
-                ("nk", ctypes.c_void_p), ("usage", ctypes.c_void_p), ("sched", ctypes.c_void_p),
-                ("sched_slot", _lib.Slot), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
-                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("B", ctypes.c_int), ("N", ctypes.c_int),
-                ("D", ctypes.c_int), ("K", ctypes.c_int)]
-
-
 def vq_fused_sizes(N, D, K):
     """True iff (num_vars, code_dim, num_codes) fit the quantisation kernels (the GM_VQ_* limits)."""
     return (N >= 1 and _lib.VQ_MIN_D <= D <= _lib.VQ_MAX_D and D % 4 == 0 and N * D <= _lib.VQ_MAX_ND
@@ -1242,34 +1135,6 @@ def vq_step(ze, codes, E, B, N, D, moments=None, sched=None, sched_slot=NO_SLOT,
 
 
 # ---- Denoising diffusion (csrc/gm_ddpm.hip, gm_ddpm.h; ddpm.py) ----------------------------------------------------
-class DdpmNoise(ctypes.Structure):
-    """gm_ddpm_noise (include/gm_hip.h): seed, the two tags, the step and the first row's batch position."""
-    _fields_ = [("seed", ctypes.c_uint64), ("tag_t", ctypes.c_uint32), ("tag_e", ctypes.c_uint32),
-                ("step_ctr", ctypes.c_void_p), ("step_base", ctypes.c_void_p), ("step_add", ctypes.c_int64),
-                ("row0", ctypes.c_int64)]
-
-
-class DdpmTables(ctypes.Structure):
-    """gm_ddpm_tables (include/gm_hip.h): the schedule and embedding tables on the device."""
-    _fields_ = [("sa", ctypes.c_void_p), ("s1", ctypes.c_void_p), ("temb", ctypes.c_void_p), ("T", ctypes.c_int),
-                ("E", ctypes.c_int)]
-
-
-class DdpmOut(ctypes.Structure):
-    """gm_ddpm_out (include/gm_hip.h): where a q-sample writes."""
-    _fields_ = [("xin", ctypes.c_void_p), ("ldin", ctypes.c_int64), ("eps", ctypes.c_void_p), ("lde", ctypes.c_int64),
-                ("t", ctypes.c_void_p)]
-
-
-class DdpmReverseArgs(ctypes.Structure):
-    """gm_ddpm_reverse_args (include/gm_hip.h): one sampler step."""
-    _fields_ = [("xin", ctypes.c_void_p), ("ldin", ctypes.c_int64), ("eps", ctypes.c_void_p), ("lde", ctypes.c_int64),
-                ("coef", ctypes.c_void_p), ("slot", _lib.Slot), ("temb", ctypes.c_void_p), ("traj", ctypes.c_void_p),
-                ("traj_stride", ctypes.c_int64), ("seed", ctypes.c_uint64), ("tick", ctypes.c_void_p),
-                ("done", ctypes.c_void_p), ("rows", ctypes.c_int), ("I", ctypes.c_int), ("E", ctypes.c_int),
-                ("T", ctypes.c_int), ("S", ctypes.c_int), ("clip", ctypes.c_int)]
-
-
 def ddpm_noise(seed, train=True, step=0, step_ctr=None, step_base=None, row0=0):
     """A gm_ddpm_noise block: the training stream (tags DDPT / DDPM) or the validation one (DDPV / DDPW) at step =
     *step_ctr + *step_base + step (int64 device tensors, or None for 0).  The tensors must outlive every launch (and
@@ -1390,22 +1255,6 @@ def ddpm_prior(xin, temb, I, seed, step, t, traj=None, rows=None, stream=None):
 
 
 # ---- Masked autoregressive model (csrc/gm_made.hip, gm_made.h; made.py) ----------------------------------------------
-class MadeMaskArgs(ctypes.Structure):
-    """gm_made_mask_args (include/gm_hip.h): both masked layers, their moments and the degree vectors."""
-    _fields_ = [("W1", ctypes.c_void_p), ("m1", ctypes.c_void_p), ("v1", ctypes.c_void_p), ("W2", ctypes.c_void_p),
-                ("m2", ctypes.c_void_p), ("v2", ctypes.c_void_p), ("m_in", ctypes.c_void_p), ("m_h", ctypes.c_void_p),
-                ("I", ctypes.c_int), ("H", ctypes.c_int)]
-
-
-class MadeSampleArgs(ctypes.Structure):
-    """gm_made_sample_args (include/gm_hip.h): the one-launch ancestral sampler."""
-    _fields_ = [("W2", ctypes.c_void_p), ("b2", ctypes.c_void_p), ("W1T", ctypes.c_void_p), ("b1", ctypes.c_void_p),
-                ("m_h", ctypes.c_void_p), ("inv_order", ctypes.c_void_p), ("x", ctypes.c_void_p),
-                ("ldx", ctypes.c_int64), ("p", ctypes.c_void_p), ("ldp", ctypes.c_int64), ("given", ctypes.c_void_p),
-                ("ldg", ctypes.c_int64), ("seed", ctypes.c_uint64), ("n", ctypes.c_int64), ("I", ctypes.c_int),
-                ("H", ctypes.c_int), ("n_known", ctypes.c_int)]
-
-
 def _made_f32(t, shape, name):
     if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
         raise _lib.GMError("%s must be a contiguous float32 device tensor of shape %s" % (name, tuple(shape)))
@@ -1474,26 +1323,6 @@ def made_uniform(n, I, seed, row0=0, device="cuda", stream=None):
 
 
 # ---- Restricted Boltzmann machine (csrc/gm_rbm.hip, gm_rbm.h; rbm.py) --------------------------------------------------
-class RbmChainArgs(ctypes.Structure):
-    """gm_rbm_chain_args (include/gm_hip.h): the one-launch Gibbs chain."""
-    _fields_ = [("W", ctypes.c_void_p), ("WT", ctypes.c_void_p), ("c", ctypes.c_void_p), ("b", ctypes.c_void_p),
-                ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("v0_out", ctypes.c_void_p), ("ldv0", ctypes.c_int64),
-                ("v_out", ctypes.c_void_p), ("ldv", ctypes.c_int64), ("p_out", ctypes.c_void_p), ("ldp", ctypes.c_int64),
-                ("a_out", ctypes.c_void_p), ("lda", ctypes.c_int64), ("seed", ctypes.c_uint64), ("row0", ctypes.c_int64),
-                ("step_ctr", ctypes.c_void_p), ("step_base", ctypes.c_void_p), ("d_add", ctypes.c_int64),
-                ("g_mul", ctypes.c_int64), ("g_add", ctypes.c_int64), ("betas", ctypes.c_void_p),
-                ("b_A", ctypes.c_void_p), ("logw", ctypes.c_void_p), ("n", ctypes.c_int64), ("I", ctypes.c_int),
-                ("H", ctypes.c_int), ("steps", ctypes.c_int)]
-
-
-class RbmVbiasArgs(ctypes.Structure):
-    """gm_rbm_vbias_args (include/gm_hip.h): the visible bias' gradient and its Adam step."""
-    _fields_ = [("V", ctypes.c_void_p), ("ldv", ctypes.c_int64), ("g", ctypes.c_void_p), ("pb", ctypes.c_void_p),
-                ("mb", ctypes.c_void_p), ("vb", ctypes.c_void_p), ("sched", ctypes.c_void_p), ("sched_slot", _lib.Slot),
-                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
-                ("weight_decay", ctypes.c_double), ("inv_b", ctypes.c_float), ("B", ctypes.c_int), ("I", ctypes.c_int)]
-
-
 def rbm_chain(W, WT, c, b, x, steps, seed, n=None, v0_out=None, v_out=None, p_out=None, a_out=None, row0=0,
               step_ctr=None, step_base=None, d_add=0, g_mul=1, g_add=0, betas=None, b_A=None, logw=None, stream=None):
     """n Gibbs chains of `steps` steps from the binarisation of x [n, >= I], in ONE launch (gm_rbm_chain).  Outputs, each
@@ -1573,47 +1402,6 @@ def rbm_uniform(n, width, seed, tag, step=0, row0=0, step_ctr=None, step_base=No
 
 
 # ---- RealNVP coupling flow (csrc/gm_nvp.hip, gm_nvp.h; realnvp.py) ---------------------------------------------------
-class NvpPreArgs(ctypes.Structure):
-    """gm_nvp_pre_args (include/gm_hip.h): dequantise + logit + split, or the noise alone."""
-    _fields_ = [("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("ya", ctypes.c_void_p), ("lda", ctypes.c_int64),
-                ("yb", ctypes.c_void_p), ("ldb", ctypes.c_int64), ("logdet", ctypes.c_void_p), ("u", ctypes.c_void_p),
-                ("ldu", ctypes.c_int64), ("seed", ctypes.c_uint64), ("step_ctr", ctypes.c_void_p),
-                ("step_base", ctypes.c_void_p), ("step_add", ctypes.c_int64), ("row0", ctypes.c_int64),
-                ("tag", ctypes.c_uint32), ("alpha", ctypes.c_float), ("levels", ctypes.c_int), ("mask", ctypes.c_int),
-                ("mode", ctypes.c_int), ("B", ctypes.c_int), ("D", ctypes.c_int)]
-
-
-class NvpCoupleArgs(ctypes.Structure):
-    """gm_nvp_couple_args (include/gm_hip.h): one affine coupling, forward or inverse."""
-    _fields_ = [("st", ctypes.c_void_p), ("ldst", ctypes.c_int64), ("inp", ctypes.c_void_p), ("ldin", ctypes.c_int64),
-                ("out", ctypes.c_void_p), ("ldout", ctypes.c_int64), ("logdet", ctypes.c_void_p),
-                ("s_cap", ctypes.c_float), ("inverse", ctypes.c_int), ("B", ctypes.c_int), ("Dt", ctypes.c_int)]
-
-
-class NvpLossArgs(ctypes.Structure):
-    """gm_nvp_loss_args (include/gm_hip.h): the rows' negative log-likelihood and dz."""
-    _fields_ = [("za", ctypes.c_void_p), ("ldza", ctypes.c_int64), ("zb", ctypes.c_void_p), ("ldzb", ctypes.c_int64),
-                ("logdet", ctypes.c_void_p), ("part", ctypes.c_void_p), ("dza", ctypes.c_void_p),
-                ("lddza", ctypes.c_int64), ("dzb", ctypes.c_void_p), ("lddzb", ctypes.c_int64), ("cst", ctypes.c_float),
-                ("scale", ctypes.c_float), ("B", ctypes.c_int), ("Da", ctypes.c_int), ("Db", ctypes.c_int)]
-
-
-class NvpCoupleBwdArgs(ctypes.Structure):
-    """gm_nvp_couple_bwd_args (include/gm_hip.h): the coupling's backward."""
-    _fields_ = [("st", ctypes.c_void_p), ("ldst", ctypes.c_int64), ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64),
-                ("g0", ctypes.c_void_p), ("ldg0", ctypes.c_int64), ("g1", ctypes.c_void_p), ("ldg1", ctypes.c_int64),
-                ("dst", ctypes.c_void_p), ("lddst", ctypes.c_int64), ("dx", ctypes.c_void_p), ("lddx", ctypes.c_int64),
-                ("c", ctypes.c_float), ("s_cap", ctypes.c_float), ("B", ctypes.c_int), ("Dt", ctypes.c_int)]
-
-
-class NvpPostArgs(ctypes.Structure):
-    """gm_nvp_post_args (include/gm_hip.h): halves -> image, or the sampler's normals -> halves."""
-    _fields_ = [("ya", ctypes.c_void_p), ("lda", ctypes.c_int64), ("yb", ctypes.c_void_p), ("ldb", ctypes.c_int64),
-                ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("seed", ctypes.c_uint64), ("row0", ctypes.c_int64),
-                ("alpha", ctypes.c_float), ("temperature", ctypes.c_float), ("mask", ctypes.c_int), ("mode", ctypes.c_int),
-                ("B", ctypes.c_int), ("D", ctypes.c_int)]
-
-
 NVP_MASKS = {"checker": _lib.NVP_CHECKER, "half": _lib.NVP_HALF}
 
 
@@ -1727,37 +1515,6 @@ def nvp_prior(za, zb, B, D, seed, mask, temperature=1.0, row0=0, stream=None):
 
 
 # ---- Masked autoregressive flow (csrc/gm_maf.hip, gm_maf.h; maf.py) --------------------------------------------------
-class MafCoupleArgs(ctypes.Structure):
-    """gm_maf_couple_args (include/gm_hip.h): one layer, data -> noise."""
-    _fields_ = [("y", ctypes.c_void_p), ("ldy", ctypes.c_int64), ("ma", ctypes.c_void_p), ("ldma", ctypes.c_int64),
-                ("u", ctypes.c_void_p), ("ldu", ctypes.c_int64), ("logdet", ctypes.c_void_p), ("s_cap", ctypes.c_float),
-                ("B", ctypes.c_int), ("D", ctypes.c_int)]
-
-
-class MafCoupleBwdArgs(ctypes.Structure):
-    """gm_maf_couple_bwd_args (include/gm_hip.h): the layer's backward."""
-    _fields_ = [("ma", ctypes.c_void_p), ("ldma", ctypes.c_int64), ("u", ctypes.c_void_p), ("ldu", ctypes.c_int64),
-                ("g", ctypes.c_void_p), ("ldg", ctypes.c_int64), ("dout", ctypes.c_void_p), ("lddout", ctypes.c_int64),
-                ("dy", ctypes.c_void_p), ("lddy", ctypes.c_int64), ("c", ctypes.c_float), ("s_cap", ctypes.c_float),
-                ("B", ctypes.c_int), ("D", ctypes.c_int)]
-
-
-class MafMaskArgs(ctypes.Structure):
-    """gm_maf_mask_args (include/gm_hip.h): one layer's masked weights, their moments and the degree vectors."""
-    _fields_ = [("W1", ctypes.c_void_p), ("m1", ctypes.c_void_p), ("v1", ctypes.c_void_p), ("W2", ctypes.c_void_p),
-                ("m2", ctypes.c_void_p), ("v2", ctypes.c_void_p), ("m_in", ctypes.c_void_p), ("m_h", ctypes.c_void_p),
-                ("D", ctypes.c_int), ("H", ctypes.c_int)]
-
-
-class MafInvertArgs(ctypes.Structure):
-    """gm_maf_invert_args (include/gm_hip.h): one layer's inverse in one launch."""
-    _fields_ = [("u", ctypes.c_void_p), ("ldu", ctypes.c_int64), ("y", ctypes.c_void_p), ("ldy", ctypes.c_int64),
-                ("s", ctypes.c_void_p), ("lds", ctypes.c_int64), ("W2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
-                ("W1T", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("m_h", ctypes.c_void_p),
-                ("inv_order", ctypes.c_void_p), ("s_cap", ctypes.c_float), ("n", ctypes.c_int64), ("D", ctypes.c_int),
-                ("H", ctypes.c_int)]
-
-
 def maf_halves(t, D):
     """The GM_NVP_HALF view of rows t [B, >= D]: (the first ceil(D / 2) columns, the rest), both inside t -- what
     gm_nvp_pre / gm_nvp_loss / gm_nvp_post take for an unsplit MAF row array."""
@@ -2089,44 +1846,6 @@ def sw_loss(samples, data, theta):
 
 
 # ---- Flow matching (csrc/gm_fm.hip, gm_fm.h; flowmatch.py) ------------------------------------------------------------
-class FmNoise(ctypes.Structure):
-    """gm_fm_noise (include/gm_hip.h)."""
-    _fields_ = [("seed", ctypes.c_uint64), ("tag_d", ctypes.c_uint32), ("tag_t", ctypes.c_uint32),
-                ("tag_n", ctypes.c_uint32), ("step_ctr", ctypes.c_void_p), ("step_base", ctypes.c_void_p),
-                ("step_add", ctypes.c_int64), ("row0", ctypes.c_int64)]
-
-
-class FmTables(ctypes.Structure):
-    """gm_fm_tables (include/gm_hip.h)."""
-    _fields_ = [("tt", ctypes.c_void_p), ("tc", ctypes.c_void_p), ("temb", ctypes.c_void_p), ("T", ctypes.c_int),
-                ("E", ctypes.c_int)]
-
-
-class FmOut(ctypes.Structure):
-    """gm_fm_out (include/gm_hip.h)."""
-    _fields_ = [("xin", ctypes.c_void_p), ("ldin", ctypes.c_int64), ("u", ctypes.c_void_p), ("ldu", ctypes.c_int64),
-                ("logdet", ctypes.c_void_p), ("j", ctypes.c_void_p), ("y1", ctypes.c_void_p), ("ldy1", ctypes.c_int64),
-                ("y0", ctypes.c_void_p), ("ldy0", ctypes.c_int64), ("alpha", ctypes.c_float), ("levels", ctypes.c_int)]
-
-
-class FmDivArgs(ctypes.Structure):
-    """gm_fm_div_args (include/gm_hip.h)."""
-    _fields_ = [("H1", ctypes.c_void_p), ("ld1", ctypes.c_int64), ("H2", ctypes.c_void_p), ("ld2", ctypes.c_int64),
-                ("Q", ctypes.c_void_p), ("ldq", ctypes.c_int64), ("part", ctypes.c_void_p),
-                ("part_floats", ctypes.c_int64), ("div", ctypes.c_void_p), ("B", ctypes.c_int), ("H", ctypes.c_int)]
-
-
-class FmStageArgs(ctypes.Structure):
-    """gm_fm_stage_args (include/gm_hip.h): one solver stage."""
-    _fields_ = [("k", ctypes.c_void_p), ("ldk", ctypes.c_int64), ("base", ctypes.c_void_p), ("ldb", ctypes.c_int64),
-                ("acc", ctypes.c_void_p), ("lda", ctypes.c_int64), ("xin", ctypes.c_void_p), ("ldin", ctypes.c_int64),
-                ("L", ctypes.c_void_p), ("div", ctypes.c_void_p), ("div_stride", ctypes.c_int64),
-                ("div_parts", ctypes.c_int), ("tab", ctypes.c_void_p), ("slot", _lib.Slot), ("temb", ctypes.c_void_p),
-                ("traj", ctypes.c_void_p), ("traj_stride", ctypes.c_int64), ("tick", ctypes.c_void_p),
-                ("done", ctypes.c_void_p), ("rows", ctypes.c_int), ("I", ctypes.c_int), ("E", ctypes.c_int),
-                ("T", ctypes.c_int), ("S", ctypes.c_int), ("stages", ctypes.c_int)]
-
-
 def fm_noise(seed, train=True, step=0, step_ctr=None, step_base=None, row0=0):
     """A gm_fm_noise block: the training stream (tags FMTD / FMTT / FMTN) or the validation one (FMVD / FMVT / FMVN) at
     step = *step_ctr + *step_base + step (int64 device tensors, or None for 0).  The tensors must outlive every launch

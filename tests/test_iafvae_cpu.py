@@ -1,13 +1,11 @@
 """The IAF-VAE without a GPU: module surface and state_dict keys, the degrees and masks against maf's helpers, the fp64
 reference's per-layer Jacobians (triangular in the layer's degree order; their determinants pin logdet), the contract's
 closed-form backward against autograd, masked entries through optimiser steps, VAE checkpoints, the constructor's and the
-trainer's refusals, the C-ABI of the new kernels and its refusals, struct mirrors, path selection, the data-parallel
+trainer's refusals, the C-ABI of the new kernels and its refusals, path selection, the data-parallel
 refusal and the checkpoint config's strict check."""
 import ctypes
 import inspect
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -25,9 +23,6 @@ from generative_models_amd import _lib, ops_fused, philox  # noqa: E402
 from generative_models_amd import iafvae as giaf  # noqa: E402
 from generative_models_amd import iwae as giwae  # noqa: E402
 from generative_models_amd import maf as gmaf  # noqa: E402
-
-NEW = ("gm_iaf_sample", "gm_iaf_reduce", "gm_iaf_step")
-STRUCTS = {"gm_iaf_params": ops_fused.IafParams, "gm_iaf_step_args": ops_fused.IafStepArgs}
 
 
 def _loaders(n=40, batch=8, side=4):
@@ -216,16 +211,6 @@ def test_trainer_refusals(kw):
 
 
 def test_new_symbols_are_declared_and_bound():
-    lib = _lib.load()
-    declared = _lib.declared_symbols()
-    for name in NEW:
-        assert name in declared and name in _lib._SIGNATURES and hasattr(lib, name), name
-    hdr = open(os.path.join(os.path.dirname(HERE), "include", "gm_hip.h")).read()
-    for line in ("#define GM_IAF_MIN_Z %d" % _lib.IAF_MIN_Z, "#define GM_IAF_MAX_Z %d" % _lib.IAF_MAX_Z,
-                 "#define GM_IAF_MAX_K %d" % _lib.IAF_MAX_K, "#define GM_IAF_MIN_F %d" % _lib.IAF_MIN_F,
-                 "#define GM_IAF_MAX_F %d" % _lib.IAF_MAX_F, "#define GM_IAF_MAX_C %d" % _lib.IAF_MAX_C,
-                 "#define GM_IAF_PART_ROWS %d" % _lib.IAF_PART_ROWS):
-        assert line in hdr, line
     assert (_lib.IAF_MIN_Z, _lib.IAF_MAX_Z, _lib.IAF_MAX_K, _lib.IAF_MIN_F, _lib.IAF_MAX_F, _lib.IAF_MAX_C) == (
         2, 32, 8, 4, 64, 32)
     from generative_models_amd import _build
@@ -272,8 +257,8 @@ def test_kernels_reject_null_out_of_limit_and_aliased_arguments():
             assert b"bad argument" in lib.gm_last_error()
         for kw in (dict(B=0), dict(k=0), dict(k=65), dict(Z=1), dict(Z=33), dict(ml=None), dict(ldml=W - 1)):
             assert fn(**kw) == _lib.GM_EINVAL, (fn.__name__, kw)
-        assert fn(noise_=ctypes.cast(None, ctypes.c_void_p)) == _lib.GM_EINVAL
-        assert fn(flow=ctypes.cast(None, ctypes.c_void_p)) == _lib.GM_EINVAL
+        assert fn(noise_=ctypes.POINTER(ops_fused.IwaeNoise)()) == _lib.GM_EINVAL
+        assert fn(flow=ctypes.POINTER(ops_fused.IafParams)()) == _lib.GM_EINVAL
         assert fn(noise_=nz(k_total=k - 1)) == _lib.GM_EINVAL and fn(noise_=nz(j0=1)) == _lib.GM_EINVAL
     for kw in (dict(z=None), dict(lp=None), dict(ldz=Z - 1), dict(z=p(5)), dict(lp=p(5)), dict(lp=p(6)), dict(z=p(0)),
                dict(lp=p(3)), dict(ml=p(1))):
@@ -305,40 +290,6 @@ def test_kernels_reject_null_out_of_limit_and_aliased_arguments():
         assert not t.any()                                                # nothing was written
     with pytest.raises(_lib.GMError):
         _lib.call("gm_iaf_step", None, None)
-
-
-def test_struct_layout_matches_the_c_header(tmp_path):
-    gcc = shutil.which("gcc") or shutil.which("cc")
-    if gcc is None:
-        pytest.skip("no host C compiler")
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "gm_hip.h"', 'int main(void) {']
-    for cname, ct in STRUCTS.items():
-        lines.append('printf("%s size %%zu\\n", sizeof(%s));' % (cname, cname))
-        for fname, _ in ct._fields_:
-            lines.append('printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, fname, cname, fname))
-    lines.append('printf("macro stride %d\\n", GM_IAF_PART_STRIDE(20, 64, 20));')
-    lines.append('printf("macro parts %d\\n", GM_IAF_PARTS(130, 5) * 1000 + GM_IAF_PARTS(512, 64));')
-    lines += ['return 0;', '}']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run([gcc, "-I", os.path.join(os.path.dirname(HERE), "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    seen = 0
-    for line in out.splitlines():
-        cname, field, val = line.split()
-        if cname == "macro":
-            want = {"stride": ops_fused.iaf_part_stride(20, 64, 20),
-                    "parts": ops_fused.iaf_nparts(130, 5) * 1000 + ops_fused.iaf_nparts(512, 64)}[field]
-            assert int(val) == want, (field, val, want)
-            continue
-        ct = STRUCTS[cname]
-        if field == "size":
-            assert ctypes.sizeof(ct) == int(val), (cname, ctypes.sizeof(ct), val)
-        else:
-            assert getattr(ct, field).offset == int(val), (cname, field)
-        seen += 1
-    assert seen == sum(len(ct._fields_) + 1 for ct in STRUCTS.values())
 
 
 class _Mine(iaf_vae.IAFVAETrainer):

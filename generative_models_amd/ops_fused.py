@@ -7,9 +7,9 @@ from . import _lib
 from ._abi import (NO_SLOT, SN_MAX_H, SN_MAX_I, SN_NR, SN_NT, SN_NW2, SN_SIGMA, STD_WS_BYTES,  # noqa: F401
                    ACGANHeadsArgs, CatArgs, DdpmNoise, DdpmOut, DdpmReverseArgs, DdpmTables, FlowParams, FlowStepArgs,
                    FmDivArgs, FmNoise, FmOut, FmStageArgs, FmTables, IafParams, IafStepArgs, IwaeNoise, MadeMaskArgs,
-                   MadeSampleArgs, MafCoupleArgs, MafCoupleBwdArgs, MafInvertArgs, MafMaskArgs, NvpCoupleArgs,
-                   NvpCoupleBwdArgs, NvpLossArgs, NvpPostArgs, NvpPreArgs, RbmChainArgs, RbmVbiasArgs, SNGradArgs,
-                   SNHeadArgs, SNPowerArgs, VqArgs, VqStepArgs)
+                   MadeSampleArgs, MafCoupleArgs, MafCoupleBwdArgs, MafInvertArgs, MafMaskArgs, NsfCoupleArgs,
+                   NsfCoupleBwdArgs, NvpCoupleArgs, NvpCoupleBwdArgs, NvpLossArgs, NvpPostArgs, NvpPreArgs, RbmChainArgs,
+                   RbmVbiasArgs, SNGradArgs, SNHeadArgs, SNPowerArgs, VqArgs, VqStepArgs)
 from .ops import _ld, stream_ptr
 
 
@@ -1512,6 +1512,35 @@ def nvp_prior(za, zb, B, D, seed, mask, temperature=1.0, row0=0, stream=None):
     a.seed, a.row0, a.temperature = _seed64("nvp_prior", seed), int(row0), float(temperature)
     a.mask, a.mode, a.B, a.D = _nvp_mask(mask), _lib.NVP_PRIOR, B, D
     _lib.call("gm_nvp_post", stream or stream_ptr(), ctypes.byref(a))
+
+
+# ---- Neural spline flow (csrc/gm_nsf.hip, gm_nsf.h; nsf.py) ----------------------------------------------------------
+def nsf_couple(st, inp, out, B, Dt, bins, tail_bound, logdet=None, inverse=False, stream=None):
+    """out = the rational-quadratic spline of inp under the parameter-major rows st [B, (3 bins - 1) Dt] and logdet +=
+    the rows' sum of log dy/dx, or (inverse) out = the spline's inverse of inp (gm_nsf_couple)."""
+    a = NsfCoupleArgs()
+    _nvp_rows(st, B, (3 * bins - 1) * Dt, "st"), _nvp_rows(inp, B, Dt, "inp"), _nvp_rows(out, B, Dt, "out")
+    a.st, a.ldst, a.inp, a.ldin, a.out, a.ldout = st.data_ptr(), _ld(st), inp.data_ptr(), _ld(inp), out.data_ptr(), _ld(out)
+    if not inverse:
+        a.logdet = _nvp_vec(logdet, B, "logdet").data_ptr()
+    a.tail_bound, a.inverse, a.B, a.Dt, a.bins = float(tail_bound), 1 if inverse else 0, B, Dt, int(bins)
+    _lib.call("gm_nsf_couple", stream or stream_ptr(), ctypes.byref(a))
+
+
+def nsf_couple_bwd(st, x, g0, dst, B, Dt, bins, tail_bound, c, g1=None, dx=None, stream=None):
+    """dst = d(g . y + c sum log dy/dx) / d st, every column written, and dx the same with respect to x, with g = g0
+    (+ g1) (gm_nsf_couple_bwd)."""
+    W = (3 * bins - 1) * Dt
+    a = NsfCoupleBwdArgs()
+    _nvp_rows(st, B, W, "st"), _nvp_rows(x, B, Dt, "x"), _nvp_rows(g0, B, Dt, "g0"), _nvp_rows(dst, B, W, "dst")
+    a.st, a.ldst, a.x, a.ldx, a.g0, a.ldg0 = st.data_ptr(), _ld(st), x.data_ptr(), _ld(x), g0.data_ptr(), _ld(g0)
+    a.dst, a.lddst = dst.data_ptr(), _ld(dst)
+    if g1 is not None:
+        a.g1, a.ldg1 = _nvp_rows(g1, B, Dt, "g1").data_ptr(), _ld(g1)
+    if dx is not None:
+        a.dx, a.lddx = _nvp_rows(dx, B, Dt, "dx").data_ptr(), _ld(dx)
+    a.c, a.tail_bound, a.B, a.Dt, a.bins = float(c), float(tail_bound), B, Dt, int(bins)
+    _lib.call("gm_nsf_couple_bwd", stream or stream_ptr(), ctypes.byref(a))
 
 
 # ---- Masked autoregressive flow (csrc/gm_maf.hip, gm_maf.h; maf.py) --------------------------------------------------

@@ -86,18 +86,25 @@ def check_flow_settings(alpha, levels, s_cap, error):
     return alpha, levels, s_cap
 
 
+def check_coupling_shape(image_size, hidden_dim, num_couplings, mask, error):
+    """(D, H, K, mask) of a coupling flow over two halves, validated against the kernels' limits; else `error`."""
+    D, H, K = (_lib.check_int(v, n, error) for v, n in ((image_size, "image_size"), (hidden_dim, "hidden_dim"),
+                                                        (num_couplings, "num_couplings")))
+    if not NVP_MIN_D <= D <= NVP_MAX_D:
+        raise error("image_size must lie in [%d, %d], got %d" % (NVP_MIN_D, NVP_MAX_D, D))
+    if not 1 <= H <= NVP_MAX_H:
+        raise error("hidden_dim must lie in [1, %d], got %d" % (NVP_MAX_H, H))
+    if not 1 <= K <= NVP_MAX_K:
+        raise error("num_couplings must lie in [1, %d], got %d" % (NVP_MAX_K, K))
+    if not isinstance(mask, str) or mask not in MASKS:
+        raise error("mask must be one of %s, got %r" % (MASKS, mask))
+    return D, H, K, mask
+
+
 def check_config(image_size, hidden_dim, num_couplings, mask, alpha, levels, s_cap):
     """(D, H, K, mask, alpha, levels, s_cap) validated against the kernels' limits; else RealNVPError."""
-    D, H, K = _int(image_size, "image_size"), _int(hidden_dim, "hidden_dim"), _int(num_couplings, "num_couplings")
-    if not NVP_MIN_D <= D <= NVP_MAX_D:
-        raise RealNVPError("image_size must lie in [%d, %d], got %d" % (NVP_MIN_D, NVP_MAX_D, D))
-    if not 1 <= H <= NVP_MAX_H:
-        raise RealNVPError("hidden_dim must lie in [1, %d], got %d" % (NVP_MAX_H, H))
-    if not 1 <= K <= NVP_MAX_K:
-        raise RealNVPError("num_couplings must lie in [1, %d], got %d" % (NVP_MAX_K, K))
-    if not isinstance(mask, str) or mask not in MASKS:
-        raise RealNVPError("mask must be one of %s, got %r" % (MASKS, mask))
-    return (D, H, K, mask) + check_flow_settings(alpha, levels, s_cap, RealNVPError)
+    return (check_coupling_shape(image_size, hidden_dim, num_couplings, mask, RealNVPError)
+            + check_flow_settings(alpha, levels, s_cap, RealNVPError))
 
 
 # ---- the split and the noise rules in numpy (the tests' reference reads the same contract) ----------------------------
@@ -172,19 +179,18 @@ class Coupling(nn.Module):
         return ops.fused_linear(h, self.out.weight, self.out.bias, "id")
 
 
-@stock_model
-class RealNVP(nn.Module):
-    """K affine couplings over the two halves of a logit-space image."""
+class CouplingFlow(nn.Module):
+    """K couplings over the two halves of a logit-space image: the split, the alternation (even k transforms B) and the
+    two directions, shared by RealNVP and nsf.SplineFlow.  A subclass sets image_size, num_couplings, mask and
+    `couplings`, and supplies the element-wise map: _transform(k, x_t, x_c) -> (y_t, its log-determinant per row) and
+    _untransform(k, y_t, x_c) -> x_t, by autograd-able torch ops."""
 
-    def __init__(self, image_size=784, hidden_dim=400, num_couplings=4, mask="checker", alpha=0.05, levels=256,
-                 s_cap=2.0):
-        super().__init__()
-        (self.image_size, self.hidden_dim, self.num_couplings, self.mask, self.alpha, self.levels,
-         self.s_cap) = check_config(image_size, hidden_dim, num_couplings, mask, alpha, levels, s_cap)
+    def _halves(self, make):
+        """Da, Db and `couplings` = make(Dc, Dt) for every k."""
         D = self.image_size
         self.Da, self.Db = (D + 1) // 2, D // 2
         dims = [(self.Da, self.Db) if k % 2 == 0 else (self.Db, self.Da) for k in range(self.num_couplings)]
-        self.couplings = nn.ModuleList([Coupling(dc, dt, self.hidden_dim) for dc, dt in dims])
+        self.couplings = nn.ModuleList([make(dc, dt) for dc, dt in dims])
         self.shape = int(D ** 0.5)
 
     def split(self, y):
@@ -201,20 +207,14 @@ class RealNVP(nn.Module):
         y[:, torch.from_numpy(ib).to(a.device)] = b
         return y
 
-    def _st(self, k, x_c):
-        st = self.couplings[k](x_c)
-        dt = st.shape[1] // 2
-        return self.s_cap * torch.tanh(st[:, :dt]), st[:, dt:]
-
     def flow(self, y):
         """(z [n, D], logdet [n]) of logit-space rows y, by autograd-able torch ops over the fused linear kernels."""
         h = list(self.split(y))
         logdet = torch.zeros(y.shape[0], dtype=y.dtype, device=y.device)
         for k in range(len(self.couplings)):
             t = 1 - (k & 1)                          # even k transforms B
-            s, sh = self._st(k, h[1 - t])
-            h[t] = h[t] * torch.exp(s) + sh
-            logdet = logdet + s.sum(1)
+            h[t], ld = self._transform(k, h[t], h[1 - t])
+            logdet = logdet + ld
         return self.merge(h[0], h[1]), logdet
 
     def inverse(self, z):
@@ -222,12 +222,36 @@ class RealNVP(nn.Module):
         h = list(self.split(z))
         for k in reversed(range(len(self.couplings))):
             t = 1 - (k & 1)
-            s, sh = self._st(k, h[1 - t])
-            h[t] = (h[t] - sh) * torch.exp(-s)
+            h[t] = self._untransform(k, h[t], h[1 - t])
         return self.merge(h[0], h[1])
 
     def forward(self, y):
         return self.flow(y)
+
+
+@stock_model
+class RealNVP(CouplingFlow):
+    """K affine couplings over the two halves of a logit-space image."""
+
+    def __init__(self, image_size=784, hidden_dim=400, num_couplings=4, mask="checker", alpha=0.05, levels=256,
+                 s_cap=2.0):
+        super().__init__()
+        (self.image_size, self.hidden_dim, self.num_couplings, self.mask, self.alpha, self.levels,
+         self.s_cap) = check_config(image_size, hidden_dim, num_couplings, mask, alpha, levels, s_cap)
+        self._halves(lambda dc, dt: Coupling(dc, dt, self.hidden_dim))
+
+    def _st(self, k, x_c):
+        st = self.couplings[k](x_c)
+        dt = st.shape[1] // 2
+        return self.s_cap * torch.tanh(st[:, :dt]), st[:, dt:]
+
+    def _transform(self, k, x_t, x_c):
+        s, sh = self._st(k, x_c)
+        return x_t * torch.exp(s) + sh, s.sum(1)
+
+    def _untransform(self, k, y_t, x_c):
+        s, sh = self._st(k, x_c)
+        return (y_t - sh) * torch.exp(-s)
 
 
 def realnvp_fused_ok(model):
@@ -288,16 +312,31 @@ class RealNVPEngine(OneNetEngine):
     def _dt(self, k):
         return self.Db if k % 2 == 0 else self.Da
 
+    # ---- the element-wise map of a coupling (nsf.SplineFlowEngine swaps these three) ---------------------------------------
+    def _st_width(self, dt):
+        """Columns of a conditioner's output for a transformed half of dt pixels."""
+        return 2 * dt
+
+    def _couple(self, st, k, xt, b):
+        """Y[k] of the coupling's input xt and ST[k]; the rows' log-determinant grows."""
+        from . import ops_fused as of_
+        of_.nvp_couple(self.ST[k], xt, self.Y[k], b, self._dt(k), self.model.s_cap, logdet=self.logdet, stream=st)
+
+    def _couple_bwd(self, st, k, xt, g, dST, b, c):
+        """dST and dX[k] of the output half's cotangent g and the log-determinant's c."""
+        from . import ops_fused as of_
+        of_.nvp_couple_bwd(self.ST[k], xt, g, dST, b, self._dt(k), self.model.s_cap, c, dx=self.dX[k], stream=st)
+
     def _buffers(self, B):
         z = lambda *s: torch.zeros(*s, device=self.device)
         D, H, K, Da, Db = self.D, self.H, self.K, self.Da, self.Db
         self.X, self.Y0 = z(B, D), (z(B, Da), z(B, Db))
         self.H1 = [z(B, H) for _ in range(K)]
-        self.ST = [z(B, 2 * self._dt(k)) for k in range(K)]
+        self.ST = [z(B, self._st_width(self._dt(k))) for k in range(K)]
         self.Y = [z(B, self._dt(k)) for k in range(K)]
         self.logdet, self.part = z(B), z(B)
         self.dZ = (z(B, Da), z(B, Db))
-        self.dST = (z(B, 2 * Da), z(B, 2 * Db))      # by the transformed half: A's, B's
+        self.dST = (z(B, self._st_width(Da)), z(B, self._st_width(Db)))      # by the transformed half: A's, B's
         self.dH = z(B, H)
         self.dX = [z(B, self._dt(k)) if k >= 2 else None for k in range(K)]          # d loss / d (coupling k's input)
         self.G = [z(B, self._dt(k - 1)) if k >= 1 else None for k in range(K)]       # cotangent of coupling k's x_c
@@ -337,7 +376,7 @@ class RealNVPEngine(OneNetEngine):
             L1, L2 = self.C[k]
             ops.linear_fwd(xc, L1.W, L1.b, self.H1[k], "relu", M=b, stream=st)
             ops.linear_fwd(self.H1[k], L2.W, L2.b, self.ST[k], "id", M=b, stream=st)
-            of_.nvp_couple(self.ST[k], xt, self.Y[k], b, self._dt(k), m.s_cap, logdet=self.logdet, stream=st)
+            self._couple(st, k, xt, b)
         scale = float(np.float32(1.0 / b))
         cst = float(np.float32(nll_constant(self.D, m.levels)))
         of_.nvp_loss(Za, Zb, self.logdet, self.part, b, cst, scale=scale, dza=self.dZ[0] if train else None,
@@ -349,7 +388,7 @@ class RealNVPEngine(OneNetEngine):
                 L1, L2 = self.C[k]
                 dST = self.dST[th]
                 g = self.dZ[th] if k == K - 1 else self.G[k + 1]
-                of_.nvp_couple_bwd(self.ST[k], xt, g, dST, b, self._dt(k), m.s_cap, -scale, dx=self.dX[k], stream=st)
+                self._couple_bwd(st, k, xt, g, dST, b, -scale)
                 # both input gradients read the coupling's weights BEFORE the paired dW(+Adam) launch updates them
                 ops.linear_bwd_dx(dST, L2.W, self.dH, below=self.H1[k], epi="relu", M=b, stream=st)
                 if k > 0:
@@ -486,21 +525,14 @@ class DequantFlowTrainer(OneLossTrainer):
 
 
 @stock
-class RealNVPTrainer(DequantFlowTrainer):
-    """Trains a RealNVP on its exact (dequantised) negative log-likelihood; samples, encodes and decodes: a
-    DequantFlowTrainer whose code is the pair of halves (sampling is 3 K + 2 launches for a stock model).  Histories:
-    `losses` (the NLL in nats per image, one per training batch); the epoch line (mean training NLL, validation NLL);
-    best_val_loss / best_model as the other VAE-family trainers; checkpoints (+ mask, alpha, levels, s_cap, seed in the
-    optimizer state's config, checked under strict=True, and the number of training batches taken, so a resumed run
-    continues the noise stream bit for bit).  One GPU only."""
-    _one_gpu = "RealNVPTrainer"
-    _error = RealNVPError
-    _fused_ok = staticmethod(realnvp_fused_ok)
+class CouplingFlowTrainer(DequantFlowTrainer):
+    """What the trainers of the two coupling flows share (RealNVP here, the neural spline flow in nsf.py): a
+    DequantFlowTrainer whose code is the pair of halves, over a model with split, merge, inverse and `couplings` of
+    (linear, out) conditioners.  On device rows the flow is gm_nvp_pre, K x (the conditioner's two GEMMs, the coupling's
+    launch) and gm_nvp_loss; its inverse the couplings last to first and gm_nvp_post (3 K + 2 launches with the prior's
+    for a stock model).  A subclass supplies _couple_rows(st, inp, out, logdet=None, inverse=False), the coupling's one
+    launch."""
     _tag_train, _tag_eval = TAG_TRAIN, TAG_EVAL
-
-    def _flow_settings(self):
-        m = self.model
-        return m.alpha, m.levels, m.s_cap
 
     def _model_flow(self, y):
         return self.model(y)
@@ -510,13 +542,6 @@ class RealNVPTrainer(DequantFlowTrainer):
 
     def _z_to_code(self, z):
         return self.model.split(z)
-
-    def _engine_class(self):
-        return RealNVPEngine
-
-    def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
-        """VAETrainer.train with this model's defaults."""
-        return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
 
     # ---- the flow on device rows, no autograd --------------------------------------------------------------------------
     def _st(self, k, xc):
@@ -534,7 +559,7 @@ class RealNVPTrainer(DequantFlowTrainer):
         from . import ops_fused as of_
         m, n = self.model, x.shape[0]
         with torch.no_grad():
-            if not realnvp_fused_ok(m):
+            if not self._fused_ok(m):
                 u = of_.nvp_uniforms(n, m.image_size, seed, tag, step=step, row0=row0, device=x.device)
                 y, ld0 = preprocess(x, u, m.alpha, m.levels)
                 z, ld = m(y)
@@ -545,7 +570,7 @@ class RealNVPTrainer(DequantFlowTrainer):
             for k in range(m.num_couplings):
                 t = 1 - (k & 1)
                 out = torch.empty_like(h[t])
-                of_.nvp_couple(self._st(k, h[1 - t]), h[t], out, n, h[t].shape[1], m.s_cap, logdet=logdet)
+                self._couple_rows(self._st(k, h[1 - t]), h[t], out, logdet=logdet)
                 h[t] = out
             of_.nvp_loss(h[0], h[1], logdet, part, n, float(np.float32(nll_constant(m.image_size, m.levels))))
             return (h[0], h[1]), part
@@ -556,13 +581,13 @@ class RealNVPTrainer(DequantFlowTrainer):
         za, zb = code
         m, n = self.model, za.shape[0]
         with torch.no_grad():
-            if not realnvp_fused_ok(m):
+            if not self._fused_ok(m):
                 return postprocess(m.inverse(m.merge(za, zb)), m.alpha).contiguous()
             h = [za, zb]
             for k in reversed(range(m.num_couplings)):
                 t = 1 - (k & 1)
                 out = torch.empty_like(h[t])
-                of_.nvp_couple(self._st(k, h[1 - t]), h[t], out, n, h[t].shape[1], m.s_cap, inverse=True)
+                self._couple_rows(self._st(k, h[1 - t]), h[t], out, inverse=True)
                 h[t] = out
             x = torch.empty(n, m.image_size, device=za.device)
             of_.nvp_post(h[0], h[1], x, n, m.alpha, m.mask)
@@ -576,6 +601,34 @@ class RealNVPTrainer(DequantFlowTrainer):
         of_.nvp_prior(za, zb, n, m.image_size, seed, m.mask, temperature=temperature)
         return za, zb
 
+
+@stock
+class RealNVPTrainer(CouplingFlowTrainer):
+    """Trains a RealNVP on its exact (dequantised) negative log-likelihood; samples, encodes and decodes: a
+    DequantFlowTrainer whose code is the pair of halves (sampling is 3 K + 2 launches for a stock model).  Histories:
+    `losses` (the NLL in nats per image, one per training batch); the epoch line (mean training NLL, validation NLL);
+    best_val_loss / best_model as the other VAE-family trainers; checkpoints (+ mask, alpha, levels, s_cap, seed in the
+    optimizer state's config, checked under strict=True, and the number of training batches taken, so a resumed run
+    continues the noise stream bit for bit).  One GPU only."""
+    _one_gpu = "RealNVPTrainer"
+    _error = RealNVPError
+    _fused_ok = staticmethod(realnvp_fused_ok)
+
+    def _flow_settings(self):
+        m = self.model
+        return m.alpha, m.levels, m.s_cap
+
+    def _engine_class(self):
+        return RealNVPEngine
+
+    def train(self, num_epochs, lr=1e-3, weight_decay=0.0, quiet=False):
+        """VAETrainer.train with this model's defaults."""
+        return super().train(num_epochs, lr=lr, weight_decay=weight_decay, quiet=quiet)
+
+    def _couple_rows(self, st, inp, out, logdet=None, inverse=False):
+        from . import ops_fused as of_
+        of_.nvp_couple(st, inp, out, inp.shape[0], inp.shape[1], self.model.s_cap, logdet=logdet, inverse=inverse)
+
     def interpolate(self, a, b, steps=8, seed=0):
         """[steps, D]: the decoded line from image a to image b in z."""
         steps = _int(steps, "steps")
@@ -586,5 +639,6 @@ class RealNVPTrainer(DequantFlowTrainer):
         return self.decode((1.0 - w) * z[0:1] + w * z[1:2])
 
 
-__all__ = ["Coupling", "RealNVP", "RealNVPTrainer", "RealNVPEngine", "RealNVPError", "split_indices", "philox_words",
+__all__ = ["Coupling", "CouplingFlow", "CouplingFlowTrainer", "RealNVP", "RealNVPTrainer", "RealNVPEngine",
+           "RealNVPError", "split_indices", "philox_words",
            "uniforms_reference", "normals_reference", "preprocess", "postprocess", "nll_constant", "realnvp_fused_ok"]

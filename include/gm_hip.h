@@ -1421,6 +1421,48 @@ typedef struct gm_nvp_post_args {
 } gm_nvp_post_args;
 int gm_nvp_post(void* stream, const gm_nvp_post_args* a);
 
+/* ---- neural spline flow, NSF (Durkan, Bortoli, Murray & Papamakarios, arXiv 1906.04032; nsf.py holds the contract;
+ * DESIGN.md section 37; csrc/gm_nsf.hip, the shared arithmetic in csrc/gm_nsf.h) ---------------------------------------
+ * RealNVP's halves, preprocessing, loss, post-processing and noise (the gm_nvp_* kernels above, unchanged) around
+ * couplings whose element-wise map is a monotone rational-quadratic spline with linear tails.  ST [B, >= P Dt], P =
+ * 3 bins - 1, is parameter-major: column p Dt + j is parameter p of pixel j of the transformed half; parameters
+ * 0 .. bins - 1 are theta_w, the next bins theta_h, the last bins - 1 theta_d.  With T = tail_bound, m = 1e-3:
+ *   w_i = 2 T (m + (1 - m bins) softmax(theta_w)_i), x_i = -T + (w_0 + .. + w_{i-1}); h_i, y_i likewise of theta_h;
+ *   d_0 = d_bins = 1, d_i = m + softplus(theta_d_{i-1} + log(exp(1 - m) - 1)).
+ * A pixel with x <= -T or x >= T passes unchanged (log-derivative 0, parameter gradients 0).  Otherwise, in the bin k =
+ * #{1 <= i < bins: x >= x_i}, xi = (x - x_k) / w_k clamped to [0, 1], s = h_k / w_k, q = s + (d_{k+1} + d_k - 2 s)
+ * xi (1 - xi):  y = y_k + h_k (s xi^2 + d_k xi (1 - xi)) / q,  log dy/dx = 2 log s + log(d_{k+1} xi^2 + 2 s xi (1 - xi) +
+ * d_k (1 - xi)^2) - 2 log q.  One 256-thread workgroup per row, a pixel per thread at a time, dword accesses only: any
+ * leading dimension >= the width is legal.  bins is one of 4, 8, 16.  Out-of-limit fields, NULL and an output that is
+ * an input return GM_EINVAL before any launch. */
+#define GM_NSF_MIN_BINS 4
+#define GM_NSF_MAX_BINS 16
+#define GM_NSF_MAX_TAIL 64
+/* forward:  out = the spline of inp, logdet[r] += sum_j log dy/dx (a plain read-add-write by the row's owner);
+ * inverse:  out = the spline's inverse of inp (the bin found on the y knots);  logdet is not touched (may be NULL). */
+typedef struct gm_nsf_couple_args {
+    const float* st; int64_t ldst;            /* [B, >= P Dt] */
+    const float* inp; int64_t ldin;           /* [B, >= Dt] */
+    float* out; int64_t ldout;                /* [B, >= Dt]; none of st, inp */
+    float* logdet;                            /* [B] (forward) */
+    float tail_bound;                         /* in (0, GM_NSF_MAX_TAIL] */
+    int inverse, B, Dt, bins;
+} gm_nsf_couple_args;
+int gm_nsf_couple(void* stream, const gm_nsf_couple_args* a);
+/* The coupling's backward.  g = g0 (+ g1 when not NULL) is the transformed half's cotangent, c the log-determinant's:
+ * dst = d(g . y + c sum_j log dy/dx) / d st, every one of its P Dt columns written (zeros for a pixel in the tails), and
+ * dx = the same with respect to x (g itself in the tails; dx may be NULL). */
+typedef struct gm_nsf_couple_bwd_args {
+    const float* st; int64_t ldst;            /* [B, >= P Dt] */
+    const float* x; int64_t ldx;              /* [B, >= Dt]: the coupling's input */
+    const float* g0; int64_t ldg0; const float* g1; int64_t ldg1;
+    float* dst; int64_t lddst;                /* [B, >= P Dt] */
+    float* dx; int64_t lddx;                  /* [B, >= Dt] or NULL */
+    float c, tail_bound;
+    int B, Dt, bins;
+} gm_nsf_couple_bwd_args;
+int gm_nsf_couple_bwd(void* stream, const gm_nsf_couple_bwd_args* a);
+
 /* ---- masked autoregressive flow, MAF (Papamakarios, Pavlakou & Murray, arXiv 1705.07057; maf.py holds the contract;
  * DESIGN.md section 30; csrc/gm_maf.hip, the shared arithmetic in csrc/gm_maf.h) ------------------------------------------
  * K layers, each a D -> H -> 2 D MLP masked by the degrees m_in [D] (a permutation of 1 .. D) and m_h [H] (in [1, D - 1]),
